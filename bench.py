@@ -14,7 +14,11 @@ reference kernels evaluate, particle_cs.glsl:30,35).  K steps run as ONE Perform
 harness' update(w, dt, 100) (bench.c:30-33); particles are resident in HBM before the timed region (SetSimulationData is
 outside it).
 
-N = 1: the CPU baseline runs FIRST (the reference's own UpdateWorld_CPU, compiled where it lies, the product's on the
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, the K timed steps, the outputs
+(--dump-outputs DIR: the Particle array those steps left, as .npy files) and the line.  Everything below that is not the
+headline runs with --full only.
+
+N = 1 with --full: the CPU baseline runs FIRST (the reference's own UpdateWorld_CPU, compiled where it lies, the product's on the
 same World and thread count, and -- informational -- the fastest CPU variant the host runs: cpu_baseline.best_cpu), then the
 GPU legs back to back: headline K steps -- from here on the line is in hand and
 every later leg runs under a C-level last-gasp handler --, the clock probe, the headline's parity stamp, two repeats of
@@ -34,7 +38,7 @@ over the next transport; the line carries one "transport_fallback" entry per ste
 between the ranks (nbody_amd/ranklink.py): torch is NOT imported, so the HIP runtime and the librccl the data path binds
 are /opt/rocm's -- the stack every single-GPU test runs on (`--rendezvous gloo` keeps the round-3 route).  The JSON dict
 is COMPLETE after the headline leg and the self-check (mandatory for every N > 1 headline: all ranks agree and match a
-single-GPU run; what the RCCL communicator itself reports; per-step kernel / all-gather times); every later leg
+single-GPU run; what the RCCL communicator itself reports; per-step kernel / all-gather times); with --full every later leg
 (`extra_configs`: overlapped step, the chain captured as a hipGraph, BASELINE.json's config 5 at N = 2^22 plain and
 overlapped, the direct exchange with its own self-check) runs under a host-side deadline -- as does the headline leg itself,
 inside the attempt's share of the budget: if one stalls, rank 0 writes the line with what is in hand plus "extras_aborted":
@@ -43,7 +47,7 @@ re-exec.  Failure rehearsals are not in this file: tests/bench_rehearsal.py regi
 
 `runtime` in the JSON line says which HIP runtime and librccl the run bound.
 
-Every single-GPU leg carries a parity stamp: OUTSIDE the timed region the state the timed steps left is read back, one
+With --full every single-GPU leg carries a parity stamp: OUTSIDE the timed region the state the timed steps left is read back, one
 more step runs, and that step is checked -- sampled accelerations against the oracle's float64 sum (the stated
 tolerance) and against the reference AVX order, the integrator identity bit for bit over all N particles.
 
@@ -291,6 +295,23 @@ def parity_stamp(sim, mass_len, dt=DT, samples=256):
                     "gpu_vs_avx_max = |acc_gpu - acc_avx| / sum|contrib|; integrator identity over all particles"}
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_FIELDS = (("positions", slice(0, 2)), ("velocities", slice(2, 4)), ("accelerations", slice(4, 6)), ("masses", 6), ("radii", 7))
+
+
+def dump_outputs(directory, particles, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the Particle array the timed steps left -- what GetSimulationData hands a caller -- one float32 .npy per
+    field.  Above `limit` bytes in all: the same fixed, seeded sample of rows in every file, their indices in rows.npy (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    n, row_bytes, budget = particles.shape[0], particles.shape[1] * 4, limit - 4096   # six .npy headers fit in 4 KiB
+    if n * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(11037).choice(n, budget // (row_bytes + 8), replace=False))
+        particles = particles[rows]
+        np.save(os.path.join(directory, "rows.npy"), rows.astype(np.float64))
+    for name, cols in DUMP_FIELDS:
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(particles[:, cols], dtype=np.float32))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -333,7 +354,18 @@ def parse_args(argv=None):
                          "without touching a GPU: no step runs and the reported value is 0")
     ap.add_argument("--leg-deadline-s", type=float, default=120.0,
                     help="N > 1: host-side deadline of every optional leg (below the library's own 180 s collective watchdog)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything that is not the headline: CPU baseline, clock probe, parity stamps, repeats, the LDS "
+                         "route, extra_configs (1 GPU); extra_configs (N GPUs).  The --no-* options above subtract from it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the particle state they left to DIR/{positions,velocities,accelerations,"
+                         "masses,radii}.npy (float32; above 64 MB a fixed, seeded sample of rows, indices in DIR/rows.npy)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_cpu_baseline = args.no_clock_probe = args.no_parity = args.no_extras = True
+    return args
 
 
 def worker_main(args):
@@ -619,6 +651,10 @@ def worker_main(args):
             extras["rccl"] = comm_evidence(sim)
             d = sharded_detail(sim, args.steps)
             extras["comm_ms_per_step"], extras["kernel_ms_per_step"] = d["comm_ms_per_step"], d["kernel_ms_per_step"]
+        if args.dump_outputs:
+            state = sim.get_data()   # collective when sharded; outside the timed region, before any later leg steps again
+            if rank == 0:
+                dump_outputs(args.dump_outputs, state)
     if sharded:
         # every rank's bring-up record, on the line (the supervisor also holds the per-stage trail of attempts that died)
         extras["preflight"] = [json.loads(b.decode()) for b in gather_bytes(json.dumps(flight).encode())]

@@ -114,6 +114,7 @@ class RankProcess:
     def __init__(self, script, argv, env, rank, capture_stdout):
         self.rank = rank
         self.lines, self.tail, self.preflight = [], [], []
+        self.dumping = False
         self.proc = subprocess.Popen([sys.executable, script] + argv, env=env, preexec_fn=_die_with_parent,
                                      stdout=subprocess.PIPE if capture_stdout else sys.stderr.fileno(), stderr=subprocess.PIPE)
         self.threads = [threading.Thread(target=self._pump_err, daemon=True)]
@@ -137,6 +138,9 @@ class RankProcess:
                 except ValueError:
                     pass
                 continue
+            if self.dumping:
+                continue    # faulthandler's dump of every thread, with full paths: it would push the last words out of the tail
+            self.dumping = text.startswith("Fatal Python error")
             self.tail.append(text)
             del self.tail[:-40]
 

@@ -47,6 +47,10 @@ PARTITION_CASES = [
     ([0, 1, 2, 0, 3, 0], [3, 1, 2, 0, 0, 0], 3),
 ]
 
+# MakeGalaxies(n, galaxies) after srand(seed) at other sizes, galaxy counts and seeds: digests only (50 000 particles would
+# not fit a fixture file); tests/test_world_cpu.py holds the product's MakeGalaxies to them
+MAKE_GALAXIES_CASES = [(6000, 3, 1), (100, 1, 7), (50000, 5, 42), (1000, 10, 3), (250, 2, 11037)]
+
 
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
@@ -111,6 +115,8 @@ def main():
                 entry["steps"][tag]["file"] = f"ref_avx_{n}_{tag}.bin"
             print(f"N={n} {tag}: {digest}")
         manifest["sets"][str(n)] = entry
+
+    manifest["make_galaxies_digests"] = {f"{n}_{g}_{seed}": sha(make_ic(n, g, seed)) for n, g, seed in MAKE_GALAXIES_CASES}
 
     # the reference's other SIMD_SET builds (SSE: 4-wide packs, scalar: 1-wide), digests only
     manifest["simd_variants"] = {}

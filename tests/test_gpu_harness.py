@@ -340,7 +340,7 @@ def test_single_gpu_bench_line_survives_a_leg_that_aborts(leg):
     with "extras_aborted" naming the leg, and the run does not report success."""
     import json
     env = dict(os.environ, NB_BENCH_REHEARSE=json.dumps({"crash_leg": leg}))
-    r = subprocess.run([sys.executable, os.path.join(nb.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(nb.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=nb.ROOT)
     assert r.returncode == 6, (r.returncode, r.stderr[-1500:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -355,7 +355,7 @@ def test_single_gpu_bench_skips_the_legs_its_budget_no_longer_holds():
     that need more than what is left are LISTED (legs_skipped_for_budget) instead of started, the headline is unaffected, and
     the run reports success -- a slow box costs legs, never the line."""
     import json
-    r = subprocess.run([sys.executable, os.path.join(nb.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--budget-s", "14"],
+    r = subprocess.run([sys.executable, os.path.join(nb.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full", "--budget-s", "14"],
                        capture_output=True, text=True, timeout=600, cwd=nb.ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -365,6 +365,39 @@ def test_single_gpu_bench_skips_the_legs_its_budget_no_longer_holds():
     skipped = out["legs_skipped_for_budget"]
     assert "extra_configs C2/C3/N2/C1" in skipped and "extra_configs S2/S4/S8/C5S8" in skipped
     assert out.get("extra_configs", []) == []
+
+
+def test_plain_bench_run_is_the_headline_and_dumps_what_its_timed_steps_computed(tmp_path):
+    """`python bench.py --steps K --warmup W` without --full: the headline and nothing else on the line, ms_per_step the
+    wall clock of ONE timed step; --dump-outputs writes the state the K timed steps left, bit for bit what the same
+    calls on a pipeline of the same workload leave."""
+    import json
+    sys.path.insert(0, nb.ROOT)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k != "NB_BENCH_REHEARSE"}
+    r = subprocess.run([sys.executable, os.path.join(nb.ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--particles", "65536", "--dump-outputs", str(tmp_path)],
+                       env=env, capture_output=True, text=True, timeout=600, cwd=nb.ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, r.stdout[-1000:]
+    out = json.loads(lines[0])
+    assert out["unit"] == "interactions/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["value"] > 1e11
+    for key in ("cpu_baseline", "parity", "repeat_ms_per_step", "extra_configs", "legs_skipped_for_budget", "extras_aborted"):
+        assert key not in out, key
+    assert "alt_lds" not in out["roofline"] and out["roofline"]["held_clock_ghz"] is None
+    _, part, m = bench_universe(65536)
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 / (65536.0 * m) - 1.0) < 1e-9      # interactions of ONE step / its time
+    sim = nb.SimPipeline(65536, m)
+    sim.configure(graph=1)
+    sim.set_data(part)
+    sim.update(2, 0.01)
+    sim.update(3, 0.01)
+    want = sim.get_data()
+    sim.close()
+    got = np.column_stack([np.load(tmp_path / f"{name}.npy") for name, _ in bench.DUMP_FIELDS])
+    assert got.dtype == np.float32 and got.tobytes() == want.tobytes()
 
 
 @pytest.mark.parametrize("ranks", [2, 3, 8])

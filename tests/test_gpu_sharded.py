@@ -246,7 +246,7 @@ def test_bench_under_torchrun_with_one_forced_sharded_rank(mode, rendezvous):
     port = {("plain", "socket"): "29731", ("sharded_graph", "socket"): "29732", ("plain", "gloo"): "29733"}[(mode, rendezvous)]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", port, os.path.join(nb.ROOT, "bench.py"), "--gpus", "1",
-           "--steps", "4", "--warmup", "2", "--particles", "65536", "--extra-particles", "131072", "--rendezvous", rendezvous]
+           "--steps", "4", "--warmup", "2", "--particles", "65536", "--extra-particles", "131072", "--rendezvous", rendezvous, "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=nb.ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -316,7 +316,7 @@ def test_bench_with_two_real_ranks_on_one_gpu(transport):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29741" if transport == "host" else "29742", os.path.join(nb.ROOT, "bench.py"), "--gpus", "2",
-           "--transport", transport, "--steps", "4", "--warmup", "1", "--particles", "65536", "--extra-particles", "131072"]
+           "--transport", transport, "--steps", "4", "--warmup", "1", "--particles", "65536", "--extra-particles", "131072", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=nb.ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = r.stdout.splitlines()
@@ -358,7 +358,7 @@ def test_bench_line_survives_a_stuck_leg():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4", NB_BENCH_REHEARSE='{"stall_leg": "overlap"}')
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29743", os.path.join(nb.ROOT, "bench.py"), "--gpus", "2", "--transport", "host",
-           "--steps", "4", "--warmup", "1", "--particles", "65536", "--extra-particles", "131072", "--leg-deadline-s", "10"]
+           "--steps", "4", "--warmup", "1", "--particles", "65536", "--extra-particles", "131072", "--leg-deadline-s", "10", "--full"]
     t0 = time.time()
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=nb.ROOT)
     assert r.returncode != 0, "a run whose leg stalled must not report success"
@@ -380,7 +380,7 @@ def test_bench_line_survives_a_leg_that_aborts():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="4", NB_BENCH_REHEARSE='{"crash_leg": "config5"}')
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29745", os.path.join(nb.ROOT, "bench.py"), "--gpus", "2", "--transport", "host",
-           "--steps", "4", "--warmup", "1", "--particles", "65536", "--extra-particles", "131072"]
+           "--steps", "4", "--warmup", "1", "--particles", "65536", "--extra-particles", "131072", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=nb.ROOT)
     assert r.returncode != 0
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -39,7 +39,7 @@ def test_bench_multi_rank_control_flow_dry_run(world, rendezvous):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(29610 + world + (10 if rendezvous == "gloo" else 0)),
            os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--particles", "65536",
-           "--extra-particles", "131072", "--dry-run", "--rendezvous", rendezvous]
+           "--extra-particles", "131072", "--dry-run", "--rendezvous", rendezvous, "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -239,6 +239,74 @@ def test_bench_help_lists_no_rehearsal_flag_and_the_rehearsals_live_with_the_tes
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dry-run"], env=_clean_env(NB_BENCH_REHEARSE='{"typo": 1}'),
                        capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "unknown keys" in r.stderr
+
+
+def test_bench_plain_run_is_the_headline_and_full_brings_the_other_legs_back():
+    """A plain run does what its headline needs: no extra_configs (and, on one GPU, no CPU baseline, clock probe, parity
+    stamps, repeats or LDS-route leg); --full runs all of them as before.  Both options are on the help page."""
+    root = os.path.dirname(HERE)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    sys.path.insert(0, root)
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert plain.no_cpu_baseline and plain.no_clock_probe and plain.no_parity and plain.no_extras
+    full = bench.parse_args(["--full"])
+    assert not (full.no_cpu_baseline or full.no_clock_probe or full.no_parity or full.no_extras)
+    assert bench.parse_args(["--full", "--no-parity"]).no_parity                 # the --no-* options still subtract
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    lines = {}
+    for extra in ([], ["--full"]):
+        r = subprocess.run(_bench_cmd("bare", 2, 0)[:-1] + extra, env=_clean_env(), capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines[bool(extra)] = _one_json_line(r.stdout)
+    assert lines[False]["extra_configs"] == [] and len(lines[True]["extra_configs"]) == 5
+    for out in lines.values():
+        assert out["self_check"]["ranks_agree"] is True and out["steps"] == 2 and out["warmup"] == 1
+
+
+def test_bench_dump_outputs_writes_every_field_and_samples_above_the_limit(tmp_path):
+    """--dump-outputs: the Particle array as one float32 .npy per field; above the size limit the same fixed, seeded rows in
+    every file (their indices in rows.npy), identical from call to call, within the limit."""
+    root = os.path.dirname(HERE)
+    sys.path.insert(0, root)
+    import bench
+    part, m = ob.partition(np.fromfile(os.path.join(HERE, "golden", "ic_1024.bin"), dtype=np.float32).reshape(-1, 8))
+    bench.dump_outputs(str(tmp_path / "all"), part)
+    names = ["positions", "velocities", "accelerations", "masses", "radii"]
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in names}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(np.column_stack([got[n] for n in names]), part)
+    limit = 12096                                                   # bytes: 4 KiB of headers + 200 rows of 32 + 8 bytes
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), part, limit=limit)
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    assert rows.dtype == np.float64 and rows.size == 200 and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= limit
+    for n in names:
+        a, b = np.load(tmp_path / "s1" / (n + ".npy")), np.load(tmp_path / "s2" / (n + ".npy"))
+        assert a.tobytes() == b.tobytes() and np.array_equal(a, got[n][rows.astype(np.int64)])
+
+
+def test_supervisor_tail_keeps_a_ranks_last_words_under_faulthandler(tmp_path):
+    """A rank that dies by abort() with Python's faulthandler on (PYTHONFAULTHANDLER) prints a dump of every thread, with full
+    paths, after the library's message: the tail the supervisor keeps for the line must still hold the message."""
+    from nbody_amd import launch
+    script = tmp_path / "dies.py"
+    script.write_text("import ctypes, sys, threading, time\n"
+                      "threading.Thread(target=time.sleep, args=(30,), daemon=True).start()\n"
+                      "sys.stderr.write('pipeline.hip:155 [materialize] hipIpcGetMemHandle of the gathered array 0\\n')\n"
+                      "sys.stderr.flush()\n"
+                      "ctypes.CDLL(None).abort()\n")
+    p = launch.RankProcess(str(script), [], dict(os.environ, PYTHONFAULTHANDLER="1"), 0, True)
+    p.finish()
+    tail = "".join(p.tail)
+    assert p.status() == -6 and "hipIpcGetMemHandle" in tail[-900:]
+    assert tail.rstrip().endswith("Fatal Python error: Aborted") and "most recent call first" not in tail
 
 
 def test_bench_traffic_figure_is_tied_to_the_kernel_sources(tmp_path, monkeypatch):

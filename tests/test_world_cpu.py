@@ -96,9 +96,14 @@ def test_make_galaxies_survey_spot_values():
     assert int((a[:, 6] <= 0).sum()) == 2107
 
 
-@pytest.mark.skipif(not os.path.exists(ob.REF_CPU_SO), reason="oracle/_ref not built (no /root/reference here)")
 @pytest.mark.parametrize("n,g,seed", [(6000, 3, 1), (100, 1, 7), (50000, 5, 42), (1000, 10, 3), (250, 2, 11037)])
-def test_make_galaxies_bit_exact_with_compiled_reference(n, g, seed):
+def test_make_galaxies_bit_exact_with_compiled_reference(manifest, n, g, seed):
+    """Against the digests tests/golden/make_golden.py recorded from the compiled reference, and -- where oracle/_ref is
+    built -- against the compiled reference itself."""
+    got = nb.make_galaxies(n, g, seed=seed)
+    assert ob.sha256(got) == manifest["make_galaxies_digests"][f"{n}_{g}_{seed}"]
+    if not os.path.exists(ob.REF_CPU_SO):
+        return
     ref = C.CDLL(ob.REF_CPU_SO)
     ref.MakeGalaxies.restype = C.c_void_p
     ref.MakeGalaxies.argtypes = [C.c_uint32, C.c_uint32]
@@ -108,7 +113,7 @@ def test_make_galaxies_bit_exact_with_compiled_reference(n, g, seed):
     p = ref.MakeGalaxies(n, g)
     want = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n, 8)).copy()
     libc.free(p)
-    assert nb.make_galaxies(n, g, seed=seed).tobytes() == want.tobytes()
+    assert got.tobytes() == want.tobytes()
 
 
 @pytest.mark.parametrize("n", [4096, 1024, 333])

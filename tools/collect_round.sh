@@ -9,11 +9,11 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out
 cd $R
 python -m pytest tests -m gpu -q --timeout 900 --timeout-method=thread > $O/${TAG}_pytest_gpu.txt 2>&1; echo "pytest rc=$?"
-python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "bench rc=$?"
 NB_HIP_FORCE_SHARDED=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 \
-    bench.py --gpus 1 --steps 10 --warmup 2 > $O/${TAG}_rehearsal_1rank.json 2> $O/${TAG}_rehearsal_1rank.err; echo "rehearsal (socket rendezvous, /opt/rocm runtime) rc=$?"
+    bench.py --gpus 1 --full --steps 10 --warmup 2 > $O/${TAG}_rehearsal_1rank.json 2> $O/${TAG}_rehearsal_1rank.err; echo "rehearsal (socket rendezvous, /opt/rocm runtime) rc=$?"
 NB_HIP_FORCE_SHARDED=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29534 \
-    bench.py --gpus 1 --steps 10 --warmup 2 --rendezvous gloo > $O/${TAG}_rehearsal_1rank_gloo.json 2> $O/${TAG}_rehearsal_1rank_gloo.err; echo "rehearsal (gloo: torch's runtime first) rc=$?"
+    bench.py --gpus 1 --full --steps 10 --warmup 2 --rendezvous gloo > $O/${TAG}_rehearsal_1rank_gloo.json 2> $O/${TAG}_rehearsal_1rank_gloo.err; echo "rehearsal (gloo: torch's runtime first) rc=$?"
 {
   echo "== nbody_amd/lib/nbody-bench (reference harness defaults: srand(11037), 10 warm-up + 100 steps, dt = 1; us/step), MI355X box, OMP_NUM_THREADS=16 =="
   OMP_NUM_THREADS=16 ./nbody_amd/lib/nbody-bench
@@ -26,14 +26,14 @@ NB_HIP_FORCE_SHARDED=1 python -m torch.distributed.run --nnodes=1 --nproc-per-no
 } > $O/${TAG}_nbody_bench_tables.txt 2>&1; echo "tables rc=$?"
 python tools/fused_probe.py time 200 250 300 512 > $O/${TAG}_fused_chain.txt 2>&1; echo "fused rc=$?"
 for P in 2 3; do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node $P --master-addr 127.0.0.1 --master-port 2954$P bench.py --gpus $P \
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node $P --master-addr 127.0.0.1 --master-port 2954$P bench.py --gpus $P --full \
       --transport host --steps 10 --warmup 2 > $O/${TAG}_rehearsal_${P}ranks_host.json 2> $O/${TAG}_rehearsal_${P}ranks_host.err; echo "host-transport P=$P rc=$?"
 done
 # round 5: bench.py started BARE (no launcher): a GPU-free supervisor starts the rank processes itself; with both ranks on this
 # one GPU RCCL refuses the duplicate device, both ranks abort, and --transport auto answers with a fresh set of processes over
 # the direct exchange (the line carries transport_fallback); then three ranks over the direct exchange asked for outright
-python bench.py --gpus 2 --steps 10 --warmup 2 --extra-particles 262144 > $O/${TAG}_bare_2ranks_auto.json 2> $O/${TAG}_bare_2ranks_auto.err; echo "bare --gpus 2 (auto: rccl refused -> direct) rc=$?"
-python bench.py --gpus 3 --transport direct --steps 10 --warmup 2 --extra-particles 262144 > $O/${TAG}_bare_3ranks_direct.json 2> $O/${TAG}_bare_3ranks_direct.err; echo "bare --gpus 3 --transport direct rc=$?"
+python bench.py --gpus 2 --full --steps 10 --warmup 2 --extra-particles 262144 > $O/${TAG}_bare_2ranks_auto.json 2> $O/${TAG}_bare_2ranks_auto.err; echo "bare --gpus 2 (auto: rccl refused -> direct) rc=$?"
+python bench.py --gpus 3 --full --transport direct --steps 10 --warmup 2 --extra-particles 262144 > $O/${TAG}_bare_3ranks_direct.json 2> $O/${TAG}_bare_3ranks_direct.err; echo "bare --gpus 3 --transport direct rc=$?"
 # round 4: the C harness' own multi-process mode (ranks forked before any HIP call, shared page, no Python / torch)
 {
   echo "== nbody-bench --gpus 1 --force-sharded --n 20000 --n 1048576 --steps 10 --warmup 2 --dt 0.01: the RCCL path with one rank (ncclCommInitRank, in-place ncclAllGather per step, overlapped step, chain captured as a hipGraph) on /opt/rocm's HIP runtime + librccl =="

@@ -10,7 +10,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for v in 1 0; do
   export NB_HIP_VARIANT=$v
-  BENCH="python3 $R/bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1"
+  BENCH="python3 $R/bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/v${v}_stats -- $BENCH > $OUT/v${v}_stats.log 2>&1 || { echo "stats pass v=$v failed"; tail -5 $OUT/v${v}_stats.log; exit 1; }
   for pass in \
       "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_ACTIVE_INST_VALU" \

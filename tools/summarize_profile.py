@@ -30,7 +30,7 @@ lines = []
 stats = newest(os.path.join(PROF, "stats", "*", "*_kernel_stats.csv"))
 step_avg_ns = None
 if stats:
-    lines.append("== rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-extra-configs --steps 10 --warmup 2 ==")
+    lines.append("== rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-extra-configs --steps 10 --warmup 2 ==")
     for r in csv.DictReader(open(stats[0])):
         lines.append(f"{r['Name'][:90]:90s} calls={r['Calls']:>4s} avg_ns={float(r['AverageNs']):14.0f} total_ns={r['TotalDurationNs']:>14s} pct={float(r['Percentage']):7.3f}")
         if "step_kernel" in r["Name"] and step_avg_ns is None:   # rows are sorted by total time: the headline variant first

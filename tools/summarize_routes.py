@@ -52,7 +52,7 @@ def collect(v):
 
 k1, smem = collect(1)
 k0, lds = collect(0)
-lines = [f"== tools/profile_routes.sh: rocprofv3 --pmc passes of `bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1`,",
+lines = [f"== tools/profile_routes.sh: rocprofv3 --pmc passes of `bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1`,",
          f"   N = 2^20, per step-kernel launch (mean); quad-cycle counters (SQ_WAVE_CYCLES, SQ_WAIT_*, SQ_ACTIVE_INST_*) as reported ==",
          f"scalar-cache route: {k1}", f"LDS-tile route:     {k0}", "",
          f"{'counter':30s} {'scalar cache (1)':>18s} {'LDS tiles (0)':>18s} {'LDS / scalar':>14s}"]
