@@ -21,6 +21,7 @@
 
 #include <stdint.h>
 #include "nbody.h"
+#include "nbody_diag.h" /* WorldEnergy */
 
 #ifdef __cplusplus
 extern "C" {
@@ -312,6 +313,21 @@ NbShardPlan nb_hip_shard_plan(uint32_t total_len, uint32_t mass_len, int rank, i
  */
 int nb_hip_local_group_create(WorldData data, int nranks, SimPipeline **out);
 void nb_hip_local_group_step(SimPipeline **sims, int nranks, uint32_t n, float dt);
+
+/*
+ * Conservation diagnostics of the state the pipeline holds (definitions: include/nbody_diag.h).
+ *   nb_hip_energy     fills *out: the potential over the M massive receivers, kinetic energy, mass, momentum, angular
+ *                     momentum and centre of mass, all reduced in a fixed order in float64 (bitwise reproducible)
+ *   nb_hip_potential  writes total_len floats: Phi_i of every particle, massless ones included, in partitioned order
+ * Both are enqueued on the pipeline's stream behind any nb_hip_step_async work and read the buffer that holds the latest
+ * state (the one GetSimulationData merges from); they block until their own result is on the host.  They change nothing
+ * observable: the state, the ping-pong phase, the cached chains (nb_hip_graph_stats), the step-size uploads, what
+ * nb_hip_last_step_ms reports and the frame loop's eager read-back are as before the call.  Abort before the first
+ * SetSimulationData and for sharded pipelines (their remote slices are current only inside a step: a sharded energy
+ * needs a collective, not supported).
+ */
+void nb_hip_energy(SimPipeline *sim, WorldEnergy *out);
+void nb_hip_potential(SimPipeline *sim, float *phi);
 
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int nb_hip_version(void);

@@ -39,6 +39,18 @@ class WorldData(C.Structure):
     _fields_ = [("total_len", C.c_uint32), ("mass_len", C.c_uint32), ("dt", C.c_float)]
 
 
+class WorldEnergy(C.Structure):
+    """include/nbody_diag.h WorldEnergy (float64 sums over the massive particles)."""
+    _fields_ = [("kinetic", C.c_double), ("potential", C.c_double), ("mass", C.c_double), ("momentum", C.c_double * 2),
+                ("angular_momentum", C.c_double), ("center_of_mass", C.c_double * 2)]
+
+    def as_dict(self):
+        return {"kinetic": self.kinetic, "potential": self.potential, "total": self.kinetic + self.potential,
+                "mass": self.mass, "momentum": (self.momentum[0], self.momentum[1]),
+                "angular_momentum": self.angular_momentum,
+                "center_of_mass": (self.center_of_mass[0], self.center_of_mass[1])}
+
+
 class NbShardPlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mass_chunk", "zero_chunk", "mass_begin", "mass_count",
                                           "zero_begin", "zero_count", "src_padded")]
@@ -88,6 +100,8 @@ HIP_API = {
     "nb_hip_shard_plan": (NbShardPlan, [C.c_uint32, C.c_uint32, C.c_int, C.c_int]),
     "nb_hip_local_group_create": (C.c_int, [WorldData, C.c_int, C.POINTER(C.c_void_p)]),
     "nb_hip_local_group_step": (None, [C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_float]),
+    "nb_hip_energy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
+    "nb_hip_potential": (None, [C.c_void_p, C.c_void_p]),
     "nb_hip_version": (C.c_int, []),
 }
 
@@ -101,10 +115,11 @@ TUNE_API = {
     "nb_hip_plan_launch_unit": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int]),
     "nb_hip_plan_fused_finish": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int]),
     "nb_hip_plan_launch_lanes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
+    "nb_hip_last_diag_ms": (C.c_double, [C.c_void_p]),
 }
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
-# include/nbody.h + include/galaxy.h
+# include/nbody.h + include/galaxy.h + include/nbody_diag.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -117,6 +132,8 @@ NBODY_API = {
     "GetWorldPipeline": (C.c_void_p, [C.c_void_p]),
     "MakeGalaxies": (C.c_void_p, [C.c_uint32, C.c_uint32]),
     "MakeGalaxiesSeeded": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_uint64]),
+    "GetWorldEnergy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
+    "GetWorldPotential": (None, [C.c_void_p, C.c_void_p]),
 }
 
 _hip = None
@@ -358,6 +375,22 @@ class SimPipeline:
         cached = hip_lib().nb_hip_graph_stats(self._h, C.byref(uploads))
         return {"cached": int(cached), "dt_uploads": int(uploads.value)}
 
+    def energy(self):
+        """nb_hip_energy: kinetic / potential / total energy, mass, momentum, angular momentum, centre of mass (float64)."""
+        e = WorldEnergy()
+        hip_lib().nb_hip_energy(self._h, C.byref(e))
+        return e.as_dict()
+
+    def potential(self):
+        """nb_hip_potential: Phi_i of every particle (float32, partitioned order)."""
+        out = np.empty(self.total_len, dtype=np.float32)
+        hip_lib().nb_hip_potential(self._h, out.ctypes.data)
+        return out
+
+    def last_diag_ms(self):
+        """tuning hook: device ms of the kernels of the last energy() / potential()."""
+        return float(hip_lib().nb_hip_last_diag_ms(self._h))
+
     def fused_steps(self):
         """steps of the last update that ran inside one-workgroup chain launches (knob fused_chain)."""
         return int(hip_lib().nb_hip_last_fused_steps(self._h))
@@ -458,6 +491,18 @@ class World:
 
     def update_gpu(self, dt, n):
         nbody_lib().UpdateWorld_GPU(self._h, dt, n)
+
+    def energy(self):
+        """GetWorldEnergy (include/nbody_diag.h) as a dict; "total" = kinetic + potential."""
+        e = WorldEnergy()
+        nbody_lib().GetWorldEnergy(self._h, C.byref(e))
+        return e.as_dict()
+
+    def potential(self):
+        """GetWorldPotential: Phi_i of every particle (float32, in the order particles() returns them)."""
+        out = np.empty(self.size, dtype=np.float32)
+        nbody_lib().GetWorldPotential(self._h, out.ctypes.data)
+        return out
 
 
 _cpu_best = None

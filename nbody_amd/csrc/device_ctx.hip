@@ -8,7 +8,7 @@
 
 #include "pipeline_internal.h"
 
-#define NB_HIP_VERSION 301  // 0.3.1: + nb_hip_preflight_* / nb_hip_comm_bringup (multi-GPU bring-up diagnostics that report instead of aborting)
+#define NB_HIP_VERSION 400  // 0.4.0: + nb_hip_energy / nb_hip_potential (0.3.1: + nb_hip_preflight_* / nb_hip_comm_bringup)
 
 namespace nbi {
 

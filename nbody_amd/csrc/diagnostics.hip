@@ -1,0 +1,352 @@
+// diagnostics.hip -- energy, momentum and per-particle potential of the state a pipeline holds (include/nbody_diag.h).
+//
+// Definitions (also in include/nbody_diag.h and DESIGN.md section 3): particles in the World's partitioned order, M =
+// mass_len, G*m_j = src_gm[j] (what the step kernels use), softening = the RECEIVER's radius added to the squared
+// distance, not squared (reference sim_cpu.c:173-176):
+//     Phi_i = - sum_{j < M, j != i} G*m_j / sqrt(|x_j - x_i|^2 + r_i)        for every receiver i, massless ones included
+// The self term is excluded BY INDEX inside the loop (subtracting it afterwards would cancel most of the fp32 digits
+// of a galaxy core, where G*m_i / sqrt(r_i) is 10^3..10^4 x the rest of the sum).
+//
+// potential_kernel: one workgroup = W waves over the same 64 * K receivers (a tile), each wave walks a 1/W slice of the
+// sources in blocks of 256 -- the step kernel's scalar-cache route: wave-uniform sources arrive in SGPRs through
+// s_load_dwordx16 / x8.  Per (receiver, source) pair:
+//     v_sub_f32 dx, v_sub_f32 dy, v_fma_f32 q = dx*dx + r, v_fma(c)_f32 q += dy*dy, v_rsq_f32 t, v_fmac_f32 phi += G*m * t
+// = 5 plain VALU + 1 rsq (~18 cycles per wave-interaction against the step kernel's 26).  Only the one source block
+// that contains the tile's own indices takes the masked path (a v_cndmask per pair); every other block runs unmasked.
+// Sums: plain fp32 over each block of 256 sources, float64 across block totals and across the W waves (fixed order).
+// With `slab`, every workgroup also reduces its receivers' float64 terms (m_i Phi_i, m_i |v_i|^2, m_i, m_i v_i,
+// m_i (x_i v_y,i - y_i v_x,i), m_i x_i) in a fixed tree and stores them to slab[workgroup]; energy_reduce_kernel then
+// adds the slab in a fixed order.  No float atomics anywhere: results are bitwise reproducible from call to call.
+//
+// The C-ABI entry points nb_hip_energy / nb_hip_potential sit at the bottom of this file.
+#include "pipeline_internal.h"
+#include "diag_sums.h"
+#include "nbody_hip_tuning.h"
+
+namespace nbd {
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int K = 2;                // receivers per lane
+constexpr int W = 8;                // waves (source slices) per workgroup
+constexpr int TILE = WAVE * K;      // receivers per workgroup
+constexpr int BLOCK = 256;          // sources per plain fp32 block sum
+constexpr int QTY = NB_DIAG_SUMS;   // float64 quantities per workgroup in the energy slab (diag_sums.h)
+constexpr int REDUCE_THREADS = 256;
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef float v8f __attribute__((ext_vector_type(8)));
+typedef const float __attribute__((address_space(4))) *ConstF;  // read-only for the whole launch: scalar loads
+
+struct DiagParams {
+    const float2 *pos;     // pos[cur]: the latest state
+    const float2 *vel;
+    const float *radius;
+    const float *mass;
+    const float *src_gm;   // G * m_j, j < n_src
+    uint32_t n_recv;       // receivers [0, n_recv)
+    uint32_t n_src;        // sources [0, n_src) = [0, M)
+    float *phi;            // nullable: Phi_i, i < n_recv
+    double *slab;          // nullable: QTY doubles per workgroup
+};
+
+template <typename V>
+__device__ __forceinline__ V cload(ConstF p) {
+    return *(const V __attribute__((address_space(4))) *)p;
+}
+
+// One source (wave-uniform, SGPRs) against the K receivers of this lane, as one asm statement per pair (as in
+// kernels.hip, and for the same reasons: left to hipcc, the two receivers' FMAs become v_pk_fma_f32, which this project
+// measured slower beside a transcendental, and the schedule drifts with unrelated edits):
+//     v_sub_f32   dx  = sx - x
+//     v_sub_f32   dy  = sy - y
+//     v_fma_f32   q   = dx * dx + radius      softening: + radius of the RECEIVER, not squared
+//     v_fmac_f32  q  += dy * dy
+//     v_rsq_f32   q   = 1 / sqrt(q)          at raised wave priority, like the step kernels' rsq
+//     v_fmac_f32  phi += (G*m) * q           (the s_setprio 0 before it is the wait state a transcendental's reader needs)
+// MASK (the diagonal block only): source j may be receiver i itself; that term is dropped by a select AFTER the rsq
+// (r_i = 0 makes it inf, and 0 * inf is NaN), so the masked statement stops at the rsq.
+#define NB_PHI_HEAD_ASM                     \
+    "v_sub_f32 %[dx], %[sx], %[px]\n\t"     \
+    "v_sub_f32 %[dy], %[sy], %[py]\n\t"     \
+    "v_fma_f32 %[q], %[dx], %[dx], %[r]\n\t" \
+    "v_fmac_f32 %[q], %[dy], %[dy]\n\t"     \
+    "s_setprio 3\n\t"                      \
+    "v_rsq_f32 %[q], %[q]\n\t"              \
+    "s_setprio 0"
+template <bool MASK>
+__device__ __forceinline__ void pair(float (&a)[K], const float (&px)[K], const float (&py)[K], const float (&r)[K],
+                                     const uint32_t (&ri)[K], float sx, float sy, float g, uint32_t j) {
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        float dx, dy, q;
+        if constexpr (MASK) {
+            asm(NB_PHI_HEAD_ASM
+                : [dx] "=&v"(dx), [dy] "=&v"(dy), [q] "=&v"(q)
+                : [sx] "s"(sx), [sy] "s"(sy), [px] "v"(px[k]), [py] "v"(py[k]), [r] "v"(r[k]));
+            const float n = __builtin_fmaf(g, q, a[k]);
+            a[k] = j != ri[k] ? n : a[k];
+        } else {
+            asm(NB_PHI_HEAD_ASM "\n\t"
+                "v_fmac_f32 %[a], %[g], %[q]"
+                : [a] "+v"(a[k]), [dx] "=&v"(dx), [dy] "=&v"(dy), [q] "=&v"(q)
+                : [sx] "s"(sx), [sy] "s"(sy), [g] "s"(g), [px] "v"(px[k]), [py] "v"(py[k]), [r] "v"(r[k]));
+        }
+    }
+}
+
+template <bool MASK>
+__device__ __forceinline__ void group8(float (&a)[K], const float (&px)[K], const float (&py)[K], const float (&r)[K],
+                                       const uint32_t (&ri)[K], const v16f &P, const v8f &G, uint32_t j) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) pair<MASK>(a, px, py, r, ri, P[2 * u], P[2 * u + 1], G[u], j + u);
+}
+
+// Sources [j0, j1) of one block (j0 a multiple of 256) added to a[]: 8 per scalar fetch (s_load_dwordx16 for the
+// positions, s_load_dwordx8 for G*m), then single sources for a ragged end.  One register set, no double buffering: the
+// kernel needs ~70 % of the step kernel's issue cycles per pair, and eight waves per SIMD hide the fetch of the next set
+// (the step kernel's two alternating sets cost the SGPRs that this kernel's operands need: they spilled to VGPR lanes).
+template <bool MASK>
+__device__ __forceinline__ void block_sum(float (&a)[K], const float (&px)[K], const float (&py)[K], const float (&r)[K],
+                                          const uint32_t (&ri)[K], ConstF sp, ConstF sg, uint32_t j0, uint32_t j1) {
+    uint32_t j = j0;
+    for (; j + 8 <= j1; j += 8) {
+        const v16f P = cload<v16f>(sp + 2 * (size_t)j);
+        const v8f G = cload<v8f>(sg + j);
+        group8<MASK>(a, px, py, r, ri, P, G, j);
+    }
+    for (; j < j1; j++) pair<MASK>(a, px, py, r, ri, sp[2 * (size_t)j], sp[2 * (size_t)j + 1], sg[j], j);
+}
+
+// 512 threads, at most 64 VGPRs (8 waves per SIMD: four workgroups per CU).
+__global__ __launch_bounds__(WAVE * W, 8) void potential_kernel(const DiagParams p) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & (WAVE - 1);
+    const uint32_t wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t rb = blockIdx.x * TILE;  // first receiver of the tile
+
+    float px[K], py[K], r[K], a[K];
+    uint32_t ri[K];
+    double s[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        uint32_t i = rb + k * WAVE + lane;
+        i = i < p.n_recv ? i : p.n_recv - 1;  // tail lanes redo the last receiver; their results are dropped
+        const float2 q = p.pos[i];
+        px[k] = q.x;
+        py[k] = q.y;
+        r[k] = p.radius[i];
+        ri[k] = i;
+        a[k] = 0.0f;
+        s[k] = 0.0;
+    }
+
+    // this wave's slice of the sources, in whole blocks
+    const uint32_t nblocks = (p.n_src + BLOCK - 1) / BLOCK;
+    const uint32_t per_wave = (nblocks + W - 1) / W;
+    const uint32_t b_lo = min(wid * per_wave, nblocks);
+    const uint32_t b_hi = min(b_lo + per_wave, nblocks);
+    const ConstF sp = (ConstF)(uintptr_t)p.pos, sg = (ConstF)(uintptr_t)p.src_gm;
+    for (uint32_t b = b_lo; b < b_hi; b++) {
+        const uint32_t j0 = b * BLOCK, j1 = min(j0 + BLOCK, p.n_src);
+        if (j0 < rb + TILE && rb < j1)  // the tile's own indices: the one masked block
+            block_sum<true>(a, px, py, r, ri, sp, sg, j0, j1);
+        else
+            block_sum<false>(a, px, py, r, ri, sp, sg, j0, j1);
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            s[k] += (double)a[k];
+            a[k] = 0.0f;
+        }
+    }
+
+    // the W slices in wave order (float64), then Phi_i = -sum
+    __shared__ double part[W][TILE];
+#pragma unroll
+    for (int k = 0; k < K; k++) part[wid][k * WAVE + lane] = s[k];
+    __syncthreads();
+    double e[QTY];
+    if (tid < TILE) {
+        double sum = 0.0;
+#pragma unroll
+        for (int w = 0; w < W; w++) sum += part[w][tid];
+        const double phi = -sum;
+        const uint32_t i = rb + tid;
+        const bool live = i < p.n_recv;
+        if (live && p.phi) p.phi[i] = (float)phi;
+        if (p.slab) {
+            const uint32_t c = live ? i : 0u;
+            const double m = live ? (double)p.mass[c] : 0.0;
+            const float2 x = p.pos[c], v = p.vel[c];
+            const double vx = v.x, vy = v.y, xx = x.x, xy = x.y;
+            e[0] = live ? m * phi : 0.0;           // the 0 * inf of a dead lane must not reach the sum
+            e[1] = m * (vx * vx + vy * vy);
+            e[2] = m;
+            e[3] = m * vx;
+            e[4] = m * vy;
+            e[5] = m * (xx * vy - xy * vx);
+            e[6] = m * xx;
+            e[7] = m * xy;
+        }
+    }
+    if (!p.slab) return;
+    // fixed tree over the tile's receivers, one quantity per row of the reused LDS
+    __syncthreads();
+    double(*red)[TILE] = part;   // QTY == W rows of TILE
+    if (tid < TILE) {
+#pragma unroll
+        for (int q = 0; q < QTY; q++) red[q][tid] = e[q];
+    }
+    __syncthreads();
+    for (uint32_t half = TILE / 2; half > 0; half /= 2) {
+        if (tid < half) {
+#pragma unroll
+            for (int q = 0; q < QTY; q++) red[q][tid] = red[q][tid] + red[q][tid + half];
+        }
+        __syncthreads();
+    }
+    if (tid < QTY) p.slab[(size_t)blockIdx.x * QTY + tid] = red[tid][0];
+}
+static_assert(QTY == W, "the slab reduction reuses the wave-partial LDS rows");
+
+// One workgroup: out[q] = sum over the slab's rows of quantity q.  Thread t of quantity q = t / 32 adds rows
+// [l * chunk, (l + 1) * chunk), l = t % 32, in index order; the 32 partial sums meet in a fixed tree.
+__global__ __launch_bounds__(REDUCE_THREADS) void energy_reduce_kernel(const double *slab, uint32_t rows, double *out) {
+    constexpr uint32_t LANES = REDUCE_THREADS / QTY;
+    __shared__ double red[QTY][LANES];
+    const uint32_t q = threadIdx.x / LANES, l = threadIdx.x % LANES;
+    const uint32_t chunk = (rows + LANES - 1) / LANES;
+    const uint32_t lo = min(l * chunk, rows), hi = min(lo + chunk, rows);
+    double s = 0.0;
+    for (uint32_t row = lo; row < hi; row++) s += slab[(size_t)row * QTY + q];
+    red[q][l] = s;
+    __syncthreads();
+    for (uint32_t half = LANES / 2; half > 0; half /= 2) {
+        if (l < half) red[q][l] = red[q][l] + red[q][l + half];
+        __syncthreads();
+    }
+    if (l == 0) out[q] = red[q][0];
+}
+
+}  // namespace
+}  // namespace nbd
+
+namespace {
+
+using namespace nbi;
+using nbd::QTY;
+
+// The state the step kernels will read next: the sources of an unsharded pipeline are its first mass_len receivers.
+nbd::DiagParams diag_params(SimPipeline *s, uint32_t n_recv) {
+    nbd::DiagParams p{};
+    p.pos = s->pos[s->cur];
+    p.vel = s->vel;
+    p.radius = s->radius;
+    p.mass = s->mass;
+    p.src_gm = s->src_gm;
+    p.n_recv = n_recv;
+    p.n_src = s->data.mass_len;
+    return p;
+}
+
+void check_diag(SimPipeline *s, const char *what) {
+    NB_ASSERT(s != nullptr, "NULL pipeline");
+    NB_ASSERT(!s->sharded, "%s of a sharded pipeline needs a collective over the ranks: not supported", what);
+    NB_ASSERT(s->on_device, "%s before SetSimulationData", what);
+}
+
+void begin_diag(SimPipeline *s) {
+    use_device();
+    if (!s->ev_diag[0]) {
+        ASSERT_HIP(hipEventCreate(&s->ev_diag[0]), "event");
+        ASSERT_HIP(hipEventCreate(&s->ev_diag[1]), "event");
+    }
+    ASSERT_HIP(hipEventRecord(s->ev_diag[0], s->stream), "record diagnostics begin");
+}
+
+void end_diag(SimPipeline *s) {
+    ASSERT_HIP(hipEventRecord(s->ev_diag[1], s->stream), "record diagnostics end");
+    s->diag_timed = true;
+}
+
+// the pipeline's float64 scratch: QTY per workgroup + QTY results, grown on demand
+double *diag_scratch(SimPipeline *s, uint32_t rows) {
+    const size_t need = (size_t)(rows + 1) * QTY;
+    if (s->diag_cap < need) {
+        if (s->diag) {
+            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the diagnostics slab");
+            dev_free(s->diag);
+        }
+        s->diag = dev_alloc<double>(need);
+        s->diag_cap = need;
+    }
+    return s->diag;
+}
+
+}  // namespace
+
+extern "C" {
+
+void nb_hip_energy(SimPipeline *s, WorldEnergy *out) {
+    check_diag(s, "nb_hip_energy");
+    NB_ASSERT(out != nullptr, "NULL WorldEnergy");
+    const uint32_t M = s->data.mass_len;
+    double q[QTY] = {0};
+    if (M > 0) {
+        begin_diag(s);
+        const uint32_t rows = (M + nbd::TILE - 1) / nbd::TILE;
+        double *slab = diag_scratch(s, rows);
+        nbd::DiagParams p = diag_params(s, M);
+        p.slab = slab;
+        hipLaunchKernelGGL(nbd::potential_kernel, dim3(rows), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
+        ASSERT_HIP(hipGetLastError(), "potential_kernel launch (energy, %u receivers)", M);
+        double *res = slab + (size_t)rows * QTY;
+        hipLaunchKernelGGL(nbd::energy_reduce_kernel, dim3(1), dim3(nbd::REDUCE_THREADS), 0, s->stream, slab, rows, res);
+        ASSERT_HIP(hipGetLastError(), "energy_reduce_kernel launch");
+        end_diag(s);
+        ASSERT_HIP(hipMemcpyAsync(q, res, sizeof(q), hipMemcpyDeviceToHost, s->stream), "D2H of the energy sums");
+        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_energy");
+    } else {
+        s->diag_timed = false;
+    }
+    nb_energy_from_sums(q, out);
+}
+
+void nb_hip_potential(SimPipeline *s, float *phi) {
+    check_diag(s, "nb_hip_potential");
+    const uint32_t N = s->data.total_len;
+    NB_ASSERT(phi != nullptr || N == 0, "NULL phi");
+    if (N == 0) {
+        s->diag_timed = false;
+        return;
+    }
+    begin_diag(s);
+    if (s->diag_phi_cap < N) {
+        if (s->diag_phi) {
+            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the potential buffer");
+            dev_free(s->diag_phi);
+        }
+        s->diag_phi = dev_alloc<float>(N);
+        s->diag_phi_cap = N;
+    }
+    nbd::DiagParams p = diag_params(s, N);
+    p.phi = s->diag_phi;
+    hipLaunchKernelGGL(nbd::potential_kernel, dim3((N + nbd::TILE - 1) / nbd::TILE), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
+    ASSERT_HIP(hipGetLastError(), "potential_kernel launch (%u receivers)", N);
+    end_diag(s);
+    ASSERT_HIP(hipMemcpyAsync(phi, s->diag_phi, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u potentials", N);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_potential");
+}
+
+// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_energy / nb_hip_potential
+double nb_hip_last_diag_ms(SimPipeline *s) {
+    NB_ASSERT(s != nullptr, "NULL pipeline");
+    if (!s->diag_timed) return 0.0;
+    use_device();
+    ASSERT_HIP(hipEventSynchronize(s->ev_diag[1]), "diagnostics end event");
+    float ms = 0.0f;
+    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev_diag[0], s->ev_diag[1]), "diagnostics elapsed time");
+    return ms;
+}
+
+}  // extern "C"

@@ -64,6 +64,10 @@ int nb_hip_plan_launch_lanes(uint32_t n_recv, uint32_t n_src, int *w);
 int nb_hip_plan_fused_finish(uint32_t n_recv, uint32_t n_src, int compute_units);
 int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units);
 
+/* Device milliseconds of the kernels of the last nb_hip_energy / nb_hip_potential (their own event pair, not the step's);
+ * 0 before the first call. */
+double nb_hip_last_diag_ms(SimPipeline *sim);
+
 #ifdef __cplusplus
 }
 #endif

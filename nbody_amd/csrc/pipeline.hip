@@ -87,6 +87,17 @@ void release_device(SimPipeline *s) {
     dev_free(s->tickets);
     s->tickets = nullptr;
     s->tickets_len = 0;
+    dev_free(s->diag);
+    s->diag = nullptr;
+    s->diag_cap = 0;
+    dev_free(s->diag_phi);
+    s->diag_phi = nullptr;
+    s->diag_phi_cap = 0;
+    for (auto &e : s->ev_diag) {
+        if (e) ASSERT_HIP(hipEventDestroy(e), "event");
+        e = nullptr;
+    }
+    s->diag_timed = false;
     ASSERT_HIP(hipEventDestroy(s->ev_begin), "event");
     ASSERT_HIP(hipEventDestroy(s->ev_end), "event");
     ASSERT_HIP(hipEventDestroy(s->ev_local), "event");

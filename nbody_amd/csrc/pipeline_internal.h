@@ -6,6 +6,7 @@
 //   step_chain.hip   one step / n steps as launches, cached hipGraph chains, the sharded step with its all-gather
 //   pipeline.hip     SimPipeline life cycle and the C-ABI entry points (Create/Destroy/Set/Get/PerformSimUpdate, knobs)
 //   kernels.hip      the gfx950 kernels (kernels.h)
+//   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -279,6 +280,15 @@ struct SimPipeline {
     uint32_t fused_steps = 0;   // steps the last update ran inside fused (one-launch) chains
 
     std::vector<nbi::StepGraph> graphs;
+
+    // diagnostics.hip (nb_hip_energy / nb_hip_potential): scratch grown on demand, an event pair of their own (the step's
+    // ev_begin / ev_end keep bracketing the last step)
+    double *diag = nullptr;      // float64 slab: NB_DIAG_SUMS per workgroup + the NB_DIAG_SUMS results
+    size_t diag_cap = 0;         // doubles allocated in diag
+    float *diag_phi = nullptr;   // nb_hip_potential's device result
+    uint32_t diag_phi_cap = 0;
+    hipEvent_t ev_diag[2] = {nullptr, nullptr};
+    bool diag_timed = false;
 };
 
 namespace nbi {

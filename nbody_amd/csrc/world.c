@@ -15,12 +15,17 @@
  * Differences: the GPU side is created lazily (no device is touched by a World
  * that only ever steps on the CPU), and DestroyWorld frees the particle array
  * (the reference leaks it, world.c:67-73).
+ * Extension (include/nbody_diag.h): GetWorldEnergy / GetWorldPotential compute
+ * on the device when it holds the newest state, without pulling the array, and
+ * on the host (diag_cpu.c) otherwise; neither moves a dirty flag.
  */
 #include "nbody.h"
+#include "nbody_diag.h"
 #include "nbody_hip.h"
 
 #include <stdbool.h>
 
+#include "diag_sums.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
 
@@ -32,6 +37,7 @@ struct World {
     CpuSim *cpu;          /* host-core stepper */
     bool host_is_newer;   /* array changed since the device last saw it */
     bool device_is_newer; /* device stepped since the array was last refreshed */
+    int nranks;           /* > 1: sharded (the pipeline holds 1/nranks of the receivers) */
 };
 
 /*
@@ -78,6 +84,7 @@ static World *create_world(const Particle *ps, uint32_t size, int rank, int nran
     w->cpu = CpuSimCreate(w->massive);
     w->host_is_newer = true;    /* the device has seen nothing yet */
     w->device_is_newer = false;
+    w->nranks = rank < 0 ? 1 : nranks;
     return w;
 }
 
@@ -146,4 +153,27 @@ void UpdateWorld_GPU(World *w, float dt, uint32_t n) {
     push_if_stale(w);
     PerformSimUpdate(w->gpu, n, dt);
     w->device_is_newer = true;
+}
+
+/* The device holds the newest state whenever the array has not changed since it was last pushed (the device may have
+ * stepped further).  A World that never stepped on the GPU keeps host_is_newer and never reaches the device here. */
+static bool diag_on_device(World *w, const char *what) {
+    NB_CHECK(w->nranks <= 1, "%s of a sharded pipeline needs a collective over the ranks: not supported", what);
+    return !w->host_is_newer;
+}
+
+void GetWorldEnergy(World *w, WorldEnergy *out) {
+    NB_CHECK(w != NULL && out != NULL, "NULL argument");
+    if (diag_on_device(w, "GetWorldEnergy"))
+        nb_hip_energy(w->gpu, out);
+    else
+        nb_cpu_energy(w->particles, w->count, w->massive, out);
+}
+
+void GetWorldPotential(World *w, float *phi) {
+    NB_CHECK(w != NULL && (phi != NULL || w->count == 0), "NULL argument");
+    if (diag_on_device(w, "GetWorldPotential"))
+        nb_hip_potential(w->gpu, phi);
+    else
+        nb_cpu_potential(w->particles, w->count, w->massive, phi);
 }
