@@ -82,21 +82,28 @@ struct ChainParams {
 
 constexpr uint32_t CHAIN_MAX_RECV = 512;   // 4 tiles of 128 receivers (K = 2)
 
+// A launch shape; 0 = "auto" in a request to choose_shape.  Write one with named fields ({.k = 2, .w = 16}): the
+// defaults are the all-auto request.
 struct LaunchShape {
-    int k;        // receivers per lane: 1, 2 (4 in tuning builds)
-    int w;        // waves per workgroup = source slices: 1, 4, 8, 16 (2 in tuning builds)
-    int variant;  // VARIANT_*
-    int split;    // workgroups per receiver tile (source parts): 1 .. MAX_SPLIT
-    int unit;     // sources per slice granule: 64 (default), 32, 16, 8
+    int k = 0;                    // receivers per lane: 1, 2 (4 in tuning builds)
+    int w = 0;                    // waves per workgroup = source slices: 1, 4, 8, 16 (2 in tuning builds)
+    int variant = VARIANT_SMEM;   // VARIANT_*
+    int split = 0;                // workgroups per receiver tile (source parts): 1 .. MAX_SPLIT
+    int unit = 0;                 // sources per slice granule: 64 (default), 32, 16, 8
     // lane groups per wave (0 / 1: a wave's 64 lanes are 64 * k receivers).  2 or 4: the lanes of a wave split into that
     // many groups over the SAME 64 / lanes receivers, each group walking its own slice of the sources (lane_split_kernel):
     // w * lanes source slices per receiver inside ONE workgroup -- the parallelism a source split buys, without its
     // second kernel.  Latency-bound launches only (k = 1, split = 1, sources staged once in LDS).
-    int lanes;
-    // experiment ("persist" hook): > 1 = the launch has 1/persist as many workgroups as (tile, part) work items and every
-    // workgroup walks `persist` of them (scalar-cache route, classic kernel only); 0 / 1 = one workgroup per item
-    int persist;
+    int lanes = 0;
 };
+
+inline bool operator==(const LaunchShape &a, const LaunchShape &b) {
+    return a.k == b.k && a.w == b.w && a.variant == b.variant && a.split == b.split && a.unit == b.unit && a.lanes == b.lanes;
+}
+
+// Every field of a request left to choose_shape: only then may it pick the lane-split kernel, and the pipeline the
+// one-workgroup chain (an explicit shape or LDS-tile route asks for the classic per-step kernel).
+inline bool shape_on_auto(const LaunchShape &want) { return want == LaunchShape{}; }
 
 constexpr uint32_t LANE_SPLIT_MAX_SRC = 1u << 18;   // sources a lane-split launch walks (one launch = one source pass)
 

@@ -168,30 +168,13 @@ __device__ __forceinline__ void interact8(Receivers<K> &R, const VP &P, const VG
 NB_INTERACT8_OVERRIDE
 #endif
 
-// Source arrays as the scalar-cache route reads them.  A wave-uniform load becomes a scalar load (s_load_dwordx8/x16) only
-// while the compiler can prove that nothing in the kernel has written the memory before it: true by construction in the
-// classic launch (all stores sit in the epilogue), not in a persistent one, where the epilogue of work item i precedes the
-// loads of item i + 1.  The sources ARE read-only for the whole launch (a step reads src_pos[in] and writes pos[in ^ 1] /
-// src_pos[in ^ 1]), which is what the constant address space says: persistent launches read them through it.
-typedef const float __attribute__((address_space(4))) *ConstF;
+// A wave-uniform load from the source arrays becomes a scalar load (s_load_dwordx8/x16) only while the compiler can prove
+// that nothing in the kernel has written memory before it: true by construction, since every store of the step kernel
+// sits in its epilogue, after the last source load.
 template <typename V>
 __device__ __forceinline__ V src_load(const float *ptr) {
     return *reinterpret_cast<const V *>(ptr);
 }
-template <typename V>
-__device__ __forceinline__ V src_load(ConstF ptr) {
-    return *(const V __attribute__((address_space(4))) *)ptr;
-}
-template <bool READ_ONLY_AS>
-struct SrcPtr {
-    typedef const float *type;
-    static __device__ __forceinline__ type of(const void *ptr) { return static_cast<const float *>(ptr); }
-};
-template <>
-struct SrcPtr<true> {
-    typedef ConstF type;
-    static __device__ __forceinline__ type of(const void *ptr) { return (ConstF)(uintptr_t)ptr; }
-};
 
 // Slot of logical receiver i (see StepParams::recv_split).
 __device__ __forceinline__ uint32_t receiver_slot(const StepParams &p, uint32_t i) {
@@ -203,28 +186,90 @@ __device__ __forceinline__ uint32_t source_index(const StepParams &p, uint32_t v
     return v < n0 ? p.src_begin[0] + v : p.src_begin[1] + (v - n0);
 }
 
-// Epilogue of one receiver: optional carried-in sum, store acc, then the reference's integrator.
+// ---- one copy of each rule the launch paths must agree on bit for bit --------------------------------------------------
+// The helpers take values their callers have already loaded: where and when each load is issued is a measured choice of
+// the call site (finish_kernel's all-at-once part loads, lane_split_kernel's early velocity fetch).
+
+__device__ __forceinline__ float2 add_rn(float2 a, float2 b) { return make_float2(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y)); }
+
+// semi-implicit Euler with the reference's roundings (mul, then add; sim_cpu.c:191-193 / particle_cs.glsl:51-52):
+// vel += acc*dt; pos += vel*dt
+__device__ __forceinline__ void integrate(float2 a, float dt, float2 &v, float2 &q) {
+    v.x = __fadd_rn(v.x, __fmul_rn(a.x, dt));
+    v.y = __fadd_rn(v.y, __fmul_rn(a.y, dt));
+    q.x = __fadd_rn(q.x, __fmul_rn(v.x, dt));
+    q.y = __fadd_rn(q.y, __fmul_rn(v.y, dt));
+}
+
+// the new velocity and position of receiver slot i (and the position's copy in the next gathered source array)
+__device__ __forceinline__ void store_moved(const StepParams &p, uint32_t i, float2 v, float2 q) {
+    p.vel[i] = v;
+    p.pos_out[i] = q;
+    if (i < p.n_mirror) p.mirror[i] = q;
+}
+
+// Receiver slot i with its sum `a` and its old acc / vel / pos (a0, v, q) in registers: carry in, store acc, integrate.
+__device__ __forceinline__ void finish_loaded(const StepParams &p, uint32_t i, float2 a, float2 a0, float2 v, float2 q, float dt) {
+    if (p.flags & STEP_ACC_IN) a = add_rn(a0, a);
+    p.acc[i] = a;
+    if (p.flags & STEP_NO_FINALIZE) return;
+    integrate(a, dt, v, q);
+    store_moved(p, i, v, q);
+}
+
+// One term of the part-order sum of a split step, 0 + p0 + p1 + ... with the roundings of a sequential loop.  Callers load
+// all MAX_SPLIT parts before the first add (unused slots re-read the last part) and pass live = s < split: the unused
+// ones are dropped by a select, not a branch.  Per term, with the sum in two floats: a helper that took the whole array
+// and returned a float2 let the compiler wait for the first part before issuing the loads of the others.
+__device__ __forceinline__ void add_part(float &sx, float &sy, float2 part, bool live) {
+    const float nx = __fadd_rn(sx, part.x), ny = __fadd_rn(sy, part.y);
+    sx = live ? nx : sx;
+    sy = live ? ny : sy;
+}
+
+// The partial sums of n source slices of one receiver, in slice (= wave) order: first[0], first[stride], ...
+__device__ __forceinline__ float2 wave_sum(const float2 *first, uint32_t stride, uint32_t n) {
+    float sx = 0.0f, sy = 0.0f;
+    for (uint32_t s = 0; s < n; s++) {
+        const float2 t = first[s * stride];
+        sx = __fadd_rn(sx, t.x);
+        sy = __fadd_rn(sy, t.y);
+    }
+    return make_float2(sx, sy);
+}
+
+// The source slice [lo, hi) of one wave (or lane group): the `total` sources, in whole granules of `unit` sources, are cut
+// into `parts` parts (the source split of a step; 1 elsewhere), and part `part` into n slices, of which this is slice i.
+// The last granule may be ragged and trailing slices are empty (hi == lo, also past a ragged last granule: 7 granules
+// of 8 over 16 slices, 50 sources, start slice 7 at 56).  Every launch path slices with this, which is what makes their
+// summation orders agree.
+struct SourceSlice {
+    uint32_t lo, hi;
+};
+__device__ __forceinline__ SourceSlice source_slice(uint32_t total, uint32_t unit, uint32_t parts, uint32_t part, uint32_t n,
+                                                    uint32_t i) {
+    const uint32_t nunits = (total + unit - 1) / unit;
+    const uint32_t per_part = (nunits + parts - 1) / parts;
+    const uint32_t part_lo = min(part * per_part, nunits);
+    const uint32_t part_hi = min(part_lo + per_part, nunits);
+    const uint32_t per = (part_hi - part_lo + n - 1) / n;
+    const uint32_t u_lo = min(part_lo + i * per, part_hi);
+    const uint32_t u_hi = min(u_lo + per, part_hi);
+    const uint32_t lo = u_lo * unit;
+    return {lo, max(min(u_hi * unit, total), lo)};
+}
+
+// Epilogue of one receiver of an unsplit launch: acc is loaded only to carry it in, vel / pos only to integrate.
 __device__ __forceinline__ void finish_receiver(const StepParams &p, uint32_t logical, float sx, float sy, float dt) {
     if (logical >= p.n_recv) return;
     const uint32_t i = receiver_slot(p, logical);
     float2 a = make_float2(sx, sy);
-    if (p.flags & STEP_ACC_IN) {
-        const float2 a0 = p.acc[i];
-        a.x = __fadd_rn(a0.x, a.x);
-        a.y = __fadd_rn(a0.y, a.y);
-    }
+    if (p.flags & STEP_ACC_IN) a = add_rn(p.acc[i], a);
     p.acc[i] = a;
     if (p.flags & STEP_NO_FINALIZE) return;
-    // semi-implicit Euler with the reference's roundings: vel += acc*dt; pos += vel*dt
-    float2 v = p.vel[i];
-    v.x = __fadd_rn(v.x, __fmul_rn(a.x, dt));
-    v.y = __fadd_rn(v.y, __fmul_rn(a.y, dt));
-    float2 q = p.pos_in[i];
-    q.x = __fadd_rn(q.x, __fmul_rn(v.x, dt));
-    q.y = __fadd_rn(q.y, __fmul_rn(v.y, dt));
-    p.vel[i] = v;
-    p.pos_out[i] = q;
-    if (i < p.n_mirror) p.mirror[i] = q;
+    float2 v = p.vel[i], q = p.pos_in[i];
+    integrate(a, dt, v, q);
+    store_moved(p, i, v, q);
 }
 
 // Second kernel of a split step: one thread per receiver adds the parts in part order and finishes.
@@ -242,7 +287,6 @@ __global__ __launch_bounds__(256) void finish_kernel(const StepParams p) {
 #pragma unroll
     for (uint32_t s = 0; s < (uint32_t)MAX_SPLIT; s++)
         part[s] = p.parts[(size_t)(s < p.split ? s : p.split - 1) * p.n_recv + logical];
-    const bool carry = (p.flags & STEP_ACC_IN) != 0, integrate = (p.flags & STEP_NO_FINALIZE) == 0;
     // clamped-to-valid addresses again: acc / vel / pos_in exist for every slot whatever the flags say
     const float2 a0 = p.acc[i];
     const float2 v0 = p.vel[i];
@@ -250,28 +294,8 @@ __global__ __launch_bounds__(256) void finish_kernel(const StepParams p) {
     const float dt = *p.dt;
     float sx = 0.0f, sy = 0.0f;
 #pragma unroll
-    for (uint32_t s = 0; s < (uint32_t)MAX_SPLIT; s++) {
-        // same order and roundings as a sequential loop over the parts: 0 + p0 + p1 + ...
-        const float nx = __fadd_rn(sx, part[s].x), ny = __fadd_rn(sy, part[s].y);
-        sx = s < p.split ? nx : sx;
-        sy = s < p.split ? ny : sy;
-    }
-    float2 a = make_float2(sx, sy);
-    if (carry) {
-        a.x = __fadd_rn(a0.x, a.x);
-        a.y = __fadd_rn(a0.y, a.y);
-    }
-    p.acc[i] = a;
-    if (!integrate) return;
-    // semi-implicit Euler with the reference's roundings (finish_receiver): vel += acc*dt; pos += vel*dt
-    float2 v = v0, q = q0;
-    v.x = __fadd_rn(v.x, __fmul_rn(a.x, dt));
-    v.y = __fadd_rn(v.y, __fmul_rn(a.y, dt));
-    q.x = __fadd_rn(q.x, __fmul_rn(v.x, dt));
-    q.y = __fadd_rn(q.y, __fmul_rn(v.y, dt));
-    p.vel[i] = v;
-    p.pos_out[i] = q;
-    if (i < p.n_mirror) p.mirror[i] = q;
+    for (uint32_t s = 0; s < (uint32_t)MAX_SPLIT; s++) add_part(sx, sy, part[s], s < p.split);
+    finish_loaded(p, i, make_float2(sx, sy), a0, v0, q0, dt);
 }
 
 // Everything must stay within 64 VGPRs: a 1024-thread workgroup puts 4 waves on every SIMD, so 65 VGPRs (7 waves
@@ -279,24 +303,14 @@ __global__ __launch_bounds__(256) void finish_kernel(const StepParams p) {
 // the second launch-bound argument (waves per SIMD) makes the limit explicit.  K = 4 then keeps its Kahan state in
 // scratch, touched only at block closes outside the inner loop, and runs as fast as K = 2.
 //
-// PERSIST (experiment, tuning hook "persist"): the launch has FEWER workgroups than (receiver tile, source part) work items
-// and every workgroup walks items blockIdx.x, blockIdx.x + gridDim.x, ... -- fewer, longer-lived waves, so that dispatch
-// ramp and end-of-kernel write-back are paid by fewer workgroups.  Same bits as the classic launch: an
-// item is computed by exactly the code a classic workgroup (tile, part) runs.
-template <int K, int W, int VARIANT, bool FUSED = false, bool PERSIST = false>
+// A workgroup computes receiver tile blockIdx.x against source part blockIdx.y.
+template <int K, int W, int VARIANT, bool FUSED = false>
 __global__ __launch_bounds__(WAVE *W, 8) void step_kernel(const StepParams p) {
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & (WAVE - 1);
     // wave id as an SGPR value so that everything derived from it stays scalar
     const uint32_t wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // the work item of this workgroup: receiver tile and source part (classic launch: the grid coordinates)
-    uint32_t tile_x = blockIdx.x, part_y = blockIdx.y;
-    [[maybe_unused]] uint32_t item = blockIdx.x;
-    [[maybe_unused]] const uint32_t n_tiles = (p.n_recv + WAVE * K - 1) / (WAVE * K);
-    if constexpr (PERSIST) {
-        tile_x = item % n_tiles;
-        part_y = item / n_tiles;
-    }
+    const uint32_t tile_x = blockIdx.x, part_y = blockIdx.y;
 
     // per wave, double-buffered: 64 interleaved (x, y) pairs, then 64 G*m
     __shared__ __attribute__((aligned(16))) float tile[VARIANT == VARIANT_LDS ? W : 1][2][3 * CHUNK];
@@ -307,248 +321,203 @@ __global__ __launch_bounds__(WAVE *W, 8) void step_kernel(const StepParams p) {
     // profiles/r02_ab_early_fetch.txt.)
     const float dt = *p.dt;
 
-#pragma clang loop unroll(disable)
-    for (;;) {
-        const uint32_t recv_base = tile_x * (WAVE * K);
-        Receivers<K> R;
+    const uint32_t recv_base = tile_x * (WAVE * K);
+    Receivers<K> R;
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-            uint32_t i = recv_base + k * WAVE + lane;
-            i = i < p.n_recv ? i : p.n_recv - 1;  // tail lanes redo the last receiver; their stores are masked
-            i = receiver_slot(p, i);
-            const float2 q = p.pos_in[i];
-            R.p[k] = f2v{q.x, q.y};
-            R.r[k] = p.radius[i];
-        }
-        R.clear();
+    for (int k = 0; k < K; k++) {
+        uint32_t i = recv_base + k * WAVE + lane;
+        i = i < p.n_recv ? i : p.n_recv - 1;  // tail lanes redo the last receiver; their stores are masked
+        i = receiver_slot(p, i);
+        const float2 q = p.pos_in[i];
+        R.p[k] = f2v{q.x, q.y};
+        R.r[k] = p.radius[i];
+    }
+    R.clear();
 
-        // this wave's slice of the concatenated source ranges, in whole chunks
-        const uint32_t n0 = p.src_end[0] - p.src_begin[0];
-        const uint32_t n1 = p.src_end[1] - p.src_begin[1];
-        const uint32_t total = n0 + n1;
-        // this workgroup's part of the sources (all of them unless the step is split), then this wave's slice of it, both
-        // in whole granules of p.unit sources (64 = one tile; finer for latency-bound launches, see StepParams::unit)
-        const uint32_t unit = p.unit;
-        const uint32_t nunits = (total + unit - 1) / unit;
-        const uint32_t per_part = (nunits + p.split - 1) / p.split;
-        const uint32_t part_lo = min(part_y * per_part, nunits);
-        const uint32_t part_hi = min(part_lo + per_part, nunits);
-        const uint32_t per_wave = (part_hi - part_lo + W - 1) / W;
-        const uint32_t u_lo = min(part_lo + wid * per_wave, part_hi);
-        const uint32_t u_hi = min(u_lo + per_wave, part_hi);
-        const uint32_t v_lo = u_lo * unit;                // first source of the slice: a multiple of 8
-        const uint32_t v_hi = min(u_hi * unit, total);    // one past its last source
+    // the concatenated source ranges
+    const uint32_t n0 = p.src_end[0] - p.src_begin[0];
+    const uint32_t n1 = p.src_end[1] - p.src_begin[1];
+    const uint32_t total = n0 + n1;
+    // this workgroup's part of the sources (all of them unless the step is split), then this wave's slice of it, both
+    // in whole granules of p.unit sources (64 = one tile; finer for latency-bound launches, see StepParams::unit)
+    const SourceSlice wave_src = source_slice(total, p.unit, p.split, part_y, W, wid);
+    const uint32_t v_lo = wave_src.lo;   // first source of the slice: a multiple of 8
+    const uint32_t v_hi = wave_src.hi;   // one past its last source
 
-        if constexpr (VARIANT == VARIANT_LDS) {
-            float(*T)[3 * CHUNK] = tile[wid];
-            float2 sp = make_float2(0.f, 0.f);
-            float sg = 0.f;
-            auto fetch = [&](uint32_t c) {
-                const uint32_t v = c * CHUNK + lane;
-                const bool live = v < total;
-                const uint32_t j = source_index(p, live ? v : total - 1, n0);
-                sp = p.src_pos[j];                 // 512 B per wave, coalesced
-                sg = live ? p.src_gm[j] : 0.0f;    // pad sources: a real position, zero mass
-            };
-            // whole 64-source tiles only: this route always runs with the 64-source granule (choose_shape), so the slice
-            // is [c_lo, c_hi) tiles and the last one may be ragged (pads: a real position, zero mass)
-            const uint32_t c_lo = v_lo / CHUNK, c_hi = (v_hi + CHUNK - 1) / CHUNK;
-            if (c_lo < c_hi) fetch(c_lo);
-            int buf = 0;
-            for (uint32_t c = c_lo; c < c_hi; c++) {
-                *reinterpret_cast<float2 *>(&T[buf][2 * lane]) = sp;  // ds_write_b64
-                T[buf][2 * CHUNK + lane] = sg;
-                if (c + 1 < c_hi) fetch(c + 1);  // next tile's HBM/L2 latency hides under this tile's math
-                // LDS executes one wave's accesses in order; this only stops the compiler from reordering
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                for (int jj = 0; jj < CHUNK; jj += 4) {
-                    // broadcast ds_read_b128: every lane reads the same 16 bytes.  Four sources per read group (two reads
-                    // of positions, one of G*m): 12 staging VGPRs instead of 24, which is what leaves room for the
-                    // paired-rsq body with two receivers per lane
-                    const v8f P = *reinterpret_cast<const v8f *>(&T[buf][2 * jj]);
-                    const v4f G = *reinterpret_cast<const v4f *>(&T[buf][2 * CHUNK + jj]);
-#pragma unroll
-                    for (int u = 0; u < 4; u++) interact<K, false>(R, f2v{P[2 * u], P[2 * u + 1]}, G[u]);
-                }
-                if (((c - c_lo) & (CLOSE_EVERY - 1)) == CLOSE_EVERY - 1) R.close_chunk();
-                buf ^= 1;
-            }
-            if ((c_hi - c_lo) & (CLOSE_EVERY - 1)) R.close_chunk();  // a short last block
-        } else {
-            // scalar-cache route: indices are wave-uniform, the loads become s_load_dwordx8/x16
-#pragma unroll
-            for (int range = 0; range < 2; range++) {
-                // intersection of [v_lo, v_hi) with this range, as indices of the source arrays
-                const uint32_t r_lo = range == 0 ? 0u : n0;
-                const uint32_t r_hi = range == 0 ? n0 : total;
-                const uint32_t a = max(v_lo, r_lo), b = min(v_hi, r_hi);
-                if (a >= b) continue;
-                uint32_t j = p.src_begin[range] + (a - r_lo);
-                const uint32_t j_end = p.src_begin[range] + (b - r_lo);
-                // 8 sources per scalar fetch: s_load_dwordx16 (x,y pairs) + s_load_dwordx8 (G*m).  Slices start on
-                // multiples of 64 sources from 64-aligned range starts, so j is a multiple of 8 here.
-                const typename SrcPtr<PERSIST>::type sp = SrcPtr<PERSIST>::of(p.src_pos), sg = SrcPtr<PERSIST>::of(p.src_gm);
-                // every 8 * CLOSE_EVERY groups (256 sources) the block sums are closed, exactly where the LDS variant
-                // closes them, so both variants add in the same order; a short last block may end in single sources
-                const uint32_t groups = (j_end - j) / 8;
-                const uint32_t g0 = (a - v_lo) / 8;  // groups of this slice that lie in the previous range
-                if (groups > 0) {
-                    // Two register sets, A and B, each fetched while the other one is being consumed (the scalar
-                    // cache's latency hides under 8 * K interactions) and each dead before its refill is issued, so
-                    // no set is ever copied.  g0 is even (range starts are 64-aligned) and a block ends on an odd
-                    // group index, so only the second group of a pair can close one.  The refill address is clamped to
-                    // the last group instead of branching around the load.
-                    const uint32_t j_last = j + (groups - 1) * 8;
-                    v16f PA = src_load<v16f>(sp + 2 * (size_t)j);
-                    v8f GA = src_load<v8f>(sg + j);
-                    uint32_t g = 0;
-                    while (g + 2 <= groups) {
-                        // pairs up to the end of the current 32-group block, as one branch-free inner loop
-                        const uint32_t to_close = (8u * CLOSE_EVERY - ((g0 + g) & (8u * CLOSE_EVERY - 1))) / 2;
-                        const uint32_t pairs = min(to_close, (groups - g) / 2);
-                        for (uint32_t i = 0; i < pairs; i++) {
-                            // Scalar loads return out of order, so the only wait there is is "all of them"
-                            // (lgkmcnt(0)).  The empty asm makes the next fetch's address depend on the set about to
-                            // be consumed: the wait lands BEFORE that fetch is issued, where nothing is in flight but
-                            // loads that had a whole group's math to land.  (Not volatile: a volatile asm counts as a
-                            // memory clobber and would turn the scalar loads into vector loads.)  The scheduling
-                            // barriers keep each fetch ahead of the math that hides it.
-                            asm("" : "+s"(j) : "s"(PA), "s"(GA));
-                            const v16f PB = src_load<v16f>(sp + 2 * (size_t)(j + 8));
-                            const v8f GB = src_load<v8f>(sg + j + 8);
-                            __builtin_amdgcn_sched_barrier(0);
-                            interact8<K, true>(R, PA, GA);
-                            __builtin_amdgcn_sched_barrier(0);
-                            j = min(j + 16, j_last);
-                            asm("" : "+s"(j) : "s"(PB), "s"(GB));
-                            PA = src_load<v16f>(sp + 2 * (size_t)j);
-                            GA = src_load<v8f>(sg + j);
-                            __builtin_amdgcn_sched_barrier(0);
-                            interact8<K, true>(R, PB, GB);
-                        }
-                        g += 2 * pairs;
-                        if (pairs == to_close) R.close_chunk();
-                    }
-                    if (g < groups) interact8<K, true>(R, PA, GA);  // odd count: the last refill fetched it
-                    j = j_last + 8;
-                }
-                for (; j < j_end; j++) interact<K, true>(R, f2v{sp[2 * (size_t)j], sp[2 * (size_t)j + 1]}, sg[j]);
-            }
-            // a short last block: anything after the last multiple of 256 sources of this slice (same blocks as the
-            // LDS variant, whose last tile may be padded)
-            if ((v_hi - v_lo) & (CHUNK * CLOSE_EVERY - 1)) R.close_chunk();
-        }
-
-        // ---- combine the W slices in wave order, integrate, store -------------------------------------------
-        auto finish = [&](uint32_t logical, float sx, float sy) {
-            if (p.split > 1) {
-                if (logical < p.n_recv) {
-                    float2 *slot = &p.parts[(size_t)part_y * p.n_recv + logical];
-                    if constexpr (FUSED) {
-                        // agent-scope relaxed store (one 8-byte access): written through to the point every XCD's loads of the
-                        // same scope read
-                        const uint64_t bits = (uint64_t)__float_as_uint(sx) | ((uint64_t)__float_as_uint(sy) << 32);
-                        __hip_atomic_store(reinterpret_cast<uint64_t *>(slot), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    } else {
-                        *slot = make_float2(sx, sy);
-                    }
-                }
-            } else {
-                finish_receiver(p, logical, sx, sy, dt);
-            }
+    if constexpr (VARIANT == VARIANT_LDS) {
+        float(*T)[3 * CHUNK] = tile[wid];
+        float2 sp = make_float2(0.f, 0.f);
+        float sg = 0.f;
+        auto fetch = [&](uint32_t c) {
+            const uint32_t v = c * CHUNK + lane;
+            const bool live = v < total;
+            const uint32_t j = source_index(p, live ? v : total - 1, n0);
+            sp = p.src_pos[j];                 // 512 B per wave, coalesced
+            sg = live ? p.src_gm[j] : 0.0f;    // pad sources: a real position, zero mass
         };
-
-        if constexpr (W == 1) {
+        // whole 64-source tiles only: this route always runs with the 64-source granule (choose_shape), so the slice
+        // is [c_lo, c_hi) tiles and the last one may be ragged (pads: a real position, zero mass)
+        const uint32_t c_lo = v_lo / CHUNK, c_hi = (v_hi + CHUNK - 1) / CHUNK;
+        if (c_lo < c_hi) fetch(c_lo);
+        int buf = 0;
+        for (uint32_t c = c_lo; c < c_hi; c++) {
+            *reinterpret_cast<float2 *>(&T[buf][2 * lane]) = sp;  // ds_write_b64
+            T[buf][2 * CHUNK + lane] = sg;
+            if (c + 1 < c_hi) fetch(c + 1);  // next tile's HBM/L2 latency hides under this tile's math
+            // LDS executes one wave's accesses in order; this only stops the compiler from reordering
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int jj = 0; jj < CHUNK; jj += 4) {
+                // broadcast ds_read_b128: every lane reads the same 16 bytes.  Four sources per read group (two reads
+                // of positions, one of G*m): 12 staging VGPRs instead of 24, which is what leaves room for the
+                // paired-rsq body with two receivers per lane
+                const v8f P = *reinterpret_cast<const v8f *>(&T[buf][2 * jj]);
+                const v4f G = *reinterpret_cast<const v4f *>(&T[buf][2 * CHUNK + jj]);
 #pragma unroll
-            for (int k = 0; k < K; k++) finish(recv_base + k * WAVE + lane, R.s[k].x, R.s[k].y);
-        } else {
-#pragma unroll
-            for (int k = 0; k < K; k++) partial[wid][k * WAVE + lane] = make_float2(R.s[k].x, R.s[k].y);
-            __syncthreads();
-#pragma unroll
-            for (uint32_t slot = tid; slot < WAVE * K; slot += WAVE * W) {
-                float sx = 0.0f, sy = 0.0f;
-#pragma unroll
-                for (int s = 0; s < W; s++) {
-                    const float2 t = partial[s][slot];
-                    sx = __fadd_rn(sx, t.x);
-                    sy = __fadd_rn(sy, t.y);
-                }
-                finish(recv_base + slot, sx, sy);
+                for (int u = 0; u < 4; u++) interact<K, false>(R, f2v{P[2 * u], P[2 * u + 1]}, G[u]);
             }
+            if (((c - c_lo) & (CLOSE_EVERY - 1)) == CLOSE_EVERY - 1) R.close_chunk();
+            buf ^= 1;
         }
-
-        if constexpr (FUSED) {
-            // EVERY workgroup must reach this tail: there is no early return anywhere above, and none may be added -- a
-            // workgroup that left without drawing its ticket would leave its tile unfinished in this launch and the ticket
-            // non-zero for the next (the host re-zeroes the tickets at every upload and chain build, step_chain.hip zero_tickets).
-            // The last workgroup of this receiver tile to get here adds the parts, in part order like finish_kernel, and
-            // integrates.  Every thread's part stores have been acknowledged (vmcnt(0)) before the workgroup takes its ticket;
-            // the last arriver therefore finds all parts written, and reads them with the same scope they were written with.
-            if (p.split > 1) {
-                __shared__ uint32_t is_last;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                if (tid == 0) {
-                    const uint32_t t = __hip_atomic_fetch_add(&p.tickets[tile_x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    is_last = t == p.split - 1 ? 1u : 0u;
-                    if (is_last) __hip_atomic_store(&p.tickets[tile_x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
-                }
-                __syncthreads();
-                if (is_last) {
-                    for (uint32_t slot = tid; slot < WAVE * K; slot += WAVE * W) {
-                        const uint32_t logical = recv_base + slot;
-                        if (logical >= p.n_recv) continue;
-                        // like finish_kernel: every part load issued before the first use (unused slots re-read the last part
-                        // and are dropped by a select), or the loads would queue up behind each other's round trips
-                        uint64_t bits[MAX_SPLIT];
+        if ((c_hi - c_lo) & (CLOSE_EVERY - 1)) R.close_chunk();  // a short last block
+    } else {
+        // scalar-cache route: indices are wave-uniform, the loads become s_load_dwordx8/x16
 #pragma unroll
-                        for (uint32_t s = 0; s < (uint32_t)MAX_SPLIT; s++)
-                            bits[s] = __hip_atomic_load(reinterpret_cast<const uint64_t *>(&p.parts[(size_t)(s < p.split ? s : p.split - 1) * p.n_recv + logical]),
-                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        // the integrator's state rides the same round trip (finish_receiver would fetch it behind the sums)
-                        const uint32_t i = receiver_slot(p, logical);
-                        const float2 a0 = p.acc[i], v0 = p.vel[i], q0 = p.pos_in[i];
-                        float sx = 0.0f, sy = 0.0f;
-#pragma unroll
-                        for (uint32_t s = 0; s < (uint32_t)MAX_SPLIT; s++) {
-                            const float nx = __fadd_rn(sx, __uint_as_float((uint32_t)bits[s])), ny = __fadd_rn(sy, __uint_as_float((uint32_t)(bits[s] >> 32)));
-                            sx = s < p.split ? nx : sx;
-                            sy = s < p.split ? ny : sy;
-                        }
-                        // same arithmetic, same roundings as finish_receiver / finish_kernel
-                        float2 a = make_float2(sx, sy);
-                        if (p.flags & STEP_ACC_IN) {
-                            a.x = __fadd_rn(a0.x, a.x);
-                            a.y = __fadd_rn(a0.y, a.y);
-                        }
-                        p.acc[i] = a;
-                        if (p.flags & STEP_NO_FINALIZE) continue;
-                        float2 v = v0, q = q0;
-                        v.x = __fadd_rn(v.x, __fmul_rn(a.x, dt));
-                        v.y = __fadd_rn(v.y, __fmul_rn(a.y, dt));
-                        q.x = __fadd_rn(q.x, __fmul_rn(v.x, dt));
-                        q.y = __fadd_rn(q.y, __fmul_rn(v.y, dt));
-                        p.vel[i] = v;
-                        p.pos_out[i] = q;
-                        if (i < p.n_mirror) p.mirror[i] = q;
+        for (int range = 0; range < 2; range++) {
+            // intersection of [v_lo, v_hi) with this range, as indices of the source arrays
+            const uint32_t r_lo = range == 0 ? 0u : n0;
+            const uint32_t r_hi = range == 0 ? n0 : total;
+            const uint32_t a = max(v_lo, r_lo), b = min(v_hi, r_hi);
+            if (a >= b) continue;
+            uint32_t j = p.src_begin[range] + (a - r_lo);
+            const uint32_t j_end = p.src_begin[range] + (b - r_lo);
+            // 8 sources per scalar fetch: s_load_dwordx16 (x,y pairs) + s_load_dwordx8 (G*m).  Slices start on
+            // multiples of 64 sources from 64-aligned range starts, so j is a multiple of 8 here.
+            const float *sp = reinterpret_cast<const float *>(p.src_pos), *sg = p.src_gm;
+            // every 8 * CLOSE_EVERY groups (256 sources) the block sums are closed, exactly where the LDS variant
+            // closes them, so both variants add in the same order; a short last block may end in single sources
+            const uint32_t groups = (j_end - j) / 8;
+            const uint32_t g0 = (a - v_lo) / 8;  // groups of this slice that lie in the previous range
+            if (groups > 0) {
+                // Two register sets, A and B, each fetched while the other one is being consumed (the scalar
+                // cache's latency hides under 8 * K interactions) and each dead before its refill is issued, so
+                // no set is ever copied.  g0 is even (range starts are 64-aligned) and a block ends on an odd
+                // group index, so only the second group of a pair can close one.  The refill address is clamped to
+                // the last group instead of branching around the load.
+                const uint32_t j_last = j + (groups - 1) * 8;
+                v16f PA = src_load<v16f>(sp + 2 * (size_t)j);
+                v8f GA = src_load<v8f>(sg + j);
+                uint32_t g = 0;
+                while (g + 2 <= groups) {
+                    // pairs up to the end of the current 32-group block, as one branch-free inner loop
+                    const uint32_t to_close = (8u * CLOSE_EVERY - ((g0 + g) & (8u * CLOSE_EVERY - 1))) / 2;
+                    const uint32_t pairs = min(to_close, (groups - g) / 2);
+                    for (uint32_t i = 0; i < pairs; i++) {
+                        // Scalar loads return out of order, so the only wait there is is "all of them"
+                        // (lgkmcnt(0)).  The empty asm makes the next fetch's address depend on the set about to
+                        // be consumed: the wait lands BEFORE that fetch is issued, where nothing is in flight but
+                        // loads that had a whole group's math to land.  (Not volatile: a volatile asm counts as a
+                        // memory clobber and would turn the scalar loads into vector loads.)  The scheduling
+                        // barriers keep each fetch ahead of the math that hides it.
+                        asm("" : "+s"(j) : "s"(PA), "s"(GA));
+                        const v16f PB = src_load<v16f>(sp + 2 * (size_t)(j + 8));
+                        const v8f GB = src_load<v8f>(sg + j + 8);
+                        __builtin_amdgcn_sched_barrier(0);
+                        interact8<K, true>(R, PA, GA);
+                        __builtin_amdgcn_sched_barrier(0);
+                        j = min(j + 16, j_last);
+                        asm("" : "+s"(j) : "s"(PB), "s"(GB));
+                        PA = src_load<v16f>(sp + 2 * (size_t)j);
+                        GA = src_load<v8f>(sg + j);
+                        __builtin_amdgcn_sched_barrier(0);
+                        interact8<K, true>(R, PB, GB);
                     }
+                    g += 2 * pairs;
+                    if (pairs == to_close) R.close_chunk();
+                }
+                if (g < groups) interact8<K, true>(R, PA, GA);  // odd count: the last refill fetched it
+                j = j_last + 8;
+            }
+            for (; j < j_end; j++) interact<K, true>(R, f2v{sp[2 * (size_t)j], sp[2 * (size_t)j + 1]}, sg[j]);
+        }
+        // a short last block: anything after the last multiple of 256 sources of this slice (same blocks as the
+        // LDS variant, whose last tile may be padded)
+        if ((v_hi - v_lo) & (CHUNK * CLOSE_EVERY - 1)) R.close_chunk();
+    }
+
+    // ---- combine the W slices in wave order, integrate, store -------------------------------------------
+    auto finish = [&](uint32_t logical, float sx, float sy) {
+        if (p.split > 1) {
+            if (logical < p.n_recv) {
+                float2 *slot = &p.parts[(size_t)part_y * p.n_recv + logical];
+                if constexpr (FUSED) {
+                    // agent-scope relaxed store (one 8-byte access): written through to the point every XCD's loads of the
+                    // same scope read
+                    const uint64_t bits = (uint64_t)__float_as_uint(sx) | ((uint64_t)__float_as_uint(sy) << 32);
+                    __hip_atomic_store(reinterpret_cast<uint64_t *>(slot), bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                } else {
+                    *slot = make_float2(sx, sy);
                 }
             }
-        }
-
-        if constexpr (!PERSIST) {
-            break;
         } else {
-            // the next work item of this workgroup; the LDS reduction buffers are reused, so every wave must be done with them
-            // (readfirstlane: the compiler must keep seeing wave-uniform values, or the source loads stop being scalar loads)
-            item = __builtin_amdgcn_readfirstlane(item + gridDim.x);
-            if (item >= n_tiles * p.split) break;
-            tile_x = __builtin_amdgcn_readfirstlane(item % n_tiles);
-            part_y = __builtin_amdgcn_readfirstlane(item / n_tiles);
+            finish_receiver(p, logical, sx, sy, dt);
+        }
+    };
+
+    if constexpr (W == 1) {
+#pragma unroll
+        for (int k = 0; k < K; k++) finish(recv_base + k * WAVE + lane, R.s[k].x, R.s[k].y);
+    } else {
+#pragma unroll
+        for (int k = 0; k < K; k++) partial[wid][k * WAVE + lane] = make_float2(R.s[k].x, R.s[k].y);
+        __syncthreads();
+#pragma unroll
+        for (uint32_t slot = tid; slot < WAVE * K; slot += WAVE * W) {
+            const float2 a = wave_sum(&partial[0][slot], WAVE * K, W);
+            finish(recv_base + slot, a.x, a.y);
+        }
+    }
+
+    if constexpr (FUSED) {
+        // EVERY workgroup must reach this tail: there is no early return anywhere above, and none may be added -- a
+        // workgroup that left without drawing its ticket would leave its tile unfinished in this launch and the ticket
+        // non-zero for the next (the host re-zeroes the tickets at every upload and chain build, step_chain.hip zero_tickets).
+        // The last workgroup of this receiver tile to get here adds the parts, in part order like finish_kernel, and
+        // integrates.  Every thread's part stores have been acknowledged (vmcnt(0)) before the workgroup takes its ticket;
+        // the last arriver therefore finds all parts written, and reads them with the same scope they were written with.
+        if (p.split > 1) {
+            __shared__ uint32_t is_last;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
+            if (tid == 0) {
+                const uint32_t t = __hip_atomic_fetch_add(&p.tickets[tile_x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                is_last = t == p.split - 1 ? 1u : 0u;
+                if (is_last) __hip_atomic_store(&p.tickets[tile_x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
+            }
+            __syncthreads();
+            if (is_last) {
+                for (uint32_t slot = tid; slot < WAVE * K; slot += WAVE * W) {
+                    const uint32_t logical = recv_base + slot;
+                    if (logical >= p.n_recv) continue;
+                    // like finish_kernel: every part load issued before the first use (unused slots re-read the last part
+                    // and are dropped by a select), or the loads would queue up behind each other's round trips
+                    float2 part[MAX_SPLIT];
+#pragma unroll
+                    for (uint32_t s = 0; s < (uint32_t)MAX_SPLIT; s++) {
+                        const uint64_t bits = __hip_atomic_load(reinterpret_cast<const uint64_t *>(&p.parts[(size_t)(s < p.split ? s : p.split - 1) * p.n_recv + logical]),
+                                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        part[s] = make_float2(__uint_as_float((uint32_t)bits), __uint_as_float((uint32_t)(bits >> 32)));
+                    }
+                    // the integrator's state rides the same round trip (finish_receiver would fetch it behind the sums)
+                    const uint32_t i = receiver_slot(p, logical);
+                    const float2 a0 = p.acc[i], v0 = p.vel[i], q0 = p.pos_in[i];
+                    float sx = 0.0f, sy = 0.0f;
+#pragma unroll
+                    for (uint32_t s = 0; s < (uint32_t)MAX_SPLIT; s++) add_part(sx, sy, part[s], s < p.split);
+                    finish_loaded(p, i, make_float2(sx, sy), a0, v0, q0, dt);
+                }
+            }
         }
     }
 }
@@ -626,14 +595,9 @@ __global__ __launch_bounds__(WAVE *W) void lane_split_kernel(const StepParams p)
         if (t + 1 < ntiles) fetch(t + 1);   // lands while this tile is being walked
         __syncthreads();
 
-        // this lane's slice of the tile, in whole 8-source granules; empty slices have v_hi == v_lo (clamped: no wrap-around)
-        const uint32_t n_t = min(T, n0 - t * T);
-        const uint32_t nunits = (n_t + 7u) / 8u;
-        const uint32_t per = (nunits + V - 1) / V;
-        const uint32_t u_lo = min(v * per, nunits);
-        const uint32_t u_hi = min(u_lo + per, nunits);
-        const uint32_t v_lo = u_lo * 8u;
-        const uint32_t v_hi = max(min(u_hi * 8u, n_t), v_lo);
+        // this lane's slice of the tile, in whole 8-source granules
+        const SourceSlice lane_src = source_slice(min(T, n0 - t * T), 8u, 1, 0, V, v);
+        const uint32_t v_lo = lane_src.lo, v_hi = lane_src.hi;
 
         // Four sources per group: two 16-byte reads of positions, one of G*m (lanes of one lane group read the same
         // address, the groups different ones).  The next group's reads are issued before this group's arithmetic: a
@@ -702,19 +666,13 @@ __global__ __launch_bounds__(WAVE *W) void lane_split_kernel(const StepParams p)
                 ay = __fadd_rn(ay, t.y);
             }
             if (integrates) {
-                // finish_receiver with everything it reads already in registers: acc, then the reference's integrator
-                // roundings (vel += acc*dt; pos += vel*dt; sim_cpu.c:191-193)
+                // finish_receiver with everything it reads already in registers (flags == 0: no carry-in, always integrate)
                 const uint32_t i = receiver_slot(p, my_logical);
-                p.acc[i] = make_float2(ax, ay);
-                float2 vv = vel0;
-                vv.x = __fadd_rn(vv.x, __fmul_rn(ax, dt));
-                vv.y = __fadd_rn(vv.y, __fmul_rn(ay, dt));
-                float2 q = make_float2(Rv.p[0].x, Rv.p[0].y);
-                q.x = __fadd_rn(q.x, __fmul_rn(vv.x, dt));
-                q.y = __fadd_rn(q.y, __fmul_rn(vv.y, dt));
-                p.vel[i] = vv;
-                p.pos_out[i] = q;
-                if (i < p.n_mirror) p.mirror[i] = q;
+                const float2 a = make_float2(ax, ay);
+                p.acc[i] = a;
+                float2 vv = vel0, q = make_float2(Rv.p[0].x, Rv.p[0].y);
+                integrate(a, dt, vv, q);
+                store_moved(p, i, vv, q);
             } else {
                 finish_receiver(p, my_logical, ax, ay, dt);   // chained passes (flags): the general epilogue
             }
@@ -776,14 +734,8 @@ __global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) {
     if (integrates) v = p.vel[mine];
 
     // this wave's slice of the sources: whole 8-source granules, exactly StepParams::unit = 8 with split = 1
-    const uint32_t nunits = (p.n_src + 7u) / 8u;
-    const uint32_t per_wave = (nunits + W - 1) / W;
-    const uint32_t u_lo = min(slice * per_wave, nunits);
-    const uint32_t u_hi = min(u_lo + per_wave, nunits);
-    const uint32_t v_lo = u_lo * 8u;
-    // an empty slice past a ragged last granule would have v_hi < v_lo (7 granules over 16 waves, 50 sources: wave 7
-    // starts at 56): clamp, so that the unsigned lengths below are 0 there and the loops cannot run away
-    const uint32_t v_hi = max(min(u_hi * 8u, p.n_src), v_lo);
+    const SourceSlice wave_src = source_slice(p.n_src, 8u, 1, 0, W, slice);
+    const uint32_t v_lo = wave_src.lo, v_hi = wave_src.hi;
     __syncthreads();
 
     int cur = 0;
@@ -806,21 +758,11 @@ __global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) {
         for (int k = 0; k < K; k++) partial[wid][k * WAVE + lane] = make_float2(R.s[k].x, R.s[k].y);
         __syncthreads();
         if (integrates) {
-            float sx = 0.0f, sy = 0.0f;
-            for (uint32_t s = 0; s < W; s++) {   // the tile's slices in wave order: deterministic, = the per-step kernel
-                const float2 t = partial[tile * W + s][local];
-                sx = __fadd_rn(sx, t.x);
-                sy = __fadd_rn(sy, t.y);
-            }
-            a = make_float2(sx, sy);
-            // semi-implicit Euler with the reference's roundings (finish_receiver): vel += acc*dt; pos += vel*dt
-            v.x = __fadd_rn(v.x, __fmul_rn(a.x, dt));
-            v.y = __fadd_rn(v.y, __fmul_rn(a.y, dt));
-            float qx = S[2 * mine], qy = S[2 * mine + 1];
-            qx = __fadd_rn(qx, __fmul_rn(v.x, dt));
-            qy = __fadd_rn(qy, __fmul_rn(v.y, dt));
-            spos[cur ^ 1][2 * mine] = qx;
-            spos[cur ^ 1][2 * mine + 1] = qy;
+            a = wave_sum(&partial[tile * W][local], WAVE * K, W);   // the tile's slices in wave order, = the per-step kernel
+            float2 q = make_float2(S[2 * mine], S[2 * mine + 1]);
+            integrate(a, dt, v, q);
+            spos[cur ^ 1][2 * mine] = q.x;
+            spos[cur ^ 1][2 * mine + 1] = q.y;
         }
         __syncthreads();
         cur ^= 1;
@@ -929,23 +871,6 @@ const void *pick_fused(int k, int w) {
     return nullptr;
 }
 
-// persistent launches (experiment, "persist" hook): scalar-cache route, with and without the fused finish
-// (built only with make TUNING=1: the experiment lost at every size, profiles/r05_persist_probe.txt, and twelve more
-// instantiations of the step kernel are not worth carrying in the library that ships)
-template <bool FUSED>
-const void *pick_persist(int k, int w) {
-#ifdef NB_TUNING_SHAPES
-#define NB_CASE(KK, WW) \
-    if (k == KK && w == WW) return reinterpret_cast<const void *>(&step_kernel<KK, WW, VARIANT_SMEM, FUSED, true>);
-    NB_CASE(1, 4) NB_CASE(1, 8) NB_CASE(1, 16) NB_CASE(2, 4) NB_CASE(2, 8) NB_CASE(2, 16)
-#undef NB_CASE
-#else
-    (void)k;
-    (void)w;
-#endif
-    return nullptr;
-}
-
 const void *pick_lane_split(int w, int h) {
 #define NB_CASE(WW, HH) \
     if (w == WW && h == HH) return reinterpret_cast<const void *>(&lane_split_kernel<WW, HH>);
@@ -1029,8 +954,7 @@ LaunchShape choose_shape(LaunchShape want, uint32_t n_recv, uint32_t n_src, int 
     // smaller split.  More, shorter workgroups also shrink the launch's ramp-up/ragged-end share.  K = 4 is left out: 71 VGPRs, lower
     // occupancy, never faster (profiles/r01_sweep4_shapes_by_n.txt).
     if (compute_units <= 0) compute_units = 256;
-    if (want.lanes == 0 && want.k == 0 && want.w == 0 && want.split == 0 && want.unit == 0 && want.persist <= 1 && want.variant == VARIANT_SMEM) {
-        // everything on auto (an explicit LDS-tile route or shape knob asks for the classic kernel)
+    if (shape_on_auto(want)) {   // an explicit LDS-tile route or shape knob asks for the classic kernel
         int w = 16;
         const int lanes = lane_split_rule(n_recv, n_src, &w);
         if (lanes > 1) {
@@ -1048,7 +972,6 @@ LaunchShape choose_shape(LaunchShape want, uint32_t n_recv, uint32_t n_src, int 
         sh.split = 1;
         sh.unit = 8;
         sh.variant = VARIANT_LDS;
-        sh.persist = 0;
         return sh;
     }
     if (want.variant == VARIANT_LDS) want.unit = CHUNK;  // the LDS route stages whole 64-source tiles, whatever was asked
@@ -1117,29 +1040,19 @@ LaunchShape choose_shape(LaunchShape want, uint32_t n_recv, uint32_t n_src, int 
 }
 
 // NB_HASH_ON
-bool shape_is_persistent(LaunchShape s) { return s.persist > 1 && s.lanes <= 1 && s.variant == VARIANT_SMEM && s.w >= 4 && s.k <= 2; }
-
 const void *step_kernel_fn(LaunchShape s) {
     if (s.lanes > 1) return pick_lane_split(s.w, s.lanes);
-    if (shape_is_persistent(s)) return pick_persist<false>(s.k, s.w);
     return s.variant == VARIANT_SMEM ? pick<VARIANT_SMEM>(s.k, s.w) : pick<VARIANT_LDS>(s.k, s.w);
 }
 
 const void *step_kernel_fused_fn(LaunchShape s) {
     if (s.lanes > 1 || s.variant != VARIANT_SMEM) return nullptr;
-    if (shape_is_persistent(s)) return pick_persist<true>(s.k, s.w);
     return pick_fused(s.k, s.w);
 }
 
 dim3 step_grid(LaunchShape s, uint32_t n_recv) {
     if (s.lanes > 1) return dim3((n_recv + WAVE / s.lanes - 1) / (WAVE / s.lanes), 1);
-    const uint32_t tiles = (n_recv + WAVE * s.k - 1) / (WAVE * s.k), parts = s.split > 1 ? s.split : 1;
-    if (shape_is_persistent(s)) {
-        // `persist` work items (tile, part) per workgroup, walked with a stride of the grid size
-        const uint64_t items = (uint64_t)tiles * parts;
-        return dim3((uint32_t)((items + (uint32_t)s.persist - 1) / (uint32_t)s.persist), 1);
-    }
-    return dim3(tiles, parts);
+    return dim3((n_recv + WAVE * s.k - 1) / (WAVE * s.k), s.split > 1 ? s.split : 1);
 }
 
 size_t step_lds_bytes(LaunchShape s, uint32_t n_src) {

@@ -216,7 +216,7 @@ SimPipeline *CreateSimPipeline(WorldData data) {
     // presets from the environment: the knobs of include/nbody_hip.h only; launch-shape and experiment knobs can be preset
     // in TUNING=1 builds (tools/ sweeps), never in the library that ships
     const char *v = getenv("NB_HIP_VARIANT");
-    if (v) s->want_variant = atoi(v) ? nb::VARIANT_SMEM : nb::VARIANT_LDS;
+    if (v) s->want.variant = atoi(v) ? nb::VARIANT_SMEM : nb::VARIANT_LDS;
     const char *gr = getenv("NB_HIP_GRAPH");
     if (gr) s->use_graph = atoi(gr) < 0 || atoi(gr) > 2 ? 2 : atoi(gr);
 #ifdef NB_TUNING_SHAPES
@@ -274,7 +274,7 @@ SimPipeline *CreateSimPipelineShardedDirect(WorldData data, int rank, int nranks
 }
 
 void nb_hip_plan_launch(uint32_t n_recv, uint32_t n_src, int compute_units, int *k, int *w, int *split, uint32_t *workgroups) {
-    const nb::LaunchShape sh = nb::choose_shape({0, 0, nb::VARIANT_SMEM, 0, 0, 1, 0}, n_recv, n_src, compute_units);
+    const nb::LaunchShape sh = nb::choose_shape({.lanes = 1}, n_recv, n_src, compute_units);
     if (k) *k = sh.k;
     if (w) *w = sh.w;
     if (split) *split = sh.split;
@@ -292,12 +292,12 @@ int nb_hip_plan_launch_lanes(uint32_t n_recv, uint32_t n_src, int *w) {
 }
 
 int nb_hip_plan_fused_finish(uint32_t n_recv, uint32_t n_src, int compute_units) {
-    const nb::LaunchShape sh = nb::choose_shape({0, 0, nb::VARIANT_SMEM, 0, 0, 1, 0}, n_recv, n_src, compute_units);
+    const nb::LaunchShape sh = nb::choose_shape({.lanes = 1}, n_recv, n_src, compute_units);
     return sh.split > 1 && nb_hip_plan_launch_lanes(n_recv, n_src, nullptr) <= 1 && fused_finish_rule(n_recv, n_src) ? 1 : 0;
 }
 
 int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units) {
-    return nb::choose_shape({0, 0, nb::VARIANT_SMEM, 0, 0, 1, 0}, n_recv, n_src, compute_units).unit;
+    return nb::choose_shape({.lanes = 1}, n_recv, n_src, compute_units).unit;
 }
 
 int nb_hip_local_group_create(WorldData data, int nranks, SimPipeline **out) {
@@ -602,8 +602,8 @@ int nb_hip_configure(SimPipeline *s, const char *key, int value) {
     int old = 0;
     if (!strcmp(key, "variant")) {
         NB_ASSERT(value == 0 || value == 1, "variant must be 0 (lds) or 1 (smem), got %d", value);
-        old = s->want_variant;
-        s->want_variant = value;
+        old = s->want.variant;
+        s->want.variant = value;
     } else if (!strcmp(key, "graph")) {
         NB_ASSERT(value >= 0 && value <= 2, "graph must be 0 (never), 1 (always) or 2 (from the second use), got %d", value);
         old = s->use_graph;
@@ -640,25 +640,25 @@ int nb_hip_tune(SimPipeline *s, const char *key, int value) {
     int old = 0;
     if (!strcmp(key, "k")) {
         NB_ASSERT(value == 0 || value == 1 || value == 2 || value == 4, "k must be 0, 1, 2 or 4, got %d", value);
-        old = s->want_k;
-        s->want_k = value;
+        old = s->want.k;
+        s->want.k = value;
     } else if (!strcmp(key, "w")) {
         NB_ASSERT(value == 0 || value == 1 || value == 2 || value == 4 || value == 8 || value == 16,
                   "w must be 0, 1, 2, 4, 8 or 16, got %d", value);
-        old = s->want_w;
-        s->want_w = value;
+        old = s->want.w;
+        s->want.w = value;
     } else if (!strcmp(key, "split")) {
         NB_ASSERT(value >= 0 && value <= nb::MAX_SPLIT, "split must be 0 (auto) .. %d, got %d", nb::MAX_SPLIT, value);
-        old = s->want_split;
-        s->want_split = value;
+        old = s->want.split;
+        s->want.split = value;
     } else if (!strcmp(key, "unit")) {
         NB_ASSERT(value == 0 || value == 8 || value == 16 || value == 32 || value == 64, "unit must be 0, 8, 16, 32 or 64, got %d", value);
-        old = s->want_unit;
-        s->want_unit = value;
+        old = s->want.unit;
+        s->want.unit = value;
     } else if (!strcmp(key, "lanes")) {
         NB_ASSERT(value == 0 || value == 1 || value == 2 || value == 4 || value == 8, "lanes must be 0 (auto), 1, 2, 4 or 8, got %d", value);
-        old = s->want_lanes;
-        s->want_lanes = value;
+        old = s->want.lanes;
+        s->want.lanes = value;
     } else if (!strcmp(key, "fused_chain")) {
         NB_ASSERT(value >= 0 && value <= 2, "fused_chain must be 0 (never), 1 (whenever the world fits one workgroup) or 2 (auto), got %d", value);
         old = s->fused_chain;
@@ -672,13 +672,6 @@ int nb_hip_tune(SimPipeline *s, const char *key, int value) {
             s->graphs.clear();
         }
         s->fused_finish = value;
-    } else if (!strcmp(key, "persist")) {
-        NB_ASSERT(value >= 0 && value <= 64, "persist must be 0 (classic) .. 64 work items per workgroup, got %d", value);
-#ifndef NB_TUNING_SHAPES
-        NB_ASSERT(value <= 1, "the persistent-launch experiment kernels are built with make TUNING=1 only (persist = %d)", value);
-#endif
-        old = s->want_persist;
-        s->want_persist = value;
     } else if (!strcmp(key, "passes")) {
         NB_ASSERT(value >= 0 && value <= 64, "passes must be 0 (auto) .. 64, got %d", value);
         old = s->want_passes;

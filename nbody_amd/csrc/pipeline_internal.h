@@ -162,7 +162,7 @@ struct StepGraph {
     std::vector<hipGraphNode_t> nodes;  // one kernel node per launch, in order
     std::vector<nb::StepParams> params; // what each node currently holds
     int phase = -1;                     // which pos buffer the chain reads first
-    nb::LaunchShape shape = {0, 0, 0, 0, 0, 0, 0};
+    nb::LaunchShape shape;
     uint64_t last_use = 0;              // for eviction: the cache holds at most GRAPH_CACHE_MAX chains
 };
 
@@ -264,7 +264,9 @@ struct SimPipeline {
     uint64_t use_clock = 0;     // ticks once per graph lookup (LRU)
 
     // knobs
-    int want_variant = nb::VARIANT_SMEM, want_k = 0, want_w = 0, want_split = 0;  // the scalar-cache route is 8 % faster than LDS tiles at N = 2^20 (roofline.alt_lds)
+    // the launch shape asked for ("variant" knob, shape hooks; kernels.h LaunchShape): all auto by default -- the
+    // scalar-cache route is 8 % faster than LDS tiles at N = 2^20 (roofline.alt_lds)
+    nb::LaunchShape want;
     int use_graph = 2, overlap = 0, sharded_graph = 0;  // use_graph: 0 never, 1 always, 2 from a chain length's second use
     int fused_chain = 2;                                // one-launch n-step chains for one-workgroup worlds: 0 never, 2 auto
     std::vector<uint32_t> seen_chains;                  // chain lengths already run once as plain launches
@@ -272,10 +274,7 @@ struct SimPipeline {
     double first_gather_ms = 0.0;  // sharded: device time of the probe all-gather at creation (includes lazy setup)
     double comm_init_ms = 0.0;     // sharded over RCCL: host time of ncclCommInitRank
     double small_gather_us = 0.0;  // sharded over RCCL: device time of one warm 8-byte-per-rank all-gather (mean of 16 in-stream)
-    nb::LaunchShape last_shape = {0, 0, 0, 0, 0, 0, 0};
-    int want_unit = 0;  // source-slice granule: 0 = auto, else 64 / 32 / 16 / 8
-    int want_persist = 0;  // experiment: work items per workgroup of a persistent launch (0 / 1 = classic)
-    int want_lanes = 0; // lane groups per wave: 0 = auto, 1 = never, 2 / 4 = lane-split kernel (kernels.h LaunchShape::lanes)
+    nb::LaunchShape last_shape = {.variant = nb::VARIANT_LDS};   // all zero until the first step
     uint32_t last_groups = 0;
     uint32_t fused_steps = 0;   // steps the last update ran inside fused (one-launch) chains
 

@@ -60,7 +60,7 @@ void destroy_graph(StepGraph &g) {
 }
 
 nb::LaunchShape resolve_shape(SimPipeline *s) {
-    nb::LaunchShape want = {s->want_k, s->want_w, s->want_variant, s->want_split, s->want_unit, s->want_lanes, s->want_persist};
+    nb::LaunchShape want = s->want;
     // the model sees one launch: with source passes that is 1/passes of the sources
     nb::StepParams probe;
     memset(&probe, 0, sizeof probe);
@@ -237,16 +237,14 @@ void fill_node(hipKernelNodeParams &kp, void **args, const void *fn, dim3 grid, 
     kp.extra = nullptr;
 }
 
-// A cached chain is keyed on (length, passes, shape, PHASE): an odd chain length flips the ping-pong phase, so a
-// frame loop that asks for the same odd n alternates between two phases -- with the phase in the key it gets two
-// instantiated graphs and replays them untouched, instead of re-patching every node of one graph on every call.
-// dt is not part of the key and never forces a rebuild or a patch: the nodes read it from device memory (upload_dt).
+// A cached chain, single-device or sharded, is keyed on (length, passes, shape, PHASE): an odd chain length flips the
+// ping-pong phase, so a frame loop that asks for the same odd n alternates between two phases -- with the phase in the
+// key it gets two instantiated graphs and replays them untouched, instead of re-patching every node of one graph on
+// every call.  dt is not part of the key and never forces a rebuild or a patch: the nodes read it from device memory
+// (upload_dt).
 StepGraph *find_graph(SimPipeline *s, uint32_t n, uint32_t passes, nb::LaunchShape sh, int phase) {
     for (auto &c : s->graphs)
-        if (c.n == n && c.passes == passes && c.phase == phase && c.shape.k == sh.k && c.shape.w == sh.w &&
-            c.shape.variant == sh.variant && c.shape.split == sh.split && c.shape.unit == sh.unit && c.shape.lanes == sh.lanes &&
-            c.shape.persist == sh.persist)
-            return &c;
+        if (c.n == n && c.passes == passes && c.phase == phase && c.shape == sh) return &c;
     return nullptr;
 }
 
@@ -320,10 +318,9 @@ constexpr uint32_t CHAIN_MAX_STEPS_PER_LAUNCH = 1u << 16;
 bool wants_fused_chain(const SimPipeline *s) {
     if (s->sharded || s->fused_chain == 0 || s->n_real == 0 || nb::chain_tiles(s->n_real) == 0) return false;
     if (s->fused_chain == 1) return true;
-    // an explicit k / w / split / unit / passes / lanes / route asks for the per-step kernel (choose_shape treats them so too)
-    const bool shape_on_auto = s->want_k == 0 && s->want_w == 0 && s->want_split == 0 && s->want_unit == 0 && s->want_passes == 0 &&
-                               s->want_lanes == 0 && s->want_persist == 0 && s->want_variant == nb::VARIANT_SMEM;
-    return shape_on_auto && s->n_real <= CHAIN_AUTO_MAX_RECV && (double)s->n_real * (double)(s->n_src ? s->n_src : 1) <= CHAIN_MAX_PAIRS;
+    // an explicit shape, route or passes asks for the per-step kernel
+    return nb::shape_on_auto(s->want) && s->want_passes == 0 && s->n_real <= CHAIN_AUTO_MAX_RECV &&
+           (double)s->n_real * (double)(s->n_src ? s->n_src : 1) <= CHAIN_MAX_PAIRS;
 }
 
 void enqueue_fused(SimPipeline *s, uint32_t n) {
@@ -344,7 +341,8 @@ void enqueue_fused(SimPipeline *s, uint32_t n) {
         left -= p.steps;
     }
     s->fused_steps = n;
-    s->last_shape = {2, (int)(16u / p.tiles), nb::VARIANT_LDS, 1, 8, 1, 0};   // the per-step shape it is bit-equal to
+    // the per-step shape it is bit-equal to
+    s->last_shape = {.k = 2, .w = (int)(16u / p.tiles), .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = 1};
     s->last_groups = 1;
 }
 
@@ -570,17 +568,17 @@ void sharded_step(SimPipeline *s, nb::LaunchShape sh, float dt, hipStream_t cs, 
 // chain length keeps the ping-pong phase so a cached graph can be replayed as is.  Off by default: RCCL inside
 // stream capture is the least-travelled path of this library (exercised with one rank only, tests).
 StepGraph *capture_sharded_chain(SimPipeline *s, uint32_t n, float dt, nb::LaunchShape sh) {
-    for (auto &c : s->graphs)
-        if (c.n == n && c.phase == s->cur && c.shape.k == sh.k && c.shape.w == sh.w &&
-            c.shape.variant == sh.variant && c.shape.split == sh.split && c.shape.unit == sh.unit) {
-            c.last_use = ++s->use_clock;
-            return &c;
-        }
+    const uint32_t passes = passes_for(s, whole_step(s, s->cur, dt));
+    if (StepGraph *c = find_graph(s, n, passes, sh, s->cur)) {
+        c->last_use = ++s->use_clock;
+        return c;
+    }
     evict_for_one_more(s);  // captured RCCL nodes pin communicator resources: the cache stays small
     s->graphs.emplace_back();
     StepGraph *g = &s->graphs.back();
     g->last_use = ++s->use_clock;
     g->n = n;
+    g->passes = passes;
     g->phase = s->cur;
     g->shape = sh;
     const int cur0 = s->cur;

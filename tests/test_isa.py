@@ -86,7 +86,7 @@ def test_every_rsq_has_a_wait_state_before_its_consumer(isa):
     assert total >= 16 * 8, total
 
 
-def test_step_kernels_fit_the_occupancy_the_launch_bounds_promise(isa):
+def test_step_kernel_instantiations_fit_the_occupancy_the_launch_bounds_promise(isa):
     meta = re.findall(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)\n\s+\.sgpr_count:\s+(\d+)"
                       r"(?:\n.*?)*?\n\s+\.vgpr_count:\s+(\d+)", isa)
     step = [(n, int(scratch), int(sgpr), int(vgpr)) for n, scratch, sgpr, vgpr in meta if "step_kernel" in n]
@@ -96,8 +96,8 @@ def test_step_kernels_fit_the_occupancy_the_launch_bounds_promise(isa):
         assert scratch == 0, f"{name}: {scratch} bytes of scratch (spills)"
         assert sgpr <= 102, f"{name}: {sgpr} SGPRs"
     # the default (scalar-cache) route keeps the asm body's footprint: well under the limit
-    # (template arguments: K, W, VARIANT = 1, FUSED, PERSIST = 0)
-    smem = [v for n, _, _, v in step if re.search(r"ELi1ELb[01]ELb0EEEvNS_10StepParamsE$", n)]
+    # (template arguments: K, W, VARIANT = 1, FUSED)
+    smem = [v for n, _, _, v in step if re.search(r"ELi1ELb[01]EEEvNS_10StepParamsE$", n)]
     assert len(smem) >= 14 and max(smem) <= 48, smem
 
 
@@ -152,19 +152,33 @@ def test_the_gravitational_constant_is_written_down_once(isa):
         assert not any(literal in ins.lower() or re.search(r"\b10\.0\b", ins) for ins in body), (name, literal)
 
 
-def test_fused_finish_tail_uses_agent_scope_accesses_and_leaves_the_other_kernels_alone(isa):
+def test_the_shipped_build_holds_exactly_the_picked_step_kernels(isa):
+    """The step_kernel instantiations of the shipped build are exactly the ones kernels.hip pick / pick_fused enumerate:
+    both routes at K = 1, 2 and W = 1, 4, 8, 16, plus the six fused-finish ones (scalar-cache route, W >= 4).  The tuning-only
+    shapes (K = 4, W = 2) exist in make TUNING=1 builds only."""
+    shipped = {(k, w, v, 0) for v in (0, 1) for k in (1, 2) for w in (1, 4, 8, 16)}
+    shipped |= {(k, w, 1, 1) for k in (1, 2) for w in (4, 8, 16)}
+    built = set()
+    for n in functions(isa):
+        if "step_kernel" in n:
+            # template arguments <K, W, VARIANT, FUSED>
+            m = re.search(r"step_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb([01])EEEvNS_10StepParamsE$", n)
+            assert m, n
+            built.add(tuple(int(x) for x in m.groups()))
+    assert built == shipped, sorted(built ^ shipped)
+
+
+def test_fused_finish_tail_uses_agent_scope_accesses_and_leaves_the_unfused_kernels_alone(isa):
     """The fused-finish instantiations (step_kernel<K, W, SMEM, true>) hand the parts over with agent-scope accesses: one
     8-byte `sc1` store per receiver, a wait for the workgroup's own stores before the ticket (`global_atomic_add` with
     return), sixteen 8-byte `sc1` loads issued back to back in the last arriver's tail -- and no fence (`buffer_wbl2` /
     `buffer_inv`, the L2 write-back that made round 1's first version 5-13x slower).  The unfused instantiations contain
     none of it: their code is what it was."""
     fn = functions(isa)
-    # template arguments <K, W, VARIANT, FUSED, PERSIST>: ...Lb<FUSED>ELb<PERSIST>EEEv (the persistent experiment kernels,
-    # PERSIST = 1, exist in TUNING=1 builds only; this is the library that ships)
-    fused = {n: b for n, b in fn.items() if "step_kernel" in n and re.search(r"Lb1ELb0EEEv", n)}
-    plain = {n: b for n, b in fn.items() if "step_kernel" in n and re.search(r"Lb0ELb0EEEv", n)}
+    # template arguments <K, W, VARIANT, FUSED>: ...ELi<K>ELi<W>ELi<VARIANT>ELb<FUSED>EEEv
+    fused = {n: b for n, b in fn.items() if "step_kernel" in n and re.search(r"Lb1EEEv", n)}
+    plain = {n: b for n, b in fn.items() if "step_kernel" in n and re.search(r"Lb0EEEv", n)}
     assert len(fused) == 6 and len(plain) >= 16
-    assert not [n for n in fn if "step_kernel" in n and re.search(r"ELb1EEEv", n)], "persistent kernels in the shipped build"
     for name, body in fused.items():
         text = "\n".join(body)
         assert len(re.findall(r"global_store_dwordx2 .* sc1", text)) >= 1, name

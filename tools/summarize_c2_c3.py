@@ -37,7 +37,7 @@ def short(name):
 lines = ["Kernels BASELINE.json's configs 2 and 3 launch with every knob on auto, profiled through the C harness",
          "(tools/profile_c2_c3.sh; rocprofv3 with the program itself after `--`).  frac = interactions per launch x 14 flop /",
          "mean launch duration / 157.3 TFLOP/s -- the same convention as bench.py's roofline.frac, recomputable from this file.",
-         "step_kernel<K, W, VARIANT, FUSED, PERSIST>: K receivers per lane, W waves per workgroup, VARIANT 1 = scalar-cache route."]
+         "step_kernel<K, W, VARIANT, FUSED>: K receivers per lane, W waves per workgroup, VARIANT 1 = scalar-cache route."]
 for cfg in ("c2", "c3", "c3h"):
     d = os.path.join(PROF, cfg)
     if not os.path.isdir(d):
