@@ -8,8 +8,9 @@
  * src/shader/particle_cs.glsl, links this library, and world.c is unchanged
  * (INTEGRATION.md shows it; oracle/_ref/libnbody_ref_world.so is exactly that
  * build).  Part 2 adds what a single-queue Vulkan backend had no notion of:
- * device-resident stepping, kernel timing, and the N/P sharded multi-GPU
- * pipeline with its per-step all-gather of source positions over RCCL.
+ * device-resident stepping, kernel timing, the N/P sharded multi-GPU
+ * pipeline with its per-step all-gather of source positions over RCCL, and
+ * ensembles of small worlds stepped by one launch (SimBatch).
  *
  * Plain C types only; no HIP, RCCL or torch types cross this boundary.
  * Error convention = the reference's (src/lib/util.h:17-29,47-60): any failure
@@ -328,6 +329,56 @@ void nb_hip_local_group_step(SimPipeline **sims, int nranks, uint32_t n, float d
  */
 void nb_hip_energy(SimPipeline *sim, WorldEnergy *out);
 void nb_hip_potential(SimPipeline *sim, float *phi);
+
+/*
+ * World ensembles: `count` independent worlds with the same particle count, stepped together.
+ *
+ * One world of a few hundred to a few thousand particles keeps one or a handful of the chip's 256 compute units busy;
+ * a SimBatch steps many of them per launch (seeds of one galaxy set-up, a sweep over dt, training data).  Members never
+ * interact.  Member b has its own source count mass_len[b] and may have its own step size.  Particles travel member-major:
+ * count * total_len records, member b at [b * total_len, (b + 1) * total_len), each member partitioned "mass > 0 first".
+ *
+ * The contract: after any sequence of calls member b's particles are BIT-IDENTICAL to the same particles stepped alone
+ * in a SimPipeline(total_len, mass_len[b]) by the same calls with its launch shape pinned to the ensemble's (below).  A
+ * member's bits therefore do not depend on count, on its index, on the other members, or on how the steps are cut into
+ * calls.  The launch path is a function of total_len alone:
+ *   total_len <= 512          one workgroup per member runs the whole call (one launch per call of up to 65 536 steps)
+ *   512 < total_len <= 3 000  one lane-split launch per step for the whole ensemble
+ * Larger worlds fill the chip on their own: use one SimPipeline each.
+ *
+ * Same conventions as the rest of this header: create allocates nothing on the GPU (device work starts at the first
+ * nb_hip_batch_set_data), failures print "file:line [func] ..." and abort() -- count = 0 or > NB_HIP_BATCH_MAX_COUNT,
+ * total_len = 0 or > NB_HIP_BATCH_MAX_LEN, a mass_len[b] > total_len, an update or read-back before set_data -- there is
+ * no CPU fallback, and the caller's rand() stream is left alone.  mass_len[b] = 0 (a member without sources) and n = 0
+ * (no-op) are legal.  Step sizes live in device memory and are uploaded only when a value changes; a per-member upload
+ * first waits for the steps already queued (they keep their step sizes).  A SimBatch shares no state with any SimPipeline.
+ * These calls were added WITHOUT a version bump (nb_hip_version() stays 400): detect them by symbol
+ * (dlsym "nb_hip_batch_create").
+ */
+#define NB_HIP_BATCH_MAX_COUNT 65535u
+#define NB_HIP_BATCH_MAX_LEN 3000u
+
+typedef struct SimBatch SimBatch;
+
+SimBatch *nb_hip_batch_create(uint32_t count, uint32_t total_len, const uint32_t *mass_len /* [count] */);
+void nb_hip_batch_destroy(SimBatch *batch); /* NULL is accepted */
+void nb_hip_batch_set_data(SimBatch *batch, const Particle *ps);
+void nb_hip_batch_get_data(const SimBatch *batch, Particle *ps);
+void nb_hip_batch_get_member(const SimBatch *batch, uint32_t member, Particle *ps); /* total_len records */
+void nb_hip_batch_update(SimBatch *batch, uint32_t n, float dt);            /* blocking, one dt for every member */
+void nb_hip_batch_update_dts(SimBatch *batch, uint32_t n, const float *dt); /* blocking, dt[count] */
+void nb_hip_batch_step_async(SimBatch *batch, uint32_t n, const float *dt); /* enqueue only, dt[count] */
+void nb_hip_batch_sync(SimBatch *batch);
+/* device milliseconds of the kernels of the last update (an event pair of the ensemble's own; 0 before the first) */
+double nb_hip_batch_last_ms(SimBatch *batch);
+/* how often step sizes were written to device memory */
+uint32_t nb_hip_batch_dt_uploads(const SimBatch *batch);
+/*
+ * The launch shape, fixed at creation: path 0 = one-workgroup chain (k = 2, w = 16 / tiles waves per receiver tile,
+ * lanes = 1: the per-step shape k, w, split = 1, unit = 8 it is bit-equal to), path 1 = lane-split (k = 1, w waves per
+ * workgroup, `lanes` lane groups per wave); workgroups per launch.  Any pointer may be NULL.
+ */
+void nb_hip_batch_launch_shape(const SimBatch *batch, int *path, int *k, int *w, int *lanes, uint32_t *workgroups);
 
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int nb_hip_version(void);

@@ -102,6 +102,19 @@ HIP_API = {
     "nb_hip_local_group_step": (None, [C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_float]),
     "nb_hip_energy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
     "nb_hip_potential": (None, [C.c_void_p, C.c_void_p]),
+    "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "nb_hip_batch_destroy": (None, [C.c_void_p]),
+    "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
+    "nb_hip_batch_get_data": (None, [C.c_void_p, C.c_void_p]),
+    "nb_hip_batch_get_member": (None, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nb_hip_batch_update": (None, [C.c_void_p, C.c_uint32, C.c_float]),
+    "nb_hip_batch_update_dts": (None, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),
+    "nb_hip_batch_step_async": (None, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),
+    "nb_hip_batch_sync": (None, [C.c_void_p]),
+    "nb_hip_batch_last_ms": (C.c_double, [C.c_void_p]),
+    "nb_hip_batch_dt_uploads": (C.c_uint32, [C.c_void_p]),
+    "nb_hip_batch_launch_shape": (None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "nb_hip_version": (C.c_int, []),
 }
 
@@ -119,7 +132,7 @@ TUNE_API = {
 }
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
-# include/nbody.h + include/galaxy.h + include/nbody_diag.h
+# include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -134,6 +147,12 @@ NBODY_API = {
     "MakeGalaxiesSeeded": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "GetWorldEnergy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
     "GetWorldPotential": (None, [C.c_void_p, C.c_void_p]),
+    # include/nbody_batch.h
+    "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "DestroyWorldBatch": (None, [C.c_void_p]),
+    "GetWorldBatchParticles": (C.c_void_p, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "UpdateWorldBatch_GPU": (None, [C.c_void_p, C.c_float, C.c_uint32]),
+    "UpdateWorldBatch_GPU_dts": (None, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
 }
 
 _hip = None
@@ -408,6 +427,130 @@ class SimPipeline:
         return {"k": k.value, "w": w.value, "variant": "smem" if v.value else "lds", "split": sp.value,
                 "workgroups": g.value, "unit": int(hip_lib().nb_hip_launch_unit(self._h)),
                 "lanes": int(hip_lib().nb_hip_launch_lanes(self._h))}
+
+
+def as_ensemble(a):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 8:
+        raise ValueError("an ensemble must have shape (members, n, 8)")
+    return a
+
+
+def _dt_array(dts, count):
+    a = np.ascontiguousarray(dts, dtype=np.float32)
+    if a.shape != (count,):
+        raise ValueError(f"expected {count} step sizes")
+    return a
+
+
+class SimBatch:
+    """include/nbody_hip.h SimBatch: B independent worlds of the same size, stepped together (nb_hip_batch_*).
+
+    Particles are float32 arrays of shape (B, n, 8), every member already partitioned (mass > 0 first) with
+    `mass_len[b]` massive ones.  Member b ends bit-identical to the same particles alone in a SimPipeline pinned to
+    launch_shape()."""
+
+    def __init__(self, total_len, mass_len):
+        m = np.ascontiguousarray(mass_len, dtype=np.uint32)
+        if m.ndim != 1:
+            raise ValueError("mass_len must be a sequence with one entry per member")
+        self.count, self.total_len, self.mass_len = int(m.shape[0]), int(total_len), m.copy()
+        self._h = hip_lib().nb_hip_batch_create(self.count, self.total_len, m.ctypes.data_as(C.POINTER(C.c_uint32)))
+
+    def close(self):
+        if self._h:
+            hip_lib().nb_hip_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_data(self, particles):
+        a = as_ensemble(particles)
+        assert a.shape[:2] == (self.count, self.total_len)
+        hip_lib().nb_hip_batch_set_data(self._h, a.ctypes.data)
+
+    def get_data(self):
+        out = np.empty((self.count, self.total_len, 8), dtype=np.float32)
+        hip_lib().nb_hip_batch_get_data(self._h, out.ctypes.data)
+        return out
+
+    def get_member(self, b):
+        out = np.empty((self.total_len, 8), dtype=np.float32)
+        hip_lib().nb_hip_batch_get_member(self._h, int(b), out.ctypes.data)
+        return out
+
+    def update(self, n, dt):
+        """Blocking n steps of every member; dt: one step size, or one per member."""
+        if np.ndim(dt) == 0:
+            hip_lib().nb_hip_batch_update(self._h, n, float(dt))
+        else:
+            hip_lib().nb_hip_batch_update_dts(self._h, n, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)))
+
+    def step_async(self, n, dts):
+        hip_lib().nb_hip_batch_step_async(self._h, n, _dt_array(dts, self.count).ctypes.data_as(C.POINTER(C.c_float)))
+
+    def sync(self):
+        hip_lib().nb_hip_batch_sync(self._h)
+
+    def last_ms(self):
+        """device ms of the kernels of the last update"""
+        return float(hip_lib().nb_hip_batch_last_ms(self._h))
+
+    def dt_uploads(self):
+        return int(hip_lib().nb_hip_batch_dt_uploads(self._h))
+
+    def launch_shape(self):
+        """path "chain" / "lanes" plus the knobs that pin a SimPipeline to the same summation order (pinned_knobs)."""
+        path, k, w, lanes, g = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_uint32()
+        hip_lib().nb_hip_batch_launch_shape(self._h, C.byref(path), C.byref(k), C.byref(w), C.byref(lanes), C.byref(g))
+        return {"path": "lanes" if path.value else "chain", "k": k.value, "w": w.value, "lanes": lanes.value,
+                "workgroups": g.value}
+
+    def pinned_knobs(self):
+        """SimPipeline.configure(**pinned_knobs()) pins a single pipeline to this ensemble's launch shape."""
+        s = self.launch_shape()
+        if s["path"] == "chain":
+            return dict(k=s["k"], w=s["w"], split=1, unit=8, fused_chain=0)
+        return dict(lanes=s["lanes"], w=s["w"], fused_chain=0)
+
+
+class WorldBatch:
+    """include/nbody_batch.h WorldBatch, bound 1:1: (B, n, 8) particles in caller order; every member is partitioned
+    like CreateWorld partitions it."""
+
+    def __init__(self, particles):
+        a = as_ensemble(particles)
+        self.count, self.size = int(a.shape[0]), int(a.shape[1])
+        self._h = nbody_lib().CreateWorldBatch(a.ctypes.data, self.size, self.count)
+
+    def close(self):
+        if self._h:
+            nbody_lib().DestroyWorldBatch(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def member(self, b):
+        n = C.c_uint32(0)
+        p = nbody_lib().GetWorldBatchParticles(self._h, int(b), C.byref(n))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value, 8)).copy()
+
+    def particles(self):
+        return np.stack([self.member(b) for b in range(self.count)])
+
+    def update_gpu(self, dt, n):
+        if np.ndim(dt) == 0:
+            nbody_lib().UpdateWorldBatch_GPU(self._h, float(dt), n)
+        else:
+            nbody_lib().UpdateWorldBatch_GPU_dts(self._h, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)), n)
 
 
 class LocalShardGroup:

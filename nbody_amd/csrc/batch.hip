@@ -1,0 +1,279 @@
+// batch.hip -- SimBatch: an ensemble of B independent worlds with the same particle count, stepped together
+// (include/nbody_hip.h "World ensembles").
+//
+// One small world cannot use the chip: below N ~ 4 000 a step is the kernel boundary plus one wave's dependency chain, and
+// the one-workgroup chain sits on ONE of 256 compute units.  The other CUs can only be used by more
+// worlds, so this file steps B of them per launch:
+//   N <= 512          batch_chain_kernel: workgroup b runs member b's whole n-step call (positions ping-pong in LDS), one
+//                     launch per call, for every call length and every B;
+//   512 < N <= 3 000  batch_lane_split_kernel<W, H>: gridDim.y = B, one launch per step, positions ping-pong between two
+//                     device arrays; (W, H) = lane_split_rule(N, N), a function of N alone.
+// The path is chosen by N alone -- never by B or by the members' source counts -- and the kernels run the very bodies of
+// chain_kernel / lane_split_kernel, so member b's bits are those of the same particles alone in a SimPipeline pinned to
+// that shape (tests/test_gpu_batch.py).  Members share nothing with each other and a SimBatch shares nothing with any
+// SimPipeline: own stream, own buffers, own events.
+#include "pipeline_internal.h"
+
+using namespace nbi;
+
+struct SimBatch {
+    uint32_t count = 0;     // members
+    uint32_t n = 0;         // particles per member
+    uint32_t stride = 0;    // rows per member in the SoA arrays: n rounded up to 64 (256-byte aligned float rows)
+    std::vector<uint32_t> mass_len;   // [count]
+    std::vector<float> dt_host;       // [count]: what dt_dev holds (valid once dt_valid)
+    bool dt_valid = false;
+    uint32_t dt_uploads = 0;
+
+    bool on_device = false;
+    bool has_data = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool timed = false;
+    float2 *pos[2] = {nullptr, nullptr};
+    float2 *vel = nullptr, *acc = nullptr;
+    float *radius = nullptr, *mass = nullptr, *gm = nullptr;
+    uint32_t *mass_len_dev = nullptr;
+    float *dt_dev = nullptr;
+    void *aos = nullptr;   // device staging of Set / Get: [count][n] Particle
+    int cur = 0;           // pos[cur] is the latest state (the chain path never moves it)
+
+    // the launch shape, fixed at creation
+    int path = 0;          // 0 chain, 1 lane-split
+    int k = 2, w = 16, lanes = 1;
+    uint32_t tiles = 0;
+    uint32_t workgroups = 0;
+};
+
+namespace {
+
+void materialize(SimBatch *s) {
+    use_device();
+    if (s->on_device) return;
+    ASSERT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "stream");
+    for (auto &e : s->ev) ASSERT_HIP(hipEventCreate(&e), "event");
+    const size_t rows = (size_t)s->count * s->stride;
+    for (int b = 0; b < 2; b++) {
+        if (b == 1 && s->path == 0) break;   // the chain updates positions in place
+        s->pos[b] = dev_alloc<float2>(rows);
+        ASSERT_HIP(hipMemsetAsync(s->pos[b], 0, rows * sizeof(float2), s->stream), "clear positions");
+    }
+    s->vel = dev_alloc<float2>(rows);
+    s->acc = dev_alloc<float2>(rows);
+    s->radius = dev_alloc<float>(rows);
+    s->mass = dev_alloc<float>(rows);
+    s->gm = dev_alloc<float>(rows);
+    s->mass_len_dev = dev_alloc<uint32_t>(s->count);
+    s->dt_dev = dev_alloc<float>(s->count);
+    s->aos = dev_alloc<Particle>((size_t)s->count * s->n);
+    ASSERT_HIP(hipMemcpyAsync(s->mass_len_dev, s->mass_len.data(), (size_t)s->count * sizeof(uint32_t), hipMemcpyHostToDevice,
+                              s->stream),
+               "H2D of %u source counts", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after the first device set-up");
+    s->on_device = true;
+}
+
+// The step sizes of everything enqueued from here on; uploaded only when a value changed.  One dt for all: a fill
+// launch in stream order.  Per-member values: the stream is drained first, so steps already queued keep theirs.
+void upload_dts(SimBatch *s, const float *dt, bool uniform) {
+    bool same = s->dt_valid;
+    for (uint32_t b = 0; same && b < s->count; b++) {
+        const float v = uniform ? dt[0] : dt[b];
+        same = memcmp(&v, &s->dt_host[b], sizeof v) == 0;
+    }
+    if (same) return;
+    for (uint32_t b = 0; b < s->count; b++) s->dt_host[b] = uniform ? dt[0] : dt[b];
+    if (uniform) {
+        nb::launch_batch_fill(s->stream, s->dt_dev, s->count, dt[0]);
+    } else {
+        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before a per-member step-size upload");
+        ASSERT_HIP(hipMemcpy(s->dt_dev, s->dt_host.data(), (size_t)s->count * sizeof(float), hipMemcpyHostToDevice),
+                   "H2D of %u step sizes", s->count);
+    }
+    s->dt_valid = true;
+    s->dt_uploads++;
+}
+
+void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
+    NB_ASSERT(s != nullptr && dt != nullptr, "NULL argument");
+    NB_ASSERT(s->has_data, "ensemble update before nb_hip_batch_set_data");
+    if (n == 0) return;
+    use_device();
+    upload_dts(s, dt, uniform);
+    nb::BatchParams p;
+    memset(&p, 0, sizeof p);
+    p.vel = s->vel;
+    p.acc = s->acc;
+    p.radius = s->radius;
+    p.gm = s->gm;
+    p.mass_len = s->mass_len_dev;
+    p.dt = s->dt_dev;
+    p.n_recv = s->n;
+    p.stride = s->stride;
+    p.tiles = s->tiles;
+    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+    if (s->path == 0) {
+        p.pos_in = p.pos_out = s->pos[s->cur];
+        for (uint32_t left = n; left > 0; left -= p.steps) {
+            p.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
+            nb::launch_batch_chain(s->stream, p, s->count);
+        }
+    } else {
+        const void *fn = nb::batch_lane_split_fn(s->w, s->lanes);
+        const nb::LaunchShape sh = {.k = 1, .w = s->w, .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = s->lanes};
+        dim3 grid = nb::step_grid(sh, s->n);
+        grid.y = s->count;
+        for (uint32_t i = 0; i < n; i++) {
+            p.pos_in = s->pos[s->cur];
+            p.pos_out = s->pos[s->cur ^ 1];
+            void *args[] = {&p};
+            ASSERT_HIP(hipLaunchKernel(fn, grid, nb::step_block(sh), args, nb::step_lds_bytes(sh, s->n), s->stream),
+                       "ensemble lane-split launch (w=%d lanes=%d, %u members of %u)", s->w, s->lanes, s->count, s->n);
+            s->cur ^= 1;
+        }
+    }
+    ASSERT_HIP(hipGetLastError(), "ensemble launch (%u members of %u particles, %u steps)", s->count, s->n, n);
+    ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
+    s->timed = true;
+}
+
+void read_back(SimBatch *s, uint32_t first, uint32_t members, Particle *ps) {
+    NB_ASSERT(s != nullptr && ps != nullptr, "NULL argument");
+    NB_ASSERT(s->has_data, "ensemble read-back before nb_hip_batch_set_data");
+    use_device();
+    nb::launch_batch_merge(s->stream, s->aos, first, members, s->n, s->stride, s->pos[s->cur], s->vel, s->acc, s->radius, s->mass);
+    ASSERT_HIP(hipMemcpyAsync(ps, static_cast<const Particle *>(s->aos) + (size_t)first * s->n,
+                              (size_t)members * s->n * sizeof(Particle), hipMemcpyDeviceToHost, s->stream),
+               "D2H of %u members", members);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after an ensemble read-back");
+}
+
+}  // namespace
+
+extern "C" {
+
+SimBatch *nb_hip_batch_create(uint32_t count, uint32_t total_len, const uint32_t *mass_len) {
+    NB_ASSERT(count > 0, "an ensemble needs at least one member (count = 0)");
+    NB_ASSERT(count <= NB_HIP_BATCH_MAX_COUNT, "count %u > %u members (the grid's y extent)", count, NB_HIP_BATCH_MAX_COUNT);
+    NB_ASSERT(total_len > 0, "total_len = 0: an ensemble of empty worlds");
+    NB_ASSERT(total_len <= nb::BATCH_MAX_RECV, "total_len %u > %u: ensembles step worlds of at most %u particles", total_len,
+              nb::BATCH_MAX_RECV, nb::BATCH_MAX_RECV);
+    NB_ASSERT(mass_len != nullptr, "NULL mass_len array");
+    for (uint32_t b = 0; b < count; b++)
+        NB_ASSERT(mass_len[b] <= total_len, "member %u: mass_len %u > total_len %u", b, mass_len[b], total_len);
+    SimBatch *s = new SimBatch();
+    s->count = count;
+    s->n = total_len;
+    s->stride = round_up(total_len, 64);
+    s->mass_len.assign(mass_len, mass_len + count);
+    s->dt_host.assign(count, 0.0f);
+    s->tiles = nb::chain_tiles(total_len);
+    if (s->tiles) {
+        s->path = 0;
+        s->k = 2;
+        s->w = (int)(16u / s->tiles);
+        s->lanes = 1;
+        s->workgroups = count;
+    } else {
+        s->path = 1;
+        s->k = 1;
+        s->lanes = nb::batch_lane_shape(total_len, &s->w);
+        NB_ASSERT(s->lanes > 1 && nb::batch_lane_split_fn(s->w, s->lanes) != nullptr, "no ensemble kernel for w=%d lanes=%d", s->w,
+                  s->lanes);
+        s->workgroups = count * ((total_len + 64u / (uint32_t)s->lanes - 1) / (64u / (uint32_t)s->lanes));
+    }
+    return s;
+}
+
+void nb_hip_batch_destroy(SimBatch *s) {
+    if (s == nullptr) return;
+    if (s->on_device) {
+        use_device();
+        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before destroying an ensemble");
+        for (auto &p : s->pos) dev_free(p);
+        dev_free(s->vel);
+        dev_free(s->acc);
+        dev_free(s->radius);
+        dev_free(s->mass);
+        dev_free(s->gm);
+        dev_free(s->mass_len_dev);
+        dev_free(s->dt_dev);
+        dev_free(s->aos);
+        for (auto &e : s->ev) ASSERT_HIP(hipEventDestroy(e), "event");
+        ASSERT_HIP(hipStreamDestroy(s->stream), "stream");
+    }
+    delete s;
+}
+
+void nb_hip_batch_set_data(SimBatch *s, const Particle *ps) {
+    NB_ASSERT(s != nullptr && ps != nullptr, "NULL argument");
+    if (!s->on_device) {
+        // first touch: stream, HBM, code objects -- none of it may move the caller's rand() stream
+        RandGuard keep_callers_rand_stream;
+        materialize(s);
+    }
+    use_device();
+    s->cur = 0;
+    ASSERT_HIP(hipMemcpyAsync(s->aos, ps, (size_t)s->count * s->n * sizeof(Particle), hipMemcpyHostToDevice, s->stream),
+               "H2D of %u x %u particles", s->count, s->n);
+    nb::launch_batch_split(s->stream, s->aos, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0], s->vel, s->acc, s->radius, s->mass,
+                           s->gm, NB_G);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_batch_set_data");
+    s->has_data = true;
+}
+
+void nb_hip_batch_get_data(const SimBatch *s, Particle *ps) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    read_back(const_cast<SimBatch *>(s), 0, s->count, ps);
+}
+
+void nb_hip_batch_get_member(const SimBatch *s, uint32_t b, Particle *ps) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(b < s->count, "member %u of %u", b, s->count);
+    read_back(const_cast<SimBatch *>(s), b, 1, ps);
+}
+
+void nb_hip_batch_step_async(SimBatch *s, uint32_t n, const float *dt) { enqueue(s, n, dt, false); }
+
+void nb_hip_batch_sync(SimBatch *s) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (!s->on_device) return;
+    use_device();
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "stream sync");
+}
+
+void nb_hip_batch_update(SimBatch *s, uint32_t n, float dt) {
+    enqueue(s, n, &dt, true);
+    nb_hip_batch_sync(s);
+}
+
+void nb_hip_batch_update_dts(SimBatch *s, uint32_t n, const float *dt) {
+    enqueue(s, n, dt, false);
+    nb_hip_batch_sync(s);
+}
+
+double nb_hip_batch_last_ms(SimBatch *s) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (!s->timed) return 0.0;
+    use_device();
+    ASSERT_HIP(hipEventSynchronize(s->ev[1]), "event sync");
+    float ms = 0.0f;
+    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]), "elapsed time");
+    return (double)ms;
+}
+
+uint32_t nb_hip_batch_dt_uploads(const SimBatch *s) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    return s->dt_uploads;
+}
+
+void nb_hip_batch_launch_shape(const SimBatch *s, int *path, int *k, int *w, int *lanes, uint32_t *workgroups) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (path) *path = s->path;
+    if (k) *k = s->k;
+    if (w) *w = s->w;
+    if (lanes) *lanes = s->lanes;
+    if (workgroups) *workgroups = s->workgroups;
+}
+
+}  // extern "C"

@@ -82,6 +82,26 @@ struct ChainParams {
 
 constexpr uint32_t CHAIN_MAX_RECV = 512;   // 4 tiles of 128 receivers (K = 2)
 
+// An ensemble of `count` independent worlds with the same particle count, stepped by one launch (batch_chain_kernel: one
+// workgroup per member runs the whole chain; batch_lane_split_kernel: gridDim.y = count, one launch per step).  Member-major
+// SoA: every array is [count][stride], stride >= n_recv and a multiple of 64, so each member's rows stay 256-byte aligned.
+// Member b's sources are its first mass_len[b] particles; its step size is dt[b].  Both are read from device memory.
+struct BatchParams {
+    float2 *pos_in;       // state before the step (chain: before the call, updated in place)
+    float2 *pos_out;      // lane-split: state after the step; chain: unused
+    float2 *vel;
+    float2 *acc;
+    const float *radius;
+    const float *gm;      // G*m, 0 in rows that are not sources
+    const uint32_t *mass_len;   // [count]
+    const float *dt;            // [count]
+    uint32_t n_recv;      // particles per member
+    uint32_t stride;      // rows per member
+    uint32_t steps;       // chain only: steps of this launch, >= 1
+    uint32_t tiles;       // chain only: chain_tiles(n_recv)
+};
+constexpr uint32_t BATCH_MAX_RECV = 3000;   // lane_split_rule's own cut-off at n_src = n_recv (N x N <= 9e6)
+
 // A launch shape; 0 = "auto" in a request to choose_shape.  Write one with named fields ({.k = 2, .w = 16}): the
 // defaults are the all-auto request.
 struct LaunchShape {
@@ -129,6 +149,18 @@ dim3 finish_block();
 // the one-workgroup chain: 1024 threads, one block; tiles from chain_tiles(n_recv) (0: the world does not fit)
 uint32_t chain_tiles(uint32_t n_recv);
 void launch_chain(hipStream_t st, const ChainParams &p);
+
+// ensembles: the lane-split shape for members of n_recv particles (lanes; 1 = none: N > BATCH_MAX_RECV), the kernel of a
+// shape (nullptr when not instantiated), and the launches
+int batch_lane_shape(uint32_t n_recv, int *w);
+const void *batch_lane_split_fn(int w, int lanes);
+void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count);
+// whole-ensemble converters: member-major AoS [count][n] <-> SoA [count][stride]; split also writes G*m
+void launch_batch_split(hipStream_t st, const void *aos, const uint32_t *mass_len, uint32_t count, uint32_t n, uint32_t stride,
+                        float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g);
+void launch_batch_merge(hipStream_t st, void *aos, uint32_t first, uint32_t count, uint32_t n, uint32_t stride, const float2 *pos,
+                        const float2 *vel, const float2 *acc, const float *radius, const float *mass);
+void launch_batch_fill(hipStream_t st, float *dst, uint32_t count, float value);   // dst[0 .. count) = value, in stream order
 
 // AoS <-> SoA converters (reference Particle layout, include/nbody.h).
 // split: aos[first .. first+count) -> soa slots [slot0 .. slot0+count)

@@ -534,8 +534,11 @@ __global__ __launch_bounds__(WAVE *W, 8) void step_kernel(const StepParams p) {
 // sources per tile, coalesced loads, fetched into registers one tile ahead), and every lane reads its own slice of the
 // tile -- per-lane data is what LDS is for (cf. "Why the LDS-tile route trails").  K = 1, split = 1, slices in 8-source
 // granules, Kahan block closes every 128 sources a lane has added.
+//
+// The body is a device function of the parameter block: lane_split_kernel runs it for one world, batch_lane_split_kernel
+// (below) for member blockIdx.y of an ensemble.  blockIdx.x is the receiver tile in both.
 template <int W, int H>
-__global__ __launch_bounds__(WAVE *W) void lane_split_kernel(const StepParams p) {
+__device__ __forceinline__ void lane_split_body(const StepParams &p) {
     constexpr uint32_t R = WAVE / H;        // receivers per workgroup
     constexpr uint32_t V = W * H;           // source slices per receiver
     constexpr uint32_t T = 2 * WAVE * W;    // sources per staged tile: two per thread (12 KB at W = 8, 24 KB at W = 16)
@@ -680,6 +683,11 @@ __global__ __launch_bounds__(WAVE *W) void lane_split_kernel(const StepParams p)
     }
 }
 
+template <int W, int H>
+__global__ __launch_bounds__(WAVE *W) void lane_split_kernel(const StepParams p) {
+    lane_split_body<W, H>(p);
+}
+
 // ---- the one-workgroup chain -------------------------------------------------------------------------------------
 //
 // Worlds of a few hundred particles are bound by the kernel boundary, not by arithmetic: at N = 250 a step is 30 000
@@ -696,7 +704,8 @@ __global__ __launch_bounds__(WAVE *W) void lane_split_kernel(const StepParams p)
 // roundings -- tests/test_gpu_parity.py holds it to plain launches of k = 2, w = 16 / tiles, split = 1, unit = 8.
 constexpr uint32_t CHAIN_K = 2;
 
-__global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) {
+// (the body as a device function: chain_kernel runs it for one world, batch_chain_kernel for one member per workgroup)
+__device__ __forceinline__ void chain_body(const ChainParams &p) {
     constexpr int K = CHAIN_K;
     __shared__ __attribute__((aligned(16))) float spos[2][2 * CHAIN_MAX_RECV];  // (x, y) interleaved, ping-pong
     __shared__ __attribute__((aligned(16))) float sgm[CHAIN_MAX_RECV];
@@ -774,6 +783,61 @@ __global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) {
     }
 }
 
+__global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) { chain_body(p); }
+
+// ---- world ensembles: B independent worlds of the same N in one launch -------------------------------------------
+//
+// A single world of N <= 3 000 keeps one (chain) or a handful (lane-split) of the chip's 256 compute units busy; the
+// others can only be used by MORE WORLDS.  The two kernels below run the bodies above once per member: nothing is
+// copied, so member b's bits are those of the same world alone in chain_kernel / lane_split_kernel<W, H>, whatever B,
+// its index or its neighbours are.  Layout: member-major SoA, every array [B][stride]; a member's source count and step
+// size come from device memory (mass_len[b], dt[b]), so neither is baked into a launch.
+__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+
+__global__ __launch_bounds__(1024) void batch_chain_kernel(const BatchParams bp) {
+    const size_t base = (size_t)blockIdx.x * bp.stride;
+    ChainParams p;
+    p.pos = bp.pos_in + base;   // updated in place, like the single chain
+    p.vel = bp.vel + base;
+    p.acc = bp.acc + base;
+    p.radius = bp.radius + base;
+    p.src_gm = bp.gm + base;
+    p.n_recv = bp.n_recv;
+    p.n_src = uniform_u32(bp.mass_len[blockIdx.x]);
+    p.steps = bp.steps;
+    p.tiles = bp.tiles;
+    p.dt = bp.dt + blockIdx.x;
+    chain_body(p);
+}
+
+template <int W, int H>
+__global__ __launch_bounds__(WAVE *W) void batch_lane_split_kernel(const BatchParams bp) {
+    const size_t base = (size_t)blockIdx.y * bp.stride;
+    StepParams p;
+    p.src_pos = bp.pos_in + base;   // the first mass_len[b] receivers of a member ARE its sources
+    p.src_gm = bp.gm + base;
+    p.src_begin[0] = 0;
+    p.src_end[0] = uniform_u32(bp.mass_len[blockIdx.y]);
+    p.src_begin[1] = p.src_end[1] = 0;
+    p.pos_in = bp.pos_in + base;
+    p.pos_out = bp.pos_out + base;
+    p.vel = bp.vel + base;
+    p.acc = bp.acc + base;
+    p.radius = bp.radius + base;
+    p.n_recv = bp.n_recv;
+    p.recv_split = bp.n_recv;
+    p.recv_gap = 0;
+    p.mirror = nullptr;
+    p.n_mirror = 0;
+    p.dt = bp.dt + blockIdx.y;
+    p.flags = 0;
+    p.parts = nullptr;
+    p.split = 1;
+    p.tickets = nullptr;
+    p.unit = 8;
+    lane_split_body<W, H>(p);
+}
+
 // ---- AoS <-> SoA ----------------------------------------------------------------------------------------
 
 struct alignas(16) ParticleRec {  // == Particle (include/nbody.h): pos vel | acc mass radius
@@ -842,6 +906,40 @@ __global__ void split_sources_kernel(const ParticleRec *aos, uint32_t mass_len, 
     pos0[i] = q;
     pos1[i] = q;
     gm[i] = g;
+}
+
+// Ensemble upload: member blockIdx.y's AoS records into its SoA rows, and G*m of its sources (as make_gm_kernel; rows
+// past mass_len[b] hold no source and get 0).  One launch for the whole ensemble.
+__global__ void batch_split_kernel(const ParticleRec *aos, const uint32_t *mass_len, uint32_t n, uint32_t stride, float2 *pos,
+                                   float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= n) return;
+    const ParticleRec r = aos[(size_t)b * n + i];
+    const size_t o = (size_t)b * stride + i;
+    pos[o] = make_float2(r.a.x, r.a.y);
+    vel[o] = make_float2(r.a.z, r.a.w);
+    acc[o] = make_float2(r.b.x, r.b.y);
+    mass[o] = r.b.z;
+    radius[o] = r.b.w;
+    gm[o] = (i < mass_len[b] && r.b.z > 0.0f) ? __fmul_rn(r.b.z, g) : 0.0f;
+}
+
+// Ensemble read-back: members [first, first + gridDim.y) back into their AoS records.
+__global__ void batch_merge_kernel(ParticleRec *aos, uint32_t first, uint32_t n, uint32_t stride, const float2 *pos,
+                                   const float2 *vel, const float2 *acc, const float *radius, const float *mass) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = first + blockIdx.y;
+    if (i >= n) return;
+    const size_t o = (size_t)b * stride + i;
+    const float2 q = pos[o], v = vel[o], a = acc[o];
+    ParticleRec r;
+    r.a = make_float4(q.x, q.y, v.x, v.y);
+    r.b = make_float4(a.x, a.y, mass[o], radius[o]);
+    aos[(size_t)b * n + i] = r;
+}
+
+__global__ void batch_fill_kernel(float *dst, uint32_t count, float value) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) dst[i] = value;
 }
 
 inline dim3 grid1d(uint32_t count) { return dim3((count + 255u) / 256u); }
@@ -1073,6 +1171,39 @@ uint32_t chain_tiles(uint32_t n_recv) {
 
 void launch_chain(hipStream_t st, const ChainParams &p) {
     hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(1024), 0, st, p);
+}
+
+// ---- ensembles ------------------------------------------------------------------------------------------------------
+// The lane-split shape of an ensemble is a function of N alone (members differ in their source counts, and a member's bits
+// must not depend on them): the auto rule at n_src = n_recv, whose cut-off N x N <= 9e6 is N <= 3 000.
+int batch_lane_shape(uint32_t n_recv, int *w) { return lane_split_rule(n_recv, n_recv, w); }
+
+const void *batch_lane_split_fn(int w, int h) {
+    // the two shapes batch_lane_shape reaches for 512 < N <= 3 000
+    if (w == 8 && h == 8) return reinterpret_cast<const void *>(&batch_lane_split_kernel<8, 8>);
+    if (w == 16 && h == 4) return reinterpret_cast<const void *>(&batch_lane_split_kernel<16, 4>);
+    return nullptr;
+}
+
+void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count) {
+    hipLaunchKernelGGL(batch_chain_kernel, dim3(count), dim3(1024), 0, st, p);
+}
+
+void launch_batch_split(hipStream_t st, const void *aos, const uint32_t *mass_len, uint32_t count, uint32_t n, uint32_t stride,
+                        float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g) {
+    hipLaunchKernelGGL(batch_split_kernel, dim3((n + 255u) / 256u, count), dim3(256), 0, st, static_cast<const ParticleRec *>(aos),
+                       mass_len, n, stride, pos, vel, acc, radius, mass, gm, g);
+}
+
+void launch_batch_merge(hipStream_t st, void *aos, uint32_t first, uint32_t count, uint32_t n, uint32_t stride, const float2 *pos,
+                        const float2 *vel, const float2 *acc, const float *radius, const float *mass) {
+    if (count == 0) return;
+    hipLaunchKernelGGL(batch_merge_kernel, dim3((n + 255u) / 256u, count), dim3(256), 0, st, static_cast<ParticleRec *>(aos), first, n,
+                       stride, pos, vel, acc, radius, mass);
+}
+
+void launch_batch_fill(hipStream_t st, float *dst, uint32_t count, float value) {
+    hipLaunchKernelGGL(batch_fill_kernel, grid1d(count), dim3(256), 0, st, dst, count, value);
 }
 
 void launch_split(hipStream_t st, const void *aos, uint32_t first, uint32_t count, float2 *pos, float2 *vel, float2 *acc,

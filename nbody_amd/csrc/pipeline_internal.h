@@ -6,6 +6,7 @@
 //   step_chain.hip   one step / n steps as launches, cached hipGraph chains, the sharded step with its all-gather
 //   pipeline.hip     SimPipeline life cycle and the C-ABI entry points (Create/Destroy/Set/Get/PerformSimUpdate, knobs)
 //   kernels.hip      the gfx950 kernels (kernels.h)
+//   batch.hip        SimBatch: ensembles of small worlds stepped by one launch (nb_hip_batch_*)
 //   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
 #pragma once
 
@@ -295,6 +296,7 @@ namespace nbi {
 // ---- step_chain.hip ------------------------------------------------------------------------------------------
 
 constexpr uint32_t CANON_STEPS = 32;  // length of the prebuilt chain of small worlds (see wants_canonical)
+constexpr uint32_t CHAIN_MAX_STEPS_PER_LAUNCH = 1u << 16;   // steps one launch of the one-workgroup chain runs (batch.hip too)
 constexpr uint32_t DETAIL_STEPS_MAX = 256;  // steps per call whose kernels / gathers get their own event pairs
 
 void destroy_graph(StepGraph &g);

@@ -313,7 +313,6 @@ constexpr double CANON_MAX_PAIRS = 6.0e7;  // N x M up to which a replay still p
 // per-step kernel).  1 = whenever the world fits (N <= 512), whatever the other knobs say; 0 = never.
 constexpr double CHAIN_MAX_PAIRS = 3.6e4;
 constexpr uint32_t CHAIN_AUTO_MAX_RECV = 256;
-constexpr uint32_t CHAIN_MAX_STEPS_PER_LAUNCH = 1u << 16;
 
 bool wants_fused_chain(const SimPipeline *s) {
     if (s->sharded || s->fused_chain == 0 || s->n_real == 0 || nb::chain_tiles(s->n_real) == 0) return false;

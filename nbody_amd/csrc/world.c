@@ -28,6 +28,7 @@
 #include "diag_sums.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
+#include "world_partition.h"
 
 struct World {
     Particle *particles;  /* partitioned copy of the caller's array */
@@ -39,28 +40,6 @@ struct World {
     bool device_is_newer; /* device stepped since the array was last refreshed */
     int nranks;           /* > 1: sharded (the pipeline holds 1/nranks of the receivers) */
 };
-
-/*
- * In-place unstable partition, massive particles first; returns their count.
- * `lo` hunts upward for a massless slot, `hi` downward for a massive one, and
- * they swap until they meet -- the reference's scheme, kept because its output
- * permutation is part of the observable contract.
- */
-static uint32_t partition_by_mass(Particle *p, uint32_t count) {
-    uint32_t lo = 0, hi = count;
-    for (;;) {
-        for (; lo < hi && p[lo].mass > 0; lo++) {
-        }
-        while (lo < hi) {
-            hi--;
-            if (!(p[hi].mass <= 0)) break;
-        }
-        if (lo == hi) return hi;
-        const Particle keep = p[lo];
-        p[lo] = p[hi];
-        p[hi] = keep;
-    }
-}
 
 /* rank < 0: an ordinary single-GPU World; otherwise the sharded pipeline of include/nbody_hip.h. */
 static World *create_world(const Particle *ps, uint32_t size, int rank, int nranks, const void *unique_id128,

@@ -1,0 +1,85 @@
+/*
+ * world_batch.c -- the include/nbody_batch.h surface: an ensemble of Worlds over one SimBatch (include/nbody_hip.h).
+ *
+ * The World protocol (world.c) for `count` members at once: the caller's particles are copied and every member is
+ * partitioned "mass > 0 first" with CreateWorld's own routine (world_partition.h); the array is uploaded before the
+ * first GPU step and pulled back only when a read follows a step.  Nothing on the host changes the array after
+ * creation (no CPU stepper for ensembles), so one upload is all there ever is.
+ */
+#include "nbody_batch.h"
+#include "nbody_hip.h"
+
+#include <stdbool.h>
+
+#include "nb_util.h"
+#include "world_partition.h"
+
+struct WorldBatch {
+    Particle *particles;  /* count * size, member-major, each member partitioned */
+    uint32_t size;        /* particles per member */
+    uint32_t count;       /* members */
+    SimBatch *gpu;
+    bool uploaded;        /* the device has seen the array */
+    bool device_is_newer; /* the device stepped since the array was last refreshed */
+};
+
+WorldBatch *CreateWorldBatch(const Particle *ps, uint32_t world_size, uint32_t count) {
+    NB_CHECK(ps != NULL, "NULL particle array");
+    NB_CHECK(count > 0 && count <= NB_HIP_BATCH_MAX_COUNT, "count %u outside 1 .. %u", count, NB_HIP_BATCH_MAX_COUNT);
+    NB_CHECK(world_size > 0 && world_size <= NB_HIP_BATCH_MAX_LEN, "world_size %u outside 1 .. %u", world_size, NB_HIP_BATCH_MAX_LEN);
+    WorldBatch *w = NB_NEW(1, WorldBatch);
+    NB_CHECK(w != NULL, "Failed to alloc WorldBatch");
+    const size_t total = (size_t)world_size * count;
+    w->particles = NB_NEW(total, Particle);
+    uint32_t *massive = NB_NEW(count, uint32_t);
+    NB_CHECK(w->particles != NULL && massive != NULL, "Failed to alloc %u x %u particles", count, world_size);
+    memcpy(w->particles, ps, total * sizeof(Particle));
+    for (uint32_t b = 0; b < count; b++) massive[b] = partition_by_mass(w->particles + (size_t)b * world_size, world_size);
+    w->size = world_size;
+    w->count = count;
+    w->gpu = nb_hip_batch_create(count, world_size, massive);
+    free(massive);
+    w->uploaded = false;
+    w->device_is_newer = false;
+    return w;
+}
+
+void DestroyWorldBatch(WorldBatch *w) {
+    if (w == NULL) return;
+    nb_hip_batch_destroy(w->gpu);
+    free(w->particles);
+    free(w);
+}
+
+const Particle *GetWorldBatchParticles(WorldBatch *w, uint32_t member, uint32_t *size) {
+    NB_CHECK(w != NULL, "NULL WorldBatch");
+    NB_CHECK(member < w->count, "member %u of %u", member, w->count);
+    if (w->device_is_newer) {
+        nb_hip_batch_get_data(w->gpu, w->particles);
+        w->device_is_newer = false;
+    }
+    if (size != NULL) *size = w->size;
+    return w->particles + (size_t)member * w->size;
+}
+
+static void push_once(WorldBatch *w) {
+    if (w->uploaded) return;
+    nb_hip_batch_set_data(w->gpu, w->particles);
+    w->uploaded = true;
+}
+
+void UpdateWorldBatch_GPU(WorldBatch *w, float dt, uint32_t n) {
+    NB_CHECK(w != NULL, "NULL WorldBatch");
+    if (n == 0) return;
+    push_once(w);
+    nb_hip_batch_update(w->gpu, n, dt);
+    w->device_is_newer = true;
+}
+
+void UpdateWorldBatch_GPU_dts(WorldBatch *w, const float *dt, uint32_t n) {
+    NB_CHECK(w != NULL && dt != NULL, "NULL argument");
+    if (n == 0) return;
+    push_once(w);
+    nb_hip_batch_update_dts(w->gpu, n, dt);
+    w->device_is_newer = true;
+}
