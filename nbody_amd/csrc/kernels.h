@@ -1,5 +1,6 @@
-// kernels.h -- internal (C++) launch interface between the pipeline and the gfx950 kernels.
-// Not part of the C-ABI; include/nbody_hip.h is.
+// kernels.h -- internal (C++) interface between the pipeline and the gfx950 force kernels (kernels.hip): their parameter
+// blocks, entry points and the two launches that have no shape to choose.  Which shape a launch gets is launch_shape.h,
+// the AoS <-> SoA converters are convert.h.  Not part of the C-ABI; include/nbody_hip.h is.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -62,6 +63,17 @@ struct StepParams {
     uint32_t unit;
 };
 
+// The parameters of a plain step: one source range [0, n_src), receivers without a gap or a mirror, sums from zero,
+// integrated, unsplit.  The one-world pipeline starts from it (step_chain.hip whole_step), an ensemble member's
+// lane-split step is exactly it (kernels.hip batch_lane_split_kernel).
+__host__ __device__ inline StepParams plain_step(const float2 *src_pos, const float *src_gm, uint32_t n_src, const float2 *pos_in,
+                                                 float2 *pos_out, float2 *vel, float2 *acc, const float *radius, uint32_t n_recv,
+                                                 const float *dt, uint32_t unit) {
+    return StepParams{.src_pos = src_pos, .src_gm = src_gm, .src_begin = {0, 0}, .src_end = {n_src, 0}, .pos_in = pos_in,
+                      .pos_out = pos_out, .vel = vel, .acc = acc, .radius = radius, .n_recv = n_recv, .recv_split = n_recv,
+                      .dt = dt, .split = 1, .unit = unit};   // every field not named is zero / null
+}
+
 // A whole n-step chain of a world that fits ONE workgroup, run inside one launch (chain_kernel): positions ping-pong in
 // LDS, velocities and radii stay in registers, two workgroup barriers per step and no kernel boundary (1.6-1.8 us each
 // on this chip, more than such a step's arithmetic).  Sixteen waves: `tiles` receiver tiles of 64 * K receivers, 16 / tiles
@@ -80,6 +92,7 @@ struct ChainParams {
     const float *dt;      // step size in device memory, as for the per-step kernels
 };
 
+constexpr uint32_t CHAIN_K = 2;            // receivers per lane of the chain
 constexpr uint32_t CHAIN_MAX_RECV = 512;   // 4 tiles of 128 receivers (K = 2)
 
 // An ensemble of `count` independent worlds with the same particle count, stepped by one launch (batch_chain_kernel: one
@@ -100,84 +113,22 @@ struct BatchParams {
     uint32_t steps;       // chain only: steps of this launch, >= 1
     uint32_t tiles;       // chain only: chain_tiles(n_recv)
 };
-constexpr uint32_t BATCH_MAX_RECV = 3000;   // lane_split_rule's own cut-off at n_src = n_recv (N x N <= 9e6)
-
-// A launch shape; 0 = "auto" in a request to choose_shape.  Write one with named fields ({.k = 2, .w = 16}): the
-// defaults are the all-auto request.
-struct LaunchShape {
-    int k = 0;                    // receivers per lane: 1, 2 (4 in tuning builds)
-    int w = 0;                    // waves per workgroup = source slices: 1, 4, 8, 16 (2 in tuning builds)
-    int variant = VARIANT_SMEM;   // VARIANT_*
-    int split = 0;                // workgroups per receiver tile (source parts): 1 .. MAX_SPLIT
-    int unit = 0;                 // sources per slice granule: 64 (default), 32, 16, 8
-    // lane groups per wave (0 / 1: a wave's 64 lanes are 64 * k receivers).  2 or 4: the lanes of a wave split into that
-    // many groups over the SAME 64 / lanes receivers, each group walking its own slice of the sources (lane_split_kernel):
-    // w * lanes source slices per receiver inside ONE workgroup -- the parallelism a source split buys, without its
-    // second kernel.  Latency-bound launches only (k = 1, split = 1, sources staged once in LDS).
-    int lanes = 0;
-};
-
-inline bool operator==(const LaunchShape &a, const LaunchShape &b) {
-    return a.k == b.k && a.w == b.w && a.variant == b.variant && a.split == b.split && a.unit == b.unit && a.lanes == b.lanes;
-}
-
-// Every field of a request left to choose_shape: only then may it pick the lane-split kernel, and the pipeline the
-// one-workgroup chain (an explicit shape or LDS-tile route asks for the classic per-step kernel).
-inline bool shape_on_auto(const LaunchShape &want) { return want == LaunchShape{}; }
-
-constexpr uint32_t LANE_SPLIT_MAX_SRC = 1u << 18;   // sources a lane-split launch walks (one launch = one source pass)
 
 constexpr int MAX_SPLIT = 16;
 
-// The auto rule for lane-split shapes: lanes (1 = use the classic kernel) and waves per workgroup.
-int lane_split_rule(uint32_t n_recv, uint32_t n_src, int *w);
+struct LaunchShape;   // launch_shape.h
 
-// Resolve "auto" (0) entries of `want` for a launch over n_recv receivers and n_src sources.
-LaunchShape choose_shape(LaunchShape want, uint32_t n_recv, uint32_t n_src, int compute_units);
-
-// Kernel entry point and grid for a shape; used both for direct launches and for graph nodes.
+// Kernel entry point for a shape; used both for direct launches and for graph nodes.
 const void *step_kernel_fn(LaunchShape s);
 const void *step_kernel_fused_fn(LaunchShape s);   // nullptr when the shape has no fused-finish instantiation
-dim3 step_grid(LaunchShape s, uint32_t n_recv);
-dim3 step_block(LaunchShape s);
-size_t step_lds_bytes(LaunchShape s, uint32_t n_src);   // dynamic LDS of the launch (0 except for lane-split shapes)
 // second kernel of a split step (split > 1): adds the parts and finishes like the step kernel's epilogue
 const void *finish_kernel_fn();
-dim3 finish_grid(uint32_t n_recv);
-dim3 finish_block();
 
-// the one-workgroup chain: 1024 threads, one block; tiles from chain_tiles(n_recv) (0: the world does not fit)
-uint32_t chain_tiles(uint32_t n_recv);
+// the one-workgroup chain: 1024 threads, one block; tiles from chain_tiles(n_recv)
 void launch_chain(hipStream_t st, const ChainParams &p);
 
-// ensembles: the lane-split shape for members of n_recv particles (lanes; 1 = none: N > BATCH_MAX_RECV), the kernel of a
-// shape (nullptr when not instantiated), and the launches
-int batch_lane_shape(uint32_t n_recv, int *w);
+// ensembles: the kernel of a lane-split shape (nullptr when not instantiated), and the chain launch
 const void *batch_lane_split_fn(int w, int lanes);
 void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count);
-// whole-ensemble converters: member-major AoS [count][n] <-> SoA [count][stride]; split also writes G*m
-void launch_batch_split(hipStream_t st, const void *aos, const uint32_t *mass_len, uint32_t count, uint32_t n, uint32_t stride,
-                        float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g);
-void launch_batch_merge(hipStream_t st, void *aos, uint32_t first, uint32_t count, uint32_t n, uint32_t stride, const float2 *pos,
-                        const float2 *vel, const float2 *acc, const float *radius, const float *mass);
-void launch_batch_fill(hipStream_t st, float *dst, uint32_t count, float value);   // dst[0 .. count) = value, in stream order
-
-// AoS <-> SoA converters (reference Particle layout, include/nbody.h).
-// split: aos[first .. first+count) -> soa slots [slot0 .. slot0+count)
-void launch_split(hipStream_t st, const void *aos, uint32_t first, uint32_t count, float2 *pos, float2 *vel, float2 *acc,
-                  float *radius, float *mass, uint32_t slot0);
-// fill pad slots so that they are inert sources / harmless receivers
-void launch_fill_pad(hipStream_t st, float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, uint32_t slot0,
-                     uint32_t count);
-// gm[j] = g * mass[j] for j < count (0 where mass <= 0); g = the host's NB_G, the only place the value is written down
-void launch_make_gm(hipStream_t st, const float *mass, float *gm, uint32_t count, float g);
-// merge: soa slots [slot0 .. slot0+count) -> aos[first .. first+count)
-void launch_merge(hipStream_t st, void *aos, uint32_t first, uint32_t count, const float2 *pos, const float2 *vel,
-                  const float2 *acc, const float *radius, const float *mass, uint32_t slot0);
-// *dst = value, in stream order (the step-size upload)
-void launch_set_scalar(hipStream_t st, float *dst, float value);
-// sharded upload: both gathered source arrays + G*m from the AoS world; slots in [mass_len, n_src) become inert pads
-void launch_split_sources(hipStream_t st, const void *aos, uint32_t mass_len, uint32_t n_src, float2 *pos0, float2 *pos1,
-                          float *gm, float g);
 
 }  // namespace nb

@@ -25,8 +25,14 @@
 //     DESIGN.md states the tolerance.
 //
 // fp32 throughout.  No MFMA: the loop is rsqrt/fma on independent (receiver, source) pairs, not a contraction.
+//
+// This file holds the force path and nothing else: it, kernels.h and interaction_asm.h are the sources whose hash ties a
+// PMC profile to the code that was profiled (benchlib.KERNEL_SOURCES), so every device function a force kernel compiles
+// lives in one of the three.  Which shape a launch gets is host arithmetic in launch_shape.hip; the AoS <-> SoA
+// converters, pads and fills are convert.hip.
 #include "kernels.h"
 #include "interaction_asm.h"
+#include "launch_shape.h"
 
 #include <hip/hip_runtime.h>
 
@@ -121,39 +127,33 @@ struct Receivers {
 
 // SRC_IN_SGPR: the source sits in SGPRs (scalar-cache route) or in VGPRs holding a wave-uniform value
 // (LDS broadcast reads); the instructions are the same, only the operand class differs.
+// One statement per K; SRC is the constraint letter of the three source operands.
+#define NB_INTERACT2(SRC)                                                                                                       \
+    asm(NB_INTERACTION2_ASM                                                                                                     \
+        : [ax0] "+v"(R.a[0].x), [ay0] "+v"(R.a[0].y), [ax1] "+v"(R.a[1].x), [ay1] "+v"(R.a[1].y)                                \
+        : [sx] SRC(sxy.x), [sy] SRC(sxy.y), [g] SRC(sg), [px0] "v"(R.p[0].x), [py0] "v"(R.p[0].y), [r0] "v"(R.r[0]),            \
+          [px1] "v"(R.p[1].x), [py1] "v"(R.p[1].y), [r1] "v"(R.r[1])                                                            \
+        : NB_CLOBBERS2)
+#define NB_INTERACT1(SRC)                                                                                                       \
+    asm(NB_INTERACTION_ASM                                                                                                      \
+        : [ax] "+v"(R.a[k].x), [ay] "+v"(R.a[k].y)                                                                              \
+        : [sx] SRC(sxy.x), [sy] SRC(sxy.y), [g] SRC(sg), [px] "v"(R.p[k].x), [py] "v"(R.p[k].y), [r] "v"(R.r[k])                \
+        : NB_CLOBBERS)
 template <int K, bool SRC_IN_SGPR>
 __device__ __forceinline__ void interact(Receivers<K> &R, f2v sxy, float sg) {
     if constexpr (K == 2) {
-        if constexpr (SRC_IN_SGPR) {
-            asm(NB_INTERACTION2_ASM
-                : [ax0] "+v"(R.a[0].x), [ay0] "+v"(R.a[0].y), [ax1] "+v"(R.a[1].x), [ay1] "+v"(R.a[1].y)
-                : [sx] "s"(sxy.x), [sy] "s"(sxy.y), [g] "s"(sg), [px0] "v"(R.p[0].x), [py0] "v"(R.p[0].y), [r0] "v"(R.r[0]),
-                  [px1] "v"(R.p[1].x), [py1] "v"(R.p[1].y), [r1] "v"(R.r[1])
-                : NB_CLOBBERS2);
-        } else {
-            asm(NB_INTERACTION2_ASM
-                : [ax0] "+v"(R.a[0].x), [ay0] "+v"(R.a[0].y), [ax1] "+v"(R.a[1].x), [ay1] "+v"(R.a[1].y)
-                : [sx] "v"(sxy.x), [sy] "v"(sxy.y), [g] "v"(sg), [px0] "v"(R.p[0].x), [py0] "v"(R.p[0].y), [r0] "v"(R.r[0]),
-                  [px1] "v"(R.p[1].x), [py1] "v"(R.p[1].y), [r1] "v"(R.r[1])
-                : NB_CLOBBERS2);
-        }
+        if constexpr (SRC_IN_SGPR) NB_INTERACT2("s");
+        else NB_INTERACT2("v");
         return;
     }
 #pragma unroll
     for (int k = 0; k < K; k++) {
-        if constexpr (SRC_IN_SGPR) {
-            asm(NB_INTERACTION_ASM
-                : [ax] "+v"(R.a[k].x), [ay] "+v"(R.a[k].y)
-                : [sx] "s"(sxy.x), [sy] "s"(sxy.y), [g] "s"(sg), [px] "v"(R.p[k].x), [py] "v"(R.p[k].y), [r] "v"(R.r[k])
-                : NB_CLOBBERS);
-        } else {
-            asm(NB_INTERACTION_ASM
-                : [ax] "+v"(R.a[k].x), [ay] "+v"(R.a[k].y)
-                : [sx] "v"(sxy.x), [sy] "v"(sxy.y), [g] "v"(sg), [px] "v"(R.p[k].x), [py] "v"(R.p[k].y), [r] "v"(R.r[k])
-                : NB_CLOBBERS);
-        }
+        if constexpr (SRC_IN_SGPR) NB_INTERACT1("s");
+        else NB_INTERACT1("v");
     }
 }
+#undef NB_INTERACT2
+#undef NB_INTERACT1
 
 // 8 sources (x,y interleaved in P, G*m in G) against the K receivers: 8*K interaction statements, source-major.
 // (Schedule experiments replace this one function from outside the product tree: tools/exp_body_hook.h, force-included
@@ -669,13 +669,10 @@ __device__ __forceinline__ void lane_split_body(const StepParams &p) {
                 ay = __fadd_rn(ay, t.y);
             }
             if (integrates) {
-                // finish_receiver with everything it reads already in registers (flags == 0: no carry-in, always integrate)
-                const uint32_t i = receiver_slot(p, my_logical);
-                const float2 a = make_float2(ax, ay);
-                p.acc[i] = a;
-                float2 vv = vel0, q = make_float2(Rv.p[0].x, Rv.p[0].y);
-                integrate(a, dt, vv, q);
-                store_moved(p, i, vv, q);
+                // finish_receiver with everything it reads already in registers; `integrates` implies flags == 0, so the
+                // carry-in (and with it the old acc, passed as zero) and the no-finalize exit fold away
+                finish_loaded(p, receiver_slot(p, my_logical), make_float2(ax, ay), make_float2(0.f, 0.f), vel0,
+                              make_float2(Rv.p[0].x, Rv.p[0].y), dt);
             } else {
                 finish_receiver(p, my_logical, ax, ay, dt);   // chained passes (flags): the general epilogue
             }
@@ -702,8 +699,6 @@ __global__ __launch_bounds__(WAVE *W) void lane_split_kernel(const StepParams p)
 // Bit-compatible with the per-step kernel by construction: same interaction statements, same slicing arithmetic
 // (granule 8, W = 16 / tiles slices per receiver tile), same block closes, same reduction order, same integrator
 // roundings -- tests/test_gpu_parity.py holds it to plain launches of k = 2, w = 16 / tiles, split = 1, unit = 8.
-constexpr uint32_t CHAIN_K = 2;
-
 // (the body as a device function: chain_kernel runs it for one world, batch_chain_kernel for one member per workgroup)
 __device__ __forceinline__ void chain_body(const ChainParams &p) {
     constexpr int K = CHAIN_K;
@@ -813,331 +808,47 @@ __global__ __launch_bounds__(1024) void batch_chain_kernel(const BatchParams bp)
 template <int W, int H>
 __global__ __launch_bounds__(WAVE *W) void batch_lane_split_kernel(const BatchParams bp) {
     const size_t base = (size_t)blockIdx.y * bp.stride;
-    StepParams p;
-    p.src_pos = bp.pos_in + base;   // the first mass_len[b] receivers of a member ARE its sources
-    p.src_gm = bp.gm + base;
-    p.src_begin[0] = 0;
-    p.src_end[0] = uniform_u32(bp.mass_len[blockIdx.y]);
-    p.src_begin[1] = p.src_end[1] = 0;
-    p.pos_in = bp.pos_in + base;
-    p.pos_out = bp.pos_out + base;
-    p.vel = bp.vel + base;
-    p.acc = bp.acc + base;
-    p.radius = bp.radius + base;
-    p.n_recv = bp.n_recv;
-    p.recv_split = bp.n_recv;
-    p.recv_gap = 0;
-    p.mirror = nullptr;
-    p.n_mirror = 0;
-    p.dt = bp.dt + blockIdx.y;
-    p.flags = 0;
-    p.parts = nullptr;
-    p.split = 1;
-    p.tickets = nullptr;
-    p.unit = 8;
+    // the first mass_len[b] receivers of a member ARE its sources
+    const StepParams p = plain_step(bp.pos_in + base, bp.gm + base, uniform_u32(bp.mass_len[blockIdx.y]), bp.pos_in + base,
+                                    bp.pos_out + base, bp.vel + base, bp.acc + base, bp.radius + base, bp.n_recv,
+                                    bp.dt + blockIdx.y, 8);
     lane_split_body<W, H>(p);
 }
 
-// ---- AoS <-> SoA ----------------------------------------------------------------------------------------
 
-struct alignas(16) ParticleRec {  // == Particle (include/nbody.h): pos vel | acc mass radius
-    float4 a, b;
-};
-
-__global__ void split_kernel(const ParticleRec *aos, uint32_t first, uint32_t count, float2 *pos, float2 *vel, float2 *acc,
-                             float *radius, float *mass, uint32_t slot0) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const ParticleRec r = aos[first + i];
-    pos[slot0 + i] = make_float2(r.a.x, r.a.y);
-    vel[slot0 + i] = make_float2(r.a.z, r.a.w);
-    acc[slot0 + i] = make_float2(r.b.x, r.b.y);
-    mass[slot0 + i] = r.b.z;
-    radius[slot0 + i] = r.b.w;
-}
-
-__global__ void merge_kernel(ParticleRec *aos, uint32_t first, uint32_t count, const float2 *pos, const float2 *vel,
-                             const float2 *acc, const float *radius, const float *mass, uint32_t slot0) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const float2 q = pos[slot0 + i], v = vel[slot0 + i], a = acc[slot0 + i];
-    ParticleRec r;
-    r.a = make_float4(q.x, q.y, v.x, v.y);
-    r.b = make_float4(a.x, a.y, mass[slot0 + i], radius[slot0 + i]);
-    aos[first + i] = r;
-}
-
-__global__ void fill_pad_kernel(float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, uint32_t slot0,
-                                uint32_t count) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    // far away, finite, massless: contributes exactly 0 as a source and stays finite as a receiver
-    pos[slot0 + i] = make_float2(1.0e15f, 1.0e15f);
-    vel[slot0 + i] = make_float2(0.f, 0.f);
-    acc[slot0 + i] = make_float2(0.f, 0.f);
-    radius[slot0 + i] = 1.0f;
-    mass[slot0 + i] = 0.0f;
-}
-
-__global__ void set_scalar_kernel(float *dst, float value) { *dst = value; }
-
-// `g` is the host's NB_G (include/nbody.h), handed in at launch like the reference's specialisation constant
-// (sim_gpu.c:54-72, particle_cs.glsl:26): the device code holds no copy of the value.
-__global__ void make_gm_kernel(const float *mass, float *gm, uint32_t count, float g) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
-    const float m = mass[i];
-    gm[i] = m > 0.0f ? __fmul_rn(m, g) : 0.0f;  // rounded as the reference's `gm = m * g` (sim_cpu.c:179)
-}
-
-// Sharded upload: the gathered source arrays (both ping-pong buffers) and the static G*m straight from the AoS
-// world every rank holds.  Slots past mass_len are pads: far away, finite, massless (exact zero contribution).
-__global__ void split_sources_kernel(const ParticleRec *aos, uint32_t mass_len, uint32_t n_src, float2 *pos0, float2 *pos1,
-                                     float *gm, float big_g) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_src) return;
-    float2 q = make_float2(1.0e15f, 1.0e15f);
-    float g = 0.0f;
-    if (i < mass_len) {
-        const ParticleRec r = aos[i];
-        q = make_float2(r.a.x, r.a.y);
-        g = r.b.z > 0.0f ? __fmul_rn(r.b.z, big_g) : 0.0f;  // as make_gm_kernel
-    }
-    pos0[i] = q;
-    pos1[i] = q;
-    gm[i] = g;
-}
-
-// Ensemble upload: member blockIdx.y's AoS records into its SoA rows, and G*m of its sources (as make_gm_kernel; rows
-// past mass_len[b] hold no source and get 0).  One launch for the whole ensemble.
-__global__ void batch_split_kernel(const ParticleRec *aos, const uint32_t *mass_len, uint32_t n, uint32_t stride, float2 *pos,
-                                   float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (i >= n) return;
-    const ParticleRec r = aos[(size_t)b * n + i];
-    const size_t o = (size_t)b * stride + i;
-    pos[o] = make_float2(r.a.x, r.a.y);
-    vel[o] = make_float2(r.a.z, r.a.w);
-    acc[o] = make_float2(r.b.x, r.b.y);
-    mass[o] = r.b.z;
-    radius[o] = r.b.w;
-    gm[o] = (i < mass_len[b] && r.b.z > 0.0f) ? __fmul_rn(r.b.z, g) : 0.0f;
-}
-
-// Ensemble read-back: members [first, first + gridDim.y) back into their AoS records.
-__global__ void batch_merge_kernel(ParticleRec *aos, uint32_t first, uint32_t n, uint32_t stride, const float2 *pos,
-                                   const float2 *vel, const float2 *acc, const float *radius, const float *mass) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = first + blockIdx.y;
-    if (i >= n) return;
-    const size_t o = (size_t)b * stride + i;
-    const float2 q = pos[o], v = vel[o], a = acc[o];
-    ParticleRec r;
-    r.a = make_float4(q.x, q.y, v.x, v.y);
-    r.b = make_float4(a.x, a.y, mass[o], radius[o]);
-    aos[(size_t)b * n + i] = r;
-}
-
-__global__ void batch_fill_kernel(float *dst, uint32_t count, float value) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) dst[i] = value;
-}
-
-inline dim3 grid1d(uint32_t count) { return dim3((count + 255u) / 256u); }
+// ---- kernel entry points -------------------------------------------------------------------------------------------
+// One row of a lookup: run-time keys (a, b) == (A, B) select KERNEL<A, B, further template arguments>.
+#define NB_CASE(KERNEL, A, B, ...) \
+    if (a == A && b == B) return reinterpret_cast<const void *>(&KERNEL<A, B, ##__VA_ARGS__>);
 
 template <int VARIANT>
-const void *pick(int k, int w) {
-#define NB_CASE(KK, WW) \
-    if (k == KK && w == WW) return reinterpret_cast<const void *>(&step_kernel<KK, WW, VARIANT>);
+const void *pick(int a, int b) {   // (k, w)
     // W = 4, 8, 16 are what choose_shape picks from; W = 1 is the shape whose summation order does not depend on
     // how the sources are cut up (one wave walks them all), which the sharded-vs-single bit-equality tests rely on.
-    NB_CASE(1, 1) NB_CASE(1, 4) NB_CASE(1, 8) NB_CASE(1, 16)
-    NB_CASE(2, 1) NB_CASE(2, 4) NB_CASE(2, 8) NB_CASE(2, 16)
+    NB_CASE(step_kernel, 1, 1, VARIANT) NB_CASE(step_kernel, 1, 4, VARIANT) NB_CASE(step_kernel, 1, 8, VARIANT) NB_CASE(step_kernel, 1, 16, VARIANT)
+    NB_CASE(step_kernel, 2, 1, VARIANT) NB_CASE(step_kernel, 2, 4, VARIANT) NB_CASE(step_kernel, 2, 8, VARIANT) NB_CASE(step_kernel, 2, 16, VARIANT)
 #ifdef NB_TUNING_SHAPES
     // never auto-selected (profiles/r01_sweep4_shapes_by_n.txt): built only for shape scans (make TUNING=1)
-    NB_CASE(1, 2) NB_CASE(2, 2)
-    NB_CASE(4, 1) NB_CASE(4, 2) NB_CASE(4, 4) NB_CASE(4, 8) NB_CASE(4, 16)
+    NB_CASE(step_kernel, 1, 2, VARIANT) NB_CASE(step_kernel, 2, 2, VARIANT) NB_CASE(step_kernel, 4, 1, VARIANT) NB_CASE(step_kernel, 4, 2, VARIANT)
+    NB_CASE(step_kernel, 4, 4, VARIANT) NB_CASE(step_kernel, 4, 8, VARIANT) NB_CASE(step_kernel, 4, 16, VARIANT)
 #endif
-#undef NB_CASE
     return nullptr;
 }
 
-const void *pick_fused(int k, int w) {
-#define NB_CASE(KK, WW) \
-    if (k == KK && w == WW) return reinterpret_cast<const void *>(&step_kernel<KK, WW, VARIANT_SMEM, true>);
-    NB_CASE(1, 4) NB_CASE(1, 8) NB_CASE(1, 16) NB_CASE(2, 4) NB_CASE(2, 8) NB_CASE(2, 16)
-#undef NB_CASE
+const void *pick_fused(int a, int b) {   // (k, w)
+    NB_CASE(step_kernel, 1, 4, VARIANT_SMEM, true) NB_CASE(step_kernel, 1, 8, VARIANT_SMEM, true) NB_CASE(step_kernel, 1, 16, VARIANT_SMEM, true)
+    NB_CASE(step_kernel, 2, 4, VARIANT_SMEM, true) NB_CASE(step_kernel, 2, 8, VARIANT_SMEM, true) NB_CASE(step_kernel, 2, 16, VARIANT_SMEM, true)
     return nullptr;
 }
 
-const void *pick_lane_split(int w, int h) {
-#define NB_CASE(WW, HH) \
-    if (w == WW && h == HH) return reinterpret_cast<const void *>(&lane_split_kernel<WW, HH>);
-    NB_CASE(4, 2) NB_CASE(8, 2) NB_CASE(16, 2) NB_CASE(4, 4) NB_CASE(8, 4) NB_CASE(16, 4) NB_CASE(8, 8) NB_CASE(16, 8)
-#undef NB_CASE
+const void *pick_lane_split(int a, int b) {   // (w, lanes)
+    NB_CASE(lane_split_kernel, 4, 2) NB_CASE(lane_split_kernel, 8, 2) NB_CASE(lane_split_kernel, 16, 2) NB_CASE(lane_split_kernel, 4, 4)
+    NB_CASE(lane_split_kernel, 8, 4) NB_CASE(lane_split_kernel, 16, 4) NB_CASE(lane_split_kernel, 8, 8) NB_CASE(lane_split_kernel, 16, 8)
     return nullptr;
 }
 
 }  // namespace
 
-// NB_HASH_OFF -- host-side launch-shape arithmetic: not part of the kernel-source hash bench.py ties PMC figures to
-// Launches that do not even fill the chip once with K = 2 / W = 16 workgroups (fewer than 65 536 receivers on 256
-// CUs) are priced in microseconds by a model fitted to exhaustive (K, W, split, unit) scans at N = 250 ... 50 000
-// (tools/sweep_shapes.py; profiles/r02_sweep_shapes_units.txt holds the latest scan, 3 360 timed shapes).  There a wave is
-// latency-bound, not issue-bound: alone on its SIMD it needs LAT us per 64-source chunk and receiver set (a serial
-// dependency chain), and only beyond ~2 waves per SIMD does the chunk time grow with occupancy -- at THR us per wave,
-// worse (factor A) the emptier the SIMD, and worse again for K = 1 (K1A).  Every wave also costs UFIX chunks of fixed
-// work (launch, receiver loads, the LDS reduction), which is what stops the split from growing without bound, and a
-// split adds the finish kernel.  Cutting the sources into more parts and finer granules shortens every wave's chain, so
-// small launches want shapes the big-launch model would never pay for: N = 250 runs 3.2 us per step with 16 waves of 8
-// sources instead of 4.6 us with two waves of 64, N = 2 000 5.4 instead of 6.7, N = 4 000 6.8 with 8 parts of 256-thread
-// workgroups.  Mean regret of the model's pick against the scan's best: 1.7 % (worst 4.4 %).
-static double small_launch_cost_us(uint32_t n_recv, uint32_t n_src, int k, int w, int sp, int unit, int cus) {
-    constexpr double LAT = 1.575, THR = 0.7545, K1 = 0.987, K1A = 0.178, A = 0.179, MIX = 0.874;
-    constexpr double FINISH = 2.08, W4 = 1.035, UFIX = 0.15, BASE = 2.27;
-    // the longest wave slice of a workgroup, in 64-source chunks (a fraction of one when the slice granule is finer)
-    const uint32_t granules = (n_src + unit - 1) / unit;
-    const uint64_t groups = ((uint64_t)n_recv + WAVE * k - 1) / (WAVE * k) * (uint64_t)sp;
-    const uint64_t capacity = (uint64_t)cus * (32 / w);
-    const uint64_t full = groups / capacity, left = groups % capacity;
-    const uint32_t part_granules = (granules + sp - 1) / sp;
-    const uint32_t wave_granules = (part_granules + w - 1) / w;
-    const double units = (double)k * (wave_granules ? wave_granules : 1) * (double)unit / (double)CHUNK + UFIX;
-    auto chunk_time = [&](double occ) {  // us per chunk and receiver set with `occ` waves on every SIMD
-        const double f = k == 1 ? K1 + K1A * (8.0 - occ) / 8.0 : 1.0;
-        const double busy = occ * THR * f * (1.0 + A * (8.0 - occ) / 8.0);
-        return LAT > busy ? LAT : busy;
-    };
-    double t = (double)full * units * chunk_time(8.0);
-    if (left) {
-        // the busiest CU holds ceil(left / CUs) workgroups of w waves on its 4 SIMDs
-        double occ = (w / 4.0) * (double)((left + cus - 1) / cus);
-        if (occ > 8.0) occ = 8.0;
-        const double lock = units * chunk_time(occ);                                    // runs after the full rounds
-        const double fluid = units * chunk_time(8.0) * (double)left / (double)capacity;  // packs in behind them
-        t += full ? MIX * lock + (1.0 - MIX) * fluid : lock;
-    }
-    if (sp > 1) t += FINISH;
-    if (w == 4) t *= W4;
-    return t + BASE;  // what every step pays whatever its shape (dispatch, kernel boundary): keeps ties ties
-}
-
-// Lane-split shapes ("lanes" = 0, auto), from a scan of lanes x w over N = 300 ... 10 000 (tools/lane_probe.py,
-// profiles/r03_lane_split_scan.txt; us per step, best lane-split shape vs the best classic shape the model above picks):
-//   N = 500: 3.11 vs 3.86   800: 3.25 vs 4.25   1 200: 3.70 vs 4.98   2 000: 3.93 vs 5.41   4 000: 5.88 vs 6.93
-//   5 000: 8.62 vs 8.42     8 000: 13.3 vs 12.7   10 000: 20.6 vs 15.8
-// i.e. 15-28 % faster while a step is latency (N x M <~ 9e6), slower once it is throughput: every workgroup stages ALL
-// the sources in LDS and the per-lane LDS reads cost issue slots a wave-uniform scalar operand does not.  Which (lanes, w)
-// wins moves with the size; neighbours are within 2-3 % of each other.
-int lane_split_rule(uint32_t n_recv, uint32_t n_src, int *w) {
-    const double pairs = (double)n_recv * (double)n_src;
-    *w = 16;
-    if (n_src == 0 || n_recv == 0 || n_src > LANE_SPLIT_MAX_SRC || pairs > 9.0e6) return 1;
-    if (pairs <= 1.5e5) {
-        *w = 8;
-        return 4;
-    }
-    if (pairs <= 2.5e6) {
-        *w = 8;
-        return 8;
-    }
-    return 4;
-}
-
-LaunchShape choose_shape(LaunchShape want, uint32_t n_recv, uint32_t n_src, int compute_units) {
-    // Workgroups of one launch all take the same time, so a launch costs
-    //     (rounds + tail) * (work per workgroup),   rounds = ceil(workgroups / resident capacity),
-    // and one workgroup past a round boundary costs a whole round (1025 workgroups on 512 slots run 1.5x as
-    // long as 1024; profiles/r01_shard_overhead_before_fix.txt).  Work per workgroup = K receivers per lane x
-    // the 64-source chunks one wave walks.  Pick the cheapest (K, W, split); ties go to the larger K, larger W,
-    // smaller split.  More, shorter workgroups also shrink the launch's ramp-up/ragged-end share.  K = 4 is left out: 71 VGPRs, lower
-    // occupancy, never faster (profiles/r01_sweep4_shapes_by_n.txt).
-    if (compute_units <= 0) compute_units = 256;
-    if (shape_on_auto(want)) {   // an explicit LDS-tile route or shape knob asks for the classic kernel
-        int w = 16;
-        const int lanes = lane_split_rule(n_recv, n_src, &w);
-        if (lanes > 1) {
-            want.lanes = lanes;
-            want.w = w;
-        }
-    }
-    if (want.lanes > 1) {
-        // one receiver per lane, no source split, 8-source granules, LDS-staged sources
-        LaunchShape sh = want;
-        sh.k = 1;
-        sh.w = (want.w == 4 || want.w == 8 || want.w == 16) ? want.w : 16;
-        if (sh.lanes == 8 && sh.w == 4) sh.w = 8;   // eight groups: instantiated for 8 and 16 waves
-        if (sh.lanes != 2 && sh.lanes != 4 && sh.lanes != 8) sh.lanes = 4;
-        sh.split = 1;
-        sh.unit = 8;
-        sh.variant = VARIANT_LDS;
-        return sh;
-    }
-    if (want.variant == VARIANT_LDS) want.unit = CHUNK;  // the LDS route stages whole 64-source tiles, whatever was asked
-    const uint32_t chunks = (n_src + CHUNK - 1) / CHUNK;
-    const bool small = ((uint64_t)n_recv + 2 * WAVE - 1) / (2 * WAVE) < (uint64_t)compute_units * 2;
-    LaunchShape best = want;
-    best.lanes = 1;
-    double best_cost = -1.0;
-    for (int k = 2; k >= 1; k--) {
-        if (want.k != 0 && want.k != k) continue;
-        for (int w = 16; w >= 4; w /= 2) {
-            if (want.w != 0 && want.w != w) continue;
-            for (int sp = 1; sp <= MAX_SPLIT; sp++) {
-                if (want.split != 0 && want.split != sp) continue;
-                // small launches: 1024-thread workgroups exactly while the whole launch is a handful of unsplit tiles
-                // (16 waves per tile beat 8 there: 4.2 vs 4.6 us at N = 800); beyond that 256- and 512-thread
-                // workgroups pack better, and the model overrates W = 16
-                const bool few_unsplit_tiles = sp == 1 && ((uint64_t)n_recv + WAVE * k - 1) / (WAVE * k) <= 24;
-                // ... with at least ~16 sources for every wave: 8 waves when there are no more than 128 sources
-                // (N = 250: 2.9 us with 8 waves of 16 sources, 3.2 with 16 waves of 8)
-                const int tiny_w = n_src <= 128 ? 8 : 16;
-                if (small && want.w == 0 && (few_unsplit_tiles ? w != tiny_w : w == 16)) continue;
-                // slice granule: 64 unless the launch is latency-bound; a finer one only has to win where a part holds
-                // fewer chunks than the workgroup has waves, and ties keep the coarser granule (64 first)
-                for (int unit = CHUNK; unit >= 8; unit /= 2) {
-                    if (want.unit != 0 && want.unit != unit) continue;
-                    if (!small && want.unit == 0 && unit != CHUNK) continue;
-                    double cost;
-                    if (small) {
-                        cost = small_launch_cost_us(n_recv, n_src, k, w, sp, unit, compute_units);
-                    } else {
-                        const uint64_t groups = ((uint64_t)n_recv + WAVE * k - 1) / (WAVE * k) * (uint64_t)sp;
-                        const uint64_t capacity = (uint64_t)compute_units * (32 / w);  // 8 waves per SIMD at <= 64 VGPRs
-                        const uint64_t rounds = (groups + capacity - 1) / capacity;
-                        const uint32_t part_chunks = (chunks + sp - 1) / sp;
-                        const uint32_t wave_chunks = (part_chunks + w - 1) / w;
-                        // + 1 chunk-equivalent per workgroup for prologue/epilogue; + TAIL rounds per launch for ramp-up
-                        // and the ragged end (measured: 2-round launches run 4.5 % over, 16-round ones 0.1 % over:
-                        // profiles/r01_shard_overhead_split.txt); a split adds the finish kernel and the parts traffic
-                        constexpr double TAIL = 0.13;
-                        cost = ((double)rounds + TAIL) * ((double)k * (wave_chunks ? wave_chunks : 1) + 1.0);
-                        if (sp > 1) cost += 3.0 + 0.02 * sp;
-                        if (w < 16) cost *= 1.01;
-                        // K = 1 per interaction at large N: 1.6 % slower than K = 2 with the plain body (48.6 vs 47.8 ms
-                        // per launch at N = 2^20; it was 25 % with the packed body, whose single statement ran alone)
-                        if (k == 1) cost *= 1.02;
-                    }
-                    if (best_cost < 0.0 || cost < best_cost * 0.999) {
-                        best_cost = cost;
-                        best.k = k;
-                        best.w = w;
-                        best.split = sp;
-                        best.unit = unit;
-                    }
-                }
-            }
-        }
-    }
-    if (best_cost < 0.0) {  // explicit w = 1 (or a tuning-build shape): honour the request as given
-        best.k = want.k ? want.k : 2;
-        best.w = want.w ? want.w : 16;
-        best.split = want.split ? want.split : 1;
-        best.unit = want.unit ? want.unit : CHUNK;
-    }
-    return best;
-}
-
-// NB_HASH_ON
 const void *step_kernel_fn(LaunchShape s) {
     if (s.lanes > 1) return pick_lane_split(s.w, s.lanes);
     return s.variant == VARIANT_SMEM ? pick<VARIANT_SMEM>(s.k, s.w) : pick<VARIANT_LDS>(s.k, s.w);
@@ -1148,98 +859,21 @@ const void *step_kernel_fused_fn(LaunchShape s) {
     return pick_fused(s.k, s.w);
 }
 
-dim3 step_grid(LaunchShape s, uint32_t n_recv) {
-    if (s.lanes > 1) return dim3((n_recv + WAVE / s.lanes - 1) / (WAVE / s.lanes), 1);
-    return dim3((n_recv + WAVE * s.k - 1) / (WAVE * s.k), s.split > 1 ? s.split : 1);
-}
-
-size_t step_lds_bytes(LaunchShape s, uint32_t n_src) {
-    if (s.lanes <= 1) return 0;
-    (void)n_src;   // the sources pass through one tile of 2 * 64 * w entries, whatever their number
-    return (size_t)2 * WAVE * s.w * 12 + ((size_t)s.w + 1) * WAVE * sizeof(float2);   // tile (x, y, G*m) + [w * lanes][64 / lanes] partial sums + 64 second-level sums
-}
 const void *finish_kernel_fn() { return reinterpret_cast<const void *>(&finish_kernel); }
-dim3 finish_grid(uint32_t n_recv) { return dim3((n_recv + 255u) / 256u); }
-dim3 finish_block() { return dim3(256); }
-dim3 step_block(LaunchShape s) { return dim3(WAVE * s.w); }
 
-uint32_t chain_tiles(uint32_t n_recv) {
-    for (uint32_t t = 1; t <= 4; t *= 2)
-        if (n_recv <= t * WAVE * CHAIN_K) return t;
-    return 0;
+const void *batch_lane_split_fn(int a, int b) {   // (w, lanes)
+    // the two shapes batch_lane_shape reaches for 512 < N <= 3 000
+    NB_CASE(batch_lane_split_kernel, 8, 8) NB_CASE(batch_lane_split_kernel, 16, 4)
+    return nullptr;
 }
+#undef NB_CASE
 
 void launch_chain(hipStream_t st, const ChainParams &p) {
     hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(1024), 0, st, p);
 }
 
-// ---- ensembles ------------------------------------------------------------------------------------------------------
-// The lane-split shape of an ensemble is a function of N alone (members differ in their source counts, and a member's bits
-// must not depend on them): the auto rule at n_src = n_recv, whose cut-off N x N <= 9e6 is N <= 3 000.
-int batch_lane_shape(uint32_t n_recv, int *w) { return lane_split_rule(n_recv, n_recv, w); }
-
-const void *batch_lane_split_fn(int w, int h) {
-    // the two shapes batch_lane_shape reaches for 512 < N <= 3 000
-    if (w == 8 && h == 8) return reinterpret_cast<const void *>(&batch_lane_split_kernel<8, 8>);
-    if (w == 16 && h == 4) return reinterpret_cast<const void *>(&batch_lane_split_kernel<16, 4>);
-    return nullptr;
-}
-
 void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count) {
     hipLaunchKernelGGL(batch_chain_kernel, dim3(count), dim3(1024), 0, st, p);
-}
-
-void launch_batch_split(hipStream_t st, const void *aos, const uint32_t *mass_len, uint32_t count, uint32_t n, uint32_t stride,
-                        float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g) {
-    hipLaunchKernelGGL(batch_split_kernel, dim3((n + 255u) / 256u, count), dim3(256), 0, st, static_cast<const ParticleRec *>(aos),
-                       mass_len, n, stride, pos, vel, acc, radius, mass, gm, g);
-}
-
-void launch_batch_merge(hipStream_t st, void *aos, uint32_t first, uint32_t count, uint32_t n, uint32_t stride, const float2 *pos,
-                        const float2 *vel, const float2 *acc, const float *radius, const float *mass) {
-    if (count == 0) return;
-    hipLaunchKernelGGL(batch_merge_kernel, dim3((n + 255u) / 256u, count), dim3(256), 0, st, static_cast<ParticleRec *>(aos), first, n,
-                       stride, pos, vel, acc, radius, mass);
-}
-
-void launch_batch_fill(hipStream_t st, float *dst, uint32_t count, float value) {
-    hipLaunchKernelGGL(batch_fill_kernel, grid1d(count), dim3(256), 0, st, dst, count, value);
-}
-
-void launch_split(hipStream_t st, const void *aos, uint32_t first, uint32_t count, float2 *pos, float2 *vel, float2 *acc,
-                  float *radius, float *mass, uint32_t slot0) {
-    if (count == 0) return;
-    hipLaunchKernelGGL(split_kernel, grid1d(count), dim3(256), 0, st, static_cast<const ParticleRec *>(aos), first, count,
-                       pos, vel, acc, radius, mass, slot0);
-}
-
-void launch_fill_pad(hipStream_t st, float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, uint32_t slot0,
-                     uint32_t count) {
-    if (count == 0) return;
-    hipLaunchKernelGGL(fill_pad_kernel, grid1d(count), dim3(256), 0, st, pos, vel, acc, radius, mass, slot0, count);
-}
-
-void launch_set_scalar(hipStream_t st, float *dst, float value) {
-    hipLaunchKernelGGL(set_scalar_kernel, dim3(1), dim3(1), 0, st, dst, value);
-}
-
-void launch_make_gm(hipStream_t st, const float *mass, float *gm, uint32_t count, float g) {
-    if (count == 0) return;
-    hipLaunchKernelGGL(make_gm_kernel, grid1d(count), dim3(256), 0, st, mass, gm, count, g);
-}
-
-void launch_merge(hipStream_t st, void *aos, uint32_t first, uint32_t count, const float2 *pos, const float2 *vel,
-                  const float2 *acc, const float *radius, const float *mass, uint32_t slot0) {
-    if (count == 0) return;
-    hipLaunchKernelGGL(merge_kernel, grid1d(count), dim3(256), 0, st, static_cast<ParticleRec *>(aos), first, count, pos,
-                       vel, acc, radius, mass, slot0);
-}
-
-void launch_split_sources(hipStream_t st, const void *aos, uint32_t mass_len, uint32_t n_src, float2 *pos0, float2 *pos1,
-                          float *gm, float g) {
-    if (n_src == 0) return;
-    hipLaunchKernelGGL(split_sources_kernel, grid1d(n_src), dim3(256), 0, st, static_cast<const ParticleRec *>(aos), mass_len,
-                       n_src, pos0, pos1, gm, g);
 }
 
 }  // namespace nb

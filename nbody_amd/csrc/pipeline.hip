@@ -6,7 +6,8 @@
 //   * device-to-host copy only when GetSimulationData asks (the reference copies after every call, sim_gpu.c:336-341);
 //   * nothing is created on the GPU until SetSimulationData, so CPU-only worlds never touch a device.
 // The rest of the seam lives next door: device_ctx.hip (device pick), step_chain.hip (what a step call enqueues),
-// rccl_bind.hip + shard_plan.hip (the sharded pipeline's communicator and ownership plan), kernels.hip (gfx950 code).
+// rccl_bind.hip + shard_plan.hip (the sharded pipeline's communicator and ownership plan), kernels.hip (gfx950 force
+// kernels), launch_shape.hip (launch policy), convert.hip (AoS <-> SoA).
 #include "pipeline_internal.h"
 #include "nbody_hip_tuning.h"
 
@@ -293,7 +294,7 @@ int nb_hip_plan_launch_lanes(uint32_t n_recv, uint32_t n_src, int *w) {
 
 int nb_hip_plan_fused_finish(uint32_t n_recv, uint32_t n_src, int compute_units) {
     const nb::LaunchShape sh = nb::choose_shape({.lanes = 1}, n_recv, n_src, compute_units);
-    return sh.split > 1 && nb_hip_plan_launch_lanes(n_recv, n_src, nullptr) <= 1 && fused_finish_rule(n_recv, n_src) ? 1 : 0;
+    return sh.split > 1 && nb_hip_plan_launch_lanes(n_recv, n_src, nullptr) <= 1 && nb::fused_finish_rule(n_recv, n_src) ? 1 : 0;
 }
 
 int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units) {

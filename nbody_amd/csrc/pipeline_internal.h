@@ -5,7 +5,9 @@
 //   shard_plan.hip   nb_hip_shard_plan: who owns which receivers and sources (pure host arithmetic)
 //   step_chain.hip   one step / n steps as launches, cached hipGraph chains, the sharded step with its all-gather
 //   pipeline.hip     SimPipeline life cycle and the C-ABI entry points (Create/Destroy/Set/Get/PerformSimUpdate, knobs)
-//   kernels.hip      the gfx950 kernels (kernels.h)
+//   kernels.hip      the gfx950 force kernels and their entry points (kernels.h)
+//   launch_shape.hip the host-side launch policy: shape, grid, LDS of a launch (launch_shape.h)
+//   convert.hip      AoS <-> SoA converters, pads, G*m, fills (convert.h)
 //   batch.hip        SimBatch: ensembles of small worlds stepped by one launch (nb_hip_batch_*)
 //   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
 #pragma once
@@ -23,7 +25,9 @@
 #include <utility>
 #include <vector>
 
+#include "convert.h"
 #include "kernels.h"
+#include "launch_shape.h"
 #include "nbody_hip.h"
 
 // ---- error convention: print where, abort (reference src/lib/util.h:17-29,47-60) -------------------------
@@ -248,7 +252,7 @@ struct SimPipeline {
     uint32_t *tickets = nullptr;  // fused finish: one arrival counter per receiver tile, zero between launches (re-zeroed at every upload
     uint32_t tickets_len = 0;     // and before a chain is built: a launch that ended part-way must not leave a tile unfinished for ever)
     int fused_finish = 2;         // 0: step kernel + finish kernel; 1: the last workgroup of a tile finishes it, whenever
-                                  // the shape allows; 2 (default): auto (step_chain.hip fused_finish_rule)
+                                  // the shape allows; 2 (default): auto (launch_shape.hip fused_finish_rule)
     int cur = 0;             // pos[cur] is the latest state
 
     hipStream_t stream = nullptr;
@@ -265,7 +269,7 @@ struct SimPipeline {
     uint64_t use_clock = 0;     // ticks once per graph lookup (LRU)
 
     // knobs
-    // the launch shape asked for ("variant" knob, shape hooks; kernels.h LaunchShape): all auto by default -- the
+    // the launch shape asked for ("variant" knob, shape hooks; launch_shape.h LaunchShape): all auto by default -- the
     // scalar-cache route is 8 % faster than LDS tiles at N = 2^20 (roofline.alt_lds)
     nb::LaunchShape want;
     int use_graph = 2, overlap = 0, sharded_graph = 0;  // use_graph: 0 never, 1 always, 2 from a chain length's second use
@@ -310,6 +314,5 @@ void sharded_step(SimPipeline *s, nb::LaunchShape sh, float dt, hipStream_t cs, 
 // in-place all-gather of a device array of nranks slots through the caller's host transport
 void host_allgather(SimPipeline *s, void *dev_base, size_t bytes_per_rank, hipStream_t st);
 void enqueue_steps(SimPipeline *s, uint32_t n, float dt);  // what PerformSimUpdate / nb_hip_step_async enqueue
-bool fused_finish_rule(uint32_t n_recv, uint32_t n_src);   // the auto rule of the "fused_finish" knob (pure host)
 
 }  // namespace nbi

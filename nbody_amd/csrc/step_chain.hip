@@ -94,21 +94,9 @@ nb::LaunchShape resolve_shape(SimPipeline *s) {
 
 // Parameters of the single-kernel step that reads phase `in` and writes phase `in ^ 1`.
 nb::StepParams whole_step(const SimPipeline *s, int in, float dt) {
-    nb::StepParams p;
-    memset(&p, 0, sizeof p);
-    p.src_pos = s->src_pos[in];
-    p.src_gm = s->src_gm;
-    p.src_begin[0] = 0;
-    p.src_end[0] = s->n_src;
-    p.src_begin[1] = p.src_end[1] = 0;
-    p.pos_in = s->pos[in];
-    p.pos_out = s->pos[in ^ 1];
-    p.vel = s->vel;
-    p.acc = s->acc;
-    p.radius = s->radius;
-    p.n_recv = s->n_real;
-    p.recv_split = s->n_real;
-    p.recv_gap = 0;
+    (void)dt;  // the value travels through device memory (upload_dt), the parameter block only points at it
+    nb::StepParams p = nb::plain_step(s->src_pos[in], s->src_gm, s->n_src, s->pos[in], s->pos[in ^ 1], s->vel, s->acc, s->radius,
+                                      s->n_real, s->dt_dev, 64);
     if (s->sharded) {
         // slots [0, mass_count) massive, [mass_count, Mc) pads (never computed), [Mc, Mc + zero_count) massless
         p.recv_split = s->plan.mass_count;
@@ -116,12 +104,6 @@ nb::StepParams whole_step(const SimPipeline *s, int in, float dt) {
         p.mirror = s->src_pos[in ^ 1] + (size_t)s->rank * s->plan.mass_chunk;
         p.n_mirror = s->plan.mass_count;
     }
-    (void)dt;  // the value travels through device memory (upload_dt), the parameter block only points at it
-    p.dt = s->dt_dev;
-    p.flags = 0;
-    p.parts = nullptr;
-    p.split = 1;
-    p.unit = 64;
     return p;
 }
 
@@ -130,24 +112,12 @@ nb::StepParams whole_step(const SimPipeline *s, int in, float dt) {
 // last -- all other parts are complete by then: each workgroup waits for its own stores (vmcnt(0)) before it draws --
 // reads the parts back with the same scope, adds them in part order exactly like finish_kernel and integrates.  Same
 // bits as the two-kernel form (the GPU suite runs green with it forced on; tools/fused_finish_soak.py: 20 000 steps at
-// N = 10 000 + 300 random shapes, 0 differences).  What it buys is the finish kernel's boundary minus the ticket's
-// round trip (profiles/r04_fused_finish.txt, us per step, cached graph replays | plain launches):
-//   N = 5 000 +0.6 | -0.6    8 000 0.0 | -0.5    10 000 -0.4 | -1.0    14 000 -1.2 | -0.8    20 000 -0.7 | -0.9
-//   50 000 -1.5 | -1.6    100 000 -2.3 | -2.3
-// Auto (2, default): unsharded steps on the scalar-cache route with N x M >= 4e7 (N >~ 9 000: from where it also wins
-// inside a hipGraph) and at most 200 000 receivers (beyond that the finish kernel is < 0.3 % of a step, and the kernels
-// of the BASELINE sizes stay the ones the PMC profiles describe).  Sharded steps keep the two-kernel form.
-constexpr double FUSED_FINISH_MIN_PAIRS = 4.0e7;
-constexpr uint32_t FUSED_FINISH_MAX_RECV = 200000;
-
-bool fused_finish_rule(uint32_t n_recv, uint32_t n_src) {
-    return (double)n_recv * (double)n_src >= FUSED_FINISH_MIN_PAIRS && n_recv <= FUSED_FINISH_MAX_RECV;
-}
-
+// N = 10 000 + 300 random shapes, 0 differences).  What it buys, and from which size on it is the default:
+// launch_shape.hip fused_finish_rule.
 bool fused_finish_applies(const SimPipeline *s, nb::LaunchShape sh) {
     if (s->fused_finish == 0 || s->sharded || sh.split <= 1 || sh.lanes > 1 || s->tickets == nullptr) return false;
     if (nb::step_kernel_fused_fn(sh) == nullptr) return false;   // scalar-cache route, W >= 4
-    return s->fused_finish == 1 || fused_finish_rule(s->n_real, s->n_src);
+    return s->fused_finish == 1 || nb::fused_finish_rule(s->n_real, s->n_src);
 }
 
 nb::StepParams shaped(const SimPipeline *s, nb::StepParams p, nb::LaunchShape sh) {

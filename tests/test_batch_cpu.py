@@ -10,10 +10,9 @@ import pytest
 
 import nbody_amd as nb
 from test_abi import declared_functions, exported
-from test_isa import functions, reads_register
+from isa_common import check_rsq_wait_states, compile_isa, functions, kernel_meta
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-HIPCC = "/opt/rocm/bin/hipcc"
 
 BATCH_HIP = ["nb_hip_batch_create", "nb_hip_batch_destroy", "nb_hip_batch_set_data", "nb_hip_batch_get_data",
              "nb_hip_batch_get_member", "nb_hip_batch_update", "nb_hip_batch_update_dts", "nb_hip_batch_step_async",
@@ -173,14 +172,7 @@ print("OK")
 
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    out = tmp_path_factory.mktemp("batch_isa") / "kernels.s"
-    cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-Wno-unused-command-line-argument",
-           f"-I{ROOT}/include", f"-I{ROOT}/nbody_amd/csrc", "--cuda-device-only", "-S", "-o", str(out),
-           os.path.join(ROOT, "nbody_amd", "csrc", "kernels.hip")]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    return out.read_text()
+    return compile_isa(tmp_path_factory.mktemp("batch_isa"), "kernels.hip")
 
 
 def _batch(names):
@@ -193,24 +185,12 @@ def test_ensemble_kernels_keep_the_wait_state_behind_every_rsq(isa):
     assert len(names) == 3, names          # the chain and the two lane-split shapes the rule reaches
     assert not [n for n in fns if "batch" in n and "step_kernel" in n]   # test_isa.py matches step kernels by name
     for name in names:
-        body, total = fns[name], 0
-        for i, ins in enumerate(body):
-            if not ins.startswith("v_rsq_f32"):
-                continue
-            total += 1
-            dest = int(re.match(r"v_rsq_f32(?:_e\d+)?\s+v(\d+)", ins).group(1))
-            nxt = body[i + 1]
-            assert not (nxt.startswith("v_") and reads_register(nxt, dest)), f"{name}: `{ins}` read by `{nxt}`"
-            assert any(x.startswith("s_setprio 0") for x in body[i + 1:i + 3]), (name, body[i + 1:i + 3])
-            reader = next(j for j in range(i + 1, len(body)) if body[j].startswith("v_") and reads_register(body[j], dest))
-            assert any(x.startswith("s_") for x in body[i + 1:reader]), (name, ins, body[reader])
+        total = check_rsq_wait_states(name, fns[name])
         assert total >= 5, (name, total)
 
 
 def test_ensemble_kernels_fit_their_launch_bounds_without_scratch(isa):
-    meta = re.findall(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)\n\s+\.sgpr_count:\s+(\d+)"
-                      r"(?:\n.*?)*?\n\s+\.vgpr_count:\s+(\d+)", isa)
-    rows = {n: (int(scratch), int(sgpr), int(vgpr)) for n, scratch, sgpr, vgpr in meta}
+    rows = {n: (scratch, sgpr, vgpr) for n, scratch, sgpr, vgpr in kernel_meta(isa)}
     names = _batch(rows)
     assert len(names) == 3, names
     for name in names:

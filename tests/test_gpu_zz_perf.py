@@ -35,7 +35,7 @@ def _replay_us_per_step(part, m, steps=100, **knobs):
 @pytest.mark.parametrize("n", [2000, 10000, 20000, 65536])
 def test_auto_launch_shape_is_near_the_best_of_its_neighbours_on_this_box(n):
     """Ask the hardware, not the scan file: below N ~ 65 000 ten fitted constants and five thresholds pick every launch
-    shape (kernels.hip small_launch_cost_us / lane_split_rule), and the CPU tests pin them to the scans they were fitted
+    shape (launch_shape.hip small_launch_cost_us / lane_split_rule), and the CPU tests pin them to the scans they were fitted
     on.  Here the auto pick and its explicit neighbours (k, w, split around it; lane-split variants where they apply) are
     timed on whatever box and runtime the suite landed on; auto more than 10 % slower than the best neighbour fails."""
     _, part, m = bench_universe(n)

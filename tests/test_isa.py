@@ -11,85 +11,32 @@ only the GPU parity tests would otherwise notice:
 """
 import os
 import re
-import subprocess
+import struct
 
 import pytest
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-HIPCC = "/opt/rocm/bin/hipcc"
+from isa_common import ROOT, check_rsq_wait_states, compile_isa, functions, kernel_meta
 
 
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not installed")
-    out = tmp_path_factory.mktemp("isa") / "kernels.s"
-    src = os.path.join(ROOT, "nbody_amd", "csrc", "kernels.hip")
-    # the flags of nbody_amd/csrc/Makefile (HIPFLAGS), device side only, assembly out
-    cmd = [HIPCC, "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-std=c++17", "-Wno-unused-command-line-argument",
-           f"-I{ROOT}/include", f"-I{ROOT}/nbody_amd/csrc", "--cuda-device-only", "-S", "-o", str(out), src]
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    return out.read_text()
+    return compile_isa(tmp_path_factory.mktemp("isa"), "kernels.hip")
 
 
-def functions(text):
-    """name -> list of instruction lines (labels, directives and comments dropped)."""
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.match(r"^(_ZN2nb\S+):", line)
-        if m:
-            name = m.group(1)
-            out[name] = []
-            continue
-        if line.startswith(".Lfunc_end"):
-            name = None
-            continue
-        if name is None:
-            continue
-        ins = line.split(";")[0].strip()
-        if not ins or ins.startswith(".") or ins.endswith(":"):
-            continue
-        out[name].append(ins)
-    return out
-
-
-def reads_register(ins, reg):
-    """Does instruction text `ins` mention VGPR number `reg` (alone or inside a v[a:b] range)?"""
-    for m in re.finditer(r"\bv(\d+)\b", ins):
-        if int(m.group(1)) == reg:
-            return True
-    for m in re.finditer(r"\bv\[(\d+):(\d+)\]", ins):
-        if int(m.group(1)) <= reg <= int(m.group(2)):
-            return True
-    return False
+@pytest.fixture(scope="module")
+def convert_isa(tmp_path_factory):
+    return compile_isa(tmp_path_factory.mktemp("convert_isa"), "convert.hip")
 
 
 def test_every_rsq_has_a_wait_state_before_its_consumer(isa):
     fns = {n: body for n, body in functions(isa).items() if "step_kernel" in n}
     assert len(fns) >= 16, sorted(fns)
-    total = 0
-    for name, body in fns.items():
-        for i, ins in enumerate(body):
-            if not ins.startswith("v_rsq_f32"):
-                continue
-            total += 1
-            dest = int(re.match(r"v_rsq_f32(?:_e\d+)?\s+v(\d+)", ins).group(1))
-            nxt = body[i + 1]
-            assert not (nxt.startswith("v_") and reads_register(nxt, dest)), \
-                f"{name}: `{ins}` is read by the very next instruction `{nxt}` (no wait state)"
-            # the shipped bodies: one rsq (K = 1) or two back to back (K = 2) inside a raised-priority window whose
-            # closing s_setprio 0 is the wait state before the first dependent multiply
-            assert any(x.startswith("s_setprio 0") for x in body[i + 1:i + 3]), f"{name}: no s_setprio 0 after `{ins}`: {body[i + 1:i + 3]}"
-            assert any(x.startswith("s_setprio 3") for x in body[i - 2:i]), f"{name}: rsq not issued at raised priority: {body[i - 2:i]}"
-            reader = next(j for j in range(i + 1, len(body)) if body[j].startswith("v_") and reads_register(body[j], dest))
-            assert any(x.startswith("s_") for x in body[i + 1:reader]), f"{name}: no scalar slot between `{ins}` and `{body[reader]}`"
+    total = sum(check_rsq_wait_states(name, body) for name, body in fns.items())
     assert total >= 16 * 8, total
 
 
 def test_step_kernel_instantiations_fit_the_occupancy_the_launch_bounds_promise(isa):
-    meta = re.findall(r"\.name:\s+(\S+)\n\s+\.private_segment_fixed_size:\s+(\d+)\n\s+\.sgpr_count:\s+(\d+)"
-                      r"(?:\n.*?)*?\n\s+\.vgpr_count:\s+(\d+)", isa)
-    step = [(n, int(scratch), int(sgpr), int(vgpr)) for n, scratch, sgpr, vgpr in meta if "step_kernel" in n]
+    step = [row for row in kernel_meta(isa) if "step_kernel" in row[0]]
     assert len(step) >= 16
     for name, scratch, sgpr, vgpr in step:
         assert vgpr <= 64, f"{name}: {vgpr} VGPRs (> 64 halves the occupancy of a 1024-thread workgroup)"
@@ -123,14 +70,13 @@ def test_interaction_body_is_the_twelve_instruction_sequence(isa):
             assert not any(op.startswith("v_pk_") for op in ops[a:b]), ops[a:b]
 
 
-def test_the_gravitational_constant_is_written_down_once(isa):
+def test_the_gravitational_constant_is_written_down_once(convert_isa):
     """NB_G lives in include/nbody.h and nowhere else: the kernels get it as a launch argument from the host, like the
     reference's specialisation constant (reference src/lib/sim_gpu.c:54-72, src/shader/particle_cs.glsl:26).  No source
-    under nbody_amd/csrc may spell the value, and the device code of the two kernels that multiply by G must not hold
-    it as an instruction literal either."""
+    under nbody_amd/csrc may spell the value, and the device code of the kernels that multiply by G (convert.hip: exactly the
+    callers of g_times_m) must not hold it as an instruction literal either."""
     header = open(os.path.join(ROOT, "include", "nbody.h")).read()
     value = float(re.search(r"^#define\s+NB_G\s+([0-9.eE+-]+)f\s*$", header, re.M).group(1))
-    import struct
     literal = "0x%08x" % struct.unpack("<I", struct.pack("<f", value))[0]          # 0x41200000 for 10.0f
     spelled = re.compile(r"(?<![\w.])%s(?:\.0*)?f?(?![\w.])" % re.escape(("%g" % value)))
     csrc = os.path.join(ROOT, "nbody_amd", "csrc")
@@ -141,12 +87,22 @@ def test_the_gravitational_constant_is_written_down_once(isa):
         for m in spelled.finditer(text):
             line = text[text.rfind("\n", 0, m.start()) + 1:text.find("\n", m.end())]
             assert not re.search(r"f\b", m.group(0)) and "mul" not in line, f"{name}: `{line.strip()}` spells NB_G's value"
-    for src in ("kernels.hip", "pipeline.hip"):
+    for src in ("kernels.hip", "convert.hip", "launch_shape.hip", "pipeline.hip"):
         assert "10.0f" not in open(os.path.join(csrc, src)).read(), src
     assert "NB_G" in open(os.path.join(csrc, "pipeline.hip")).read()
-    fns = functions(isa)
-    users = {n: b for n, b in fns.items() if "make_gm_kernel" in n or "split_sources_kernel" in n}
-    assert len(users) == 2, sorted(fns)
+    # the kernels that multiply by G are exactly the ones that call the shared helper, and nothing outside convert.hip does
+    text = open(os.path.join(csrc, "convert.hip")).read()
+    callers = set()
+    for m in re.finditer(r"__global__ void (\w+)\(.*?\n}\n", text, flags=re.S):
+        if "g_times_m(" in m.group(0):
+            callers.add(m.group(1))
+    assert callers == {"make_gm_kernel", "split_sources_kernel", "batch_split_kernel"}, callers
+    assert len(re.findall(r"\bg_times_m\(", text)) == len(callers) + 1                    # one definition, one call each
+    assert not [n for n in sorted(os.listdir(csrc)) if n != "convert.hip" and "g_times_m" in open(os.path.join(csrc, n), errors="replace").read()]
+    fns = functions(convert_isa)
+    multiply = {n for n, b in fns.items() if any(ins.startswith(("v_mul_f32", "v_pk_mul_f32")) for ins in b)}
+    users = {n: b for n, b in fns.items() if any(c in n for c in callers)}
+    assert len(users) == 3 and set(users) == multiply, (sorted(users), sorted(multiply))
     for name, body in users.items():
         assert any(ins.startswith("v_mul_f32") for ins in body), name
         assert not any(literal in ins.lower() or re.search(r"\b10\.0\b", ins) for ins in body), (name, literal)
@@ -193,3 +149,18 @@ def test_fused_finish_tail_uses_agent_scope_accesses_and_leaves_the_unfused_kern
     for name, body in plain.items():
         text = "\n".join(body)
         assert "global_atomic" not in text and not re.search(r"global_(load|store)\S* .* sc1", text), name
+
+
+def test_the_launch_policy_holds_no_device_code(tmp_path):
+    """launch_shape.hip is host arithmetic only: its device-side compilation emits no kernel and no device function, so
+    policy edits cannot move the kernel-source hash (benchlib.KERNEL_SOURCES) and kernels cannot hide outside it."""
+    text = compile_isa(tmp_path, "launch_shape.hip")
+    assert ".amdhsa_kernel" not in text and "s_endpgm" not in text and "s_setpc_b64" not in text, text[:2000]
+    assert not functions(text)
+    assert not re.findall(r"^\s*[vs]_\w+", text, flags=re.M)        # not one instruction
+    # and the three hashed files hold no launch policy in return
+    csrc = os.path.join(ROOT, "nbody_amd", "csrc")
+    hashed = "".join(open(os.path.join(csrc, n)).read() for n in ("kernels.hip", "kernels.h", "interaction_asm.h"))
+    assert "NB_HASH_O" not in hashed
+    for name in ("small_launch_cost_us", "choose_shape(LaunchShape want", "struct LaunchShape {"):
+        assert name not in hashed, name

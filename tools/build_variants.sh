@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 build() { # name, extra flags
   name=$1; shift
   mkdir -p tools/exp/$name
-  for f in kernels pipeline step_chain device_ctx rccl_bind shard_plan; do
+  for f in kernels launch_shape convert pipeline step_chain device_ctx rccl_bind shard_plan; do
     /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -std=c++17 -Iinclude -Inbody_amd/csrc "$@" -c nbody_amd/csrc/$f.hip -o tools/exp/$name/$f.o &
   done
   wait
