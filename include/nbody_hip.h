@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include "nbody.h"
 #include "nbody_diag.h" /* WorldEnergy */
+#include "nbody_render.h" /* RenderView, RenderPalette */
 
 #ifdef __cplusplus
 extern "C" {
@@ -329,6 +330,24 @@ void nb_hip_local_group_step(SimPipeline **sims, int nranks, uint32_t n, float d
  */
 void nb_hip_energy(SimPipeline *sim, WorldEnergy *out);
 void nb_hip_potential(SimPipeline *sim, float *phi);
+
+/*
+ * Rendering the state the pipeline holds (definitions: include/nbody_render.h; all three results are bitwise functions of
+ * the state and the view):
+ *   nb_hip_bounds         bounds[4] = {min.x, min.y, max.x, max.y} over the particles with finite x and y
+ *   nb_hip_render_counts  counts[3][height][width] uint32: particles of each class covering each pixel
+ *   nb_hip_render_rgba    rgba[height][width][4] uint8: the count image shaded with *palette (not NULL)
+ * Like the diagnostics above they are enqueued on the pipeline's stream behind any nb_hip_step_async work, read the buffer
+ * that holds the latest state, block until their own result is in the caller's host buffer, and change nothing observable:
+ * the state, the ping-pong phase, the cached chains (nb_hip_graph_stats), the step-size uploads, what nb_hip_last_step_ms
+ * reports and the frame loop's eager read-back are as before the call.  The count image, the disc list and the frame live
+ * in device buffers of the pipeline that grow on demand and are freed by DestroySimPipeline.  Abort before the first
+ * SetSimulationData, for an invalid view or palette, and for sharded pipelines (a sharded render needs a collective over
+ * the ranks: not supported).  Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_render_rgba").
+ */
+void nb_hip_bounds(SimPipeline *sim, float *bounds);
+void nb_hip_render_counts(SimPipeline *sim, const RenderView *view, uint32_t *counts);
+void nb_hip_render_rgba(SimPipeline *sim, const RenderView *view, const RenderPalette *palette, uint8_t *rgba);
 
 /*
  * World ensembles: `count` independent worlds with the same particle count, stepped together.

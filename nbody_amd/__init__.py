@@ -51,6 +51,36 @@ class WorldEnergy(C.Structure):
                 "center_of_mass": (self.center_of_mass[0], self.center_of_mass[1])}
 
 
+class RenderView(C.Structure):
+    """include/nbody_render.h RenderView: sx = (x - target) * zoom + offset on a width x height screen."""
+    _fields_ = [("target", C.c_float * 2), ("offset", C.c_float * 2), ("zoom", C.c_float), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("core_mass", C.c_float)]
+
+    @classmethod
+    def make(cls, target, offset, zoom, width, height, core_mass):
+        return cls((C.c_float * 2)(*target), (C.c_float * 2)(*offset), zoom, width, height, core_mass)
+
+    def as_dict(self):
+        return {"target": (self.target[0], self.target[1]), "offset": (self.offset[0], self.offset[1]), "zoom": self.zoom,
+                "width": self.width, "height": self.height, "core_mass": self.core_mass}
+
+
+class RenderPalette(C.Structure):
+    """include/nbody_render.h RenderPalette: RGBA background, RGBA per class, the count at which a pixel saturates."""
+    _fields_ = [("background", C.c_uint8 * 4), ("color", (C.c_uint8 * 4) * 3), ("saturation", C.c_uint32)]
+
+    @classmethod
+    def make(cls, background, color, saturation):
+        return cls((C.c_uint8 * 4)(*background), ((C.c_uint8 * 4) * 3)(*[(C.c_uint8 * 4)(*c) for c in color]), saturation)
+
+
+def default_palette():
+    """DefaultRenderPalette (include/nbody_render.h)."""
+    p = RenderPalette()
+    nbody_lib().DefaultRenderPalette(C.byref(p))
+    return p
+
+
 class NbShardPlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mass_chunk", "zero_chunk", "mass_begin", "mass_count",
                                           "zero_begin", "zero_count", "src_padded")]
@@ -102,6 +132,9 @@ HIP_API = {
     "nb_hip_local_group_step": (None, [C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_float]),
     "nb_hip_energy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
     "nb_hip_potential": (None, [C.c_void_p, C.c_void_p]),
+    "nb_hip_bounds": (None, [C.c_void_p, C.c_void_p]),
+    "nb_hip_render_counts": (None, [C.c_void_p, C.POINTER(RenderView), C.c_void_p]),
+    "nb_hip_render_rgba": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
     "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nb_hip_batch_destroy": (None, [C.c_void_p]),
     "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
@@ -129,10 +162,11 @@ TUNE_API = {
     "nb_hip_plan_fused_finish": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int]),
     "nb_hip_plan_launch_lanes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
     "nb_hip_last_diag_ms": (C.c_double, [C.c_void_p]),
+    "nb_hip_last_render_ms": (C.c_double, [C.c_void_p, C.POINTER(C.c_double)]),
 }
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
-# include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h
+# include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_render.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -147,6 +181,12 @@ NBODY_API = {
     "MakeGalaxiesSeeded": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "GetWorldEnergy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
     "GetWorldPotential": (None, [C.c_void_p, C.c_void_p]),
+    # include/nbody_render.h
+    "DefaultRenderPalette": (None, [C.POINTER(RenderPalette)]),
+    "GetWorldBounds": (None, [C.c_void_p, C.c_void_p]),
+    "FitWorldView": (None, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RenderView)]),
+    "RenderWorldCounts": (None, [C.c_void_p, C.POINTER(RenderView), C.c_void_p]),
+    "RenderWorld": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
     # include/nbody_batch.h
     "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "DestroyWorldBatch": (None, [C.c_void_p]),
@@ -410,6 +450,32 @@ class SimPipeline:
         """tuning hook: device ms of the kernels of the last energy() / potential()."""
         return float(hip_lib().nb_hip_last_diag_ms(self._h))
 
+    def bounds(self):
+        """nb_hip_bounds: float32 [min.x, min.y, max.x, max.y] over the particles with finite x and y."""
+        out = np.empty(4, dtype=np.float32)
+        hip_lib().nb_hip_bounds(self._h, out.ctypes.data)
+        return out
+
+    def render_counts(self, view):
+        """nb_hip_render_counts: uint32 (3, height, width), particles of each class covering each pixel."""
+        out = np.empty((3, view.height, view.width), dtype=np.uint32)
+        hip_lib().nb_hip_render_counts(self._h, C.byref(view), out.ctypes.data)
+        return out
+
+    def render(self, view, palette=None):
+        """nb_hip_render_rgba: uint8 (height, width, 4); palette None = DefaultRenderPalette."""
+        out = np.empty((view.height, view.width, 4), dtype=np.uint8)
+        pal = palette if palette is not None else default_palette()
+        hip_lib().nb_hip_render_rgba(self._h, C.byref(view), C.byref(pal), out.ctypes.data)
+        return out
+
+    def last_render_ms(self):
+        """tuning hook: (device ms of the last render, [bounds, clear + splat, disc, shade]); the last three need
+        configure(render_detail=1)."""
+        parts = (C.c_double * 4)()
+        total = hip_lib().nb_hip_last_render_ms(self._h, parts)
+        return float(total), [float(v) for v in parts]
+
     def fused_steps(self):
         """steps of the last update that ran inside one-workgroup chain launches (knob fused_chain)."""
         return int(hip_lib().nb_hip_last_fused_steps(self._h))
@@ -645,6 +711,31 @@ class World:
         """GetWorldPotential: Phi_i of every particle (float32, in the order particles() returns them)."""
         out = np.empty(self.size, dtype=np.float32)
         nbody_lib().GetWorldPotential(self._h, out.ctypes.data)
+        return out
+
+
+    def bounds(self):
+        """GetWorldBounds (include/nbody_render.h): float32 [min.x, min.y, max.x, max.y]."""
+        out = np.empty(4, dtype=np.float32)
+        nbody_lib().GetWorldBounds(self._h, out.ctypes.data)
+        return out
+
+    def fit_view(self, width, height):
+        """FitWorldView: the RenderView that shows every finite particle on a width x height screen."""
+        v = RenderView()
+        nbody_lib().FitWorldView(self._h, width, height, C.byref(v))
+        return v
+
+    def render_counts(self, view):
+        """RenderWorldCounts: uint32 (3, height, width)."""
+        out = np.empty((3, view.height, view.width), dtype=np.uint32)
+        nbody_lib().RenderWorldCounts(self._h, C.byref(view), out.ctypes.data)
+        return out
+
+    def render(self, view, palette=None):
+        """RenderWorld: uint8 (height, width, 4); palette None = DefaultRenderPalette."""
+        out = np.empty((view.height, view.width, 4), dtype=np.uint8)
+        nbody_lib().RenderWorld(self._h, C.byref(view), C.byref(palette) if palette is not None else None, out.ctypes.data)
         return out
 
 

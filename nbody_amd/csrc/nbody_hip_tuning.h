@@ -38,6 +38,11 @@ extern "C" {
  *   "readback"  when the device state reaches the array named by nb_hip_note_host_array: 0 = only when GetSimulationData
  *               asks, 1 = at the end of every blocking PerformSimUpdate, 2 (default) = auto (eager once two updates in a
  *               row were each followed by a Get into the noted array)
+ *   "render_merge"  how splat_kernel adds points to the count image: 1 (default) = lanes of a wave that hit the same word
+ *               are merged first (one add per distinct word while merging pays), 0 = one atomic add per lane (the A/B of
+ *               tools/render_probe.py; same bits)
+ *   "render_detail" 1 = nb_hip_last_render_ms can split the last render into splat / disc / shade (three more event
+ *               records per call), 0 (default) = the whole render only
  *   "zero_copy_upload"  1 (default) = SetSimulationData from the noted, page-locked array lets the split kernel read the
  *               records over PCIe itself; 0 = DMA copy into device staging, then the kernel
  * Returns the previous value; aborts on an unknown key or value.
@@ -65,6 +70,11 @@ int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units);
 /* Device milliseconds of the kernels of the last nb_hip_energy / nb_hip_potential (their own event pair, not the step's);
  * 0 before the first call. */
 double nb_hip_last_diag_ms(SimPipeline *sim);
+
+/* Device milliseconds of the kernels of the last nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba (an event pair
+ * of their own); 0 before the first call.  parts (may be NULL) receives {bounds, clear + splat, disc, shade}: the last
+ * bounds call in parts[0]; the other three need the "render_detail" hook and read 0 without it. */
+double nb_hip_last_render_ms(SimPipeline *sim, double *parts);
 
 #ifdef __cplusplus
 }

@@ -99,6 +99,7 @@ void release_device(SimPipeline *s) {
         e = nullptr;
     }
     s->diag_timed = false;
+    render_release(s);
     ASSERT_HIP(hipEventDestroy(s->ev_begin), "event");
     ASSERT_HIP(hipEventDestroy(s->ev_end), "event");
     ASSERT_HIP(hipEventDestroy(s->ev_local), "event");
@@ -682,6 +683,13 @@ int nb_hip_tune(SimPipeline *s, const char *key, int value) {
         old = s->readback;
         s->readback = value;
         s->frame_streak = 0;
+    } else if (!strcmp(key, "render_merge")) {
+        NB_ASSERT(value == 0 || value == 1, "render_merge must be 0 (one atomic per lane) or 1 (merged), got %d", value);
+        old = s->render_merge;
+        s->render_merge = value;
+    } else if (!strcmp(key, "render_detail")) {
+        old = s->render_detail;
+        s->render_detail = value ? 1 : 0;
     } else if (!strcmp(key, "zero_copy_upload")) {
         old = s->zero_copy_upload;
         s->zero_copy_upload = value ? 1 : 0;

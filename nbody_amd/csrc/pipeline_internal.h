@@ -10,6 +10,7 @@
 //   convert.hip      AoS <-> SoA converters, pads, G*m, fills (convert.h)
 //   batch.hip        SimBatch: ensembles of small worlds stepped by one launch (nb_hip_batch_*)
 //   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
+//   render.hip       bounds, count image and RGBA frame of the state a pipeline holds (nb_hip_bounds, nb_hip_render_*)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -293,6 +294,18 @@ struct SimPipeline {
     uint32_t diag_phi_cap = 0;
     hipEvent_t ev_diag[2] = {nullptr, nullptr};
     bool diag_timed = false;
+
+    // render.hip (nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba): buffers grown on demand, events of their own
+    uint32_t *render_counts = nullptr;   // count image [3][height][width]
+    size_t render_counts_cap = 0;        // uint32 allocated in render_counts
+    void *render_discs = nullptr;        // compact disc list, total_len entries
+    uint32_t *render_words = nullptr;    // [0] discs appended by the last splat, [4..7] the bounds' ordered keys
+    uint32_t *render_rgba = nullptr;     // frame, one packed RGBA word per pixel
+    size_t render_rgba_cap = 0;          // pixels allocated in render_rgba
+    hipEvent_t ev_render[4] = {nullptr, nullptr, nullptr, nullptr};   // begin, after splat, after disc, end
+    hipEvent_t ev_bounds[2] = {nullptr, nullptr};
+    bool render_timed = false, render_detailed = false, bounds_timed = false;
+    int render_merge = 1, render_detail = 0;   // tuning hooks (nbody_hip_tuning.h)
 };
 
 namespace nbi {
@@ -314,5 +327,9 @@ void sharded_step(SimPipeline *s, nb::LaunchShape sh, float dt, hipStream_t cs, 
 // in-place all-gather of a device array of nranks slots through the caller's host transport
 void host_allgather(SimPipeline *s, void *dev_base, size_t bytes_per_rank, hipStream_t st);
 void enqueue_steps(SimPipeline *s, uint32_t n, float dt);  // what PerformSimUpdate / nb_hip_step_async enqueue
+
+// ---- render.hip ----------------------------------------------------------------------------------------------
+
+void render_release(SimPipeline *s);   // frees the render buffers and events (release_device)
 
 }  // namespace nbi

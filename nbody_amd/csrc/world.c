@@ -18,14 +18,19 @@
  * Extension (include/nbody_diag.h): GetWorldEnergy / GetWorldPotential compute
  * on the device when it holds the newest state, without pulling the array, and
  * on the host (diag_cpu.c) otherwise; neither moves a dirty flag.
+ * Extension (include/nbody_render.h): GetWorldBounds / FitWorldView /
+ * RenderWorldCounts / RenderWorld follow the same rule (render.hip on the
+ * device, render_cpu.c on the host).
  */
 #include "nbody.h"
 #include "nbody_diag.h"
 #include "nbody_hip.h"
+#include "nbody_render.h"
 
 #include <stdbool.h>
 
 #include "diag_sums.h"
+#include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
 #include "world_partition.h"
@@ -155,4 +160,39 @@ void GetWorldPotential(World *w, float *phi) {
         nb_hip_potential(w->gpu, phi);
     else
         nb_cpu_potential(w->particles, w->count, w->massive, phi);
+}
+
+void GetWorldBounds(World *w, float *bounds) {
+    NB_CHECK(w != NULL && bounds != NULL, "NULL argument");
+    if (diag_on_device(w, "GetWorldBounds"))
+        nb_hip_bounds(w->gpu, bounds);
+    else
+        nb_cpu_bounds(w->particles, w->count, bounds);
+}
+
+void FitWorldView(World *w, uint32_t width, uint32_t height, RenderView *view) {
+    float bounds[4];
+    GetWorldBounds(w, bounds);
+    nb_fit_view(bounds, width, height, view);
+}
+
+void RenderWorldCounts(World *w, const RenderView *view, uint32_t *counts) {
+    NB_CHECK(w != NULL && view != NULL && counts != NULL, "NULL argument");
+    if (diag_on_device(w, "RenderWorldCounts"))
+        nb_hip_render_counts(w->gpu, view, counts);
+    else
+        nb_cpu_render_counts(w->particles, w->count, view, counts);
+}
+
+void RenderWorld(World *w, const RenderView *view, const RenderPalette *palette, uint8_t *rgba) {
+    NB_CHECK(w != NULL && view != NULL && rgba != NULL, "NULL argument");
+    RenderPalette pal;
+    if (palette)
+        pal = *palette;
+    else
+        DefaultRenderPalette(&pal);
+    if (diag_on_device(w, "RenderWorld"))
+        nb_hip_render_rgba(w->gpu, view, &pal, rgba);
+    else
+        nb_cpu_render_rgba(w->particles, w->count, view, &pal, rgba);
 }
