@@ -399,6 +399,25 @@ uint32_t nb_hip_batch_dt_uploads(const SimBatch *batch);
  */
 void nb_hip_batch_launch_shape(const SimBatch *batch, int *path, int *k, int *w, int *lanes, uint32_t *workgroups);
 
+/*
+ * Conservation diagnostics of every member of an ensemble, in one pass over all members (definitions:
+ * include/nbody_diag.h; M_b = mass_len[b]):
+ *   nb_hip_ensemble_energy     fills out[count]: member b's WorldEnergy
+ *   nb_hip_ensemble_potential  writes count * total_len floats, member-major: Phi_i of every particle of every member
+ * Member b's result is BIT-IDENTICAL to nb_hip_energy / nb_hip_potential of a SimPipeline holding the same particles: it
+ * does not depend on count, on the member's index or on the other members (the sums run in a fixed order that both kernels
+ * share).  A member with M_b = 0 gives all-zero sums and Phi = 0; M_b = 1 gives Phi_0 = 0.
+ * Like nb_hip_energy for a pipeline: both are enqueued on the ensemble's stream behind any nb_hip_batch_step_async work,
+ * read the buffer that holds the latest state, block until their result is on the host, and change nothing observable --
+ * the state, the ping-pong phase, the step sizes on the device, nb_hip_batch_dt_uploads and nb_hip_batch_last_ms are as
+ * before the call.  The particles are not read back: energy is two launches and one copy of 64 * count bytes, potential
+ * one launch and one copy of 4 * count * total_len bytes, for any count.  Their scratch belongs to the SimBatch, is made
+ * on first use and freed by nb_hip_batch_destroy.  Abort before nb_hip_batch_set_data.  Added WITHOUT a version bump:
+ * detect them by symbol (dlsym "nb_hip_ensemble_energy").
+ */
+void nb_hip_ensemble_energy(SimBatch *batch, WorldEnergy *out /* [count] */);
+void nb_hip_ensemble_potential(SimBatch *batch, float *phi /* [count * total_len], member-major */);
+
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int nb_hip_version(void);
 

@@ -148,6 +148,8 @@ HIP_API = {
     "nb_hip_batch_dt_uploads": (C.c_uint32, [C.c_void_p]),
     "nb_hip_batch_launch_shape": (None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                          C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "nb_hip_ensemble_energy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
+    "nb_hip_ensemble_potential": (None, [C.c_void_p, C.c_void_p]),
     "nb_hip_version": (C.c_int, []),
 }
 
@@ -163,10 +165,12 @@ TUNE_API = {
     "nb_hip_plan_launch_lanes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
     "nb_hip_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_last_render_ms": (C.c_double, [C.c_void_p, C.POINTER(C.c_double)]),
+    "nb_hip_ensemble_last_diag_ms": (C.c_double, [C.c_void_p]),
 }
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
-# include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_render.h
+# include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
+# include/nbody_render.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -193,6 +197,9 @@ NBODY_API = {
     "GetWorldBatchParticles": (C.c_void_p, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "UpdateWorldBatch_GPU": (None, [C.c_void_p, C.c_float, C.c_uint32]),
     "UpdateWorldBatch_GPU_dts": (None, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
+    # include/nbody_batch_diag.h
+    "GetWorldBatchEnergy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
+    "GetWorldBatchPotential": (None, [C.c_void_p, C.c_void_p]),
 }
 
 _hip = None
@@ -569,6 +576,23 @@ class SimBatch:
     def dt_uploads(self):
         return int(hip_lib().nb_hip_batch_dt_uploads(self._h))
 
+    def energy(self):
+        """nb_hip_ensemble_energy: one dict per member (WorldEnergy.as_dict), each bit-identical to SimPipeline.energy() of
+        the same particles; two launches for the whole ensemble, no read-back of the particles."""
+        out = (WorldEnergy * self.count)()
+        hip_lib().nb_hip_ensemble_energy(self._h, out)
+        return [e.as_dict() for e in out]
+
+    def potential(self):
+        """nb_hip_ensemble_potential: Phi_i of every particle of every member, float32 (B, n), partitioned order."""
+        out = np.empty((self.count, self.total_len), dtype=np.float32)
+        hip_lib().nb_hip_ensemble_potential(self._h, out.ctypes.data)
+        return out
+
+    def last_diag_ms(self):
+        """tuning hook: device ms of the kernels of the last energy() / potential()."""
+        return float(hip_lib().nb_hip_ensemble_last_diag_ms(self._h))
+
     def launch_shape(self):
         """path "chain" / "lanes" plus the knobs that pin a SimPipeline to the same summation order (pinned_knobs)."""
         path, k, w, lanes, g = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_uint32()
@@ -617,6 +641,18 @@ class WorldBatch:
             nbody_lib().UpdateWorldBatch_GPU(self._h, float(dt), n)
         else:
             nbody_lib().UpdateWorldBatch_GPU_dts(self._h, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)), n)
+
+    def energy(self):
+        """GetWorldBatchEnergy (include/nbody_batch_diag.h): one dict per member, as World.energy() gives it."""
+        out = (WorldEnergy * self.count)()
+        nbody_lib().GetWorldBatchEnergy(self._h, out)
+        return [e.as_dict() for e in out]
+
+    def potential(self):
+        """GetWorldBatchPotential: Phi_i of every particle of every member, float32 (B, n), in member(b)'s order."""
+        out = np.empty((self.count, self.size), dtype=np.float32)
+        nbody_lib().GetWorldBatchPotential(self._h, out.ctypes.data)
+        return out
 
 
 class LocalShardGroup:

@@ -13,6 +13,9 @@
 // that shape (tests/test_gpu_batch.py).  Members share nothing with each other and a SimBatch shares nothing with any
 // SimPipeline: own stream, own buffers, own events.
 #include "pipeline_internal.h"
+#include "batch_diag.h"
+#include "diag_sums.h"
+#include "nbody_hip_tuning.h"
 
 using namespace nbi;
 
@@ -43,6 +46,16 @@ struct SimBatch {
     int k = 2, w = 16, lanes = 1;
     uint32_t tiles = 0;
     uint32_t workgroups = 0;
+
+    // nb_hip_ensemble_energy / nb_hip_ensemble_potential (kernels: batch_diag.hip): scratch made on first use, an event
+    // pair of their own (ev[] keeps bracketing the last update)
+    double *diag = nullptr;      // float64 slab: [count][tiles of 128][NB_DIAG_SUMS] + the [count][NB_DIAG_SUMS] results
+    size_t diag_cap = 0;         // doubles allocated in diag
+    float *diag_phi = nullptr;   // the potentials on the device: [count][n]
+    size_t diag_phi_cap = 0;
+    std::vector<double> diag_host;   // the results on the host before they become WorldEnergy
+    hipEvent_t ev_diag[2] = {nullptr, nullptr};
+    bool diag_timed = false;
 };
 
 namespace {
@@ -148,6 +161,50 @@ void read_back(SimBatch *s, uint32_t first, uint32_t members, Particle *ps) {
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after an ensemble read-back");
 }
 
+// ---- diagnostics: the state every member holds, without reading the particles back ----------------------------------
+
+void check_diag(SimBatch *s, const void *out, const char *what) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(out != nullptr, "%s: NULL result array", what);
+    NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
+}
+
+nbd::EnsembleDiagParams begin_diag(SimBatch *s) {
+    use_device();
+    if (!s->ev_diag[0]) {
+        for (auto &e : s->ev_diag) ASSERT_HIP(hipEventCreate(&e), "event");
+    }
+    ASSERT_HIP(hipEventRecord(s->ev_diag[0], s->stream), "record diagnostics begin");
+    nbd::EnsembleDiagParams p{};
+    p.pos = s->pos[s->cur];
+    p.vel = s->vel;
+    p.radius = s->radius;
+    p.mass = s->mass;
+    p.gm = s->gm;
+    p.mass_len = s->mass_len_dev;
+    p.n = s->n;
+    p.stride = s->stride;
+    return p;
+}
+
+void end_diag(SimBatch *s) {
+    ASSERT_HIP(hipEventRecord(s->ev_diag[1], s->stream), "record diagnostics end");
+    s->diag_timed = true;
+}
+
+template <typename T>
+T *grown(SimBatch *s, T *&buf, size_t &cap, size_t need) {
+    if (cap < need) {
+        if (buf) {
+            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing a diagnostics buffer");
+            dev_free(buf);
+        }
+        buf = dev_alloc<T>(need);
+        cap = need;
+    }
+    return buf;
+}
+
 }  // namespace
 
 extern "C" {
@@ -199,6 +256,10 @@ void nb_hip_batch_destroy(SimBatch *s) {
         dev_free(s->mass_len_dev);
         dev_free(s->dt_dev);
         dev_free(s->aos);
+        if (s->diag) dev_free(s->diag);
+        if (s->diag_phi) dev_free(s->diag_phi);
+        for (auto &e : s->ev_diag)
+            if (e) ASSERT_HIP(hipEventDestroy(e), "event");
         for (auto &e : s->ev) ASSERT_HIP(hipEventDestroy(e), "event");
         ASSERT_HIP(hipStreamDestroy(s->stream), "stream");
     }
@@ -265,6 +326,50 @@ double nb_hip_batch_last_ms(SimBatch *s) {
 uint32_t nb_hip_batch_dt_uploads(const SimBatch *s) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
     return s->dt_uploads;
+}
+
+void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
+    check_diag(s, out, "nb_hip_ensemble_energy");
+    constexpr size_t Q = NB_DIAG_SUMS;
+    nbd::EnsembleDiagParams p = begin_diag(s);
+    const uint32_t tiles = nbd::ensemble_tiles(s->n);
+    double *slab = grown(s, s->diag, s->diag_cap, (size_t)s->count * (tiles + 1) * Q);
+    double *res = slab + (size_t)s->count * tiles * Q;
+    p.slab = slab;
+    nbd::launch_ensemble_potential(s->stream, p, s->count);
+    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (energy, %u members of %u)", s->count, s->n);
+    nbd::launch_ensemble_reduce(s->stream, slab, s->mass_len_dev, tiles, s->count, res);
+    ASSERT_HIP(hipGetLastError(), "ensemble_reduce_kernel launch (%u members)", s->count);
+    end_diag(s);
+    s->diag_host.resize((size_t)s->count * Q);
+    ASSERT_HIP(hipMemcpyAsync(s->diag_host.data(), res, (size_t)s->count * Q * sizeof(double), hipMemcpyDeviceToHost, s->stream),
+               "D2H of %u members' energy sums", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_energy");
+    for (uint32_t b = 0; b < s->count; b++) nb_energy_from_sums(s->diag_host.data() + (size_t)b * Q, out + b);
+}
+
+void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
+    check_diag(s, phi, "nb_hip_ensemble_potential");
+    nbd::EnsembleDiagParams p = begin_diag(s);
+    const size_t total = (size_t)s->count * s->n;
+    p.phi = grown(s, s->diag_phi, s->diag_phi_cap, total);
+    nbd::launch_ensemble_potential(s->stream, p, s->count);
+    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
+    end_diag(s);
+    ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u x %u potentials",
+               s->count, s->n);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_potential");
+}
+
+// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_ensemble_energy / _potential
+double nb_hip_ensemble_last_diag_ms(SimBatch *s) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (!s->diag_timed) return 0.0;
+    use_device();
+    ASSERT_HIP(hipEventSynchronize(s->ev_diag[1]), "diagnostics end event");
+    float ms = 0.0f;
+    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev_diag[0], s->ev_diag[1]), "diagnostics elapsed time");
+    return (double)ms;
 }
 
 void nb_hip_batch_launch_shape(const SimBatch *s, int *path, int *k, int *w, int *lanes, uint32_t *workgroups) {

@@ -1,0 +1,139 @@
+// diag_common.h -- the arithmetic of the energy / potential diagnostics, written once for the two translation units that
+// run it on the device: diagnostics.hip (one pipeline: potential_kernel slices the SOURCES over the 8 waves of a
+// workgroup) and batch_diag.hip (an ensemble: every wave owns its receivers and walks its member's whole source list).
+// Both must give the same bits for the same world (include/nbody_hip.h "World ensembles"), so what defines a result
+// lives here and nowhere else:
+//   * the pair statement and the fp32 sum over one block of 256 sources, j ascending (pair, group8, block_sum);
+//   * the eight float64 terms of one receiver (energy_terms);
+//   * the sum of the per-tile rows of one world (reduce_rows).
+// What differs between the two kernels is only which wave adds which block; the ORDER of the float64 additions is the
+// same in both: blocks [w * per, (w + 1) * per) from 0.0 for w = 0..7, per = ceil(ceil(M / 256) / 8), then
+// 0.0 + s_0 + ... + s_7.  -ffp-contract=off keeps the float64 expressions as written.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "diag_sums.h"
+
+namespace nbd {
+
+constexpr int WAVE = 64;
+constexpr int K = 2;                // receivers per lane
+constexpr int W = 8;                // source slices of the float64 sum (potential_kernel: one wave each)
+constexpr int TILE = WAVE * K;      // receivers per tile
+constexpr int BLOCK = 256;          // sources per plain fp32 block sum
+constexpr int QTY = NB_DIAG_SUMS;   // float64 quantities per tile row of an energy slab (diag_sums.h)
+constexpr int REDUCE_THREADS = 256;
+
+typedef float v16f __attribute__((ext_vector_type(16)));
+typedef float v8f __attribute__((ext_vector_type(8)));
+typedef const float __attribute__((address_space(4))) *ConstF;  // read-only for the whole launch: scalar loads
+
+template <typename V>
+__device__ __forceinline__ V cload(ConstF p) {
+    return *(const V __attribute__((address_space(4))) *)p;
+}
+
+// One source (wave-uniform, SGPRs) against the K receivers of this lane, as one asm statement per pair (as in
+// kernels.hip, and for the same reasons: left to hipcc, the two receivers' FMAs become v_pk_fma_f32, which this project
+// measured slower beside a transcendental, and the schedule drifts with unrelated edits):
+//     v_sub_f32   dx  = sx - x
+//     v_sub_f32   dy  = sy - y
+//     v_fma_f32   q   = dx * dx + radius      softening: + radius of the RECEIVER, not squared
+//     v_fmac_f32  q  += dy * dy
+//     v_rsq_f32   q   = 1 / sqrt(q)          at raised wave priority, like the step kernels' rsq
+//     v_fmac_f32  phi += (G*m) * q           (the s_setprio 0 before it is the wait state a transcendental's reader needs)
+// MASK (the diagonal block only): source j may be receiver i itself; that term is dropped by a select AFTER the rsq
+// (r_i = 0 makes it inf, and 0 * inf is NaN), so the masked statement stops at the rsq.
+#define NB_PHI_HEAD_ASM                     \
+    "v_sub_f32 %[dx], %[sx], %[px]\n\t"     \
+    "v_sub_f32 %[dy], %[sy], %[py]\n\t"     \
+    "v_fma_f32 %[q], %[dx], %[dx], %[r]\n\t" \
+    "v_fmac_f32 %[q], %[dy], %[dy]\n\t"     \
+    "s_setprio 3\n\t"                      \
+    "v_rsq_f32 %[q], %[q]\n\t"              \
+    "s_setprio 0"
+template <bool MASK>
+__device__ __forceinline__ void pair(float (&a)[K], const float (&px)[K], const float (&py)[K], const float (&r)[K],
+                                     const uint32_t (&ri)[K], float sx, float sy, float g, uint32_t j) {
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        float dx, dy, q;
+        if constexpr (MASK) {
+            asm(NB_PHI_HEAD_ASM
+                : [dx] "=&v"(dx), [dy] "=&v"(dy), [q] "=&v"(q)
+                : [sx] "s"(sx), [sy] "s"(sy), [px] "v"(px[k]), [py] "v"(py[k]), [r] "v"(r[k]));
+            const float n = __builtin_fmaf(g, q, a[k]);
+            a[k] = j != ri[k] ? n : a[k];
+        } else {
+            asm(NB_PHI_HEAD_ASM "\n\t"
+                "v_fmac_f32 %[a], %[g], %[q]"
+                : [a] "+v"(a[k]), [dx] "=&v"(dx), [dy] "=&v"(dy), [q] "=&v"(q)
+                : [sx] "s"(sx), [sy] "s"(sy), [g] "s"(g), [px] "v"(px[k]), [py] "v"(py[k]), [r] "v"(r[k]));
+        }
+    }
+}
+
+template <bool MASK>
+__device__ __forceinline__ void group8(float (&a)[K], const float (&px)[K], const float (&py)[K], const float (&r)[K],
+                                       const uint32_t (&ri)[K], const v16f &P, const v8f &G, uint32_t j) {
+#pragma unroll
+    for (int u = 0; u < 8; u++) pair<MASK>(a, px, py, r, ri, P[2 * u], P[2 * u + 1], G[u], j + u);
+}
+
+// Sources [j0, j1) of one block (j0 a multiple of 256) added to a[]: 8 per scalar fetch (s_load_dwordx16 for the
+// positions, s_load_dwordx8 for G*m), then single sources for a ragged end.  One register set, no double buffering: the
+// kernel needs ~70 % of the step kernel's issue cycles per pair, and eight waves per SIMD hide the fetch of the next set
+// (the step kernel's two alternating sets cost the SGPRs that this kernel's operands need: they spilled to VGPR lanes).
+template <bool MASK>
+__device__ __forceinline__ void block_sum(float (&a)[K], const float (&px)[K], const float (&py)[K], const float (&r)[K],
+                                          const uint32_t (&ri)[K], ConstF sp, ConstF sg, uint32_t j0, uint32_t j1) {
+    uint32_t j = j0;
+    for (; j + 8 <= j1; j += 8) {
+        const v16f P = cload<v16f>(sp + 2 * (size_t)j);
+        const v8f G = cload<v8f>(sg + j);
+        group8<MASK>(a, px, py, r, ri, P, G, j);
+    }
+    for (; j < j1; j++) pair<MASK>(a, px, py, r, ri, sp[2 * (size_t)j], sp[2 * (size_t)j + 1], sg[j], j);
+}
+
+// The eight float64 terms of receiver i of a tile, in diag_sums.h order.  A dead lane (past the last receiver) reads
+// particle c = 0 with m = 0 and contributes no Phi term (the 0 * inf of a dead lane must not reach the sum).
+__device__ __forceinline__ void energy_terms(double (&e)[QTY], bool live, double phi, const float *mass, const float2 *pos,
+                                             const float2 *vel, uint32_t i) {
+    const uint32_t c = live ? i : 0u;
+    const double m = live ? (double)mass[c] : 0.0;
+    const float2 x = pos[c], v = vel[c];
+    const double vx = v.x, vy = v.y, xx = x.x, xy = x.y;
+    e[0] = live ? m * phi : 0.0;
+    e[1] = m * (vx * vx + vy * vy);
+    e[2] = m;
+    e[3] = m * vx;
+    e[4] = m * vy;
+    e[5] = m * (xx * vy - xy * vx);
+    e[6] = m * xx;
+    e[7] = m * xy;
+}
+
+// One workgroup of REDUCE_THREADS: out[q] = sum over the `rows` tile rows of quantity q.  Thread t of quantity q = t / 32
+// adds rows [l * chunk, (l + 1) * chunk), l = t % 32, in index order; the 32 partial sums meet in a fixed tree.
+__device__ __forceinline__ void reduce_rows(const double *slab, uint32_t rows, double *out) {
+    constexpr uint32_t LANES = REDUCE_THREADS / QTY;
+    __shared__ double red[QTY][LANES];
+    const uint32_t q = threadIdx.x / LANES, l = threadIdx.x % LANES;
+    const uint32_t chunk = (rows + LANES - 1) / LANES;
+    const uint32_t lo = min(l * chunk, rows), hi = min(lo + chunk, rows);
+    double s = 0.0;
+    for (uint32_t row = lo; row < hi; row++) s += slab[(size_t)row * QTY + q];
+    red[q][l] = s;
+    __syncthreads();
+    for (uint32_t half = LANES / 2; half > 0; half /= 2) {
+        if (l < half) red[q][l] = red[q][l] + red[q][l + half];
+        __syncthreads();
+    }
+    if (l == 0) out[q] = red[q][0];
+}
+
+}  // namespace nbd

@@ -71,6 +71,10 @@ int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units);
  * 0 before the first call. */
 double nb_hip_last_diag_ms(SimPipeline *sim);
 
+/* The same for an ensemble: device milliseconds of the kernels of the last nb_hip_ensemble_energy /
+ * nb_hip_ensemble_potential (an event pair of their own, not the update's); 0 before the first call. */
+double nb_hip_ensemble_last_diag_ms(SimBatch *batch);
+
 /* Device milliseconds of the kernels of the last nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba (an event pair
  * of their own); 0 before the first call.  parts (may be NULL) receives {bounds, clear + splat, disc, shade}: the last
  * bounds call in parts[0]; the other three need the "render_detail" hook and read 0 without it. */

@@ -10,6 +10,8 @@
 //   convert.hip      AoS <-> SoA converters, pads, G*m, fills (convert.h)
 //   batch.hip        SimBatch: ensembles of small worlds stepped by one launch (nb_hip_batch_*)
 //   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
+//   batch_diag.hip   the same for every member of a SimBatch: the kernels behind nb_hip_ensemble_energy / _potential
+//                    (batch_diag.h; the arithmetic both share: diag_common.h)
 //   render.hip       bounds, count image and RGBA frame of the state a pipeline holds (nb_hip_bounds, nb_hip_render_*)
 #pragma once
 

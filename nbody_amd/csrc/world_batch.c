@@ -5,12 +5,18 @@
  * partitioned "mass > 0 first" with CreateWorld's own routine (world_partition.h); the array is uploaded before the
  * first GPU step and pulled back only when a read follows a step.  Nothing on the host changes the array after
  * creation (no CPU stepper for ensembles), so one upload is all there ever is.
+ *
+ * include/nbody_batch_diag.h: GetWorldBatchEnergy / GetWorldBatchPotential compute on the device when it holds the
+ * newest state, without pulling the array, and on the host (diag_cpu.c, member by member) otherwise; neither moves
+ * device_is_newer.
  */
 #include "nbody_batch.h"
+#include "nbody_batch_diag.h"
 #include "nbody_hip.h"
 
 #include <stdbool.h>
 
+#include "diag_sums.h"
 #include "nb_util.h"
 #include "world_partition.h"
 
@@ -18,6 +24,7 @@ struct WorldBatch {
     Particle *particles;  /* count * size, member-major, each member partitioned */
     uint32_t size;        /* particles per member */
     uint32_t count;       /* members */
+    uint32_t *massive;    /* [count] particles with mass > 0 of each member; they come first */
     SimBatch *gpu;
     bool uploaded;        /* the device has seen the array */
     bool device_is_newer; /* the device stepped since the array was last refreshed */
@@ -38,7 +45,7 @@ WorldBatch *CreateWorldBatch(const Particle *ps, uint32_t world_size, uint32_t c
     w->size = world_size;
     w->count = count;
     w->gpu = nb_hip_batch_create(count, world_size, massive);
-    free(massive);
+    w->massive = massive;
     w->uploaded = false;
     w->device_is_newer = false;
     return w;
@@ -48,6 +55,7 @@ void DestroyWorldBatch(WorldBatch *w) {
     if (w == NULL) return;
     nb_hip_batch_destroy(w->gpu);
     free(w->particles);
+    free(w->massive);
     free(w);
 }
 
@@ -82,4 +90,23 @@ void UpdateWorldBatch_GPU_dts(WorldBatch *w, const float *dt, uint32_t n) {
     push_once(w);
     nb_hip_batch_update_dts(w->gpu, n, dt);
     w->device_is_newer = true;
+}
+
+void GetWorldBatchEnergy(WorldBatch *w, WorldEnergy *out) {
+    NB_CHECK(w != NULL && out != NULL, "NULL argument");
+    if (w->device_is_newer) {
+        nb_hip_ensemble_energy(w->gpu, out);
+        return;
+    }
+    for (uint32_t b = 0; b < w->count; b++) nb_cpu_energy(w->particles + (size_t)b * w->size, w->size, w->massive[b], out + b);
+}
+
+void GetWorldBatchPotential(WorldBatch *w, float *phi) {
+    NB_CHECK(w != NULL && phi != NULL, "NULL argument");
+    if (w->device_is_newer) {
+        nb_hip_ensemble_potential(w->gpu, phi);
+        return;
+    }
+    for (uint32_t b = 0; b < w->count; b++)
+        nb_cpu_potential(w->particles + (size_t)b * w->size, w->size, w->massive[b], phi + (size_t)b * w->size);
 }
