@@ -418,6 +418,29 @@ void nb_hip_batch_launch_shape(const SimBatch *batch, int *path, int *k, int *w,
 void nb_hip_ensemble_energy(SimBatch *batch, WorldEnergy *out /* [count] */);
 void nb_hip_ensemble_potential(SimBatch *batch, float *phi /* [count * total_len], member-major */);
 
+/*
+ * Traced updates: the n steps of nb_hip_batch_update(_dts) with every member's WorldEnergy recorded every `every` steps,
+ * in one call (what a sweep over step sizes or seeds compares is the drift of the energy over time).
+ *   nb_hip_ensemble_trace_rows  host arithmetic: R = 1 + n / every, the records such a call makes
+ *   nb_hip_ensemble_trace       one dt for every member
+ *   nb_hip_ensemble_trace_dts   dt[count]
+ * out is WorldEnergy[R][count], record-major: row 0 is the state on entry, row r the state after r * every steps; the
+ * trailing n mod every steps run and are not recorded; n = 0 gives row 0 alone and changes nothing.  Exactly the n steps
+ * of an untraced update run: the particles, the ping-pong phase, the step sizes on the device and nb_hip_batch_dt_uploads
+ * afterwards are bit for bit what nb_hip_batch_update(_dts)(n) leaves, and nb_hip_batch_last_ms brackets the whole call.
+ * Row r of member b is BIT-IDENTICAL to what nb_hip_ensemble_energy returns after the same steps made by separate update
+ * calls (and so to nb_hip_energy of the same world alone).  Nothing returns to the host between records: the rows collect
+ * in a device buffer of the SimBatch (made on first use, freed by nb_hip_batch_destroy) and one copy of R * count * 64
+ * bytes and one stream sync end the call.  total_len <= 512: the one launch that runs the call records from the state it
+ * holds (still one launch per 65 536 steps, whatever R is); above: the two launches of nb_hip_ensemble_energy are
+ * enqueued behind every `every`-th step launch.  Both calls block and queue behind earlier nb_hip_batch_step_async work.
+ * Abort for every = 0, a NULL argument, more than 2^24 rows (R * count; 1 GiB) and before nb_hip_batch_set_data.  Added
+ * WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_ensemble_trace").
+ */
+uint32_t nb_hip_ensemble_trace_rows(uint32_t n, uint32_t every);
+void nb_hip_ensemble_trace(SimBatch *batch, uint32_t n, float dt, uint32_t every, WorldEnergy *out /* [R][count] */);
+void nb_hip_ensemble_trace_dts(SimBatch *batch, uint32_t n, const float *dt /* [count] */, uint32_t every, WorldEnergy *out);
+
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int nb_hip_version(void);
 

@@ -51,6 +51,19 @@ class WorldEnergy(C.Structure):
                 "center_of_mass": (self.center_of_mass[0], self.center_of_mass[1])}
 
 
+def energy_row(row):
+    """One [8] row of a traced update (WorldEnergy field order: kinetic, potential, mass, momentum x / y, angular momentum,
+    centre of mass x / y) as the dict energy() returns for that state: rows compare with `==`."""
+    e = WorldEnergy()
+    C.memmove(C.byref(e), np.ascontiguousarray(row, dtype=np.float64).ctypes.data, C.sizeof(WorldEnergy))
+    return e.as_dict()
+
+
+def trace_rows(n, every):
+    """nb_hip_ensemble_trace_rows: the records a traced update of n steps makes, 1 + n // every."""
+    return int(hip_lib().nb_hip_ensemble_trace_rows(int(n), int(every)))
+
+
 class RenderView(C.Structure):
     """include/nbody_render.h RenderView: sx = (x - target) * zoom + offset on a width x height screen."""
     _fields_ = [("target", C.c_float * 2), ("offset", C.c_float * 2), ("zoom", C.c_float), ("width", C.c_uint32),
@@ -150,6 +163,9 @@ HIP_API = {
                                          C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "nb_hip_ensemble_energy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
     "nb_hip_ensemble_potential": (None, [C.c_void_p, C.c_void_p]),
+    "nb_hip_ensemble_trace_rows": (C.c_uint32, [C.c_uint32, C.c_uint32]),
+    "nb_hip_ensemble_trace": (None, [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
+    "nb_hip_ensemble_trace_dts": (None, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_void_p]),
     "nb_hip_version": (C.c_int, []),
 }
 
@@ -166,6 +182,8 @@ TUNE_API = {
     "nb_hip_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_last_render_ms": (C.c_double, [C.c_void_p, C.POINTER(C.c_double)]),
     "nb_hip_ensemble_last_diag_ms": (C.c_double, [C.c_void_p]),
+    "nb_hip_ensemble_trace_mode": (None, [C.c_void_p, C.c_int]),
+    "nb_hip_ensemble_last_trace_info": (None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
 }
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
@@ -200,6 +218,9 @@ NBODY_API = {
     # include/nbody_batch_diag.h
     "GetWorldBatchEnergy": (None, [C.c_void_p, C.POINTER(WorldEnergy)]),
     "GetWorldBatchPotential": (None, [C.c_void_p, C.c_void_p]),
+    # include/nbody_batch_trace.h
+    "UpdateWorldBatch_GPU_Traced": (None, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "UpdateWorldBatch_GPU_Traced_dts": (None, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_void_p]),
 }
 
 _hip = None
@@ -576,6 +597,28 @@ class SimBatch:
     def dt_uploads(self):
         return int(hip_lib().nb_hip_batch_dt_uploads(self._h))
 
+    def trace(self, n, dt, every):
+        """nb_hip_ensemble_trace(_dts): update(n, dt) that records every member's energy on entry and after every `every`-th
+        step, in one call.  float64 (R, count, 8) in WorldEnergy field order, R = 1 + n // every; energy_row(a[r, b]) is
+        what energy() gives member b for that state."""
+        out = np.empty((trace_rows(n, every), self.count, 8), dtype=np.float64)
+        if np.ndim(dt) == 0:
+            hip_lib().nb_hip_ensemble_trace(self._h, n, float(dt), every, out.ctypes.data)
+        else:
+            hip_lib().nb_hip_ensemble_trace_dts(self._h, n, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)), every,
+                                             out.ctypes.data)
+        return out
+
+    def trace_mode(self, mode):
+        """tuning hook: 0 = auto, 1 = interleave the diagnostics launches even where the chain records by itself."""
+        hip_lib().nb_hip_ensemble_trace_mode(self._h, int(mode))
+
+    def last_trace_info(self):
+        """tuning hook: {"fused": 0 / 1, "launches": kernel launches} of the last trace()."""
+        fused, launches = C.c_int(0), C.c_uint32(0)
+        hip_lib().nb_hip_ensemble_last_trace_info(self._h, C.byref(fused), C.byref(launches))
+        return {"fused": fused.value, "launches": launches.value}
+
     def energy(self):
         """nb_hip_ensemble_energy: one dict per member (WorldEnergy.as_dict), each bit-identical to SimPipeline.energy() of
         the same particles; two launches for the whole ensemble, no read-back of the particles."""
@@ -641,6 +684,17 @@ class WorldBatch:
             nbody_lib().UpdateWorldBatch_GPU(self._h, float(dt), n)
         else:
             nbody_lib().UpdateWorldBatch_GPU_dts(self._h, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)), n)
+
+    def update_gpu_traced(self, dt, n, every):
+        """UpdateWorldBatch_GPU_Traced(_dts): update_gpu(dt, n) that records every member's energy on entry and after every
+        `every`-th step; float64 (R, count, 8) like SimBatch.trace."""
+        out = np.empty((trace_rows(n, every), self.count, 8), dtype=np.float64)
+        if np.ndim(dt) == 0:
+            nbody_lib().UpdateWorldBatch_GPU_Traced(self._h, float(dt), n, every, out.ctypes.data)
+        else:
+            nbody_lib().UpdateWorldBatch_GPU_Traced_dts(self._h, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)), n,
+                                                        every, out.ctypes.data)
+        return out
 
     def energy(self):
         """GetWorldBatchEnergy (include/nbody_batch_diag.h): one dict per member, as World.energy() gives it."""

@@ -8,6 +8,9 @@
 //                     launch per call, for every call length and every B;
 //   512 < N <= 3 000  batch_lane_split_kernel<W, H>: gridDim.y = B, one launch per step, positions ping-pong between two
 //                     device arrays; (W, H) = lane_split_rule(N, N), a function of N alone.
+// A traced update (nb_hip_ensemble_trace) records every member's energy sums every k steps without returning to the host:
+// on the chain path batch_trace_chain_kernel records from the state it holds in LDS (still one launch per call), on the
+// lane-split path the two diagnostics launches are interleaved with the step launches; one copy and one sync at the end.
 // The path is chosen by N alone -- never by B or by the members' source counts -- and the kernels run the very bodies of
 // chain_kernel / lane_split_kernel, so member b's bits are those of the same particles alone in a SimPipeline pinned to
 // that shape (tests/test_gpu_batch.py).  Members share nothing with each other and a SimBatch shares nothing with any
@@ -56,6 +59,14 @@ struct SimBatch {
     std::vector<double> diag_host;   // the results on the host before they become WorldEnergy
     hipEvent_t ev_diag[2] = {nullptr, nullptr};
     bool diag_timed = false;
+
+    // nb_hip_ensemble_trace: the rows of the last traced call, on the device and on their way to WorldEnergy
+    double *trace = nullptr;     // [records][count][NB_DIAG_SUMS]
+    size_t trace_cap = 0;
+    std::vector<double> trace_host;
+    int trace_mode = 0;          // tuning hook: 1 = interleaved diagnostics launches also where the chain could record
+    int trace_fused = 0;         // what the last traced call did
+    uint32_t trace_launches = 0;
 };
 
 namespace {
@@ -107,12 +118,7 @@ void upload_dts(SimBatch *s, const float *dt, bool uniform) {
     s->dt_uploads++;
 }
 
-void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
-    NB_ASSERT(s != nullptr && dt != nullptr, "NULL argument");
-    NB_ASSERT(s->has_data, "ensemble update before nb_hip_batch_set_data");
-    if (n == 0) return;
-    use_device();
-    upload_dts(s, dt, uniform);
+nb::BatchParams step_params(const SimBatch *s) {
     nb::BatchParams p;
     memset(&p, 0, sizeof p);
     p.vel = s->vel;
@@ -124,27 +130,49 @@ void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
     p.n_recv = s->n;
     p.stride = s->stride;
     p.tiles = s->tiles;
-    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
-    if (s->path == 0) {
-        p.pos_in = p.pos_out = s->pos[s->cur];
-        for (uint32_t left = n; left > 0; left -= p.steps) {
-            p.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
-            nb::launch_batch_chain(s->stream, p, s->count);
-        }
-    } else {
-        const void *fn = nb::batch_lane_split_fn(s->w, s->lanes);
-        const nb::LaunchShape sh = {.k = 1, .w = s->w, .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = s->lanes};
-        dim3 grid = nb::step_grid(sh, s->n);
-        grid.y = s->count;
-        for (uint32_t i = 0; i < n; i++) {
-            p.pos_in = s->pos[s->cur];
-            p.pos_out = s->pos[s->cur ^ 1];
-            void *args[] = {&p};
-            ASSERT_HIP(hipLaunchKernel(fn, grid, nb::step_block(sh), args, nb::step_lds_bytes(sh, s->n), s->stream),
-                       "ensemble lane-split launch (w=%d lanes=%d, %u members of %u)", s->w, s->lanes, s->count, s->n);
-            s->cur ^= 1;
-        }
+    return p;
+}
+
+// n lane-split steps, one launch each
+void launch_lane_steps(SimBatch *s, nb::BatchParams &p, uint32_t n) {
+    const void *fn = nb::batch_lane_split_fn(s->w, s->lanes);
+    const nb::LaunchShape sh = {.k = 1, .w = s->w, .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = s->lanes};
+    dim3 grid = nb::step_grid(sh, s->n);
+    grid.y = s->count;
+    for (uint32_t i = 0; i < n; i++) {
+        p.pos_in = s->pos[s->cur];
+        p.pos_out = s->pos[s->cur ^ 1];
+        void *args[] = {&p};
+        ASSERT_HIP(hipLaunchKernel(fn, grid, nb::step_block(sh), args, nb::step_lds_bytes(sh, s->n), s->stream),
+                   "ensemble lane-split launch (w=%d lanes=%d, %u members of %u)", s->w, s->lanes, s->count, s->n);
+        s->cur ^= 1;
     }
+}
+
+// n steps, no record: whole chain launches or lane-split launches; returns the launches made
+uint32_t launch_steps(SimBatch *s, nb::BatchParams &p, uint32_t n) {
+    if (s->path != 0) {
+        launch_lane_steps(s, p, n);
+        return n;
+    }
+    uint32_t launches = 0;
+    p.pos_in = p.pos_out = s->pos[s->cur];
+    for (uint32_t left = n; left > 0; left -= p.steps, launches++) {
+        p.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
+        nb::launch_batch_chain(s->stream, p, s->count);
+    }
+    return launches;
+}
+
+void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
+    NB_ASSERT(s != nullptr && dt != nullptr, "NULL argument");
+    NB_ASSERT(s->has_data, "ensemble update before nb_hip_batch_set_data");
+    if (n == 0) return;
+    use_device();
+    upload_dts(s, dt, uniform);
+    nb::BatchParams p = step_params(s);
+    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+    launch_steps(s, p, n);
     ASSERT_HIP(hipGetLastError(), "ensemble launch (%u members of %u particles, %u steps)", s->count, s->n, n);
     ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
     s->timed = true;
@@ -169,12 +197,7 @@ void check_diag(SimBatch *s, const void *out, const char *what) {
     NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
 }
 
-nbd::EnsembleDiagParams begin_diag(SimBatch *s) {
-    use_device();
-    if (!s->ev_diag[0]) {
-        for (auto &e : s->ev_diag) ASSERT_HIP(hipEventCreate(&e), "event");
-    }
-    ASSERT_HIP(hipEventRecord(s->ev_diag[0], s->stream), "record diagnostics begin");
+nbd::EnsembleDiagParams diag_params(const SimBatch *s) {   // of the latest state
     nbd::EnsembleDiagParams p{};
     p.pos = s->pos[s->cur];
     p.vel = s->vel;
@@ -185,6 +208,15 @@ nbd::EnsembleDiagParams begin_diag(SimBatch *s) {
     p.n = s->n;
     p.stride = s->stride;
     return p;
+}
+
+nbd::EnsembleDiagParams begin_diag(SimBatch *s) {
+    use_device();
+    if (!s->ev_diag[0]) {
+        for (auto &e : s->ev_diag) ASSERT_HIP(hipEventCreate(&e), "event");
+    }
+    ASSERT_HIP(hipEventRecord(s->ev_diag[0], s->stream), "record diagnostics begin");
+    return diag_params(s);
 }
 
 void end_diag(SimBatch *s) {
@@ -203,6 +235,82 @@ T *grown(SimBatch *s, T *&buf, size_t &cap, size_t need) {
         cap = need;
     }
     return buf;
+}
+
+// The two launches of an energy diagnostic of the latest state: every member's eight sums -> res[count][NB_DIAG_SUMS].
+void launch_energy_sums(SimBatch *s, double *res) {
+    const uint32_t tiles = nbd::ensemble_tiles(s->n);
+    nbd::EnsembleDiagParams p = diag_params(s);
+    p.slab = s->diag;
+    nbd::launch_ensemble_potential(s->stream, p, s->count);
+    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (energy, %u members of %u)", s->count, s->n);
+    nbd::launch_ensemble_reduce(s->stream, s->diag, s->mass_len_dev, tiles, s->count, res);
+    ASSERT_HIP(hipGetLastError(), "ensemble_reduce_kernel launch (%u members)", s->count);
+}
+
+// The slab of per-tile rows, with room for one call's results behind it.
+double *energy_slab(SimBatch *s) {
+    return grown(s, s->diag, s->diag_cap, (size_t)s->count * (nbd::ensemble_tiles(s->n) + 1) * NB_DIAG_SUMS);
+}
+
+constexpr uint64_t TRACE_MAX_ROWS = 1ull << 24;   // rows of 64 bytes: 1 GiB
+
+// nb_hip_ensemble_trace / _dts: the n steps of enqueue() with a record of every member's sums before the first and after
+// every `every`-th, all in stream order; then one copy, one sync.
+void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t every, WorldEnergy *out) {
+    NB_ASSERT(s != nullptr && dt != nullptr && out != nullptr, "NULL argument");
+    NB_ASSERT(every > 0, "every = 0: a traced update records every k >= 1 steps");
+    NB_ASSERT((1ull + n / every) * s->count <= TRACE_MAX_ROWS, "%llu records x %u members > %llu rows (1 GiB of energy rows)",
+              1ull + n / every, s->count, (unsigned long long)TRACE_MAX_ROWS);
+    const uint32_t records = nb_hip_ensemble_trace_rows(n, every);
+    NB_ASSERT(s->has_data, "traced ensemble update before nb_hip_batch_set_data");
+    use_device();
+    if (n > 0) upload_dts(s, dt, uniform);
+    constexpr size_t Q = NB_DIAG_SUMS;
+    const size_t pitch = (size_t)s->count * Q;
+    double *rows = grown(s, s->trace, s->trace_cap, (size_t)records * pitch);
+    const bool fused = s->path == 0 && s->trace_mode == 0;
+    if (!fused) energy_slab(s);
+    nb::BatchParams p = step_params(s);
+    uint32_t launches = 0;
+    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+    if (fused) {
+        nb::BatchTraceParams t;
+        memset(&t, 0, sizeof t);
+        t.mass = s->mass;
+        t.rows = rows;
+        t.count = s->count;
+        t.every = every;
+        p.pos_in = p.pos_out = s->pos[s->cur];
+        do {   // n = 0 is one launch of no steps: the record on entry
+            const uint32_t left = n - t.done;
+            p.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
+            t.b = p;
+            nb::launch_batch_trace_chain(s->stream, t);
+            t.done += p.steps;
+            launches++;
+        } while (t.done < n);
+    } else {
+        launch_energy_sums(s, rows);
+        launches += 2;
+        for (uint32_t r = 1; r < records; r++) {
+            launches += launch_steps(s, p, every);
+            launch_energy_sums(s, rows + r * pitch);
+            launches += 2;
+        }
+        launches += launch_steps(s, p, n % every);
+    }
+    ASSERT_HIP(hipGetLastError(), "traced ensemble launch (%u members of %u particles, %u steps, a record every %u)", s->count, s->n,
+               n, every);
+    ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
+    s->timed = true;
+    s->trace_fused = fused;
+    s->trace_launches = launches;
+    s->trace_host.resize((size_t)records * pitch);
+    ASSERT_HIP(hipMemcpyAsync(s->trace_host.data(), rows, (size_t)records * pitch * sizeof(double), hipMemcpyDeviceToHost, s->stream),
+               "D2H of %u x %u energy rows", records, s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after a traced ensemble update");
+    for (size_t i = 0; i < (size_t)records * s->count; i++) nb_energy_from_sums(s->trace_host.data() + i * Q, out + i);
 }
 
 }  // namespace
@@ -258,6 +366,7 @@ void nb_hip_batch_destroy(SimBatch *s) {
         dev_free(s->aos);
         if (s->diag) dev_free(s->diag);
         if (s->diag_phi) dev_free(s->diag_phi);
+        if (s->trace) dev_free(s->trace);
         for (auto &e : s->ev_diag)
             if (e) ASSERT_HIP(hipEventDestroy(e), "event");
         for (auto &e : s->ev) ASSERT_HIP(hipEventDestroy(e), "event");
@@ -331,15 +440,9 @@ uint32_t nb_hip_batch_dt_uploads(const SimBatch *s) {
 void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
     check_diag(s, out, "nb_hip_ensemble_energy");
     constexpr size_t Q = NB_DIAG_SUMS;
-    nbd::EnsembleDiagParams p = begin_diag(s);
-    const uint32_t tiles = nbd::ensemble_tiles(s->n);
-    double *slab = grown(s, s->diag, s->diag_cap, (size_t)s->count * (tiles + 1) * Q);
-    double *res = slab + (size_t)s->count * tiles * Q;
-    p.slab = slab;
-    nbd::launch_ensemble_potential(s->stream, p, s->count);
-    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (energy, %u members of %u)", s->count, s->n);
-    nbd::launch_ensemble_reduce(s->stream, slab, s->mass_len_dev, tiles, s->count, res);
-    ASSERT_HIP(hipGetLastError(), "ensemble_reduce_kernel launch (%u members)", s->count);
+    begin_diag(s);
+    double *res = energy_slab(s) + (size_t)s->count * nbd::ensemble_tiles(s->n) * Q;
+    launch_energy_sums(s, res);
     end_diag(s);
     s->diag_host.resize((size_t)s->count * Q);
     ASSERT_HIP(hipMemcpyAsync(s->diag_host.data(), res, (size_t)s->count * Q * sizeof(double), hipMemcpyDeviceToHost, s->stream),
@@ -370,6 +473,30 @@ double nb_hip_ensemble_last_diag_ms(SimBatch *s) {
     float ms = 0.0f;
     ASSERT_HIP(hipEventElapsedTime(&ms, s->ev_diag[0], s->ev_diag[1]), "diagnostics elapsed time");
     return (double)ms;
+}
+
+uint32_t nb_hip_ensemble_trace_rows(uint32_t n, uint32_t every) {
+    NB_ASSERT(every > 0, "every = 0: a traced update records every k >= 1 steps");
+    return 1u + n / every;
+}
+
+void nb_hip_ensemble_trace(SimBatch *s, uint32_t n, float dt, uint32_t every, WorldEnergy *out) { trace(s, n, &dt, true, every, out); }
+
+void nb_hip_ensemble_trace_dts(SimBatch *s, uint32_t n, const float *dt, uint32_t every, WorldEnergy *out) {
+    trace(s, n, dt, false, every, out);
+}
+
+// tuning hooks (nbody_hip_tuning.h)
+void nb_hip_ensemble_trace_mode(SimBatch *s, int mode) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(mode == 0 || mode == 1, "trace mode %d (0 = auto, 1 = interleaved)", mode);
+    s->trace_mode = mode;
+}
+
+void nb_hip_ensemble_last_trace_info(const SimBatch *s, int *fused, uint32_t *launches) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (fused) *fused = s->trace_fused;
+    if (launches) *launches = s->trace_launches;
 }
 
 void nb_hip_batch_launch_shape(const SimBatch *s, int *path, int *k, int *w, int *lanes, uint32_t *workgroups) {

@@ -44,9 +44,8 @@ __global__ __launch_bounds__(WAVE * WAVES_MAX) void ensemble_phi_kernel(const En
     const size_t base = (size_t)member * p.stride;
     const float2 *pos = p.pos + base;
 
-    float px[K], py[K], r[K], a[K];
+    float px[K], py[K], r[K];
     uint32_t ri[K];
-    double sum[K];
 #pragma unroll
     for (int k = 0; k < K; k++) {
         uint32_t i = rb + k * WAVE + lane;
@@ -56,43 +55,11 @@ __global__ __launch_bounds__(WAVE * WAVES_MAX) void ensemble_phi_kernel(const En
         py[k] = q.y;
         r[k] = p.radius[base + i];
         ri[k] = i;
-        a[k] = 0.0f;
-        sum[k] = 0.0;
     }
 
-    // the eight source slices of potential_kernel's waves, one after another, in whole blocks
-    const uint32_t nblocks = (n_src + BLOCK - 1) / BLOCK;
-    const uint32_t per = (nblocks + W - 1) / W;
-    const ConstF sp = (ConstF)(uintptr_t)pos, sg = (ConstF)(uintptr_t)(p.gm + base);
-#pragma unroll 1
-    for (uint32_t w = 0; w < W; w++) {
-        const uint32_t b_lo = min(w * per, nblocks);
-        const uint32_t b_hi = min(b_lo + per, nblocks);
-        double s[K];
-#pragma unroll
-        for (int k = 0; k < K; k++) s[k] = 0.0;
-#pragma unroll 1
-        for (uint32_t b = b_lo; b < b_hi; b++) {
-            const uint32_t j0 = b * BLOCK, j1 = min(j0 + BLOCK, n_src);
-            // [j0, m0) before, [m0, m1) the tile's own indices (masked), [m1, j1) after: the same pairs in the same order
-            // as one block_sum over [j0, j1), and m0, m1 are multiples of 128 or an end of the block
-            const uint32_t m0 = min(max(rb, j0), j1), m1 = min(max(rb + TILE, j0), j1);
-#pragma unroll 1
-            for (uint32_t seg = 0; seg < 3; seg++) {
-                if (seg == 1)
-                    block_sum<true>(a, px, py, r, ri, sp, sg, m0, m1);
-                else
-                    block_sum<false>(a, px, py, r, ri, sp, sg, seg ? m1 : j0, seg ? j1 : m0);
-            }
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                s[k] += (double)a[k];
-                a[k] = 0.0f;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < K; k++) sum[k] += s[k];
-    }
+    // the eight source slices of potential_kernel's waves, one after another, in whole blocks (diag_common.h)
+    double sum[K];
+    tile_potential(sum, px, py, r, ri, rb, n_src, ScalarSources{(ConstF)(uintptr_t)pos, (ConstF)(uintptr_t)(p.gm + base)});
 
     // Phi_i = -sum; the eight terms of the lane's two receivers (tile rows lane and lane + 64)
     double e[K][QTY];
@@ -107,13 +74,7 @@ __global__ __launch_bounds__(WAVE * WAVES_MAX) void ensemble_phi_kernel(const En
     if (!p.slab) return;
     // potential_kernel's tree over the 128 rows of the tile: half = 64 is rows lane and lane + 64, the rest crosses lanes
     double t[QTY];
-#pragma unroll
-    for (int q = 0; q < QTY; q++) t[q] = e[0][q] + e[1][q];
-#pragma unroll
-    for (int half = WAVE / 2; half > 0; half /= 2) {
-#pragma unroll
-        for (int q = 0; q < QTY; q++) t[q] = t[q] + __shfl_down(t[q], half, WAVE);   // exact for lanes < half
-    }
+    tile_tree(t, e);
     if (lane == 0) {
         double *row = p.slab + ((size_t)member * p.tiles + tile) * QTY;
 #pragma unroll

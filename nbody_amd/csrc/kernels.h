@@ -114,6 +114,19 @@ struct BatchParams {
     uint32_t tiles;       // chain only: chain_tiles(n_recv)
 };
 
+// A traced ensemble chain (batch_trace_chain_kernel): the steps of BatchParams, and every `every`-th step of the CALL
+// the member's eight float64 energy sums (diag_sums.h order, the bits of ensemble_phi_kernel + ensemble_reduce_kernel for
+// that state) go to rows[record][member][8].  A call longer than one launch carries its record index across launches
+// through `done`; the launch with done = 0 also records the state on entry (record 0), and may have steps = 0.
+struct BatchTraceParams {
+    BatchParams b;
+    const float *mass;    // [count][stride], like gm
+    double *rows;         // [records][count][8]
+    uint32_t count;       // members (the row pitch)
+    uint32_t every;       // >= 1
+    uint32_t done;        // steps of this call that earlier launches ran
+};
+
 constexpr int MAX_SPLIT = 16;
 
 struct LaunchShape;   // launch_shape.h
@@ -130,5 +143,6 @@ void launch_chain(hipStream_t st, const ChainParams &p);
 // ensembles: the kernel of a lane-split shape (nullptr when not instantiated), and the chain launch
 const void *batch_lane_split_fn(int w, int lanes);
 void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count);
+void launch_batch_trace_chain(hipStream_t st, const BatchTraceParams &p);
 
 }  // namespace nb

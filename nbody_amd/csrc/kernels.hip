@@ -28,9 +28,11 @@
 //
 // This file holds the force path and nothing else: it, kernels.h and interaction_asm.h are the sources whose hash ties a
 // PMC profile to the code that was profiled (benchlib.KERNEL_SOURCES), so every device function a force kernel compiles
-// lives in one of the three.  Which shape a launch gets is host arithmetic in launch_shape.hip; the AoS <-> SoA
+// lives in one of the three -- but for the record phase of the traced ensemble chain, which is the diagnostics' arithmetic
+// and comes from diag_common.h.  Which shape a launch gets is host arithmetic in launch_shape.hip; the AoS <-> SoA
 // converters, pads and fills are convert.hip.
 #include "kernels.h"
+#include "diag_common.h"
 #include "interaction_asm.h"
 #include "launch_shape.h"
 
@@ -700,11 +702,33 @@ __global__ __launch_bounds__(WAVE *W) void lane_split_kernel(const StepParams p)
 // (granule 8, W = 16 / tiles slices per receiver tile), same block closes, same reduction order, same integrator
 // roundings -- tests/test_gpu_parity.py holds it to plain launches of k = 2, w = 16 / tiles, split = 1, unit = 8.
 // (the body as a device function: chain_kernel runs it for one world, batch_chain_kernel for one member per workgroup)
-__device__ __forceinline__ void chain_body(const ChainParams &p) {
+//
+// TRACE (batch_trace_chain_kernel): the same steps, and after every tr.every-th one the workgroup records the energy sums
+// of the state it holds -- positions and G*m are in LDS already, the masses join them at load time, the integrating
+// threads drop their velocities there when a record is due -- with the diagnostics' own functions (diag_common.h), so a
+// row has the bits of ensemble_phi_kernel + ensemble_reduce_kernel: the first wave of chain tile t IS the wave of
+// diagnostics tile t (both hold receivers 128 t + lane and + 64, and it has their radii in registers), the tiles' rows meet
+// in LDS, and the first 256 threads add them.  One extra barrier per record; the steps themselves are untouched, and
+// without TRACE nothing of this is compiled.  LDS with TRACE: 26 KB of the chain + 6.25 KB, of the workgroup's 160 KB.
+struct ChainTrace {
+    const float *mass;   // the member's masses
+    double *row;         // the member's row of the first record this launch makes
+    size_t pitch;        // doubles from one record's row to the next
+    uint32_t until;      // steps until the next record
+    uint32_t every;
+    bool entry;          // record the state on entry
+};
+
+template <bool TRACE>
+__device__ __forceinline__ void chain_body(const ChainParams &p, const ChainTrace &tr) {
     constexpr int K = CHAIN_K;
+    static_assert(CHAIN_K == nbd::K && WAVE * CHAIN_K == nbd::TILE, "a chain tile is a diagnostics tile");
     __shared__ __attribute__((aligned(16))) float spos[2][2 * CHAIN_MAX_RECV];  // (x, y) interleaved, ping-pong
     __shared__ __attribute__((aligned(16))) float sgm[CHAIN_MAX_RECV];
     __shared__ float2 partial[16][WAVE * K];
+    __shared__ float smass[TRACE ? CHAIN_MAX_RECV : 1];
+    __shared__ float2 svel[TRACE ? CHAIN_MAX_RECV : 1];
+    __shared__ double srow[TRACE ? CHAIN_MAX_RECV / (WAVE * K) : 1][nbd::QTY];
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & (WAVE - 1);
@@ -720,6 +744,8 @@ __device__ __forceinline__ void chain_body(const ChainParams &p) {
         spos[0][2 * i] = q.x;
         spos[0][2 * i + 1] = q.y;
         if (i < p.n_src) sgm[i] = p.src_gm[i];
+        if constexpr (TRACE)
+            if (i < p.n_src) smass[i] = tr.mass[i];
     }
     Receivers<K> R;
     uint32_t ridx[K];
@@ -740,10 +766,51 @@ __device__ __forceinline__ void chain_body(const ChainParams &p) {
     // this wave's slice of the sources: whole 8-source granules, exactly StepParams::unit = 8 with split = 1
     const SourceSlice wave_src = source_slice(p.n_src, 8u, 1, 0, W, slice);
     const uint32_t v_lo = wave_src.lo, v_hi = wave_src.hi;
+
+    // One record: the state in S / svel -> the member's row.  Every thread of the workgroup calls it.
+    double *row = tr.row;
+    auto record = [&](const float *S) {
+        const uint32_t rb = tile_base;
+        if (slice == 0 && rb < p.n_src) {   // the energy sums run over the massive receivers only
+            float px[K], py[K];
+            uint32_t ri[K];
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint32_t i = rb + k * WAVE + lane;
+                ri[k] = i < p.n_src ? i : p.n_src - 1;  // tail lanes redo the last receiver; their results are dropped
+                px[k] = S[2 * ri[k]];
+                py[k] = S[2 * ri[k] + 1];
+            }
+            // R.r[k] is the radius of receiver min(i, n_recv - 1): that of ri[k] in every live lane
+            double sum[K], e[K][nbd::QTY], t[nbd::QTY];
+            nbd::tile_potential(sum, px, py, R.r, ri, rb, p.n_src, nbd::LdsSources{S, sgm});
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint32_t i = rb + k * WAVE + lane;
+                nbd::energy_terms(e[k], i < p.n_src, -sum[k], smass, reinterpret_cast<const float2 *>(S), svel, i);
+            }
+            nbd::tile_tree(t, e);
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < nbd::QTY; q++) srow[tile][q] = t[q];
+            }
+        }
+        __syncthreads();
+        // the next write of srow is a record later, behind the barriers of at least one step
+        if (tid < (uint32_t)nbd::REDUCE_THREADS)
+            nbd::reduce_rows_shfl(&srow[0][0], (p.n_src + nbd::TILE - 1) / nbd::TILE, row, tid);
+        row += tr.pitch;
+    };
+    uint32_t until = tr.until;
+    if constexpr (TRACE)
+        if (tr.entry && integrates) svel[mine] = v;
     __syncthreads();
+    if constexpr (TRACE)
+        if (tr.entry) record(spos[0]);
 
     int cur = 0;
     for (uint32_t step = 0; step < p.steps; step++) {
+        const bool due = TRACE && --until == 0;
         const float *S = spos[cur];
 #pragma unroll
         for (int k = 0; k < K; k++) R.p[k] = f2v{S[2 * ridx[k]], S[2 * ridx[k] + 1]};
@@ -767,18 +834,26 @@ __device__ __forceinline__ void chain_body(const ChainParams &p) {
             integrate(a, dt, v, q);
             spos[cur ^ 1][2 * mine] = q.x;
             spos[cur ^ 1][2 * mine + 1] = q.y;
+            if constexpr (TRACE)
+                if (due) svel[mine] = v;
         }
         __syncthreads();
         cur ^= 1;
+        if constexpr (TRACE) {
+            if (due) {   // the waves that do not record wait at the record's barrier, then at the next step's
+                record(spos[cur]);
+                until = tr.every;
+            }
+        }
     }
-    if (integrates) {
+    if (integrates && (!TRACE || p.steps > 0)) {   // a traced call of no steps changes nothing
         p.pos[mine] = make_float2(spos[cur][2 * mine], spos[cur][2 * mine + 1]);
         p.vel[mine] = v;
         p.acc[mine] = a;
     }
 }
 
-__global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) { chain_body(p); }
+__global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) { chain_body<false>(p, ChainTrace{}); }
 
 // ---- world ensembles: B independent worlds of the same N in one launch -------------------------------------------
 //
@@ -789,7 +864,7 @@ __global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) { chai
 // size come from device memory (mass_len[b], dt[b]), so neither is baked into a launch.
 __device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
-__global__ __launch_bounds__(1024) void batch_chain_kernel(const BatchParams bp) {
+__device__ __forceinline__ ChainParams member_chain(const BatchParams &bp) {   // member blockIdx.x of an ensemble
     const size_t base = (size_t)blockIdx.x * bp.stride;
     ChainParams p;
     p.pos = bp.pos_in + base;   // updated in place, like the single chain
@@ -802,7 +877,25 @@ __global__ __launch_bounds__(1024) void batch_chain_kernel(const BatchParams bp)
     p.steps = bp.steps;
     p.tiles = bp.tiles;
     p.dt = bp.dt + blockIdx.x;
-    chain_body(p);
+    return p;
+}
+
+__global__ __launch_bounds__(1024) void batch_chain_kernel(const BatchParams bp) {
+    chain_body<false>(member_chain(bp), ChainTrace{});
+}
+
+// (not a "batch_chain_kernel" by name: tests/test_batch_cpu.py counts those)
+__global__ __launch_bounds__(1024) void batch_trace_chain_kernel(const BatchTraceParams tp) {
+    const uint32_t member = blockIdx.x;
+    ChainTrace tr;
+    tr.mass = tp.mass + (size_t)member * tp.b.stride;
+    tr.pitch = (size_t)tp.count * nbd::QTY;
+    tr.entry = tp.done == 0;
+    tr.every = tp.every;
+    tr.until = tp.every - tp.done % tp.every;
+    // records made before this launch: the one on entry and one per `every` steps done
+    tr.row = tp.rows + ((size_t)(tp.done == 0 ? 0u : 1u + tp.done / tp.every) * tp.count + member) * nbd::QTY;
+    chain_body<true>(member_chain(tp.b), tr);
 }
 
 template <int W, int H>
@@ -874,6 +967,10 @@ void launch_chain(hipStream_t st, const ChainParams &p) {
 
 void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count) {
     hipLaunchKernelGGL(batch_chain_kernel, dim3(count), dim3(1024), 0, st, p);
+}
+
+void launch_batch_trace_chain(hipStream_t st, const BatchTraceParams &p) {
+    hipLaunchKernelGGL(batch_trace_chain_kernel, dim3(p.count), dim3(1024), 0, st, p);
 }
 
 }  // namespace nb

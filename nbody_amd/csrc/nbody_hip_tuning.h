@@ -75,6 +75,12 @@ double nb_hip_last_diag_ms(SimPipeline *sim);
  * nb_hip_ensemble_potential (an event pair of their own, not the update's); 0 before the first call. */
 double nb_hip_ensemble_last_diag_ms(SimBatch *batch);
 
+/* Traced ensemble updates (nb_hip_ensemble_trace): mode 0 = auto, 1 = always interleave the diagnostics launches with the
+ * step launches, also where the one-workgroup chain could record by itself (total_len <= 512); and what the last traced
+ * call did: fused = 1 when the chain recorded, and the kernel launches it made.  Either pointer may be NULL. */
+void nb_hip_ensemble_trace_mode(SimBatch *batch, int mode);
+void nb_hip_ensemble_last_trace_info(const SimBatch *batch, int *fused, uint32_t *launches);
+
 /* Device milliseconds of the kernels of the last nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba (an event pair
  * of their own); 0 before the first call.  parts (may be NULL) receives {bounds, clear + splat, disc, shade}: the last
  * bounds call in parts[0]; the other three need the "render_detail" hook and read 0 without it. */

@@ -8,10 +8,11 @@
  *
  * include/nbody_batch_diag.h: GetWorldBatchEnergy / GetWorldBatchPotential compute on the device when it holds the
  * newest state, without pulling the array, and on the host (diag_cpu.c, member by member) otherwise; neither moves
- * device_is_newer.
+ * device_is_newer.  include/nbody_batch_trace.h: UpdateWorldBatch_GPU_Traced is an update that also records: same upload, same coherence.
  */
 #include "nbody_batch.h"
 #include "nbody_batch_diag.h"
+#include "nbody_batch_trace.h"
 #include "nbody_hip.h"
 
 #include <stdbool.h>
@@ -90,6 +91,22 @@ void UpdateWorldBatch_GPU_dts(WorldBatch *w, const float *dt, uint32_t n) {
     push_once(w);
     nb_hip_batch_update_dts(w->gpu, n, dt);
     w->device_is_newer = true;
+}
+
+void UpdateWorldBatch_GPU_Traced(WorldBatch *w, float dt, uint32_t n, uint32_t every, WorldEnergy *out) {
+    NB_CHECK(w != NULL && out != NULL, "NULL argument");
+    NB_CHECK(every > 0, "every = 0: a traced update records every k >= 1 steps");
+    push_once(w);
+    nb_hip_ensemble_trace(w->gpu, n, dt, every, out);
+    if (n > 0) w->device_is_newer = true;
+}
+
+void UpdateWorldBatch_GPU_Traced_dts(WorldBatch *w, const float *dt, uint32_t n, uint32_t every, WorldEnergy *out) {
+    NB_CHECK(w != NULL && dt != NULL && out != NULL, "NULL argument");
+    NB_CHECK(every > 0, "every = 0: a traced update records every k >= 1 steps");
+    push_once(w);
+    nb_hip_ensemble_trace_dts(w->gpu, n, dt, every, out);
+    if (n > 0) w->device_is_newer = true;
 }
 
 void GetWorldBatchEnergy(WorldBatch *w, WorldEnergy *out) {
