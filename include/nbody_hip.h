@@ -441,6 +441,32 @@ uint32_t nb_hip_ensemble_trace_rows(uint32_t n, uint32_t every);
 void nb_hip_ensemble_trace(SimBatch *batch, uint32_t n, float dt, uint32_t every, WorldEnergy *out /* [R][count] */);
 void nb_hip_ensemble_trace_dts(SimBatch *batch, uint32_t n, const float *dt /* [count] */, uint32_t every, WorldEnergy *out);
 
+/*
+ * Rendering an ensemble: bounds, per-class count images and RGBA frames of EVERY member, without reading a particle back
+ * (definitions: include/nbody_render.h; the World-level calls are include/nbody_batch_render.h).
+ *   nb_hip_ensemble_bounds         bounds[count][4]: member b's {min.x, min.y, max.x, max.y}
+ *   nb_hip_ensemble_render_counts  counts[count][3][height][width] under views[count], one view per member
+ *   nb_hip_ensemble_render_rgba    rgba[count][height][width][4]
+ * Member b's result is BIT-IDENTICAL to nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba of a SimPipeline holding
+ * the same particles under views[b]: it does not depend on count, on the member's index or on the other members.  All
+ * views share width and height (a mismatch aborts, naming the first member that differs), each is within the limits of
+ * include/nbody_render.h, count * width * height <= 2^24 and saturation >= 1.  While the three class planes of one image
+ * fit a workgroup's share of the LDS (3 * width * height * 4 <= 48 KiB, a 64 x 64 thumbnail) one workgroup per member
+ * builds the member's image on chip: ONE launch per call, for counts and for frames; larger images take a clear, a splat,
+ * a disc pass and (frames) a shade over all members -- in both cases a constant number of launches, one upload of the
+ * views, one copy of the images and one stream sync for any count.  The choice depends on width * height alone.  Like
+ * the diagnostics: enqueued on the ensemble's stream behind any nb_hip_batch_step_async work, they read the buffer that
+ * holds the latest state, block until the result is on the host and change nothing observable (the state, the ping-pong
+ * phase, the step sizes, nb_hip_batch_dt_uploads and nb_hip_batch_last_ms are as before; the render has an event pair of
+ * its own).  Scratch belongs to the SimBatch, is made on first use, regrown when a call needs more, and freed by
+ * nb_hip_batch_destroy.  Abort before nb_hip_batch_set_data and for a NULL argument.  Added WITHOUT a version bump:
+ * detect them by symbol (dlsym "nb_hip_ensemble_render_rgba").
+ */
+void nb_hip_ensemble_bounds(SimBatch *batch, float *bounds /* [count][4] */);
+void nb_hip_ensemble_render_counts(SimBatch *batch, const RenderView *views /* [count] */, uint32_t *counts /* [count][3][h][w] */);
+void nb_hip_ensemble_render_rgba(SimBatch *batch, const RenderView *views /* [count] */, const RenderPalette *palette,
+                                 uint8_t *rgba /* [count][h][w][4] */);
+
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int nb_hip_version(void);
 

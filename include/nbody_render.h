@@ -6,7 +6,8 @@
  * Where it runs: when the device holds the World's newest state, on the GPU (nb_hip_bounds / nb_hip_render_counts /
  * nb_hip_render_rgba of include/nbody_hip.h) and only the result crosses PCIe; otherwise on the host.  A World that only
  * ever steps on the CPU never touches a GPU.  No call changes the World's state or moves a dirty flag.  Sharded Worlds
- * abort (their remote slices are current only inside a step), WorldBatch is not covered.
+ * abort (their remote slices are current only inside a step).  A WorldBatch renders all its members at once through
+ * include/nbody_batch_render.h.
  *
  * All three products are integer or min / max results, so the contract is BITWISE: the GPU path, the host path and the
  * numpy restatement in tests/render_ref.py give the same bytes for every input, on every call, whatever the particle order.

@@ -166,6 +166,9 @@ HIP_API = {
     "nb_hip_ensemble_trace_rows": (C.c_uint32, [C.c_uint32, C.c_uint32]),
     "nb_hip_ensemble_trace": (None, [C.c_void_p, C.c_uint32, C.c_float, C.c_uint32, C.c_void_p]),
     "nb_hip_ensemble_trace_dts": (None, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint32, C.c_void_p]),
+    "nb_hip_ensemble_bounds": (None, [C.c_void_p, C.c_void_p]),
+    "nb_hip_ensemble_render_counts": (None, [C.c_void_p, C.POINTER(RenderView), C.c_void_p]),
+    "nb_hip_ensemble_render_rgba": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
     "nb_hip_version": (C.c_int, []),
 }
 
@@ -184,11 +187,14 @@ TUNE_API = {
     "nb_hip_ensemble_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_ensemble_trace_mode": (None, [C.c_void_p, C.c_int]),
     "nb_hip_ensemble_last_trace_info": (None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "nb_hip_ensemble_render_mode": (None, [C.c_void_p, C.c_int]),
+    "nb_hip_ensemble_last_render_info": (None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
+    "nb_hip_ensemble_last_render_ms": (C.c_double, [C.c_void_p]),
 }
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
-# include/nbody_render.h
+# include/nbody_render.h + include/nbody_batch_render.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -221,6 +227,11 @@ NBODY_API = {
     # include/nbody_batch_trace.h
     "UpdateWorldBatch_GPU_Traced": (None, [C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p]),
     "UpdateWorldBatch_GPU_Traced_dts": (None, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.c_void_p]),
+    # include/nbody_batch_render.h
+    "GetWorldBatchBounds": (None, [C.c_void_p, C.c_void_p]),
+    "FitWorldBatchViews": (None, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RenderView)]),
+    "RenderWorldBatchCounts": (None, [C.c_void_p, C.POINTER(RenderView), C.c_void_p]),
+    "RenderWorldBatch": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
 }
 
 _hip = None
@@ -537,6 +548,32 @@ def _dt_array(dts, count):
     return a
 
 
+def _view_array(views, count):
+    """One RenderView for every member, or a sequence of `count` of them -> (RenderView[count], width, height)."""
+    if isinstance(views, RenderView):
+        views = [views] * count
+    views = list(views)
+    if len(views) != count:
+        raise ValueError(f"expected one RenderView or {count} of them")
+    arr = (RenderView * count)()
+    for b, v in enumerate(views):
+        C.memmove(C.byref(arr[b]), C.byref(v), C.sizeof(RenderView))
+    return arr, int(arr[0].width), int(arr[0].height)
+
+
+def contact_sheet(frames, columns):
+    """(B, h, w, 4) frames -> one (rows * h, columns * w, 4) image, member b in row b // columns, column b % columns;
+    cells without a member are zero."""
+    frames = np.asarray(frames)
+    if frames.ndim != 4 or columns < 1:
+        raise ValueError("frames must have shape (B, h, w, channels) and columns must be at least 1")
+    count, h, w, ch = frames.shape
+    rows = -(-count // columns)
+    sheet = np.zeros((rows * columns, h, w, ch), dtype=frames.dtype)
+    sheet[:count] = frames
+    return sheet.reshape(rows, columns, h, w, ch).transpose(0, 2, 1, 3, 4).reshape(rows * h, columns * w, ch)
+
+
 class SimBatch:
     """include/nbody_hip.h SimBatch: B independent worlds of the same size, stepped together (nb_hip_batch_*).
 
@@ -636,6 +673,41 @@ class SimBatch:
         """tuning hook: device ms of the kernels of the last energy() / potential()."""
         return float(hip_lib().nb_hip_ensemble_last_diag_ms(self._h))
 
+    def bounds(self):
+        """nb_hip_ensemble_bounds: float32 (B, 4), member b's [min.x, min.y, max.x, max.y]."""
+        out = np.empty((self.count, 4), dtype=np.float32)
+        hip_lib().nb_hip_ensemble_bounds(self._h, out.ctypes.data)
+        return out
+
+    def render_counts(self, views):
+        """nb_hip_ensemble_render_counts: uint32 (B, 3, height, width); views: one RenderView for all, or one per member."""
+        arr, w, h = _view_array(views, self.count)
+        out = np.empty((self.count, 3, h, w), dtype=np.uint32)
+        hip_lib().nb_hip_ensemble_render_counts(self._h, arr, out.ctypes.data)
+        return out
+
+    def render(self, views, palette=None):
+        """nb_hip_ensemble_render_rgba: uint8 (B, height, width, 4); palette None = DefaultRenderPalette."""
+        arr, w, h = _view_array(views, self.count)
+        out = np.empty((self.count, h, w, 4), dtype=np.uint8)
+        pal = palette if palette is not None else default_palette()
+        hip_lib().nb_hip_ensemble_render_rgba(self._h, arr, C.byref(pal), out.ctypes.data)
+        return out
+
+    def render_mode(self, mode):
+        """tuning hook: 0 = auto, 1 = the global path (clear, splat, disc pass, shade) also where the tile path applies."""
+        hip_lib().nb_hip_ensemble_render_mode(self._h, int(mode))
+
+    def last_render_info(self):
+        """tuning hook: {"tile_path": 0 / 1, "launches": launches enqueued} of the last render_counts() / render()."""
+        tile, launches = C.c_int(0), C.c_uint32(0)
+        hip_lib().nb_hip_ensemble_last_render_info(self._h, C.byref(tile), C.byref(launches))
+        return {"tile_path": tile.value, "launches": launches.value}
+
+    def last_render_ms(self):
+        """tuning hook: device ms of the kernels of the last bounds() / render_counts() / render()."""
+        return float(hip_lib().nb_hip_ensemble_last_render_ms(self._h))
+
     def launch_shape(self):
         """path "chain" / "lanes" plus the knobs that pin a SimPipeline to the same summation order (pinned_knobs)."""
         path, k, w, lanes, g = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_uint32()
@@ -706,6 +778,32 @@ class WorldBatch:
         """GetWorldBatchPotential: Phi_i of every particle of every member, float32 (B, n), in member(b)'s order."""
         out = np.empty((self.count, self.size), dtype=np.float32)
         nbody_lib().GetWorldBatchPotential(self._h, out.ctypes.data)
+        return out
+
+    def bounds(self):
+        """GetWorldBatchBounds (include/nbody_batch_render.h): float32 (B, 4)."""
+        out = np.empty((self.count, 4), dtype=np.float32)
+        nbody_lib().GetWorldBatchBounds(self._h, out.ctypes.data)
+        return out
+
+    def fit_views(self, width, height):
+        """FitWorldBatchViews: a list of B RenderViews, each showing every finite particle of its member."""
+        arr = (RenderView * self.count)()
+        nbody_lib().FitWorldBatchViews(self._h, width, height, arr)
+        return [RenderView.from_buffer_copy(v) for v in arr]
+
+    def render_counts(self, views):
+        """RenderWorldBatchCounts: uint32 (B, 3, height, width); views: one RenderView for all, or one per member."""
+        arr, w, h = _view_array(views, self.count)
+        out = np.empty((self.count, 3, h, w), dtype=np.uint32)
+        nbody_lib().RenderWorldBatchCounts(self._h, arr, out.ctypes.data)
+        return out
+
+    def render(self, views, palette=None):
+        """RenderWorldBatch: uint8 (B, height, width, 4); palette None = DefaultRenderPalette."""
+        arr, w, h = _view_array(views, self.count)
+        out = np.empty((self.count, h, w, 4), dtype=np.uint8)
+        nbody_lib().RenderWorldBatch(self._h, arr, C.byref(palette) if palette is not None else None, out.ctypes.data)
         return out
 
 

@@ -11,14 +11,18 @@
 // A traced update (nb_hip_ensemble_trace) records every member's energy sums every k steps without returning to the host:
 // on the chain path batch_trace_chain_kernel records from the state it holds in LDS (still one launch per call), on the
 // lane-split path the two diagnostics launches are interleaved with the step launches; one copy and one sync at the end.
+// nb_hip_ensemble_bounds / _render_counts / _render_rgba look at every member without reading it back (kernels:
+// batch_render.hip): a constant number of launches, one copy of the images and one sync for any B.
 // The path is chosen by N alone -- never by B or by the members' source counts -- and the kernels run the very bodies of
 // chain_kernel / lane_split_kernel, so member b's bits are those of the same particles alone in a SimPipeline pinned to
 // that shape (tests/test_gpu_batch.py).  Members share nothing with each other and a SimBatch shares nothing with any
 // SimPipeline: own stream, own buffers, own events.
 #include "pipeline_internal.h"
 #include "batch_diag.h"
+#include "batch_render.h"
 #include "diag_sums.h"
 #include "nbody_hip_tuning.h"
+#include "render_common.h"
 
 using namespace nbi;
 
@@ -67,6 +71,21 @@ struct SimBatch {
     int trace_mode = 0;          // tuning hook: 1 = interleaved diagnostics launches also where the chain could record
     int trace_fused = 0;         // what the last traced call did
     uint32_t trace_launches = 0;
+
+    // nb_hip_ensemble_bounds / _render_counts / _render_rgba (kernels: batch_render.hip): scratch made on first use, an
+    // event pair of their own
+    RenderView *render_views = nullptr;      // [count]: the views of the last call
+    uint32_t *render_keys = nullptr;         // [count][4]
+    uint32_t *render_counts = nullptr;       // tile path: [count][3][h][w]; global path: the disc cursor behind them
+    size_t render_counts_cap = 0;
+    uint32_t *render_rgba = nullptr;         // [count][h][w]
+    size_t render_rgba_cap = 0;
+    nbr::EnsembleDisc *render_discs = nullptr;   // global path: [count * n]
+    hipEvent_t ev_render[2] = {nullptr, nullptr};
+    bool render_timed = false;
+    int render_mode = 0;                     // tuning hook: 1 = the global path also where the tile path applies
+    int render_tile = 0;                     // what the last render did (a bounds call leaves both alone)
+    uint32_t render_launches = 0;
 };
 
 namespace {
@@ -313,6 +332,72 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
     for (size_t i = 0; i < (size_t)records * s->count; i++) nb_energy_from_sums(s->trace_host.data() + i * Q, out + i);
 }
 
+// ---- rendering: bounds, count tiles and frames of every member, without reading the particles back ------------------
+
+void begin_render(SimBatch *s) {
+    use_device();
+    if (!s->ev_render[0]) {
+        for (auto &e : s->ev_render) ASSERT_HIP(hipEventCreate(&e), "event");
+    }
+    ASSERT_HIP(hipEventRecord(s->ev_render[0], s->stream), "record render begin");
+}
+
+void end_render(SimBatch *s) {
+    ASSERT_HIP(hipEventRecord(s->ev_render[1], s->stream), "record render end");
+    s->render_timed = true;
+}
+
+void check_views(const SimBatch *s, const RenderView *views, const char *what) {
+    NB_ASSERT(views != nullptr, "%s: NULL RenderView array", what);
+    uint32_t member = 0;
+    const char *fault = nb_render_views_fault(views, s->count, &member);
+    NB_ASSERT(fault == nullptr, "%s: invalid RenderView of member %u of %u (%u x %u, zoom %g): %s", what, member, s->count,
+              views[member].width, views[member].height, (double)views[member].zoom, fault);
+}
+
+// The count images of the latest state on the stream: the tile kernel (straight to the frame when a palette is given) or
+// clear + splat + disc pass (+ shade); *launches = what was enqueued.
+void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint32_t *launches) {
+    const uint32_t width = views[0].width, height = views[0].height;
+    const size_t plane = (size_t)width * height;
+    const bool tile = nbr::tile_fits(width, height) && s->render_mode == 0;
+    if (!s->render_views) s->render_views = dev_alloc<RenderView>(s->count);
+    if (palette) grown(s, s->render_rgba, s->render_rgba_cap, (size_t)s->count * plane);
+    if (!tile || !palette) grown(s, s->render_counts, s->render_counts_cap, nbr::global_count_words(s->count, width, height));
+    if (!tile && !s->render_discs) s->render_discs = dev_alloc<nbr::EnsembleDisc>((size_t)s->count * s->n);
+    ASSERT_HIP(hipMemcpyAsync(s->render_views, views, (size_t)s->count * sizeof(RenderView), hipMemcpyHostToDevice, s->stream),
+               "H2D of %u views", s->count);
+    begin_render(s);
+    nbr::EnsembleRenderParams p{};
+    p.pos = s->pos[s->cur];
+    p.mass = s->mass;
+    p.radius = s->radius;
+    p.n = s->n;
+    p.stride = s->stride;
+    p.count = s->count;
+    p.width = width;
+    p.height = height;
+    p.views = s->render_views;
+    if (tile) {
+        nbr::launch_ensemble_tile(s->stream, p, s->render_counts, palette, s->render_rgba);
+        *launches = 1;
+    } else {
+        ASSERT_HIP(hipMemsetAsync(s->render_counts, 0, nbr::global_count_words(s->count, width, height) * sizeof(uint32_t), s->stream),
+                   "clear %u count images and the disc cursor", s->count);
+        nbr::launch_ensemble_global(s->stream, p, s->render_counts, s->render_discs);
+        *launches = 3;
+        if (palette) {
+            nbr::launch_ensemble_shade(s->stream, s->render_counts, s->count, (uint32_t)plane, *palette, s->render_rgba);
+            *launches = 4;
+        }
+    }
+    ASSERT_HIP(hipGetLastError(), "ensemble render launch (%u members of %u particles, %u x %u, %s path)", s->count, s->n, width, height,
+               tile ? "tile" : "global");
+    end_render(s);
+    s->render_tile = tile;
+    s->render_launches = *launches;
+}
+
 }  // namespace
 
 extern "C" {
@@ -367,6 +452,13 @@ void nb_hip_batch_destroy(SimBatch *s) {
         if (s->diag) dev_free(s->diag);
         if (s->diag_phi) dev_free(s->diag_phi);
         if (s->trace) dev_free(s->trace);
+        if (s->render_views) dev_free(s->render_views);
+        if (s->render_keys) dev_free(s->render_keys);
+        if (s->render_counts) dev_free(s->render_counts);
+        if (s->render_rgba) dev_free(s->render_rgba);
+        if (s->render_discs) dev_free(s->render_discs);
+        for (auto &e : s->ev_render)
+            if (e) ASSERT_HIP(hipEventDestroy(e), "event");
         for (auto &e : s->ev_diag)
             if (e) ASSERT_HIP(hipEventDestroy(e), "event");
         for (auto &e : s->ev) ASSERT_HIP(hipEventDestroy(e), "event");
@@ -497,6 +589,67 @@ void nb_hip_ensemble_last_trace_info(const SimBatch *s, int *fused, uint32_t *la
     NB_ASSERT(s != nullptr, "NULL ensemble");
     if (fused) *fused = s->trace_fused;
     if (launches) *launches = s->trace_launches;
+}
+
+void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {
+    check_diag(s, bounds, "nb_hip_ensemble_bounds");
+    begin_render(s);
+    if (!s->render_keys) s->render_keys = dev_alloc<uint32_t>((size_t)s->count * 4);
+    nbr::launch_ensemble_bounds(s->stream, s->pos[s->cur], s->n, s->stride, s->count, s->render_keys);
+    ASSERT_HIP(hipGetLastError(), "ensemble_bounds_kernel launch (%u members of %u)", s->count, s->n);
+    end_render(s);   // the event pair is shared with the renders; render_tile / render_launches speak of renders only
+    std::vector<uint32_t> keys((size_t)s->count * 4);
+    ASSERT_HIP(hipMemcpyAsync(keys.data(), s->render_keys, keys.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream),
+               "D2H of %u members' bounds", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_bounds");
+    for (uint32_t b = 0; b < s->count; b++) nb_render_bounds_from_keys(keys.data() + (size_t)b * 4, bounds + (size_t)b * 4);
+}
+
+void nb_hip_ensemble_render_counts(SimBatch *s, const RenderView *views, uint32_t *counts) {
+    check_diag(s, counts, "nb_hip_ensemble_render_counts");
+    check_views(s, views, "nb_hip_ensemble_render_counts");
+    use_device();
+    uint32_t launches = 0;
+    enqueue_render(s, views, nullptr, &launches);
+    const size_t bytes = (size_t)s->count * NB_RENDER_CLASSES * views[0].width * views[0].height * sizeof(uint32_t);
+    ASSERT_HIP(hipMemcpyAsync(counts, s->render_counts, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u count images", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_render_counts");
+}
+
+void nb_hip_ensemble_render_rgba(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint8_t *rgba) {
+    check_diag(s, rgba, "nb_hip_ensemble_render_rgba");
+    check_views(s, views, "nb_hip_ensemble_render_rgba");
+    NB_ASSERT(palette != nullptr, "nb_hip_ensemble_render_rgba: NULL RenderPalette");
+    NB_ASSERT(palette->saturation >= 1u, "RenderPalette saturation must be at least 1");
+    use_device();
+    uint32_t launches = 0;
+    enqueue_render(s, views, palette, &launches);
+    const size_t bytes = (size_t)s->count * views[0].width * views[0].height * sizeof(uint32_t);
+    ASSERT_HIP(hipMemcpyAsync(rgba, s->render_rgba, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u frames", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_render_rgba");
+}
+
+// tuning hooks (nbody_hip_tuning.h)
+void nb_hip_ensemble_render_mode(SimBatch *s, int mode) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(mode == 0 || mode == 1, "render mode %d (0 = auto, 1 = global path)", mode);
+    s->render_mode = mode;
+}
+
+void nb_hip_ensemble_last_render_info(const SimBatch *s, int *tile_path, uint32_t *launches) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (tile_path) *tile_path = s->render_tile;
+    if (launches) *launches = s->render_launches;
+}
+
+double nb_hip_ensemble_last_render_ms(SimBatch *s) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (!s->render_timed) return 0.0;
+    use_device();
+    ASSERT_HIP(hipEventSynchronize(s->ev_render[1]), "render end event");
+    float ms = 0.0f;
+    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev_render[0], s->ev_render[1]), "render elapsed time");
+    return (double)ms;
 }
 
 void nb_hip_batch_launch_shape(const SimBatch *s, int *path, int *k, int *w, int *lanes, uint32_t *workgroups) {

@@ -86,6 +86,16 @@ void nb_hip_ensemble_last_trace_info(const SimBatch *batch, int *fused, uint32_t
  * bounds call in parts[0]; the other three need the "render_detail" hook and read 0 without it. */
 double nb_hip_last_render_ms(SimPipeline *sim, double *parts);
 
+/* Ensemble renders (nb_hip_ensemble_render_counts / _rgba): mode 0 = auto, 1 = the global path (clear, splat, disc pass,
+ * shade) also where the image fits the one-workgroup tile path; what the last render did: tile_path = 1 when the tile
+ * kernel ran, and the launches it enqueued (the clear counts as one), both 0 before the first render and left alone by
+ * nb_hip_ensemble_bounds; and the device milliseconds of the kernels alone (not of the upload of the views or the copy
+ * back) of the last render or bounds call (an event pair of their own, 0 before the first call).  Either pointer may be
+ * NULL. */
+void nb_hip_ensemble_render_mode(SimBatch *batch, int mode);
+void nb_hip_ensemble_last_render_info(const SimBatch *batch, int *tile_path, uint32_t *launches);
+double nb_hip_ensemble_last_render_ms(SimBatch *batch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 /*
  * render_common.h -- the arithmetic of include/nbody_render.h written once, for the GPU path (render.hip) and the host
  * path (render_cpu.c): the screen transform and classification of one particle, the pixel test of a disc, the candidate
- * box of a disc, the shade of one pixel, the total order of floats the bounds use, and the checks of a view.  Both
+ * box of a disc, the shade of one pixel, the total order of floats the bounds use, and the checks of a view and of an ensemble's views.  Both
  * translation units build with -ffp-contract=off, so every float32 operation below is rounded on its own on both sides.
  * The host path's entry points (hidden, libnbody.so) are declared at the bottom.
  */
@@ -121,6 +121,23 @@ static inline const char *nb_render_view_fault(const RenderView *v) {
     if (v->width < 1u || v->height < 1u) return "width and height must be at least 1";
     if ((uint64_t)v->width * v->height > NB_RENDER_MAX_PIXELS) return "width * height must not exceed 2^24";
     if (!nb_render_finite(v->zoom) || !(v->zoom > 0.0f)) return "zoom must be finite and > 0";
+    return NULL;
+}
+
+/*
+ * The views of one ensemble render (one per member): NULL when each is valid, all share width and height and the `count`
+ * images together hold at most 2^24 pixels; else what is wrong, with *member = the first member at fault.
+ */
+static inline const char *nb_render_views_fault(const RenderView *views, uint32_t count, uint32_t *member) {
+    for (uint32_t b = 0; b < count; b++) {
+        *member = b;
+        const char *fault = nb_render_view_fault(&views[b]);
+        if (fault) return fault;
+        if (views[b].width != views[0].width || views[b].height != views[0].height)
+            return "width and height differ from member 0's: the views of one call share one size";
+    }
+    *member = 0;
+    if ((uint64_t)count * views[0].width * views[0].height > NB_RENDER_MAX_PIXELS) return "count * width * height must not exceed 2^24";
     return NULL;
 }
 

@@ -9,9 +9,12 @@
  * include/nbody_batch_diag.h: GetWorldBatchEnergy / GetWorldBatchPotential compute on the device when it holds the
  * newest state, without pulling the array, and on the host (diag_cpu.c, member by member) otherwise; neither moves
  * device_is_newer.  include/nbody_batch_trace.h: UpdateWorldBatch_GPU_Traced is an update that also records: same upload, same coherence.
+ * include/nbody_batch_render.h: bounds, count images and frames of every member follow the same protocol (device:
+ * nb_hip_ensemble_*; host: render_cpu.c member by member).
  */
 #include "nbody_batch.h"
 #include "nbody_batch_diag.h"
+#include "nbody_batch_render.h"
 #include "nbody_batch_trace.h"
 #include "nbody_hip.h"
 
@@ -19,6 +22,7 @@
 
 #include "diag_sums.h"
 #include "nb_util.h"
+#include "render_common.h"
 #include "world_partition.h"
 
 struct WorldBatch {
@@ -126,4 +130,59 @@ void GetWorldBatchPotential(WorldBatch *w, float *phi) {
     }
     for (uint32_t b = 0; b < w->count; b++)
         nb_cpu_potential(w->particles + (size_t)b * w->size, w->size, w->massive[b], phi + (size_t)b * w->size);
+}
+
+void GetWorldBatchBounds(WorldBatch *w, float *bounds) {
+    NB_CHECK(w != NULL && bounds != NULL, "NULL argument");
+    if (w->device_is_newer) {
+        nb_hip_ensemble_bounds(w->gpu, bounds);
+        return;
+    }
+    for (uint32_t b = 0; b < w->count; b++) nb_cpu_bounds(w->particles + (size_t)b * w->size, w->size, bounds + (size_t)b * 4);
+}
+
+void FitWorldBatchViews(WorldBatch *w, uint32_t width, uint32_t height, RenderView *views) {
+    NB_CHECK(w != NULL && views != NULL, "NULL argument");
+    float *bounds = NB_NEW((size_t)w->count * 4, float);
+    NB_CHECK(bounds != NULL, "Failed to alloc %u bounds", w->count);
+    GetWorldBatchBounds(w, bounds);
+    for (uint32_t b = 0; b < w->count; b++) nb_fit_view(bounds + (size_t)b * 4, width, height, views + b);
+    free(bounds);
+}
+
+static void check_views(const WorldBatch *w, const RenderView *views) {
+    uint32_t member = 0;
+    const char *fault = nb_render_views_fault(views, w->count, &member);
+    NB_CHECK(fault == NULL, "invalid RenderView of member %u of %u (%u x %u, zoom %g): %s", member, w->count, views[member].width,
+             views[member].height, (double)views[member].zoom, fault);
+}
+
+void RenderWorldBatchCounts(WorldBatch *w, const RenderView *views, uint32_t *counts) {
+    NB_CHECK(w != NULL && views != NULL && counts != NULL, "NULL argument");
+    check_views(w, views);
+    if (w->device_is_newer) {
+        nb_hip_ensemble_render_counts(w->gpu, views, counts);
+        return;
+    }
+    const size_t image = (size_t)views[0].width * views[0].height * NB_RENDER_CLASSES;
+    for (uint32_t b = 0; b < w->count; b++)
+        nb_cpu_render_counts(w->particles + (size_t)b * w->size, w->size, views + b, counts + (size_t)b * image);
+}
+
+void RenderWorldBatch(WorldBatch *w, const RenderView *views, const RenderPalette *palette, uint8_t *rgba) {
+    NB_CHECK(w != NULL && views != NULL && rgba != NULL, "NULL argument");
+    check_views(w, views);
+    RenderPalette pal;
+    if (palette)
+        pal = *palette;
+    else
+        DefaultRenderPalette(&pal);
+    NB_CHECK(pal.saturation >= 1u, "RenderPalette saturation must be at least 1");
+    if (w->device_is_newer) {
+        nb_hip_ensemble_render_rgba(w->gpu, views, &pal, rgba);
+        return;
+    }
+    const size_t frame = (size_t)views[0].width * views[0].height * 4;
+    for (uint32_t b = 0; b < w->count; b++)
+        nb_cpu_render_rgba(w->particles + (size_t)b * w->size, w->size, views + b, &pal, rgba + (size_t)b * frame);
 }
