@@ -467,6 +467,43 @@ void nb_hip_ensemble_render_counts(SimBatch *batch, const RenderView *views /* [
 void nb_hip_ensemble_render_rgba(SimBatch *batch, const RenderView *views /* [count] */, const RenderPalette *palette,
                                  uint8_t *rgba /* [count][h][w][4] */);
 
+/*
+ * Ragged ensembles: members of DIFFERENT particle counts in one SimBatch (a sweep over resolution, MakeGalaxies worlds of
+ * unequal size), stepped by the same launches instead of one SimBatch per size.
+ *   nb_hip_ragged_create        member b has total_len[b] particles (1 .. NB_HIP_BATCH_MAX_LEN), mass_len[b] of them sources
+ *   nb_hip_ragged_layout        sizes[count] and offsets[count + 1]: offsets[b] = total_len[0] + ... + total_len[b - 1]
+ *   nb_hip_ragged_launch_shape  the launch groups: returns how many there are and describes group `group`
+ *   nb_hip_ragged_member_shape  the group and the (k, w, lanes) of one member
+ * The result is a SimBatch: every nb_hip_batch_* call, nb_hip_ensemble_energy / _potential and nb_hip_ensemble_trace(_dts)
+ * work on it as documented above, with ONE change of layout: every particle array that crosses this seam (set_data,
+ * get_data) and every per-particle result (potential) is PACKED, member b at offsets[b]; get_member returns total_len[b]
+ * records.  A uniform ensemble is the special case in which that is today's layout, and nb_hip_ragged_layout /
+ * _launch_shape / _member_shape also answer for a SimBatch made by nb_hip_batch_create (one group).
+ *
+ * The contract: member b is BIT-IDENTICAL -- particles after any number of steps and any cutting of the calls, energy,
+ * potential, every row of a traced call -- to the same particles as the single member of nb_hip_batch_create(1,
+ * total_len[b], &mass_len[b]), whatever count, its index, its neighbours, their sizes, their step sizes or the groups
+ * present are.  That holds because a member's launch shape is a function of its own size alone.  Members fall into up to
+ * three launch groups, reported in this order, absent when empty:
+ *   total_len <= 512           chain: one workgroup per member runs the whole call, w = 16, 8 or 4 by its own size
+ *   513 <= total_len <= 1581   lane-split, w = 8, lanes = 8
+ *   1582 <= total_len <= 3000  lane-split, w = 16, lanes = 4
+ * A call is one chain launch plus, per step, one launch per lane-split group; workgroups past a smaller member's last
+ * receiver leave at once.  nb_hip_ragged_launch_shape gives a group's path, k, w (chain: of its largest member), lanes,
+ * member count and workgroups per launch; any pointer may be NULL.  A traced update records inside the chain launch when
+ * every member is in the chain group and interleaves the two diagnostics launches otherwise (same bits).
+ *
+ * Not wired yet: nb_hip_ensemble_bounds / _render_counts / _render_rgba abort on a ragged ensemble with a message that
+ * says so, before they touch the device.  Create allocates nothing on the GPU; count = 0 or > NB_HIP_BATCH_MAX_COUNT, a
+ * total_len[b] of 0 or > NB_HIP_BATCH_MAX_LEN and a mass_len[b] > total_len[b] print "file:line [func] ... member b ..."
+ * and abort().  Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_ragged_create").
+ */
+SimBatch *nb_hip_ragged_create(uint32_t count, const uint32_t *total_len /* [count] */, const uint32_t *mass_len /* [count] */);
+void nb_hip_ragged_layout(const SimBatch *batch, uint32_t *sizes /* [count] */, uint64_t *offsets /* [count + 1] */);
+uint32_t nb_hip_ragged_launch_shape(const SimBatch *batch, uint32_t group, int *path, int *k, int *w, int *lanes, uint32_t *members,
+                                    uint32_t *workgroups);
+void nb_hip_ragged_member_shape(const SimBatch *batch, uint32_t member, uint32_t *group, int *k, int *w, int *lanes);
+
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int nb_hip_version(void);
 

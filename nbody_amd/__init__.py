@@ -169,6 +169,12 @@ HIP_API = {
     "nb_hip_ensemble_bounds": (None, [C.c_void_p, C.c_void_p]),
     "nb_hip_ensemble_render_counts": (None, [C.c_void_p, C.POINTER(RenderView), C.c_void_p]),
     "nb_hip_ensemble_render_rgba": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
+    "nb_hip_ragged_create": (C.c_void_p, [C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nb_hip_ragged_layout": (None, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "nb_hip_ragged_launch_shape": (C.c_uint32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nb_hip_ragged_member_shape": (None, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                          C.POINTER(C.c_int)]),
     "nb_hip_version": (C.c_int, []),
 }
 
@@ -194,7 +200,7 @@ TUNE_API = {
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
-# include/nbody_render.h + include/nbody_batch_render.h
+# include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -232,6 +238,8 @@ NBODY_API = {
     "FitWorldBatchViews": (None, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RenderView)]),
     "RenderWorldBatchCounts": (None, [C.c_void_p, C.POINTER(RenderView), C.c_void_p]),
     "RenderWorldBatch": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
+    # include/nbody_batch_ragged.h
+    "CreateWorldBatchRagged": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
 }
 
 _hip = None
@@ -541,6 +549,18 @@ def as_ensemble(a):
     return a
 
 
+def _packed(members):
+    """a list of (N_b, 8) arrays -> (one packed float32 (sum N_b, 8) array, uint32 sizes)"""
+    parts = [as_particles(m) for m in members]
+    sizes = np.array([p.shape[0] for p in parts], dtype=np.uint32)
+    flat = np.concatenate(parts, axis=0) if parts else np.zeros((0, 8), np.float32)
+    return np.ascontiguousarray(flat, dtype=np.float32), sizes
+
+
+def _unpacked(flat, offsets):
+    return [flat[int(offsets[b]):int(offsets[b + 1])].copy() for b in range(len(offsets) - 1)]
+
+
 def _dt_array(dts, count):
     a = np.ascontiguousarray(dts, dtype=np.float32)
     if a.shape != (count,):
@@ -579,7 +599,13 @@ class SimBatch:
 
     Particles are float32 arrays of shape (B, n, 8), every member already partitioned (mass > 0 first) with
     `mass_len[b]` massive ones.  Member b ends bit-identical to the same particles alone in a SimPipeline pinned to
-    launch_shape()."""
+    launch_shape().
+
+    SimBatch.ragged(total_lens, mass_lens) makes an ensemble whose members differ in size (nb_hip_ragged_create): set_data
+    takes and get_data() / potential() return a LIST of per-member arrays, everything else keeps its shape; member b is
+    bit-identical to the same particles as the single member of SimBatch(total_lens[b], [mass_lens[b]])."""
+
+    is_ragged = False
 
     def __init__(self, total_len, mass_len):
         m = np.ascontiguousarray(mass_len, dtype=np.uint32)
@@ -587,6 +613,31 @@ class SimBatch:
             raise ValueError("mass_len must be a sequence with one entry per member")
         self.count, self.total_len, self.mass_len = int(m.shape[0]), int(total_len), m.copy()
         self._h = hip_lib().nb_hip_batch_create(self.count, self.total_len, m.ctypes.data_as(C.POINTER(C.c_uint32)))
+
+    @classmethod
+    def ragged(cls, total_lens, mass_lens):
+        """nb_hip_ragged_create: member b has total_lens[b] particles, mass_lens[b] of them massive."""
+        n = np.ascontiguousarray(total_lens, dtype=np.uint32)
+        m = np.ascontiguousarray(mass_lens, dtype=np.uint32)
+        if n.ndim != 1 or m.shape != n.shape:
+            raise ValueError("total_lens and mass_lens must be sequences with one entry per member")
+        self = cls.__new__(cls)
+        self.is_ragged = True
+        self.count, self.total_lens, self.mass_len = int(n.shape[0]), n.copy(), m.copy()
+        self.total_len = int(n.max()) if n.size else 0
+        self._h = hip_lib().nb_hip_ragged_create(self.count, n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 m.ctypes.data_as(C.POINTER(C.c_uint32)))
+        self.offsets = self.layout()[1]
+        return self
+
+    def layout(self):
+        """nb_hip_ragged_layout: (sizes uint32 (B,), offsets uint64 (B + 1,)) of the packed arrays; also for a uniform ensemble."""
+        sizes, offsets = np.empty(self.count, np.uint32), np.empty(self.count + 1, np.uint64)
+        hip_lib().nb_hip_ragged_layout(self._h, sizes.ctypes.data_as(C.POINTER(C.c_uint32)), offsets.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return sizes, offsets
+
+    def sizes(self):
+        return [int(x) for x in self.layout()[0]]
 
     def close(self):
         if self._h:
@@ -600,17 +651,27 @@ class SimBatch:
             pass
 
     def set_data(self, particles):
+        if self.is_ragged:
+            flat, sizes = _packed(particles)
+            assert np.array_equal(sizes, self.total_lens)
+            hip_lib().nb_hip_batch_set_data(self._h, flat.ctypes.data)
+            return
         a = as_ensemble(particles)
         assert a.shape[:2] == (self.count, self.total_len)
         hip_lib().nb_hip_batch_set_data(self._h, a.ctypes.data)
 
     def get_data(self):
+        if self.is_ragged:
+            flat = np.empty((int(self.offsets[-1]), 8), dtype=np.float32)
+            hip_lib().nb_hip_batch_get_data(self._h, flat.ctypes.data)
+            return _unpacked(flat, self.offsets)
         out = np.empty((self.count, self.total_len, 8), dtype=np.float32)
         hip_lib().nb_hip_batch_get_data(self._h, out.ctypes.data)
         return out
 
     def get_member(self, b):
-        out = np.empty((self.total_len, 8), dtype=np.float32)
+        n = int(self.total_lens[b]) if self.is_ragged and 0 <= int(b) < self.count else self.total_len
+        out = np.empty((n, 8), dtype=np.float32)
         hip_lib().nb_hip_batch_get_member(self._h, int(b), out.ctypes.data)
         return out
 
@@ -664,7 +725,12 @@ class SimBatch:
         return [e.as_dict() for e in out]
 
     def potential(self):
-        """nb_hip_ensemble_potential: Phi_i of every particle of every member, float32 (B, n), partitioned order."""
+        """nb_hip_ensemble_potential: Phi_i of every particle of every member, float32 (B, n), partitioned order; ragged: a
+        list of B float32 (N_b,) arrays."""
+        if self.is_ragged:
+            flat = np.empty(int(self.offsets[-1]), dtype=np.float32)
+            hip_lib().nb_hip_ensemble_potential(self._h, flat.ctypes.data)
+            return _unpacked(flat, self.offsets)
         out = np.empty((self.count, self.total_len), dtype=np.float32)
         hip_lib().nb_hip_ensemble_potential(self._h, out.ctypes.data)
         return out
@@ -709,8 +775,24 @@ class SimBatch:
         return float(hip_lib().nb_hip_ensemble_last_render_ms(self._h))
 
     def launch_shape(self):
-        """path "chain" / "lanes" plus the knobs that pin a SimPipeline to the same summation order (pinned_knobs)."""
+        """path "chain" / "lanes" plus the knobs that pin a SimPipeline to the same summation order (pinned_knobs); ragged:
+        {"groups": [one such dict per launch group, with its member count], "members": [(group, k, w, lanes) per member]}."""
         path, k, w, lanes, g = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_uint32()
+        if self.is_ragged:
+            groups, i, total = [], 0, 1
+            members = C.c_uint32()
+            while i < total:
+                total = int(hip_lib().nb_hip_ragged_launch_shape(self._h, i, C.byref(path), C.byref(k), C.byref(w), C.byref(lanes),
+                                                                 C.byref(members), C.byref(g)))
+                groups.append({"path": "lanes" if path.value else "chain", "k": k.value, "w": w.value, "lanes": lanes.value,
+                               "members": members.value, "workgroups": g.value})
+                i += 1
+            per = []
+            grp = C.c_uint32()
+            for b in range(self.count):
+                hip_lib().nb_hip_ragged_member_shape(self._h, b, C.byref(grp), C.byref(k), C.byref(w), C.byref(lanes))
+                per.append((grp.value, k.value, w.value, lanes.value))
+            return {"groups": groups, "members": per}
         hip_lib().nb_hip_batch_launch_shape(self._h, C.byref(path), C.byref(k), C.byref(w), C.byref(lanes), C.byref(g))
         return {"path": "lanes" if path.value else "chain", "k": k.value, "w": w.value, "lanes": lanes.value,
                 "workgroups": g.value}
@@ -725,12 +807,29 @@ class SimBatch:
 
 class WorldBatch:
     """include/nbody_batch.h WorldBatch, bound 1:1: (B, n, 8) particles in caller order; every member is partitioned
-    like CreateWorld partitions it."""
+    like CreateWorld partitions it.  WorldBatch.ragged(list of (N_b, 8) arrays) makes a batch whose members differ in size
+    (include/nbody_batch_ragged.h): particles() and potential() then return lists of per-member arrays."""
+
+    is_ragged = False
 
     def __init__(self, particles):
         a = as_ensemble(particles)
         self.count, self.size = int(a.shape[0]), int(a.shape[1])
         self._h = nbody_lib().CreateWorldBatch(a.ctypes.data, self.size, self.count)
+
+    @classmethod
+    def ragged(cls, members):
+        flat, sizes = _packed(members)
+        self = cls.__new__(cls)
+        self.is_ragged = True
+        self.count, self._sizes = int(sizes.shape[0]), sizes
+        self.size = int(sizes.max()) if sizes.size else 0
+        self.offsets = np.concatenate([[0], np.cumsum(sizes, dtype=np.uint64)]).astype(np.uint64)
+        self._h = nbody_lib().CreateWorldBatchRagged(flat.ctypes.data, sizes.ctypes.data_as(C.POINTER(C.c_uint32)), self.count)
+        return self
+
+    def sizes(self):
+        return [int(x) for x in self._sizes] if self.is_ragged else [self.size] * self.count
 
     def close(self):
         if self._h:
@@ -749,6 +848,8 @@ class WorldBatch:
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), shape=(n.value, 8)).copy()
 
     def particles(self):
+        if self.is_ragged:
+            return [self.member(b) for b in range(self.count)]
         return np.stack([self.member(b) for b in range(self.count)])
 
     def update_gpu(self, dt, n):
@@ -776,6 +877,10 @@ class WorldBatch:
 
     def potential(self):
         """GetWorldBatchPotential: Phi_i of every particle of every member, float32 (B, n), in member(b)'s order."""
+        if self.is_ragged:
+            flat = np.empty(int(self.offsets[-1]), dtype=np.float32)
+            nbody_lib().GetWorldBatchPotential(self._h, flat.ctypes.data)
+            return _unpacked(flat, self.offsets)
         out = np.empty((self.count, self.size), dtype=np.float32)
         nbody_lib().GetWorldBatchPotential(self._h, out.ctypes.data)
         return out

@@ -17,6 +17,14 @@
 // chain_kernel / lane_split_kernel, so member b's bits are those of the same particles alone in a SimPipeline pinned to
 // that shape (tests/test_gpu_batch.py).  Members share nothing with each other and a SimBatch shares nothing with any
 // SimPipeline: own stream, own buffers, own events.
+//
+// A RAGGED ensemble (nb_hip_ragged_create) is the same SimBatch with a particle count per member.  The SoA arrays keep one
+// stride (the largest member rounded up to 64 rows), the AoS side of the seam is packed (member b at offsets[b]), and the
+// members fall into up to three launch GROUPS by their own size alone -- chain (N <= 512), lane-split (8, 8), lane-split
+// (16, 4) -- each with a device list of its member indices: one chain launch per call and one lane-split launch per group
+// and step (kernels.hip ragged_*_kernel, the same bodies with the receiver count read per member).  Member b's bits are
+// those of the same particles as the only member of a uniform SimBatch of its size.  A uniform SimBatch launches exactly
+// what it launched before ragged ones existed.
 #include "pipeline_internal.h"
 #include "batch_diag.h"
 #include "batch_render.h"
@@ -28,8 +36,11 @@ using namespace nbi;
 
 struct SimBatch {
     uint32_t count = 0;     // members
-    uint32_t n = 0;         // particles per member
+    uint32_t n = 0;         // particles per member; ragged: of the largest member
     uint32_t stride = 0;    // rows per member in the SoA arrays: n rounded up to 64 (256-byte aligned float rows)
+    std::vector<uint32_t> n_len;      // [count] particles of each member
+    std::vector<uint64_t> offsets;    // [count + 1] member b's first record in the packed AoS arrays of the seam
+    bool ragged = false;              // made by nb_hip_ragged_create
     std::vector<uint32_t> mass_len;   // [count]
     std::vector<float> dt_host;       // [count]: what dt_dev holds (valid once dt_valid)
     bool dt_valid = false;
@@ -53,6 +64,19 @@ struct SimBatch {
     int k = 2, w = 16, lanes = 1;
     uint32_t tiles = 0;
     uint32_t workgroups = 0;
+
+    // ragged only: the launch groups, in the order chain, lane-split (8, 8), lane-split (16, 4); those without members are
+    // absent.  path = 1 as soon as one member is lane-split (both position buffers exist, traces interleave).
+    struct Group {
+        int path = 0, k = 2, w = 16, lanes = 1;   // chain: w of the group's largest member
+        uint32_t max_n = 0;                       // its largest member
+        uint32_t workgroups = 0;                  // per launch
+        std::vector<uint32_t> members;            // ascending member indices
+        uint32_t *list = nullptr;                 // the same on the device
+    };
+    std::vector<Group> groups;
+    uint32_t *n_len_dev = nullptr;
+    uint64_t *offsets_dev = nullptr;
 
     // nb_hip_ensemble_energy / nb_hip_ensemble_potential (kernels: batch_diag.hip): scratch made on first use, an event
     // pair of their own (ev[] keeps bracketing the last update)
@@ -108,7 +132,27 @@ void materialize(SimBatch *s) {
     s->gm = dev_alloc<float>(rows);
     s->mass_len_dev = dev_alloc<uint32_t>(s->count);
     s->dt_dev = dev_alloc<float>(s->count);
-    s->aos = dev_alloc<Particle>((size_t)s->count * s->n);
+    s->aos = dev_alloc<Particle>((size_t)s->offsets[s->count]);
+    if (s->ragged) {
+        // pad rows stay zero for the life of the ensemble: no kernel writes a row at or beyond n_len[b]
+        ASSERT_HIP(hipMemsetAsync(s->vel, 0, rows * sizeof(float2), s->stream), "clear velocities");
+        ASSERT_HIP(hipMemsetAsync(s->acc, 0, rows * sizeof(float2), s->stream), "clear accelerations");
+        ASSERT_HIP(hipMemsetAsync(s->radius, 0, rows * sizeof(float), s->stream), "clear radii");
+        ASSERT_HIP(hipMemsetAsync(s->mass, 0, rows * sizeof(float), s->stream), "clear masses");
+        ASSERT_HIP(hipMemsetAsync(s->gm, 0, rows * sizeof(float), s->stream), "clear G*m");
+        s->n_len_dev = dev_alloc<uint32_t>(s->count);
+        s->offsets_dev = dev_alloc<uint64_t>((size_t)s->count + 1);
+        ASSERT_HIP(hipMemcpyAsync(s->n_len_dev, s->n_len.data(), (size_t)s->count * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream),
+                   "H2D of %u member sizes", s->count);
+        ASSERT_HIP(hipMemcpyAsync(s->offsets_dev, s->offsets.data(), ((size_t)s->count + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
+                                  s->stream),
+                   "H2D of %u member offsets", s->count);
+        for (auto &g : s->groups) {
+            g.list = dev_alloc<uint32_t>(g.members.size());
+            ASSERT_HIP(hipMemcpyAsync(g.list, g.members.data(), g.members.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream),
+                       "H2D of a launch group's %zu members", g.members.size());
+        }
+    }
     ASSERT_HIP(hipMemcpyAsync(s->mass_len_dev, s->mass_len.data(), (size_t)s->count * sizeof(uint32_t), hipMemcpyHostToDevice,
                               s->stream),
                "H2D of %u source counts", s->count);
@@ -168,8 +212,50 @@ void launch_lane_steps(SimBatch *s, nb::BatchParams &p, uint32_t n) {
     }
 }
 
+// n steps of a ragged ensemble: per step one launch for every lane-split group (all of them flip the ping-pong phase
+// together), then the chain group's whole call in place in the buffer it started from -- and, when the phase moved, one
+// copy of the chain members' position rows into the buffer that is now the latest, so that every reader (read-back,
+// diagnostics, the next call) finds all members in pos[cur].  Returns the launches made.
+uint32_t launch_ragged_steps(SimBatch *s, const nb::BatchParams &p0, uint32_t n) {
+    uint32_t launches = 0;
+    const int cur0 = s->cur;
+    for (uint32_t i = 0; i < n && s->path != 0; i++) {
+        for (const auto &g : s->groups) {
+            if (g.path == 0) continue;
+            nb::RaggedParams rp = {p0, s->n_len_dev, g.list};
+            rp.b.pos_in = s->pos[s->cur];
+            rp.b.pos_out = s->pos[s->cur ^ 1];
+            const nb::LaunchShape sh = {.k = 1, .w = g.w, .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = g.lanes};
+            dim3 grid = nb::step_grid(sh, g.max_n);
+            grid.y = (uint32_t)g.members.size();
+            void *args[] = {&rp};
+            ASSERT_HIP(hipLaunchKernel(nb::ragged_lane_split_fn(g.w, g.lanes), grid, nb::step_block(sh), args,
+                                       nb::step_lds_bytes(sh, g.max_n), s->stream),
+                       "ragged lane-split launch (w=%d lanes=%d, %zu members of up to %u)", g.w, g.lanes, g.members.size(), g.max_n);
+            launches++;
+        }
+        s->cur ^= 1;
+    }
+    for (const auto &g : s->groups) {
+        if (g.path != 0) continue;
+        nb::RaggedParams rp = {p0, s->n_len_dev, g.list};
+        rp.b.pos_in = rp.b.pos_out = s->pos[cur0];
+        for (uint32_t left = n; left > 0; left -= rp.b.steps, launches++) {
+            rp.b.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
+            nb::launch_ragged_chain(s->stream, rp, (uint32_t)g.members.size());
+        }
+        if (s->cur != cur0 && n > 0) {
+            nb::launch_ragged_copy_rows(s->stream, g.list, s->n_len_dev, (uint32_t)g.members.size(), g.max_n, s->stride, s->pos[cur0],
+                                        s->pos[s->cur]);
+            launches++;
+        }
+    }
+    return launches;
+}
+
 // n steps, no record: whole chain launches or lane-split launches; returns the launches made
 uint32_t launch_steps(SimBatch *s, nb::BatchParams &p, uint32_t n) {
+    if (s->ragged) return launch_ragged_steps(s, p, n);
     if (s->path != 0) {
         launch_lane_steps(s, p, n);
         return n;
@@ -201,9 +287,14 @@ void read_back(SimBatch *s, uint32_t first, uint32_t members, Particle *ps) {
     NB_ASSERT(s != nullptr && ps != nullptr, "NULL argument");
     NB_ASSERT(s->has_data, "ensemble read-back before nb_hip_batch_set_data");
     use_device();
-    nb::launch_batch_merge(s->stream, s->aos, first, members, s->n, s->stride, s->pos[s->cur], s->vel, s->acc, s->radius, s->mass);
-    ASSERT_HIP(hipMemcpyAsync(ps, static_cast<const Particle *>(s->aos) + (size_t)first * s->n,
-                              (size_t)members * s->n * sizeof(Particle), hipMemcpyDeviceToHost, s->stream),
+    if (s->ragged)
+        nb::launch_ragged_merge(s->stream, s->aos, s->offsets_dev, s->n_len_dev, first, members, s->n, s->stride, s->pos[s->cur], s->vel,
+                                s->acc, s->radius, s->mass);
+    else
+        nb::launch_batch_merge(s->stream, s->aos, first, members, s->n, s->stride, s->pos[s->cur], s->vel, s->acc, s->radius, s->mass);
+    ASSERT_HIP(hipMemcpyAsync(ps, static_cast<const Particle *>(s->aos) + s->offsets[first],
+                              (size_t)(s->offsets[first + members] - s->offsets[first]) * sizeof(Particle), hipMemcpyDeviceToHost,
+                              s->stream),
                "D2H of %u members", members);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after an ensemble read-back");
 }
@@ -214,6 +305,12 @@ void check_diag(SimBatch *s, const void *out, const char *what) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
     NB_ASSERT(out != nullptr, "%s: NULL result array", what);
     NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
+}
+
+// the three render calls are not wired for ragged ensembles: said before anything touches the device
+void check_not_ragged(const SimBatch *s, const char *what) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(!s->ragged, "%s: rendering of ragged ensembles (members of different sizes) is not supported", what);
 }
 
 nbd::EnsembleDiagParams diag_params(const SimBatch *s) {   // of the latest state
@@ -305,7 +402,10 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
             const uint32_t left = n - t.done;
             p.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
             t.b = p;
-            nb::launch_batch_trace_chain(s->stream, t);
+            if (s->ragged)   // fused means every member is in the chain group: its list is 0 .. count - 1
+                nb::launch_ragged_trace_chain(s->stream, nb::RaggedTraceParams{t, s->n_len_dev, s->groups[0].list}, s->count);
+            else
+                nb::launch_batch_trace_chain(s->stream, t);
             t.done += p.steps;
             launches++;
         } while (t.done < n);
@@ -417,6 +517,9 @@ SimBatch *nb_hip_batch_create(uint32_t count, uint32_t total_len, const uint32_t
     s->stride = round_up(total_len, 64);
     s->mass_len.assign(mass_len, mass_len + count);
     s->dt_host.assign(count, 0.0f);
+    s->n_len.assign(count, total_len);
+    s->offsets.resize((size_t)count + 1);
+    for (uint32_t b = 0; b <= count; b++) s->offsets[b] = (uint64_t)b * total_len;
     s->tiles = nb::chain_tiles(total_len);
     if (s->tiles) {
         s->path = 0;
@@ -435,6 +538,106 @@ SimBatch *nb_hip_batch_create(uint32_t count, uint32_t total_len, const uint32_t
     return s;
 }
 
+SimBatch *nb_hip_ragged_create(uint32_t count, const uint32_t *total_len, const uint32_t *mass_len) {
+    NB_ASSERT(count > 0, "an ensemble needs at least one member (count = 0)");
+    NB_ASSERT(count <= NB_HIP_BATCH_MAX_COUNT, "count %u > %u members (the grid's y extent)", count, NB_HIP_BATCH_MAX_COUNT);
+    NB_ASSERT(total_len != nullptr && mass_len != nullptr, "NULL total_len or mass_len array");
+    for (uint32_t b = 0; b < count; b++) {
+        NB_ASSERT(total_len[b] > 0, "member %u: total_len = 0: an empty world", b);
+        NB_ASSERT(total_len[b] <= nb::BATCH_MAX_RECV, "member %u: total_len %u > %u: ensembles step worlds of at most %u particles", b,
+                  total_len[b], nb::BATCH_MAX_RECV, nb::BATCH_MAX_RECV);
+        NB_ASSERT(mass_len[b] <= total_len[b], "member %u: mass_len %u > total_len %u", b, mass_len[b], total_len[b]);
+    }
+    SimBatch *s = new SimBatch();
+    s->ragged = true;
+    s->count = count;
+    s->mass_len.assign(mass_len, mass_len + count);
+    s->n_len.assign(total_len, total_len + count);
+    s->dt_host.assign(count, 0.0f);
+    s->offsets.resize((size_t)count + 1);
+    s->offsets[0] = 0;
+    SimBatch::Group slot[3];   // chain, lane-split (8, 8), lane-split (16, 4)
+    for (uint32_t b = 0; b < count; b++) {
+        const uint32_t n = total_len[b];
+        s->offsets[b + 1] = s->offsets[b] + n;
+        s->n = n > s->n ? n : s->n;
+        int which = 0, w = 16, lanes = 1;
+        if (nb::chain_tiles(n) == 0) {
+            lanes = nb::batch_lane_shape(n, &w);
+            NB_ASSERT(lanes > 1 && nb::ragged_lane_split_fn(w, lanes) != nullptr, "member %u: no ensemble kernel for w=%d lanes=%d", b, w,
+                      lanes);
+            which = lanes == 8 ? 1 : 2;
+        }
+        SimBatch::Group &g = slot[which];
+        g.path = which != 0;
+        g.k = which ? 1 : 2;
+        g.lanes = lanes;
+        g.max_n = n > g.max_n ? n : g.max_n;
+        g.w = which ? w : (int)(16u / nb::chain_tiles(g.max_n));
+        g.members.push_back(b);
+    }
+    s->stride = round_up(s->n, 64);
+    for (auto &g : slot) {
+        if (g.members.empty()) continue;
+        const uint32_t per = g.path ? (g.max_n + 64u / (uint32_t)g.lanes - 1) / (64u / (uint32_t)g.lanes) : 1u;
+        g.workgroups = (uint32_t)g.members.size() * per;
+        s->workgroups += g.workgroups;
+        if (g.path) s->path = 1;
+        s->groups.push_back(g);
+    }
+    s->k = s->groups[0].k;
+    s->w = s->groups[0].w;
+    s->lanes = s->groups[0].lanes;
+    return s;
+}
+
+void nb_hip_ragged_layout(const SimBatch *s, uint32_t *sizes, uint64_t *offsets) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (sizes) memcpy(sizes, s->n_len.data(), (size_t)s->count * sizeof(uint32_t));
+    if (offsets) memcpy(offsets, s->offsets.data(), ((size_t)s->count + 1) * sizeof(uint64_t));
+}
+
+uint32_t nb_hip_ragged_launch_shape(const SimBatch *s, uint32_t group, int *path, int *k, int *w, int *lanes, uint32_t *members,
+                                    uint32_t *workgroups) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    const uint32_t groups = s->ragged ? (uint32_t)s->groups.size() : 1u;
+    NB_ASSERT(group < groups, "launch group %u of %u", group, groups);
+    SimBatch::Group uniform;   // a uniform ensemble is one group of all members
+    if (!s->ragged) {
+        uniform.path = s->path;
+        uniform.k = s->k;
+        uniform.w = s->w;
+        uniform.lanes = s->lanes;
+        uniform.workgroups = s->workgroups;
+    }
+    const SimBatch::Group &g = s->ragged ? s->groups[group] : uniform;
+    if (path) *path = g.path;
+    if (k) *k = g.k;
+    if (w) *w = g.w;
+    if (lanes) *lanes = g.lanes;
+    if (members) *members = s->ragged ? (uint32_t)g.members.size() : s->count;
+    if (workgroups) *workgroups = g.workgroups;
+    return groups;
+}
+
+void nb_hip_ragged_member_shape(const SimBatch *s, uint32_t member, uint32_t *group, int *k, int *w, int *lanes) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(member < s->count, "member %u of %u", member, s->count);
+    const uint32_t n = s->n_len[member], tiles = nb::chain_tiles(n);
+    int mw = 16, ml = 1;
+    if (tiles)
+        mw = (int)(16u / tiles);
+    else
+        ml = nb::batch_lane_shape(n, &mw);
+    uint32_t gi = 0;
+    for (uint32_t i = 0; s->ragged && i < s->groups.size(); i++)
+        if (s->groups[i].path == (tiles ? 0 : 1) && (tiles || s->groups[i].lanes == ml)) gi = i;
+    if (group) *group = gi;
+    if (k) *k = tiles ? 2 : 1;
+    if (w) *w = mw;
+    if (lanes) *lanes = ml;
+}
+
 void nb_hip_batch_destroy(SimBatch *s) {
     if (s == nullptr) return;
     if (s->on_device) {
@@ -449,6 +652,10 @@ void nb_hip_batch_destroy(SimBatch *s) {
         dev_free(s->mass_len_dev);
         dev_free(s->dt_dev);
         dev_free(s->aos);
+        if (s->n_len_dev) dev_free(s->n_len_dev);
+        if (s->offsets_dev) dev_free(s->offsets_dev);
+        for (auto &g : s->groups)
+            if (g.list) dev_free(g.list);
         if (s->diag) dev_free(s->diag);
         if (s->diag_phi) dev_free(s->diag_phi);
         if (s->trace) dev_free(s->trace);
@@ -476,10 +683,14 @@ void nb_hip_batch_set_data(SimBatch *s, const Particle *ps) {
     }
     use_device();
     s->cur = 0;
-    ASSERT_HIP(hipMemcpyAsync(s->aos, ps, (size_t)s->count * s->n * sizeof(Particle), hipMemcpyHostToDevice, s->stream),
-               "H2D of %u x %u particles", s->count, s->n);
-    nb::launch_batch_split(s->stream, s->aos, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0], s->vel, s->acc, s->radius, s->mass,
-                           s->gm, NB_G);
+    ASSERT_HIP(hipMemcpyAsync(s->aos, ps, (size_t)s->offsets[s->count] * sizeof(Particle), hipMemcpyHostToDevice, s->stream),
+               "H2D of %u members' particles (up to %u each)", s->count, s->n);
+    if (s->ragged)
+        nb::launch_ragged_split(s->stream, s->aos, s->offsets_dev, s->n_len_dev, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0],
+                                s->vel, s->acc, s->radius, s->mass, s->gm, NB_G);
+    else
+        nb::launch_batch_split(s->stream, s->aos, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0], s->vel, s->acc, s->radius,
+                               s->mass, s->gm, NB_G);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_batch_set_data");
     s->has_data = true;
 }
@@ -546,13 +757,16 @@ void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
 void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
     check_diag(s, phi, "nb_hip_ensemble_potential");
     nbd::EnsembleDiagParams p = begin_diag(s);
-    const size_t total = (size_t)s->count * s->n;
+    const size_t total = (size_t)s->offsets[s->count];
     p.phi = grown(s, s->diag_phi, s->diag_phi_cap, total);
-    nbd::launch_ensemble_potential(s->stream, p, s->count);
+    if (s->ragged)
+        nbd::launch_ragged_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
+    else
+        nbd::launch_ensemble_potential(s->stream, p, s->count);
     ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
     end_diag(s);
-    ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u x %u potentials",
-               s->count, s->n);
+    ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u members' potentials",
+               s->count);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_potential");
 }
 
@@ -592,6 +806,7 @@ void nb_hip_ensemble_last_trace_info(const SimBatch *s, int *fused, uint32_t *la
 }
 
 void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {
+    check_not_ragged(s, "nb_hip_ensemble_bounds");
     check_diag(s, bounds, "nb_hip_ensemble_bounds");
     begin_render(s);
     if (!s->render_keys) s->render_keys = dev_alloc<uint32_t>((size_t)s->count * 4);
@@ -606,6 +821,7 @@ void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {
 }
 
 void nb_hip_ensemble_render_counts(SimBatch *s, const RenderView *views, uint32_t *counts) {
+    check_not_ragged(s, "nb_hip_ensemble_render_counts");
     check_diag(s, counts, "nb_hip_ensemble_render_counts");
     check_views(s, views, "nb_hip_ensemble_render_counts");
     use_device();
@@ -617,6 +833,7 @@ void nb_hip_ensemble_render_counts(SimBatch *s, const RenderView *views, uint32_
 }
 
 void nb_hip_ensemble_render_rgba(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint8_t *rgba) {
+    check_not_ragged(s, "nb_hip_ensemble_render_rgba");
     check_diag(s, rgba, "nb_hip_ensemble_render_rgba");
     check_views(s, views, "nb_hip_ensemble_render_rgba");
     NB_ASSERT(palette != nullptr, "nb_hip_ensemble_render_rgba: NULL RenderPalette");

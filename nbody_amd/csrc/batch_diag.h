@@ -30,4 +30,8 @@ void launch_ensemble_potential(hipStream_t stream, EnsembleDiagParams p, uint32_
 void launch_ensemble_reduce(hipStream_t stream, const double *slab, const uint32_t *mass_len, uint32_t tiles, uint32_t count,
                             double *out);
 
+// ragged ensembles (ragged_diag.hip): Phi of member b's n_len[b] particles to p.phi + offsets[b]; p.n = the largest
+// member, n_len and offsets on the device.  The energy rows of a ragged ensemble are launch_ensemble_potential's.
+void launch_ragged_potential(hipStream_t stream, EnsembleDiagParams p, uint32_t count, const uint32_t *n_len, const uint64_t *offsets);
+
 }  // namespace nbd

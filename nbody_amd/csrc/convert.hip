@@ -112,9 +112,59 @@ __global__ void batch_merge_kernel(ParticleRec *aos, uint32_t first, uint32_t n,
     aos[(size_t)b * n + i] = pack(load_soa((size_t)b * stride + i, pos, vel, acc, radius, mass));
 }
 
+// Ragged ensemble upload: member blockIdx.y's n_len[b] records, packed at offsets[b], into its SoA rows.  gm receives
+// the MASS of the member's sources (0 in rows that are none); make_gm_kernel over the same array then turns it into G*m
+// with the one rounding rule, so a source's G*m has the bits batch_split_kernel gives it.
+__global__ void ragged_split_kernel(const ParticleRec *aos, const uint64_t *offsets, const uint32_t *n_len, const uint32_t *mass_len,
+                                    uint32_t stride, float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (i >= n_len[b]) return;
+    const Soa s = unpack(aos[offsets[b] + i]);
+    const size_t o = (size_t)b * stride + i;
+    store_soa(s, o, pos, vel, acc, radius, mass);
+    gm[o] = i < mass_len[b] ? s.mass : 0.0f;
+}
+
+// Ragged ensemble read-back: members [first, first + gridDim.y) back into their packed AoS records.
+__global__ void ragged_merge_kernel(ParticleRec *aos, const uint64_t *offsets, const uint32_t *n_len, uint32_t first, uint32_t stride,
+                                    const float2 *pos, const float2 *vel, const float2 *acc, const float *radius, const float *mass) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = first + blockIdx.y;
+    if (i >= n_len[b]) return;
+    aos[offsets[b] + i] = pack(load_soa((size_t)b * stride + i, pos, vel, acc, radius, mass));
+}
+
+// The position rows of the listed members from one ping-pong buffer to the other (ragged ensembles: the chain group's
+// members step in place while the lane-split groups flip buffers).
+__global__ void ragged_copy_rows_kernel(const uint32_t *members, const uint32_t *n_len, uint32_t stride, const float2 *from, float2 *to) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = members[blockIdx.y];
+    if (i >= n_len[b]) return;
+    const size_t o = (size_t)b * stride + i;
+    to[o] = from[o];
+}
+
 inline dim3 grid1d(uint32_t count, uint32_t rows = 1) { return dim3((count + 255u) / 256u, rows); }
 
 }  // namespace
+
+void launch_ragged_split(hipStream_t st, const void *aos, const uint64_t *offsets, const uint32_t *n_len, const uint32_t *mass_len,
+                         uint32_t count, uint32_t max_n, uint32_t stride, float2 *pos, float2 *vel, float2 *acc, float *radius,
+                         float *mass, float *gm, float g) {
+    hipLaunchKernelGGL(ragged_split_kernel, grid1d(max_n, count), dim3(256), 0, st, static_cast<const ParticleRec *>(aos), offsets,
+                       n_len, mass_len, stride, pos, vel, acc, radius, mass, gm);
+    launch_make_gm(st, gm, gm, count * stride, g);   // in place: every thread reads and writes its own row
+}
+
+void launch_ragged_merge(hipStream_t st, void *aos, const uint64_t *offsets, const uint32_t *n_len, uint32_t first, uint32_t count,
+                         uint32_t max_n, uint32_t stride, const float2 *pos, const float2 *vel, const float2 *acc,
+                         const float *radius, const float *mass) {
+    if (count) hipLaunchKernelGGL(ragged_merge_kernel, grid1d(max_n, count), dim3(256), 0, st, static_cast<ParticleRec *>(aos), offsets,
+                       n_len, first, stride, pos, vel, acc, radius, mass);
+}
+
+void launch_ragged_copy_rows(hipStream_t st, const uint32_t *members, const uint32_t *n_len, uint32_t count, uint32_t max_n,
+                             uint32_t stride, const float2 *from, float2 *to) {
+    if (count) hipLaunchKernelGGL(ragged_copy_rows_kernel, grid1d(max_n, count), dim3(256), 0, st, members, n_len, stride, from, to);
+}
 
 void launch_batch_split(hipStream_t st, const void *aos, const uint32_t *mass_len, uint32_t count, uint32_t n, uint32_t stride,
                         float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g) {

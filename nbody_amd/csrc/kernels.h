@@ -127,6 +127,24 @@ struct BatchTraceParams {
     uint32_t done;        // steps of this call that earlier launches ran
 };
 
+// A ragged ensemble: the members differ in their particle counts.  The arrays keep ONE stride (the largest member rounded
+// up to 64 rows), member m holds n_len[m] particles in its first rows, and a launch covers one GROUP of members that
+// share a launch shape: workgroup (chain: blockIdx.x, lane-split: blockIdx.y) g steps member members[g].  b.n_recv and
+// b.tiles are not read: both come from n_len[m], so a member's shape is a function of its own size alone.
+struct RaggedParams {
+    BatchParams b;
+    const uint32_t *n_len;     // [count] particles per member
+    const uint32_t *members;   // [workgroups of the group] member indices
+};
+
+// The traced chain of a ragged ensemble whose members all fit the chain: rows are addressed by the member's own index,
+// so t.count stays the row pitch (the ensemble's member count).
+struct RaggedTraceParams {
+    BatchTraceParams t;
+    const uint32_t *n_len;
+    const uint32_t *members;
+};
+
 constexpr int MAX_SPLIT = 16;
 
 struct LaunchShape;   // launch_shape.h
@@ -144,5 +162,10 @@ void launch_chain(hipStream_t st, const ChainParams &p);
 const void *batch_lane_split_fn(int w, int lanes);
 void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count);
 void launch_batch_trace_chain(hipStream_t st, const BatchTraceParams &p);
+
+// ragged ensembles: one launch per group of `members` members
+const void *ragged_lane_split_fn(int w, int lanes);
+void launch_ragged_chain(hipStream_t st, const RaggedParams &p, uint32_t members);
+void launch_ragged_trace_chain(hipStream_t st, const RaggedTraceParams &p, uint32_t members);
 
 }  // namespace nb

@@ -908,6 +908,59 @@ __global__ __launch_bounds__(WAVE *W) void batch_lane_split_kernel(const BatchPa
     lane_split_body<W, H>(p);
 }
 
+// ---- ragged ensembles: members of different N in one launch ---------------------------------------------------------
+//
+// The same bodies once more, with the receiver count read per member (kernels.h RaggedParams): a launch covers one group
+// of members -- the chain group (N <= 512) or one of the two lane-split shapes -- and finds its member through the
+// group's list.  Everything a body branches on (n_recv, tiles, n_src) is wave-uniform, so member m runs the instructions
+// and the summation order of the same particles as the only member of a uniform ensemble of its size.
+__device__ __forceinline__ ChainParams ragged_member_chain(const BatchParams &bp, uint32_t member, uint32_t n) {
+    const size_t base = (size_t)member * bp.stride;
+    ChainParams p;
+    p.pos = bp.pos_in + base;
+    p.vel = bp.vel + base;
+    p.acc = bp.acc + base;
+    p.radius = bp.radius + base;
+    p.src_gm = bp.gm + base;
+    p.n_recv = n;
+    p.n_src = uniform_u32(bp.mass_len[member]);
+    p.steps = bp.steps;
+    p.tiles = n <= WAVE * CHAIN_K ? 1u : n <= 2 * WAVE * CHAIN_K ? 2u : 4u;   // chain_tiles(n), n <= CHAIN_MAX_RECV
+    p.dt = bp.dt + member;
+    return p;
+}
+
+__global__ __launch_bounds__(1024) void ragged_chain_kernel(const RaggedParams rp) {
+    const uint32_t member = uniform_u32(rp.members[blockIdx.x]);
+    chain_body<false>(ragged_member_chain(rp.b, member, uniform_u32(rp.n_len[member])), ChainTrace{});
+}
+
+__global__ __launch_bounds__(1024) void ragged_trace_chain_kernel(const RaggedTraceParams rp) {
+    const BatchTraceParams &tp = rp.t;
+    const uint32_t member = uniform_u32(rp.members[blockIdx.x]);
+    ChainTrace tr;
+    tr.mass = tp.mass + (size_t)member * tp.b.stride;
+    tr.pitch = (size_t)tp.count * nbd::QTY;
+    tr.entry = tp.done == 0;
+    tr.every = tp.every;
+    tr.until = tp.every - tp.done % tp.every;
+    tr.row = tp.rows + ((size_t)(tp.done == 0 ? 0u : 1u + tp.done / tp.every) * tp.count + member) * nbd::QTY;
+    chain_body<true>(ragged_member_chain(tp.b, member, uniform_u32(rp.n_len[member])), tr);
+}
+
+// gridDim.x covers the group's largest member: the workgroups past a smaller member's last receiver leave before the
+// first barrier (blockIdx and n are uniform over the workgroup, so all of it leaves).
+template <int W, int H>
+__global__ __launch_bounds__(WAVE *W) void ragged_lane_split_kernel(const RaggedParams rp) {
+    const uint32_t member = uniform_u32(rp.members[blockIdx.y]);
+    const uint32_t n = uniform_u32(rp.n_len[member]);
+    if (blockIdx.x * (WAVE / H) >= n) return;
+    const BatchParams &bp = rp.b;
+    const size_t base = (size_t)member * bp.stride;
+    const StepParams p = plain_step(bp.pos_in + base, bp.gm + base, uniform_u32(bp.mass_len[member]), bp.pos_in + base,
+                                    bp.pos_out + base, bp.vel + base, bp.acc + base, bp.radius + base, n, bp.dt + member, 8);
+    lane_split_body<W, H>(p);
+}
 
 // ---- kernel entry points -------------------------------------------------------------------------------------------
 // One row of a lookup: run-time keys (a, b) == (A, B) select KERNEL<A, B, further template arguments>.
@@ -959,6 +1012,11 @@ const void *batch_lane_split_fn(int a, int b) {   // (w, lanes)
     NB_CASE(batch_lane_split_kernel, 8, 8) NB_CASE(batch_lane_split_kernel, 16, 4)
     return nullptr;
 }
+
+const void *ragged_lane_split_fn(int a, int b) {   // (w, lanes): the same two shapes
+    NB_CASE(ragged_lane_split_kernel, 8, 8) NB_CASE(ragged_lane_split_kernel, 16, 4)
+    return nullptr;
+}
 #undef NB_CASE
 
 void launch_chain(hipStream_t st, const ChainParams &p) {
@@ -971,6 +1029,14 @@ void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count) {
 
 void launch_batch_trace_chain(hipStream_t st, const BatchTraceParams &p) {
     hipLaunchKernelGGL(batch_trace_chain_kernel, dim3(p.count), dim3(1024), 0, st, p);
+}
+
+void launch_ragged_chain(hipStream_t st, const RaggedParams &p, uint32_t members) {
+    hipLaunchKernelGGL(ragged_chain_kernel, dim3(members), dim3(1024), 0, st, p);
+}
+
+void launch_ragged_trace_chain(hipStream_t st, const RaggedTraceParams &p, uint32_t members) {
+    hipLaunchKernelGGL(ragged_trace_chain_kernel, dim3(members), dim3(1024), 0, st, p);
 }
 
 }  // namespace nb

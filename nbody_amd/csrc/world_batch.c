@@ -11,9 +11,13 @@
  * device_is_newer.  include/nbody_batch_trace.h: UpdateWorldBatch_GPU_Traced is an update that also records: same upload, same coherence.
  * include/nbody_batch_render.h: bounds, count images and frames of every member follow the same protocol (device:
  * nb_hip_ensemble_*; host: render_cpu.c member by member).
+ * include/nbody_batch_ragged.h: CreateWorldBatchRagged makes a batch whose members differ in size over nb_hip_ragged_create;
+ * the array is then packed (member b at offset[b]), which is all the protocol above needs to know -- a uniform batch is
+ * the case offset[b] = b * size.  The render calls are not wired for such a batch and abort.
  */
 #include "nbody_batch.h"
 #include "nbody_batch_diag.h"
+#include "nbody_batch_ragged.h"
 #include "nbody_batch_render.h"
 #include "nbody_batch_trace.h"
 #include "nbody_hip.h"
@@ -26,34 +30,67 @@
 #include "world_partition.h"
 
 struct WorldBatch {
-    Particle *particles;  /* count * size, member-major, each member partitioned */
-    uint32_t size;        /* particles per member */
+    Particle *particles;  /* packed, member b at offset[b], each member partitioned */
+    uint32_t size;        /* particles per member; ragged: of the largest */
     uint32_t count;       /* members */
+    uint32_t *sizes;      /* [count] particles of each member */
+    size_t *offset;       /* [count + 1] */
+    bool ragged;          /* made by CreateWorldBatchRagged */
     uint32_t *massive;    /* [count] particles with mass > 0 of each member; they come first */
     SimBatch *gpu;
     bool uploaded;        /* the device has seen the array */
     bool device_is_newer; /* the device stepped since the array was last refreshed */
 };
 
+/* The host side of both constructors: the packed copy, every member partitioned; sizes[b] was checked by the caller. */
+static WorldBatch *make_batch(const Particle *ps, const uint32_t *world_size, uint32_t uniform_size, uint32_t count) {
+    WorldBatch *w = NB_NEW(1, WorldBatch);
+    NB_CHECK(w != NULL, "Failed to alloc WorldBatch");
+    w->sizes = NB_NEW(count, uint32_t);
+    w->offset = NB_NEW((size_t)count + 1, size_t);
+    w->massive = NB_NEW(count, uint32_t);
+    NB_CHECK(w->sizes != NULL && w->offset != NULL && w->massive != NULL, "Failed to alloc the tables of %u members", count);
+    w->offset[0] = 0;
+    w->size = 0;
+    for (uint32_t b = 0; b < count; b++) {
+        w->sizes[b] = world_size ? world_size[b] : uniform_size;
+        w->offset[b + 1] = w->offset[b] + w->sizes[b];
+        if (w->sizes[b] > w->size) w->size = w->sizes[b];
+    }
+    const size_t total = w->offset[count];
+    w->particles = NB_NEW(total, Particle);
+    NB_CHECK(w->particles != NULL, "Failed to alloc %zu particles of %u members", total, count);
+    memcpy(w->particles, ps, total * sizeof(Particle));
+    for (uint32_t b = 0; b < count; b++) w->massive[b] = partition_by_mass(w->particles + w->offset[b], w->sizes[b]);
+    w->count = count;
+    w->ragged = world_size != NULL;
+    w->uploaded = false;
+    w->device_is_newer = false;
+    return w;
+}
+
 WorldBatch *CreateWorldBatch(const Particle *ps, uint32_t world_size, uint32_t count) {
     NB_CHECK(ps != NULL, "NULL particle array");
     NB_CHECK(count > 0 && count <= NB_HIP_BATCH_MAX_COUNT, "count %u outside 1 .. %u", count, NB_HIP_BATCH_MAX_COUNT);
     NB_CHECK(world_size > 0 && world_size <= NB_HIP_BATCH_MAX_LEN, "world_size %u outside 1 .. %u", world_size, NB_HIP_BATCH_MAX_LEN);
-    WorldBatch *w = NB_NEW(1, WorldBatch);
-    NB_CHECK(w != NULL, "Failed to alloc WorldBatch");
-    const size_t total = (size_t)world_size * count;
-    w->particles = NB_NEW(total, Particle);
-    uint32_t *massive = NB_NEW(count, uint32_t);
-    NB_CHECK(w->particles != NULL && massive != NULL, "Failed to alloc %u x %u particles", count, world_size);
-    memcpy(w->particles, ps, total * sizeof(Particle));
-    for (uint32_t b = 0; b < count; b++) massive[b] = partition_by_mass(w->particles + (size_t)b * world_size, world_size);
-    w->size = world_size;
-    w->count = count;
-    w->gpu = nb_hip_batch_create(count, world_size, massive);
-    w->massive = massive;
-    w->uploaded = false;
-    w->device_is_newer = false;
+    WorldBatch *w = make_batch(ps, NULL, world_size, count);
+    w->gpu = nb_hip_batch_create(count, world_size, w->massive);
     return w;
+}
+
+WorldBatch *CreateWorldBatchRagged(const Particle *ps, const uint32_t *world_size, uint32_t count) {
+    NB_CHECK(count > 0 && count <= NB_HIP_BATCH_MAX_COUNT, "count %u outside 1 .. %u", count, NB_HIP_BATCH_MAX_COUNT);
+    NB_CHECK(ps != NULL && world_size != NULL, "NULL argument");
+    for (uint32_t b = 0; b < count; b++)
+        NB_CHECK(world_size[b] > 0 && world_size[b] <= NB_HIP_BATCH_MAX_LEN, "member %u: world_size %u outside 1 .. %u", b, world_size[b],
+                 NB_HIP_BATCH_MAX_LEN);
+    WorldBatch *w = make_batch(ps, world_size, 0, count);
+    w->gpu = nb_hip_ragged_create(count, w->sizes, w->massive);
+    return w;
+}
+
+static void check_not_ragged(const WorldBatch *w, const char *what) {
+    NB_CHECK(w == NULL || !w->ragged, "%s: rendering of ragged ensembles (members of different sizes) is not supported", what);
 }
 
 void DestroyWorldBatch(WorldBatch *w) {
@@ -61,6 +98,8 @@ void DestroyWorldBatch(WorldBatch *w) {
     nb_hip_batch_destroy(w->gpu);
     free(w->particles);
     free(w->massive);
+    free(w->sizes);
+    free(w->offset);
     free(w);
 }
 
@@ -71,8 +110,8 @@ const Particle *GetWorldBatchParticles(WorldBatch *w, uint32_t member, uint32_t 
         nb_hip_batch_get_data(w->gpu, w->particles);
         w->device_is_newer = false;
     }
-    if (size != NULL) *size = w->size;
-    return w->particles + (size_t)member * w->size;
+    if (size != NULL) *size = w->sizes[member];
+    return w->particles + w->offset[member];
 }
 
 static void push_once(WorldBatch *w) {
@@ -119,7 +158,7 @@ void GetWorldBatchEnergy(WorldBatch *w, WorldEnergy *out) {
         nb_hip_ensemble_energy(w->gpu, out);
         return;
     }
-    for (uint32_t b = 0; b < w->count; b++) nb_cpu_energy(w->particles + (size_t)b * w->size, w->size, w->massive[b], out + b);
+    for (uint32_t b = 0; b < w->count; b++) nb_cpu_energy(w->particles + w->offset[b], w->sizes[b], w->massive[b], out + b);
 }
 
 void GetWorldBatchPotential(WorldBatch *w, float *phi) {
@@ -129,10 +168,11 @@ void GetWorldBatchPotential(WorldBatch *w, float *phi) {
         return;
     }
     for (uint32_t b = 0; b < w->count; b++)
-        nb_cpu_potential(w->particles + (size_t)b * w->size, w->size, w->massive[b], phi + (size_t)b * w->size);
+        nb_cpu_potential(w->particles + w->offset[b], w->sizes[b], w->massive[b], phi + w->offset[b]);
 }
 
 void GetWorldBatchBounds(WorldBatch *w, float *bounds) {
+    check_not_ragged(w, "GetWorldBatchBounds");
     NB_CHECK(w != NULL && bounds != NULL, "NULL argument");
     if (w->device_is_newer) {
         nb_hip_ensemble_bounds(w->gpu, bounds);
@@ -142,6 +182,7 @@ void GetWorldBatchBounds(WorldBatch *w, float *bounds) {
 }
 
 void FitWorldBatchViews(WorldBatch *w, uint32_t width, uint32_t height, RenderView *views) {
+    check_not_ragged(w, "FitWorldBatchViews");
     NB_CHECK(w != NULL && views != NULL, "NULL argument");
     float *bounds = NB_NEW((size_t)w->count * 4, float);
     NB_CHECK(bounds != NULL, "Failed to alloc %u bounds", w->count);
@@ -158,6 +199,7 @@ static void check_views(const WorldBatch *w, const RenderView *views) {
 }
 
 void RenderWorldBatchCounts(WorldBatch *w, const RenderView *views, uint32_t *counts) {
+    check_not_ragged(w, "RenderWorldBatchCounts");
     NB_CHECK(w != NULL && views != NULL && counts != NULL, "NULL argument");
     check_views(w, views);
     if (w->device_is_newer) {
@@ -170,6 +212,7 @@ void RenderWorldBatchCounts(WorldBatch *w, const RenderView *views, uint32_t *co
 }
 
 void RenderWorldBatch(WorldBatch *w, const RenderView *views, const RenderPalette *palette, uint8_t *rgba) {
+    check_not_ragged(w, "RenderWorldBatch");
     NB_CHECK(w != NULL && views != NULL && rgba != NULL, "NULL argument");
     check_views(w, views);
     RenderPalette pal;
