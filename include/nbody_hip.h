@@ -350,6 +350,27 @@ void nb_hip_render_counts(SimPipeline *sim, const RenderView *view, uint32_t *co
 void nb_hip_render_rgba(SimPipeline *sim, const RenderView *view, const RenderPalette *palette, uint8_t *rgba);
 
 /*
+ * The potential of the state the pipeline holds away from its particles (definitions: include/nbody_field.h):
+ *   nb_hip_potential_at   phi[i] = Phi(points[i]; softening) for the caller's n points ((x, y) pairs), 0 <= n <= 2^24;
+ *                         n = 0 does nothing
+ *   nb_hip_potential_map  phi[height][width] float32: Phi at every pixel centre of *view (only target, offset, zoom, width
+ *                         and height are used).  The host computes the width column and height row coordinates; only those
+ *                         width + height floats travel to the device, and the map is exactly nb_hip_potential_at of the
+ *                         grid points, row-major
+ * Phi at a point has the bits nb_hip_potential gives a massless particle of radius `softening` at the same place: the
+ * same pair statement and the same summation order.  A point with a non-finite coordinate gives NaN.  Like the
+ * diagnostics above they are enqueued on the pipeline's stream behind any nb_hip_step_async work, read the buffer that
+ * holds the latest state, block until their own result is in the caller's host buffer, and change nothing observable: the
+ * state, the ping-pong phase, the cached chains, the step-size uploads, what nb_hip_last_step_ms reports and the frame
+ * loop's eager read-back are as before the call.  Their device buffers grow on demand and are freed by
+ * DestroySimPipeline.  Abort before the first SetSimulationData, for a softening that is not finite and > 0, for an invalid
+ * view, and for sharded pipelines (a collective over the ranks: not supported).  Added WITHOUT a version bump: detect them
+ * by symbol (dlsym "nb_hip_potential_map").
+ */
+void nb_hip_potential_at(SimPipeline *sim, const float *points, uint32_t n, float softening, float *phi);
+void nb_hip_potential_map(SimPipeline *sim, const RenderView *view, float softening, float *phi);
+
+/*
  * World ensembles: `count` independent worlds with the same particle count, stepped together.
  *
  * One world of a few hundred to a few thousand particles keeps one or a handful of the chip's 256 compute units busy;

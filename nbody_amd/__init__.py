@@ -148,6 +148,8 @@ HIP_API = {
     "nb_hip_bounds": (None, [C.c_void_p, C.c_void_p]),
     "nb_hip_render_counts": (None, [C.c_void_p, C.POINTER(RenderView), C.c_void_p]),
     "nb_hip_render_rgba": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
+    "nb_hip_potential_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "nb_hip_potential_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nb_hip_batch_destroy": (None, [C.c_void_p]),
     "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
@@ -200,7 +202,7 @@ TUNE_API = {
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
-# include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h
+# include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -221,6 +223,9 @@ NBODY_API = {
     "FitWorldView": (None, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(RenderView)]),
     "RenderWorldCounts": (None, [C.c_void_p, C.POINTER(RenderView), C.c_void_p]),
     "RenderWorld": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
+    # include/nbody_field.h
+    "GetWorldPotentialAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "RenderWorldPotential": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     # include/nbody_batch.h
     "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "DestroyWorldBatch": (None, [C.c_void_p]),
@@ -291,6 +296,14 @@ def as_particles(a):
     a = np.ascontiguousarray(a, dtype=np.float32)
     if a.ndim != 2 or a.shape[1] != 8:
         raise ValueError("particles must have shape (n, 8)")
+    return a
+
+
+def as_points(points):
+    """(n, 2) float32, contiguous: the probe points of include/nbody_field.h."""
+    a = np.ascontiguousarray(points, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("points must have shape (n, 2)")
     return a
 
 
@@ -493,8 +506,21 @@ class SimPipeline:
         hip_lib().nb_hip_potential(self._h, out.ctypes.data)
         return out
 
+    def potential_at(self, points, softening):
+        """nb_hip_potential_at: Phi at the (n, 2) points with one softening (include/nbody_field.h), float32 (n,)."""
+        pts = as_points(points)
+        out = np.empty(pts.shape[0], dtype=np.float32)
+        hip_lib().nb_hip_potential_at(self._h, pts.ctypes.data, pts.shape[0], softening, out.ctypes.data)
+        return out
+
+    def potential_map(self, view, softening):
+        """nb_hip_potential_map: Phi at every pixel centre of the view, float32 (height, width)."""
+        out = np.empty((view.height, view.width), dtype=np.float32)
+        hip_lib().nb_hip_potential_map(self._h, C.byref(view), softening, out.ctypes.data)
+        return out
+
     def last_diag_ms(self):
-        """tuning hook: device ms of the kernels of the last energy() / potential()."""
+        """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map()."""
         return float(hip_lib().nb_hip_last_diag_ms(self._h))
 
     def bounds(self):
@@ -1006,6 +1032,18 @@ class World:
         nbody_lib().GetWorldPotential(self._h, out.ctypes.data)
         return out
 
+    def potential_at(self, points, softening):
+        """GetWorldPotentialAt (include/nbody_field.h): Phi at the (n, 2) points with one softening, float32 (n,)."""
+        pts = as_points(points)
+        out = np.empty(pts.shape[0], dtype=np.float32)
+        nbody_lib().GetWorldPotentialAt(self._h, pts.ctypes.data, pts.shape[0], softening, out.ctypes.data)
+        return out
+
+    def potential_map(self, view, softening):
+        """RenderWorldPotential: Phi at every pixel centre of the view, float32 (height, width)."""
+        out = np.empty((view.height, view.width), dtype=np.float32)
+        nbody_lib().RenderWorldPotential(self._h, C.byref(view), softening, out.ctypes.data)
+        return out
 
     def bounds(self):
         """GetWorldBounds (include/nbody_render.h): float32 [min.x, min.y, max.x, max.y]."""

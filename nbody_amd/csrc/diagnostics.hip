@@ -146,6 +146,25 @@ nbd::DiagParams diag_params(SimPipeline *s, uint32_t n_recv) {
     return p;
 }
 
+// the pipeline's float64 scratch: QTY per workgroup + QTY results, grown on demand
+double *diag_scratch(SimPipeline *s, uint32_t rows) {
+    const size_t need = (size_t)(rows + 1) * QTY;
+    if (s->diag_cap < need) {
+        if (s->diag) {
+            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the diagnostics slab");
+            dev_free(s->diag);
+        }
+        s->diag = dev_alloc<double>(need);
+        s->diag_cap = need;
+    }
+    return s->diag;
+}
+
+}  // namespace
+
+namespace nbi {
+
+// shared with field.hip (pipeline_internal.h): the checks and the event pair of every diagnostic of one pipeline
 void check_diag(SimPipeline *s, const char *what) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
     NB_ASSERT(!s->sharded, "%s of a sharded pipeline needs a collective over the ranks: not supported", what);
@@ -166,21 +185,7 @@ void end_diag(SimPipeline *s) {
     s->diag_timed = true;
 }
 
-// the pipeline's float64 scratch: QTY per workgroup + QTY results, grown on demand
-double *diag_scratch(SimPipeline *s, uint32_t rows) {
-    const size_t need = (size_t)(rows + 1) * QTY;
-    if (s->diag_cap < need) {
-        if (s->diag) {
-            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the diagnostics slab");
-            dev_free(s->diag);
-        }
-        s->diag = dev_alloc<double>(need);
-        s->diag_cap = need;
-    }
-    return s->diag;
-}
-
-}  // namespace
+}  // namespace nbi
 
 extern "C" {
 

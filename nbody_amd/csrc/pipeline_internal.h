@@ -13,6 +13,7 @@
 //   batch_diag.hip   the same for every member of a SimBatch: the kernels behind nb_hip_ensemble_energy / _potential
 //                    (batch_diag.h; the arithmetic both share: diag_common.h)
 //   render.hip       bounds, count image and RGBA frame of the state a pipeline holds (nb_hip_bounds, nb_hip_render_*)
+//   field.hip        the potential at probe points and as a map over a view (nb_hip_potential_at, nb_hip_potential_map)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -308,6 +309,13 @@ struct SimPipeline {
     hipEvent_t ev_bounds[2] = {nullptr, nullptr};
     bool render_timed = false, render_detailed = false, bounds_timed = false;
     int render_merge = 1, render_detail = 0;   // tuning hooks (nbody_hip_tuning.h)
+
+    // field.hip (nb_hip_potential_at / nb_hip_potential_map): buffers grown on demand; the event pair is ev_diag
+    float *field_in = nullptr;    // the probes' (x, y) pairs, or a map's width column + height row coordinates
+    size_t field_in_cap = 0;      // floats allocated in field_in
+    float *field_phi = nullptr;   // the device result, one float per sample
+    size_t field_phi_cap = 0;
+    int field_shape = 0;          // tuning hook: 0 auto, 1 source split, 2 one wave per tile
 };
 
 namespace nbi {
@@ -329,6 +337,16 @@ void sharded_step(SimPipeline *s, nb::LaunchShape sh, float dt, hipStream_t cs, 
 // in-place all-gather of a device array of nranks slots through the caller's host transport
 void host_allgather(SimPipeline *s, void *dev_base, size_t bytes_per_rank, hipStream_t st);
 void enqueue_steps(SimPipeline *s, uint32_t n, float dt);  // what PerformSimUpdate / nb_hip_step_async enqueue
+
+// ---- diagnostics.hip -----------------------------------------------------------------------------------------
+
+void check_diag(SimPipeline *s, const char *what);   // aborts on NULL, on a sharded pipeline and before SetSimulationData
+void begin_diag(SimPipeline *s);                     // records ev_diag[0] on the stream (creates the pair on first use)
+void end_diag(SimPipeline *s);                       // records ev_diag[1]; nb_hip_last_diag_ms then reports the interval
+
+// ---- field.hip -----------------------------------------------------------------------------------------------
+
+void field_release(SimPipeline *s);    // frees the field buffers (release_device)
 
 // ---- render.hip ----------------------------------------------------------------------------------------------
 

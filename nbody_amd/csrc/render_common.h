@@ -125,6 +125,22 @@ static inline const char *nb_render_view_fault(const RenderView *v) {
 }
 
 /*
+ * World coordinates of the pixel centres of a view (include/nbody_field.h): xs[px] = (((float)px + 0.5f) - offset[0]) / zoom
+ * + target[0] for the `width` columns, ys[py] likewise for the `height` rows.  Host only, float32, every operation rounded
+ * on its own: whichever side then evaluates a field at the centres starts from these width + height floats.
+ */
+static inline void nb_render_pixel_centres(const RenderView *v, float *xs, float *ys) {
+    for (uint32_t px = 0; px < v->width; px++) {
+        const float c = (float)px + 0.5f, d = c - v->offset[0], q = d / v->zoom;
+        xs[px] = q + v->target[0];
+    }
+    for (uint32_t py = 0; py < v->height; py++) {
+        const float c = (float)py + 0.5f, d = c - v->offset[1], q = d / v->zoom;
+        ys[py] = q + v->target[1];
+    }
+}
+
+/*
  * The views of one ensemble render (one per member): NULL when each is valid, all share width and height and the `count`
  * images together hold at most 2^24 pixels; else what is wrong, with *member = the first member at fault.
  */

@@ -21,15 +21,19 @@
  * Extension (include/nbody_render.h): GetWorldBounds / FitWorldView /
  * RenderWorldCounts / RenderWorld follow the same rule (render.hip on the
  * device, render_cpu.c on the host).
+ * Extension (include/nbody_field.h): GetWorldPotentialAt / RenderWorldPotential
+ * follow the same rule (field.hip on the device, field_cpu.c on the host).
  */
 #include "nbody.h"
 #include "nbody_diag.h"
+#include "nbody_field.h"
 #include "nbody_hip.h"
 #include "nbody_render.h"
 
 #include <stdbool.h>
 
 #include "diag_sums.h"
+#include "field_common.h"
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
@@ -195,4 +199,20 @@ void RenderWorld(World *w, const RenderView *view, const RenderPalette *palette,
         nb_hip_render_rgba(w->gpu, view, &pal, rgba);
     else
         nb_cpu_render_rgba(w->particles, w->count, view, &pal, rgba);
+}
+
+void GetWorldPotentialAt(World *w, const V2 *points, uint32_t n, float softening, float *phi) {
+    NB_CHECK(w != NULL && ((points != NULL && phi != NULL) || n == 0), "NULL argument");
+    if (diag_on_device(w, "GetWorldPotentialAt"))
+        nb_hip_potential_at(w->gpu, (const float *)points, n, softening, phi);
+    else
+        nb_cpu_potential_at(w->particles, w->massive, points, n, softening, phi);
+}
+
+void RenderWorldPotential(World *w, const RenderView *view, float softening, float *phi) {
+    NB_CHECK(w != NULL && view != NULL && phi != NULL, "NULL argument");
+    if (diag_on_device(w, "RenderWorldPotential"))
+        nb_hip_potential_map(w->gpu, view, softening, phi);
+    else
+        nb_cpu_potential_map(w->particles, w->massive, view, softening, phi);
 }
