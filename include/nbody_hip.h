@@ -371,6 +371,28 @@ void nb_hip_potential_at(SimPipeline *sim, const float *points, uint32_t n, floa
 void nb_hip_potential_map(SimPipeline *sim, const RenderView *view, float softening, float *phi);
 
 /*
+ * The acceleration field of the state the pipeline holds away from its particles (definitions: include/nbody_gravity.h):
+ *   nb_hip_acceleration_at   acc[2 * i], acc[2 * i + 1] = g(points[i]; softening) for the caller's n points ((x, y) pairs),
+ *                            0 <= n <= 2^24; n = 0 does nothing
+ *   nb_hip_acceleration_map  acc[height][width][2] float32: g at every pixel centre of *view (only target, offset, zoom,
+ *                            width and height are used).  The host computes the width column and height row coordinates;
+ *                            only those width + height floats travel to the device, and the map is exactly
+ *                            nb_hip_acceleration_at of the grid points, row-major
+ * The pair is the step kernels' statement with the softening in the place of the receiver's radius; the sums are those of
+ * nb_hip_potential (fp32 over a block of 256 sources, float64 block totals in eight source slices added in order), so a
+ * result is a function of the point and the state alone: not of n, the point's index or the kernel shape.  A point with a
+ * non-finite coordinate gives NaN in both components.  Like the diagnostics above they are enqueued on the pipeline's stream
+ * behind any nb_hip_step_async work, read the buffer that holds the latest state, block until their own result is in the
+ * caller's host buffer, and change nothing observable: the state, the ping-pong phase, the cached chains, the step-size
+ * uploads, what nb_hip_last_step_ms reports and the frame loop's eager read-back are as before the call.  Their device
+ * buffers grow on demand and are freed by DestroySimPipeline.  Abort before the first SetSimulationData, for a softening
+ * that is not finite and > 0, for an invalid view, and for sharded pipelines (a collective over the ranks: not supported).
+ * Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_acceleration_map").
+ */
+void nb_hip_acceleration_at(SimPipeline *sim, const float *points, uint32_t n, float softening, float *acc);
+void nb_hip_acceleration_map(SimPipeline *sim, const RenderView *view, float softening, float *acc);
+
+/*
  * World ensembles: `count` independent worlds with the same particle count, stepped together.
  *
  * One world of a few hundred to a few thousand particles keeps one or a handful of the chip's 256 compute units busy;

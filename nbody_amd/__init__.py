@@ -150,6 +150,8 @@ HIP_API = {
     "nb_hip_render_rgba": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
     "nb_hip_potential_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "nb_hip_potential_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    "nb_hip_acceleration_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "nb_hip_acceleration_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nb_hip_batch_destroy": (None, [C.c_void_p]),
     "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
@@ -202,7 +204,7 @@ TUNE_API = {
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
-# include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h
+# include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -226,6 +228,9 @@ NBODY_API = {
     # include/nbody_field.h
     "GetWorldPotentialAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "RenderWorldPotential": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    # include/nbody_gravity.h
+    "GetWorldAccelerationAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "RenderWorldAcceleration": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     # include/nbody_batch.h
     "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "DestroyWorldBatch": (None, [C.c_void_p]),
@@ -519,8 +524,22 @@ class SimPipeline:
         hip_lib().nb_hip_potential_map(self._h, C.byref(view), softening, out.ctypes.data)
         return out
 
+    def acceleration_at(self, points, softening):
+        """nb_hip_acceleration_at: g at the (n, 2) points with one softening (include/nbody_gravity.h), float32 (n, 2)."""
+        pts = as_points(points)
+        out = np.empty((pts.shape[0], 2), dtype=np.float32)
+        hip_lib().nb_hip_acceleration_at(self._h, pts.ctypes.data, pts.shape[0], softening, out.ctypes.data)
+        return out
+
+    def acceleration_map(self, view, softening):
+        """nb_hip_acceleration_map: g at every pixel centre of the view, float32 (height, width, 2)."""
+        out = np.empty((view.height, view.width, 2), dtype=np.float32)
+        hip_lib().nb_hip_acceleration_map(self._h, C.byref(view), softening, out.ctypes.data)
+        return out
+
     def last_diag_ms(self):
-        """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map()."""
+        """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
+        acceleration_at() / acceleration_map()."""
         return float(hip_lib().nb_hip_last_diag_ms(self._h))
 
     def bounds(self):
@@ -1043,6 +1062,19 @@ class World:
         """RenderWorldPotential: Phi at every pixel centre of the view, float32 (height, width)."""
         out = np.empty((view.height, view.width), dtype=np.float32)
         nbody_lib().RenderWorldPotential(self._h, C.byref(view), softening, out.ctypes.data)
+        return out
+
+    def acceleration_at(self, points, softening):
+        """GetWorldAccelerationAt (include/nbody_gravity.h): g at the (n, 2) points with one softening, float32 (n, 2)."""
+        pts = as_points(points)
+        out = np.empty((pts.shape[0], 2), dtype=np.float32)
+        nbody_lib().GetWorldAccelerationAt(self._h, pts.ctypes.data, pts.shape[0], softening, out.ctypes.data)
+        return out
+
+    def acceleration_map(self, view, softening):
+        """RenderWorldAcceleration: g at every pixel centre of the view, float32 (height, width, 2)."""
+        out = np.empty((view.height, view.width, 2), dtype=np.float32)
+        nbody_lib().RenderWorldAcceleration(self._h, C.byref(view), softening, out.ctypes.data)
         return out
 
     def bounds(self):

@@ -47,6 +47,9 @@ extern "C" {
  *               the world has at most 2 blocks of 256 sources and the call at least 4 096 tiles of 128 samples, else the
  *               source split; profiles/r12_field_probe.json), 1 = the source split (8 waves share
  *               a tile of samples, 1/8 of the sources each), 2 = one wave per tile; same bits (tests/test_gpu_field.py)
+ *   "gravity_shape" which kernel nb_hip_acceleration_at / nb_hip_acceleration_map run: 0 (default) = auto (the rule of
+ *               "field_shape", inherited and not yet measured for this pair body), 1 = the source split, 2 = one wave
+ *               per tile; same bits (tests/test_gpu_gravity.py)
  *   "zero_copy_upload"  1 (default) = SetSimulationData from the noted, page-locked array lets the split kernel read the
  *               records over PCIe itself; 0 = DMA copy into device staging, then the kernel
  * Returns the previous value; aborts on an unknown key or value.
@@ -72,7 +75,8 @@ int nb_hip_plan_fused_finish(uint32_t n_recv, uint32_t n_src, int compute_units)
 int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units);
 
 /* Device milliseconds of the kernels of the last nb_hip_energy / nb_hip_potential / nb_hip_potential_at /
- * nb_hip_potential_map (their own event pair, not the step's); 0 before the first call. */
+ * nb_hip_potential_map / nb_hip_acceleration_at / nb_hip_acceleration_map (their own event pair, not the step's); 0 before
+ * the first call. */
 double nb_hip_last_diag_ms(SimPipeline *sim);
 
 /* The same for an ensemble: device milliseconds of the kernels of the last nb_hip_ensemble_energy /

@@ -101,6 +101,7 @@ void release_device(SimPipeline *s) {
     s->diag_timed = false;
     render_release(s);
     field_release(s);
+    gravity_release(s);
     ASSERT_HIP(hipEventDestroy(s->ev_begin), "event");
     ASSERT_HIP(hipEventDestroy(s->ev_end), "event");
     ASSERT_HIP(hipEventDestroy(s->ev_local), "event");
@@ -692,6 +693,10 @@ int nb_hip_tune(SimPipeline *s, const char *key, int value) {
         NB_ASSERT(value >= 0 && value <= 2, "field_shape must be 0 (auto), 1 (source split) or 2 (one wave per tile), got %d", value);
         old = s->field_shape;
         s->field_shape = value;
+    } else if (!strcmp(key, "gravity_shape")) {
+        NB_ASSERT(value >= 0 && value <= 2, "gravity_shape must be 0 (auto), 1 (source split) or 2 (one wave per tile), got %d", value);
+        old = s->gravity_shape;
+        s->gravity_shape = value;
     } else if (!strcmp(key, "render_detail")) {
         old = s->render_detail;
         s->render_detail = value ? 1 : 0;

@@ -14,6 +14,7 @@
 //                    (batch_diag.h; the arithmetic both share: diag_common.h)
 //   render.hip       bounds, count image and RGBA frame of the state a pipeline holds (nb_hip_bounds, nb_hip_render_*)
 //   field.hip        the potential at probe points and as a map over a view (nb_hip_potential_at, nb_hip_potential_map)
+//   gravity.hip      the acceleration at probe points and as a map over a view (nb_hip_acceleration_at, nb_hip_acceleration_map)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -316,6 +317,13 @@ struct SimPipeline {
     float *field_phi = nullptr;   // the device result, one float per sample
     size_t field_phi_cap = 0;
     int field_shape = 0;          // tuning hook: 0 auto, 1 source split, 2 one wave per tile
+
+    // gravity.hip (nb_hip_acceleration_at / nb_hip_acceleration_map): buffers grown on demand; the event pair is ev_diag
+    float *gravity_in = nullptr;     // the probes' (x, y) pairs, or a map's width column + height row coordinates
+    size_t gravity_in_cap = 0;       // floats allocated in gravity_in
+    float2 *gravity_acc = nullptr;   // the device result, one float2 per sample
+    size_t gravity_acc_cap = 0;
+    int gravity_shape = 0;           // tuning hook: 0 auto, 1 source split, 2 one wave per tile
 };
 
 namespace nbi {
@@ -347,6 +355,10 @@ void end_diag(SimPipeline *s);                       // records ev_diag[1]; nb_h
 // ---- field.hip -----------------------------------------------------------------------------------------------
 
 void field_release(SimPipeline *s);    // frees the field buffers (release_device)
+
+// ---- gravity.hip ---------------------------------------------------------------------------------------------
+
+void gravity_release(SimPipeline *s);  // frees the gravity buffers (release_device)
 
 // ---- render.hip ----------------------------------------------------------------------------------------------
 

@@ -23,10 +23,13 @@
  * device, render_cpu.c on the host).
  * Extension (include/nbody_field.h): GetWorldPotentialAt / RenderWorldPotential
  * follow the same rule (field.hip on the device, field_cpu.c on the host).
+ * Extension (include/nbody_gravity.h): GetWorldAccelerationAt /
+ * RenderWorldAcceleration likewise (gravity.hip, gravity_cpu.c).
  */
 #include "nbody.h"
 #include "nbody_diag.h"
 #include "nbody_field.h"
+#include "nbody_gravity.h"
 #include "nbody_hip.h"
 #include "nbody_render.h"
 
@@ -34,6 +37,7 @@
 
 #include "diag_sums.h"
 #include "field_common.h"
+#include "gravity_common.h"
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
@@ -215,4 +219,20 @@ void RenderWorldPotential(World *w, const RenderView *view, float softening, flo
         nb_hip_potential_map(w->gpu, view, softening, phi);
     else
         nb_cpu_potential_map(w->particles, w->massive, view, softening, phi);
+}
+
+void GetWorldAccelerationAt(World *w, const V2 *points, uint32_t n, float softening, V2 *acc) {
+    NB_CHECK(w != NULL && ((points != NULL && acc != NULL) || n == 0), "NULL argument");
+    if (diag_on_device(w, "GetWorldAccelerationAt"))
+        nb_hip_acceleration_at(w->gpu, (const float *)points, n, softening, (float *)acc);
+    else
+        nb_cpu_acceleration_at(w->particles, w->massive, points, n, softening, acc);
+}
+
+void RenderWorldAcceleration(World *w, const RenderView *view, float softening, V2 *acc) {
+    NB_CHECK(w != NULL && view != NULL && acc != NULL, "NULL argument");
+    if (diag_on_device(w, "RenderWorldAcceleration"))
+        nb_hip_acceleration_map(w->gpu, view, softening, (float *)acc);
+    else
+        nb_cpu_acceleration_map(w->particles, w->massive, view, softening, acc);
 }
