@@ -24,6 +24,7 @@
 #include "nbody.h"
 #include "nbody_diag.h" /* WorldEnergy */
 #include "nbody_render.h" /* RenderView, RenderPalette */
+#include "nbody_adaptive.h" /* NbAdaptive, NbAdaptiveResult */
 
 #ifdef __cplusplus
 extern "C" {
@@ -546,6 +547,34 @@ void nb_hip_ragged_layout(const SimBatch *batch, uint32_t *sizes /* [count] */, 
 uint32_t nb_hip_ragged_launch_shape(const SimBatch *batch, uint32_t group, int *path, int *k, int *w, int *lanes, uint32_t *members,
                                     uint32_t *workgroups);
 void nb_hip_ragged_member_shape(const SimBatch *batch, uint32_t member, uint32_t *group, int *k, int *w, int *lanes);
+
+/*
+ * Adaptive time steps chosen on the device (definitions: include/nbody_adaptive.h; kernels: nbody_amd/csrc/timestep.hip).
+ *   nb_hip_adaptive_steps         n steps, each of the size the criterion gives for the state before it; blocking
+ *   nb_hip_adaptive_steps_async   the same, enqueue only
+ *   nb_hip_adaptive_collect       waits for the last adaptive call and copies its log (n floats, may be NULL) and result
+ *   nb_hip_timestep               the criterion alone (no span clip) for the latest state; changes nothing observable
+ *   nb_hip_ensemble_adaptive_steps   the same for every member of a SimBatch: dt_log[n][count], out[count], either may be NULL
+ * For every step the call enqueues the criterion launch -- a small reduction over acc and radius that writes the step size
+ * where the step kernels read it (the pipeline's device dt, an ensemble's dt[count]), advances a float64 time on the device,
+ * counts and logs -- and then exactly the launches a one-step PerformSimUpdate / nb_hip_batch_update makes, without its
+ * step-size upload.  There is no host synchronisation inside the call; one copy at the end brings the log and the result.
+ * The contract: dt_log[i] is, bit for bit, the host criterion of include/nbody_adaptive.h applied to the state before step i,
+ * and the state afterwards is bit for bit that of PerformSimUpdate(sim, 1, dt_log[i]) for i = 0 .. n - 1 (for an ensemble:
+ * nb_hip_batch_update_dts(batch, 1, dt_log[i])); a member's row does not depend on count, its index or the other members.
+ * NB_ADAPT_PRIME first runs one dt = 0 step (equal to PerformSimUpdate(sim, 1, 0)), not logged and not counted.  The step
+ * size cached on the host is dropped, so the next fixed-step call uploads its own.  Chains of adaptive steps are plain
+ * launches: they are not captured into hipGraphs, and the one-workgroup n-step chain is not used (a one-step call never is).
+ * Abort, before any device is touched, for a NULL argument, a configuration include/nbody_adaptive.h rejects and n > 2^20;
+ * for sharded pipelines and ragged ensembles; and before the first SetSimulationData / nb_hip_batch_set_data.  n = 0 does
+ * nothing.  Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_adaptive_steps").
+ */
+void nb_hip_adaptive_steps(SimPipeline *sim, uint32_t n, const NbAdaptive *cfg, float *dt_log /* n or NULL */, NbAdaptiveResult *out);
+void nb_hip_adaptive_steps_async(SimPipeline *sim, uint32_t n, const NbAdaptive *cfg);
+void nb_hip_adaptive_collect(SimPipeline *sim, float *dt_log /* n or NULL */, NbAdaptiveResult *out);
+void nb_hip_timestep(SimPipeline *sim, const NbAdaptive *cfg, float *dt);
+void nb_hip_ensemble_adaptive_steps(SimBatch *batch, uint32_t n, const NbAdaptive *cfg, float *dt_log /* [n][count] */,
+                                 NbAdaptiveResult *out /* [count] */);
 
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int nb_hip_version(void);

@@ -94,6 +94,32 @@ def default_palette():
     return p
 
 
+class NbAdaptive(C.Structure):
+    """include/nbody_adaptive.h NbAdaptive: the configuration of adaptive steps."""
+    _fields_ = [("eta", C.c_float), ("dt_min", C.c_float), ("dt_max", C.c_float), ("flags", C.c_uint32), ("span", C.c_double),
+                ("chunk", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NbAdaptiveResult(C.Structure):
+    """include/nbody_adaptive.h NbAdaptiveResult."""
+    _fields_ = [("elapsed", C.c_double), ("steps", C.c_uint32), ("idle_steps", C.c_uint32), ("dt_last", C.c_float),
+                ("dt_smallest", C.c_float)]
+
+    def as_dict(self):
+        return {"elapsed": self.elapsed, "steps": int(self.steps), "idle_steps": int(self.idle_steps), "dt_last": self.dt_last,
+                "dt_smallest": self.dt_smallest}
+
+
+NB_ADAPT_PRIME = 1      # include/nbody_adaptive.h
+NB_ADAPT_CONTINUE = 2
+
+
+def adaptive_cfg(eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, chunk=0, resume=False):
+    """NbAdaptive from the keyword arguments the adaptive methods share; eta and dt_max have no default."""
+    flags = (NB_ADAPT_PRIME if prime else 0) | (NB_ADAPT_CONTINUE if resume else 0)
+    return NbAdaptive(float(eta), float(dt_min), float(dt_max), flags, float(span), int(chunk), 0)
+
+
 class NbShardPlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mass_chunk", "zero_chunk", "mass_begin", "mass_count",
                                           "zero_begin", "zero_count", "src_padded")]
@@ -179,6 +205,11 @@ HIP_API = {
                                                 C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "nb_hip_ragged_member_shape": (None, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                           C.POINTER(C.c_int)]),
+    "nb_hip_adaptive_steps": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
+    "nb_hip_adaptive_steps_async": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive)]),
+    "nb_hip_adaptive_collect": (None, [C.c_void_p, C.c_void_p, C.POINTER(NbAdaptiveResult)]),
+    "nb_hip_timestep": (None, [C.c_void_p, C.POINTER(NbAdaptive), C.POINTER(C.c_float)]),
+    "nb_hip_ensemble_adaptive_steps": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.c_void_p]),
     "nb_hip_version": (C.c_int, []),
 }
 
@@ -204,7 +235,8 @@ TUNE_API = {
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
-# include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h
+# include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h +
+# include/nbody_adaptive.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -250,6 +282,13 @@ NBODY_API = {
     "RenderWorldBatch": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
     # include/nbody_batch_ragged.h
     "CreateWorldBatchRagged": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
+    # include/nbody_adaptive.h
+    "UpdateWorld_GPU_Adaptive": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
+    "UpdateWorld_CPU_Adaptive": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
+    "GetWorldTimestep": (None, [C.c_void_p, C.POINTER(NbAdaptive), C.POINTER(C.c_float)]),
+    "AdvanceWorld_GPU": (None, [C.c_void_p, C.c_double, C.POINTER(NbAdaptive), C.c_uint32, C.c_void_p, C.POINTER(NbAdaptiveResult)]),
+    "UpdateWorldBatch_GPU_Adaptive": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.c_void_p]),
+    "AdvanceWorldBatch_GPU": (None, [C.c_void_p, C.c_double, C.POINTER(NbAdaptive), C.c_uint32, C.c_void_p, C.c_void_p]),
 }
 
 _hip = None
@@ -461,6 +500,29 @@ class SimPipeline:
 
     def step_async(self, n, dt):
         hip_lib().nb_hip_step_async(self._h, n, dt)
+
+    def update_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False):
+        """nb_hip_adaptive_steps: n steps, each of the size the criterion of include/nbody_adaptive.h gives for the state
+        before it, chosen on the device.  Returns (dt_log float32 (n,), result dict)."""
+        cfg, res, log = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume), NbAdaptiveResult(), np.zeros(n, dtype=np.float32)
+        hip_lib().nb_hip_adaptive_steps(self._h, n, C.byref(cfg), log.ctypes.data, C.byref(res))
+        return log, res.as_dict()
+
+    def update_adaptive_async(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False):
+        """nb_hip_adaptive_steps_async: enqueue only; adaptive_collect(n) fetches the log and the result."""
+        cfg = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume)
+        hip_lib().nb_hip_adaptive_steps_async(self._h, n, C.byref(cfg))
+
+    def adaptive_collect(self, n):
+        res, log = NbAdaptiveResult(), np.zeros(n, dtype=np.float32)
+        hip_lib().nb_hip_adaptive_collect(self._h, log.ctypes.data, C.byref(res))
+        return log, res.as_dict()
+
+    def timestep(self, eta, dt_max, dt_min=0.0):
+        """nb_hip_timestep: the criterion alone for the latest state (no span clip); changes nothing."""
+        cfg, dt = adaptive_cfg(eta, dt_max, dt_min), C.c_float(0.0)
+        hip_lib().nb_hip_timestep(self._h, C.byref(cfg), C.byref(dt))
+        return float(dt.value)
 
     def sync(self):
         hip_lib().nb_hip_sync(self._h)
@@ -730,6 +792,14 @@ class SimBatch:
     def step_async(self, n, dts):
         hip_lib().nb_hip_batch_step_async(self._h, n, _dt_array(dts, self.count).ctypes.data_as(C.POINTER(C.c_float)))
 
+    def update_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False):
+        """nb_hip_ensemble_adaptive_steps: n steps, every member with its own step size at every step, chosen on the device.
+        Returns (dt_log float32 (n, B), list of B result dicts)."""
+        cfg, res = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume), (NbAdaptiveResult * self.count)()
+        log = np.zeros((n, self.count), dtype=np.float32)
+        hip_lib().nb_hip_ensemble_adaptive_steps(self._h, n, C.byref(cfg), log.ctypes.data, C.byref(res))
+        return log, [r.as_dict() for r in res]
+
     def sync(self):
         hip_lib().nb_hip_batch_sync(self._h)
 
@@ -903,6 +973,22 @@ class WorldBatch:
         else:
             nbody_lib().UpdateWorldBatch_GPU_dts(self._h, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)), n)
 
+    def update_gpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False):
+        """UpdateWorldBatch_GPU_Adaptive (include/nbody_adaptive.h): (dt_log float32 (n, B), list of B result dicts)."""
+        cfg, res = adaptive_cfg(eta, dt_max, dt_min, span, prime), (NbAdaptiveResult * self.count)()
+        log = np.zeros((n, self.count), dtype=np.float32)
+        nbody_lib().UpdateWorldBatch_GPU_Adaptive(self._h, n, C.byref(cfg), log.ctypes.data, C.byref(res))
+        return log, [r.as_dict() for r in res]
+
+    def advance_gpu(self, span, eta, dt_max, dt_min=0.0, prime=False, chunk=0, max_steps=4096):
+        """AdvanceWorldBatch_GPU: every member covers `span` (or max_steps steps are made); (dt_log float32 (steps made, B)
+        with the idle steps of members that finished early, list of B result dicts)."""
+        cfg, res = adaptive_cfg(eta, dt_max, dt_min, prime=prime, chunk=chunk), (NbAdaptiveResult * self.count)()
+        log = np.zeros((max_steps, self.count), dtype=np.float32)
+        nbody_lib().AdvanceWorldBatch_GPU(self._h, float(span), C.byref(cfg), max_steps, log.ctypes.data, C.byref(res))
+        made = max((r.steps + r.idle_steps for r in res), default=0)
+        return log[:made].copy(), [r.as_dict() for r in res]
+
     def update_gpu_traced(self, dt, n, every):
         """UpdateWorldBatch_GPU_Traced(_dts): update_gpu(dt, n) that records every member's energy on entry and after every
         `every`-th step; float64 (R, count, 8) like SimBatch.trace."""
@@ -1038,6 +1124,33 @@ class World:
 
     def update_gpu(self, dt, n):
         nbody_lib().UpdateWorld_GPU(self._h, dt, n)
+
+    def _adaptive(self, fn, n, cfg):
+        res, log = NbAdaptiveResult(), np.zeros(n, dtype=np.float32)
+        fn(self._h, n, C.byref(cfg), log.ctypes.data, C.byref(res))
+        return log, res.as_dict()
+
+    def update_gpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False):
+        """UpdateWorld_GPU_Adaptive (include/nbody_adaptive.h): (dt_log float32 (n,), result dict)."""
+        return self._adaptive(nbody_lib().UpdateWorld_GPU_Adaptive, n, adaptive_cfg(eta, dt_max, dt_min, span, prime))
+
+    def update_cpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False):
+        """UpdateWorld_CPU_Adaptive: the same on the host cores."""
+        return self._adaptive(nbody_lib().UpdateWorld_CPU_Adaptive, n, adaptive_cfg(eta, dt_max, dt_min, span, prime))
+
+    def timestep(self, eta, dt_max, dt_min=0.0):
+        """GetWorldTimestep: the criterion alone (no span clip) for the newest state; changes nothing."""
+        cfg, dt = adaptive_cfg(eta, dt_max, dt_min), C.c_float(0.0)
+        nbody_lib().GetWorldTimestep(self._h, C.byref(cfg), C.byref(dt))
+        return float(dt.value)
+
+    def advance_gpu(self, span, eta, dt_max, dt_min=0.0, prime=False, chunk=0, max_steps=4096):
+        """AdvanceWorld_GPU: adaptive calls until `span` is covered (or max_steps steps are made); (dt_log float32 of the
+        steps made, idle ones included, result dict)."""
+        cfg, res = adaptive_cfg(eta, dt_max, dt_min, prime=prime, chunk=chunk), NbAdaptiveResult()
+        log = np.zeros(max_steps, dtype=np.float32)
+        nbody_lib().AdvanceWorld_GPU(self._h, float(span), C.byref(cfg), max_steps, log.ctypes.data, C.byref(res))
+        return log[:res.steps + res.idle_steps].copy(), res.as_dict()
 
     def energy(self):
         """GetWorldEnergy (include/nbody_diag.h) as a dict; "total" = kinetic + potential."""

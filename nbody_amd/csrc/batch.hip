@@ -31,6 +31,8 @@
 #include "diag_sums.h"
 #include "nbody_hip_tuning.h"
 #include "render_common.h"
+#include "timestep.h"
+#include "timestep_common.h"
 
 using namespace nbi;
 
@@ -110,6 +112,12 @@ struct SimBatch {
     int render_mode = 0;                     // tuning hook: 1 = the global path also where the tile path applies
     int render_tile = 0;                     // what the last render did (a bounds call leaves both alone)
     uint32_t render_launches = 0;
+
+    // nb_hip_ensemble_adaptive_steps (kernels: timestep.hip): [count] AdaptState, then the call's log [n][count]; grown on demand
+    void *adapt = nullptr;
+    size_t adapt_bytes = 0;
+    bool adapt_armed = false;   // the records hold a call to continue (NB_ADAPT_CONTINUE)
+    std::vector<char> adapt_host;
 };
 
 namespace {
@@ -664,6 +672,7 @@ void nb_hip_batch_destroy(SimBatch *s) {
         if (s->render_counts) dev_free(s->render_counts);
         if (s->render_rgba) dev_free(s->render_rgba);
         if (s->render_discs) dev_free(s->render_discs);
+        if (s->adapt) dev_free(s->adapt);
         for (auto &e : s->ev_render)
             if (e) ASSERT_HIP(hipEventDestroy(e), "event");
         for (auto &e : s->ev_diag)
@@ -723,6 +732,78 @@ void nb_hip_batch_update(SimBatch *s, uint32_t n, float dt) {
 void nb_hip_batch_update_dts(SimBatch *s, uint32_t n, const float *dt) {
     enqueue(s, n, dt, false);
     nb_hip_batch_sync(s);
+}
+
+// n adaptive steps of every member: per step the criterion launch (one workgroup per member writes dt[b]), then the launches
+// of a one-step update reading the same dt[count]; nothing returns to the host until the one copy at the end.
+void nb_hip_ensemble_adaptive_steps(SimBatch *s, uint32_t n, const NbAdaptive *cfg, float *dt_log, NbAdaptiveResult *out) {
+    const char *what = "nb_hip_ensemble_adaptive_steps";
+    NB_ASSERT(s != nullptr && cfg != nullptr, "%s: NULL argument", what);
+    const char *fault = nb_timestep_cfg_fault(cfg);
+    NB_ASSERT(fault == nullptr, "%s: %s (eta %g, dt_min %g, dt_max %g, span %g)", what, fault, (double)cfg->eta, (double)cfg->dt_min,
+              (double)cfg->dt_max, cfg->span);
+    NB_ASSERT(n <= NB_ADAPT_MAX_STEPS, "%s: %u steps > 2^20 in one call", what, n);
+    NB_ASSERT(!s->ragged, "%s: adaptive steps of ragged ensembles (members of different sizes) are not supported", what);
+    if (n == 0) {
+        if (out) memset(out, 0, (size_t)s->count * sizeof *out);
+        return;
+    }
+    NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
+    use_device();
+    const size_t head = (size_t)s->count * sizeof(nb::AdaptState);
+    const size_t log_bytes = dt_log ? (size_t)n * s->count * sizeof(float) : 0;
+    if (s->adapt_bytes < head + log_bytes) {   // a regrow carries the records over: a continued call goes on from them
+        void *old = s->adapt;
+        s->adapt = dev_alloc_bytes(head + log_bytes);
+        s->adapt_bytes = head + log_bytes;
+        if (old) {
+            ASSERT_HIP(hipMemcpyAsync(s->adapt, old, head, hipMemcpyDeviceToDevice, s->stream), "carry the adaptive-step records over");
+            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before freeing the old adaptive-step buffer");
+            dev_free(old);
+        }
+    }
+    nb::TimestepParams t;
+    memset(&t, 0, sizeof t);
+    t.acc = s->acc;
+    t.radius = s->radius;
+    t.n = s->n;
+    t.stride = s->stride;
+    t.eta = cfg->eta;
+    t.dt_min = cfg->dt_min;
+    t.dt_max = cfg->dt_max;
+    t.span = cfg->span;
+    t.state = static_cast<nb::AdaptState *>(s->adapt);
+    t.dt_out = s->dt_dev;
+    t.commit = 1;
+    float *log = dt_log ? reinterpret_cast<float *>(static_cast<char *>(s->adapt) + head) : nullptr;
+    nb::BatchParams p = step_params(s);
+    if (!(cfg->flags & NB_ADAPT_CONTINUE) || !s->adapt_armed) nb::launch_arm(s->stream, t.state, s->count);
+    s->adapt_armed = true;
+    if (cfg->flags & NB_ADAPT_PRIME) {   // one dt = 0 step of the ordinary path: acc becomes the state's own
+        const float zero = 0.0f;
+        upload_dts(s, &zero, true);
+        launch_steps(s, p, 1);
+    }
+    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+    for (uint32_t i = 0; i < n; i++) {
+        t.log = log ? log + (size_t)i * s->count : nullptr;
+        nb::launch_ensemble_timestep(s->stream, t, s->count);
+        launch_steps(s, p, 1);
+    }
+    ASSERT_HIP(hipGetLastError(), "adaptive ensemble launches (%u members of %u particles, %u steps)", s->count, s->n, n);
+    ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
+    s->timed = true;
+    s->dt_valid = false;   // the device chose the step sizes: the next fixed-step update uploads its own afresh
+    s->adapt_host.resize(head + log_bytes);
+    ASSERT_HIP(hipMemcpyAsync(s->adapt_host.data(), s->adapt, head + log_bytes, hipMemcpyDeviceToHost, s->stream),
+               "D2H of %u x %u step sizes and the results", n, s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after an adaptive ensemble update");
+    for (uint32_t b = 0; out && b < s->count; b++) {
+        nb::AdaptState st;
+        memcpy(&st, s->adapt_host.data() + (size_t)b * sizeof st, sizeof st);
+        out[b] = NbAdaptiveResult{st.t, st.steps, st.idle_steps, st.dt_last, st.dt_smallest};
+    }
+    if (dt_log) memcpy(dt_log, s->adapt_host.data() + head, log_bytes);
 }
 
 double nb_hip_batch_last_ms(SimBatch *s) {

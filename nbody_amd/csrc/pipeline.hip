@@ -10,6 +10,7 @@
 // kernels), launch_shape.hip (launch policy), convert.hip (AoS <-> SoA).
 #include "pipeline_internal.h"
 #include "nbody_hip_tuning.h"
+#include "timestep.h"
 
 using namespace nbi;
 
@@ -102,6 +103,11 @@ void release_device(SimPipeline *s) {
     render_release(s);
     field_release(s);
     gravity_release(s);
+    dev_free(s->adapt);
+    s->adapt = nullptr;
+    s->adapt_cap = 0;
+    s->adapt_armed = false;
+    s->adapt_logged = 0;
     ASSERT_HIP(hipEventDestroy(s->ev_begin), "event");
     ASSERT_HIP(hipEventDestroy(s->ev_end), "event");
     ASSERT_HIP(hipEventDestroy(s->ev_local), "event");
@@ -530,6 +536,49 @@ void PerformSimUpdate(SimPipeline *s, uint32_t n, float dt) {
         }
     }
     nb_hip_sync(s);
+}
+
+// ---- adaptive steps (include/nbody_adaptive.h; kernels: timestep.hip; the launches: step_chain.hip enqueue_adaptive) ----
+
+void nb_hip_adaptive_steps_async(SimPipeline *s, uint32_t n, const NbAdaptive *cfg) {
+    check_adaptive(s, n, cfg, "nb_hip_adaptive_steps_async");
+    enqueue_adaptive(s, n, cfg);
+}
+
+void nb_hip_adaptive_collect(SimPipeline *s, float *dt_log, NbAdaptiveResult *out) {
+    NB_ASSERT(s != nullptr, "nb_hip_adaptive_collect: NULL pipeline");
+    if (out) memset(out, 0, sizeof *out);
+    const uint32_t n = s->adapt_logged;
+    if (n == 0 || !s->on_device) return;
+    use_device();
+    const size_t bytes = ADAPT_HEAD + (dt_log ? (size_t)n * sizeof(float) : 0);
+    s->adapt_host.resize(bytes);
+    ASSERT_HIP(hipMemcpyAsync(s->adapt_host.data(), s->adapt, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u step sizes and the result", n);
+    nb_hip_sync(s);
+    nb::AdaptState st;
+    memcpy(&st, s->adapt_host.data(), sizeof st);
+    if (out) *out = NbAdaptiveResult{st.t, st.steps, st.idle_steps, st.dt_last, st.dt_smallest};
+    if (dt_log) memcpy(dt_log, s->adapt_host.data() + ADAPT_HEAD, (size_t)n * sizeof(float));
+}
+
+void nb_hip_adaptive_steps(SimPipeline *s, uint32_t n, const NbAdaptive *cfg, float *dt_log, NbAdaptiveResult *out) {
+    check_adaptive(s, n, cfg, "nb_hip_adaptive_steps");
+    enqueue_adaptive(s, n, cfg);
+    nb_hip_adaptive_collect(s, dt_log, out);
+}
+
+void nb_hip_timestep(SimPipeline *s, const NbAdaptive *cfg, float *dt) {
+    check_adaptive(s, 1, cfg, "nb_hip_timestep");
+    NB_ASSERT(dt != nullptr, "nb_hip_timestep: NULL result");
+    if (s->slots == 0) {
+        *dt = cfg->dt_max;
+        return;
+    }
+    enqueue_timestep_peek(s, cfg);
+    ASSERT_HIP(hipMemcpyAsync(dt, static_cast<const char *>(s->adapt) + 2 * sizeof(nb::AdaptState), sizeof(float), hipMemcpyDeviceToHost,
+                              s->stream),
+               "D2H of the step size");
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_timestep");
 }
 
 double nb_hip_last_step_ms(SimPipeline *s, uint32_t *launches) {

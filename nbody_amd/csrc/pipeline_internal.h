@@ -15,6 +15,7 @@
 //   render.hip       bounds, count image and RGBA frame of the state a pipeline holds (nb_hip_bounds, nb_hip_render_*)
 //   field.hip        the potential at probe points and as a map over a view (nb_hip_potential_at, nb_hip_potential_map)
 //   gravity.hip      the acceleration at probe points and as a map over a view (nb_hip_acceleration_at, nb_hip_acceleration_map)
+//   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -324,6 +325,14 @@ struct SimPipeline {
     float2 *gravity_acc = nullptr;   // the device result, one float2 per sample
     size_t gravity_acc_cap = 0;
     int gravity_shape = 0;           // tuning hook: 0 auto, 1 source split, 2 one wave per tile
+
+    // adaptive steps (step_chain.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
+    // ADAPT_HEAD bytes of records (the call's AdaptState, the record and result of nb_hip_timestep), then the call's log
+    void *adapt = nullptr;
+    size_t adapt_cap = 0;            // log floats allocated behind the head
+    bool adapt_armed = false;        // the call record holds a call to continue (NB_ADAPT_CONTINUE)
+    uint32_t adapt_logged = 0;       // steps of the last adaptive call: what nb_hip_adaptive_collect copies back
+    std::vector<char> adapt_host;    // where that copy lands
 };
 
 namespace nbi {
@@ -345,6 +354,12 @@ void sharded_step(SimPipeline *s, nb::LaunchShape sh, float dt, hipStream_t cs, 
 // in-place all-gather of a device array of nranks slots through the caller's host transport
 void host_allgather(SimPipeline *s, void *dev_base, size_t bytes_per_rank, hipStream_t st);
 void enqueue_steps(SimPipeline *s, uint32_t n, float dt);  // what PerformSimUpdate / nb_hip_step_async enqueue
+// adaptive steps (include/nbody_hip.h nb_hip_adaptive_steps): per step the criterion launch, then the launches of a one-step
+// call without its dt upload; enqueue only.  check_adaptive aborts on a bad call before anything touches a device.
+constexpr size_t ADAPT_HEAD = 128;   // bytes: AdaptState of the call at 0, of nb_hip_timestep at 32, its result at 64
+void check_adaptive(const SimPipeline *s, uint32_t n, const NbAdaptive *cfg, const char *what);
+void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg);
+void enqueue_timestep_peek(SimPipeline *s, const NbAdaptive *cfg);   // the criterion alone into the head's result slot
 
 // ---- diagnostics.hip -----------------------------------------------------------------------------------------
 

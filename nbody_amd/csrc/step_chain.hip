@@ -9,6 +9,8 @@
 //   * sharded pipelines add the per-step in-place all-gather of the new source positions (RCCL, a local group, or
 //     a caller-supplied host transport), in-stream or overlapped with the own-shard launch.
 #include "pipeline_internal.h"
+#include "timestep.h"
+#include "timestep_common.h"
 
 namespace nbi {
 
@@ -601,6 +603,102 @@ void enqueue_steps(SimPipeline *s, uint32_t n, float dt) {
     if (s->fused_steps) s->timed_launches = (n + CHAIN_MAX_STEPS_PER_LAUNCH - 1) / CHAIN_MAX_STEPS_PER_LAUNCH;
     s->timed_finish_launches = s->last_shape.split > 1 && !fused_finish_applies(s, s->last_shape) ? s->timed_launches : 0;
     s->data.dt = dt;
+}
+
+// ---- adaptive steps ------------------------------------------------------------------------------------------------
+
+void check_adaptive(const SimPipeline *s, uint32_t n, const NbAdaptive *cfg, const char *what) {
+    NB_ASSERT(s != nullptr && cfg != nullptr, "%s: NULL argument", what);
+    const char *fault = nb_timestep_cfg_fault(cfg);
+    NB_ASSERT(fault == nullptr, "%s: %s (eta %g, dt_min %g, dt_max %g, span %g)", what, fault, (double)cfg->eta, (double)cfg->dt_min,
+              (double)cfg->dt_max, cfg->span);
+    NB_ASSERT(n <= NB_ADAPT_MAX_STEPS, "%s: %u steps > 2^20 in one call", what, n);
+    NB_ASSERT(!s->sharded, "%s of a sharded pipeline needs a collective over the ranks: not supported", what);
+    NB_ASSERT(n == 0 || s->on_device, "%s before SetSimulationData", what);
+}
+
+namespace {
+
+// the head and room for `log` step sizes; a regrow carries the head over (a continued call goes on from its records)
+void grow_adapt(SimPipeline *s, size_t log) {
+    if (s->adapt != nullptr && s->adapt_cap >= log) return;
+    void *old = s->adapt;
+    s->adapt_cap = log < 64 ? 64 : log;
+    s->adapt = dev_alloc_bytes(ADAPT_HEAD + s->adapt_cap * sizeof(float));
+    if (old) {
+        ASSERT_HIP(hipMemcpyAsync(s->adapt, old, ADAPT_HEAD, hipMemcpyDeviceToDevice, s->stream), "carry the adaptive-step records over");
+        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before freeing the old adaptive-step buffer");
+        dev_free(old);
+    }
+}
+
+nb::TimestepParams timestep_params(const SimPipeline *s, const NbAdaptive *cfg) {
+    nb::TimestepParams p;
+    memset(&p, 0, sizeof p);
+    p.acc = s->acc;
+    p.radius = s->radius;
+    p.n = s->n_real;
+    p.eta = cfg->eta;
+    p.dt_min = cfg->dt_min;
+    p.dt_max = cfg->dt_max;
+    p.span = cfg->span;
+    return p;
+}
+
+}  // namespace
+
+void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg) {
+    s->adapt_logged = 0;
+    if (s->slots == 0 || n == 0) return;
+    use_device();
+    grow_adapt(s, n);
+    s->pool.used = 0;
+    s->kernel_iv.clear();
+    s->comm_iv.clear();
+    s->detail_steps = 0;
+    s->fused_steps = 0;
+    s->host_current = false;
+    char *head = static_cast<char *>(s->adapt);
+    nb::TimestepParams p = timestep_params(s, cfg);
+    p.state = reinterpret_cast<nb::AdaptState *>(head);
+    p.dt_out = s->dt_dev;
+    p.commit = 1;
+    float *log = reinterpret_cast<float *>(head + ADAPT_HEAD);
+    if (!(cfg->flags & NB_ADAPT_CONTINUE) || !s->adapt_armed) nb::launch_arm(s->stream, p.state, 1);
+    s->adapt_armed = true;
+    const nb::LaunchShape sh = resolve_shape(s);
+    if (cfg->flags & NB_ADAPT_PRIME) {   // one dt = 0 step of the ordinary path: acc becomes the state's own
+        upload_dt(s, 0.0f);
+        launch_step(s, sh, whole_step(s, s->cur, 0.0f), s->stream);
+        s->cur ^= 1;
+    }
+    if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_begin, s->stream), "record begin");
+    for (uint32_t i = 0; i < n; i++) {
+        p.log = log + i;
+        nb::launch_timestep(s->stream, p);
+        launch_step(s, sh, whole_step(s, s->cur, 0.0f), s->stream);   // what a one-step call launches, minus its dt upload
+        s->cur ^= 1;
+    }
+    ASSERT_HIP(hipGetLastError(), "adaptive step launches (%u steps, %u particles)", n, s->n_real);
+    if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_end, s->stream), "record end");
+    s->timed = s->timing != 0;
+    s->timed_launches = n * passes_for(s, whole_step(s, s->cur, 0.0f));
+    s->timed_finish_launches = s->last_shape.split > 1 && !fused_finish_applies(s, s->last_shape) ? s->timed_launches : 0;
+    s->dt_valid = false;   // the device chose the last step size: the next fixed-step call uploads its own afresh
+    s->adapt_logged = n;
+}
+
+void enqueue_timestep_peek(SimPipeline *s, const NbAdaptive *cfg) {
+    use_device();
+    grow_adapt(s, 0);
+    char *head = static_cast<char *>(s->adapt);
+    nb::TimestepParams p = timestep_params(s, cfg);
+    p.state = reinterpret_cast<nb::AdaptState *>(head + sizeof(nb::AdaptState));
+    p.dt_out = reinterpret_cast<float *>(head + 2 * sizeof(nb::AdaptState));
+    p.commit = 0;
+    nb::launch_arm(s->stream, p.state, 1);
+    nb::launch_timestep(s->stream, p);
+    ASSERT_HIP(hipGetLastError(), "timestep_kernel launch (%u particles)", s->n_real);
 }
 
 }  // namespace nbi

@@ -25,8 +25,13 @@
  * follow the same rule (field.hip on the device, field_cpu.c on the host).
  * Extension (include/nbody_gravity.h): GetWorldAccelerationAt /
  * RenderWorldAcceleration likewise (gravity.hip, gravity_cpu.c).
+ * Extension (include/nbody_adaptive.h): adaptive steps.  UpdateWorld_GPU_Adaptive
+ * and AdvanceWorld_GPU follow UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Adaptive
+ * UpdateWorld_CPU's; GetWorldTimestep follows the diagnostics' (timestep.hip on the
+ * device, timestep_cpu.c on the host).
  */
 #include "nbody.h"
+#include "nbody_adaptive.h"
 #include "nbody_diag.h"
 #include "nbody_field.h"
 #include "nbody_gravity.h"
@@ -41,6 +46,7 @@
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
+#include "timestep_common.h"
 #include "world_partition.h"
 
 struct World {
@@ -235,4 +241,69 @@ void RenderWorldAcceleration(World *w, const RenderView *view, float softening, 
         nb_hip_acceleration_map(w->gpu, view, softening, (float *)acc);
     else
         nb_cpu_acceleration_map(w->particles, w->massive, view, softening, acc);
+}
+
+/* ---- include/nbody_adaptive.h ---------------------------------------------------------------------------------------- */
+
+static void check_adaptive_world(const World *w, uint32_t n, const NbAdaptive *cfg, const char *what) {
+    NB_CHECK(w != NULL && cfg != NULL, "%s: NULL argument", what);
+    const char *fault = nb_timestep_cfg_fault(cfg);
+    NB_CHECK(fault == NULL, "%s: %s (eta %g, dt_min %g, dt_max %g, span %g)", what, fault, (double)cfg->eta, (double)cfg->dt_min,
+             (double)cfg->dt_max, cfg->span);
+    NB_CHECK(n <= NB_ADAPT_MAX_STEPS, "%s: %u steps > 2^20 in one call", what, n);
+}
+
+void GetWorldTimestep(World *w, const NbAdaptive *cfg, float *dt) {
+    check_adaptive_world(w, 0, cfg, "GetWorldTimestep");
+    NB_CHECK(dt != NULL, "GetWorldTimestep: NULL argument");
+    if (diag_on_device(w, "GetWorldTimestep"))
+        nb_hip_timestep(w->gpu, cfg, dt);
+    else
+        *dt = nb_cpu_timestep(w->particles, w->count, cfg);
+}
+
+void UpdateWorld_CPU_Adaptive(World *w, uint32_t n, const NbAdaptive *cfg, float *dt_log, NbAdaptiveResult *out) {
+    check_adaptive_world(w, n, cfg, "UpdateWorld_CPU_Adaptive");
+    NbAdaptiveResult r = {0.0, 0, 0, 0.0f, 0.0f};
+    if (n > 0 && (cfg->flags & NB_ADAPT_PRIME)) UpdateWorld_CPU(w, 0.0f, 1);
+    for (uint32_t i = 0; i < n; i++) {
+        float dt;
+        GetWorldTimestep(w, cfg, &dt);
+        dt = nb_timestep_clip(dt, cfg->span, &r.elapsed);
+        nb_timestep_count(dt, &r.steps, &r.idle_steps, &r.dt_last, &r.dt_smallest);
+        UpdateWorld_CPU(w, dt, 1);
+        if (dt_log) dt_log[i] = dt;
+    }
+    if (out) *out = r;
+}
+
+void UpdateWorld_GPU_Adaptive(World *w, uint32_t n, const NbAdaptive *cfg, float *dt_log, NbAdaptiveResult *out) {
+    check_adaptive_world(w, n, cfg, "UpdateWorld_GPU_Adaptive");
+    NB_CHECK(w->nranks <= 1, "UpdateWorld_GPU_Adaptive of a sharded pipeline needs a collective over the ranks: not supported");
+    if (out) memset(out, 0, sizeof *out);
+    if (n == 0) return;
+    push_if_stale(w);
+    nb_hip_adaptive_steps(w->gpu, n, cfg, dt_log, out);
+    w->device_is_newer = true;
+}
+
+void AdvanceWorld_GPU(World *w, double span, const NbAdaptive *cfg, uint32_t max_steps, float *dt_log, NbAdaptiveResult *out) {
+    NB_CHECK(cfg != NULL, "AdvanceWorld_GPU: NULL argument");
+    NbAdaptive c = *cfg;
+    c.span = span;
+    c.flags &= ~NB_ADAPT_CONTINUE;   /* an advance starts its own clock; its inner calls then continue it on the device */
+    check_adaptive_world(w, max_steps, &c, "AdvanceWorld_GPU");
+    NB_CHECK(w->nranks <= 1, "AdvanceWorld_GPU of a sharded pipeline needs a collective over the ranks: not supported");
+    const uint32_t chunk = cfg->chunk ? cfg->chunk : 64u;
+    NbAdaptiveResult total = {0.0, 0, 0, 0.0f, 0.0f};
+    uint32_t done = 0, next = 1;
+    while (done < max_steps && total.elapsed < span) {
+        const uint32_t k = next < max_steps - done ? next : max_steps - done;
+        UpdateWorld_GPU_Adaptive(w, k, &c, dt_log ? dt_log + done : NULL, &total);   /* cumulative: the device keeps the clock */
+        c.flags = (c.flags & ~NB_ADAPT_PRIME) | NB_ADAPT_CONTINUE;
+        done += k;
+        const double left = total.dt_last > 0.0f ? floor((span - total.elapsed) / (double)total.dt_last) : 1.0;
+        next = left < 1.0 ? 1u : left > (double)chunk ? chunk : (uint32_t)left;
+    }
+    if (out) *out = total;
 }

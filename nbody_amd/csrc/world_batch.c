@@ -14,7 +14,10 @@
  * include/nbody_batch_ragged.h: CreateWorldBatchRagged makes a batch whose members differ in size over nb_hip_ragged_create;
  * the array is then packed (member b at offset[b]), which is all the protocol above needs to know -- a uniform batch is
  * the case offset[b] = b * size.  The render calls are not wired for such a batch and abort.
+ * include/nbody_adaptive.h: UpdateWorldBatch_GPU_Adaptive / AdvanceWorldBatch_GPU are updates whose step sizes the device
+ * chooses per member and step: same upload, same coherence; ragged batches abort.
  */
+#include "nbody_adaptive.h"
 #include "nbody_batch.h"
 #include "nbody_batch_diag.h"
 #include "nbody_batch_ragged.h"
@@ -27,6 +30,7 @@
 #include "diag_sums.h"
 #include "nb_util.h"
 #include "render_common.h"
+#include "timestep_common.h"
 #include "world_partition.h"
 
 struct WorldBatch {
@@ -228,4 +232,56 @@ void RenderWorldBatch(WorldBatch *w, const RenderView *views, const RenderPalett
     const size_t frame = (size_t)views[0].width * views[0].height * 4;
     for (uint32_t b = 0; b < w->count; b++)
         nb_cpu_render_rgba(w->particles + (size_t)b * w->size, w->size, views + b, &pal, rgba + (size_t)b * frame);
+}
+
+/* ---- include/nbody_adaptive.h ---------------------------------------------------------------------------------------- */
+
+static void check_adaptive_batch(const WorldBatch *w, uint32_t n, const NbAdaptive *cfg, const char *what) {
+    NB_CHECK(w != NULL && cfg != NULL, "%s: NULL argument", what);
+    const char *fault = nb_timestep_cfg_fault(cfg);
+    NB_CHECK(fault == NULL, "%s: %s (eta %g, dt_min %g, dt_max %g, span %g)", what, fault, (double)cfg->eta, (double)cfg->dt_min,
+             (double)cfg->dt_max, cfg->span);
+    NB_CHECK(n <= NB_ADAPT_MAX_STEPS, "%s: %u steps > 2^20 in one call", what, n);
+    NB_CHECK(!w->ragged, "%s: adaptive steps of ragged ensembles (members of different sizes) are not supported", what);
+}
+
+void UpdateWorldBatch_GPU_Adaptive(WorldBatch *w, uint32_t n, const NbAdaptive *cfg, float *dt_log, NbAdaptiveResult *out) {
+    check_adaptive_batch(w, n, cfg, "UpdateWorldBatch_GPU_Adaptive");
+    if (out) memset(out, 0, (size_t)w->count * sizeof *out);
+    if (n == 0) return;
+    push_once(w);
+    nb_hip_ensemble_adaptive_steps(w->gpu, n, cfg, dt_log, out);
+    w->device_is_newer = true;
+}
+
+void AdvanceWorldBatch_GPU(WorldBatch *w, double span, const NbAdaptive *cfg, uint32_t max_steps, float *dt_log, NbAdaptiveResult *out) {
+    NB_CHECK(cfg != NULL, "AdvanceWorldBatch_GPU: NULL argument");
+    NbAdaptive c = *cfg;
+    c.span = span;
+    c.flags &= ~NB_ADAPT_CONTINUE;   /* an advance starts its own clocks; its inner calls then continue them on the device */
+    check_adaptive_batch(w, max_steps, &c, "AdvanceWorldBatch_GPU");
+    const uint32_t chunk = cfg->chunk ? cfg->chunk : 64u;
+    NbAdaptiveResult *total = NB_NEW(w->count, NbAdaptiveResult);
+    NB_CHECK(total != NULL, "Failed to alloc the results of %u members", w->count);
+    memset(total, 0, (size_t)w->count * sizeof *total);
+    uint32_t done = 0, next = 1;
+    bool unfinished = true;
+    while (done < max_steps && unfinished) {
+        const uint32_t k = next < max_steps - done ? next : max_steps - done;
+        /* cumulative per member: the device keeps every member's clock, a finished member takes idle steps */
+        UpdateWorldBatch_GPU_Adaptive(w, k, &c, dt_log ? dt_log + (size_t)done * w->count : NULL, total);
+        c.flags = (c.flags & ~NB_ADAPT_PRIME) | NB_ADAPT_CONTINUE;
+        done += k;
+        double want = 1.0;
+        unfinished = false;
+        for (uint32_t b = 0; b < w->count; b++) {
+            if (!(total[b].elapsed < span)) continue;
+            unfinished = true;
+            const double left = total[b].dt_last > 0.0f ? floor((span - total[b].elapsed) / (double)total[b].dt_last) : 1.0;
+            if (left > want) want = left;
+        }
+        next = want > (double)chunk ? chunk : (uint32_t)want;
+    }
+    if (out) memcpy(out, total, (size_t)w->count * sizeof *out);
+    free(total);
 }
