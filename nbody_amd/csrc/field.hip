@@ -1,28 +1,36 @@
-// field.hip -- the potential of the state a pipeline holds at points that are not particles: probes the caller chooses and
-// the pixel centres of a view (include/nbody_field.h; nb_hip_potential_at / nb_hip_potential_map).
+// field.hip -- two fields of the state a pipeline holds at points that are not particles: probes the caller chooses and the
+// pixel centres of a view.  The potential (include/nbody_field.h; nb_hip_potential_at / nb_hip_potential_map) and the
+// acceleration (include/nbody_gravity.h; nb_hip_acceleration_at / nb_hip_acceleration_map) are one sampler with two pair
+// statements.
 //
-// Definitions (also in include/nbody_field.h and DESIGN.md section 3): for a sample p and a softening s
-//     Phi(p; s) = - sum_{j < M} G*m_j / sqrt(|x_j - p|^2 + s),      G*m_j = src_gm[j], M = mass_len
-// = diagnostics.hip's Phi_i of a massless receiver at p with radius s.  A sample is never a source, so no term is excluded
-// and only the unmasked pair statement runs.
+// Definitions (also in the two headers and DESIGN.md section 3): for a sample p and a softening s, with G*m_j = src_gm[j],
+// M = mass_len and d_j = x_j - p,
+//     Phi(p; s) = - sum_{j < M} G*m_j / sqrt(|d_j|^2 + s)          = diagnostics.hip's Phi_i of a massless receiver at p
+//     g(p; s)   =   sum_{j < M} G*m_j d_j / (|d_j|^2 + s)^(3/2)    = what a step stores in acc[] for such a receiver
+// both with radius s.  A sample is never a source, so no term is excluded: Phi runs the unmasked pair statement only, and a
+// sample exactly on a source gets d_j = 0 over a finite denominator in g, a zero term.
 //
-// The arithmetic is diag_common.h's and nothing else: the pair statement, the fp32 sum over a block of 256 sources with j
-// ascending, float64 totals per block, and the eight source slices [w * per, (w + 1) * per) added in wave order from 0.0.
-// A result is defined by that order, not by which wave adds what, so the two kernels below give the same bits, and both
-// give the bits potential_kernel gives a massless particle of radius s at the same place:
-//   field_split_kernel   potential_kernel's shape: the 8 waves of a workgroup share one tile of 128 samples (64 lanes x 2)
-//                        and each walks 1/8 of the source blocks; the slices meet in part[W][TILE] (LDS).  For large M.
-//   field_wave_kernel    ensemble_phi_kernel's shape: every wave owns a tile and walks the whole source list itself
-//                        (tile_potential over ScalarSources, with rb = M so that the masked segment of every block is
-//                        empty).  No LDS, no barrier.  For small worlds under large images, where the split's workgroups
-//                        are mostly waves without a block (7 of 8 at M <= 256) and the tiles alone fill the chip.
+// What differs between the two is the quantity policy Q (Potential, Acceleration): the pair statement behind one block of
+// sources, the number of components and the store.  The summation is written once, and it is diag_common.h's: fp32 sums
+// from 0.0f over a block of 256 sources with j ascending, float64 totals per block, and the eight source slices
+// [w * per, (w + 1) * per), per = ceil(ceil(M / 256) / 8), added in wave order from 0.0, each component rounded once to
+// float32.  A result is defined by that order, not by which wave adds what, so the two kernels below give the same bits
+// (and Phi the bits potential_kernel gives a massless particle of radius s at the same place):
+//   sample_split_kernel  potential_kernel's shape: the 8 waves of a workgroup share one tile of 128 samples (64 lanes x 2)
+//                        and each walks 1/8 of the source blocks; the slices meet in part[C][W][TILE] (LDS, float64).
+//                        For large M.
+//   sample_wave_kernel   ensemble_phi_kernel's shape: every wave owns a tile and walks the eight slices itself.  No LDS, no
+//                        barrier.  For small worlds under large images, where the split's workgroups are mostly waves
+//                        without a block (7 of 8 at M <= 256) and the tiles alone fill the chip.
 // pick_wave_shape() below chooses between them, in one place.  Sources stay on the scalar-cache route in both (wave-uniform,
-// s_load_dwordx16 / x8).  MAP = true: a lane forms its two samples from the view's column and row coordinates (sample
-// i = py * width + px reads xs[px] and ys[py]; the host computed both arrays, render_common.h); MAP = false: it loads them.
-// A sample with a non-finite coordinate stores NaN.  No atomics; vector stores only.
+// s_load_dwordx16 / x8, 8 per fetch, single sources for a ragged end).  MAP = true: a lane forms its two samples from the
+// view's column and row coordinates (sample i = py * width + px reads xs[px] and ys[py]; the host computed both arrays,
+// render_common.h); MAP = false: it loads them.  A sample with a non-finite coordinate stores NaN in every component.  No
+// atomics; vector stores only, one per sample.
 #include "pipeline_internal.h"
 #include "diag_common.h"
 #include "field_common.h"
+#include "interaction_asm.h"
 #include "nbody_hip_tuning.h"
 
 #include <math.h>
@@ -32,9 +40,9 @@ namespace field {
 
 using namespace nbd;
 
-constexpr int WAVES_MAX = 4;   // field_wave_kernel: tiles (waves) per workgroup
+constexpr int WAVES_MAX = 4;   // sample_wave_kernel: tiles (waves) per workgroup
 
-struct FieldParams {
+struct Params {
     const float2 *pos;     // pos[cur]: the latest state
     const float *src_gm;   // G * m_j, j < n_src
     uint32_t n_src;        // sources [0, M)
@@ -42,12 +50,68 @@ struct FieldParams {
     uint32_t n;            // samples
     uint32_t width;        // map only
     float soft;
-    float *phi;            // Phi of sample i, i < n
+    void *out;             // Q::Out of sample i, i < n
 };
+
+// Phi: diag_common.h's unmasked pair with the softening as every sample's radius
+struct Potential {
+    static constexpr int C = 1;
+    typedef float Out;
+    static constexpr const char *NOUN = "field";
+    static constexpr int SimPipeline::*SHAPE = &SimPipeline::field_shape;
+
+    // sources [j0, j1) of one block added to a[0][]
+    static __device__ __forceinline__ void block(float (&a)[C][K], const float (&px)[K], const float (&py)[K], float s, ConstF sp,
+                                                 ConstF sg, uint32_t j0, uint32_t j1) {
+        float r[K];
+        uint32_t ri[K];
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            r[k] = s;
+            ri[k] = 0;   // read by the masked body only
+        }
+        block_sum<false>(a[0], px, py, r, ri, sp, sg, j0, j1);
+    }
+    static __device__ __forceinline__ Out result(const double (&sum)[C]) { return (float)-sum[0]; }
+    static __device__ __forceinline__ Out nan() { return __builtin_nanf(""); }
+};
+
+// g: the step kernels' own statement (interaction_asm.h NB_INTERACTION2_ASM: the lane's two samples against one wave-uniform
+// source, both v_rsq_f32 inside one raised-priority window) with r0 = r1 = s
+struct Acceleration {
+    static constexpr int C = 2;
+    typedef float2 Out;
+    static constexpr const char *NOUN = "gravity";
+    static constexpr int SimPipeline::*SHAPE = &SimPipeline::gravity_shape;
+
+    static __device__ __forceinline__ void pair2(float (&a)[C][K], const float (&px)[K], const float (&py)[K], float s, float sx, float sy,
+                                                 float g) {
+        asm(NB_INTERACTION2_ASM
+            : [ax0] "+v"(a[0][0]), [ay0] "+v"(a[1][0]), [ax1] "+v"(a[0][1]), [ay1] "+v"(a[1][1])
+            : [sx] "s"(sx), [sy] "s"(sy), [g] "s"(g), [px0] "v"(px[0]), [py0] "v"(py[0]), [r0] "v"(s), [px1] "v"(px[1]), [py1] "v"(py[1]),
+              [r1] "v"(s)
+            : NB_CLOBBERS2);
+    }
+    // sources [j0, j1) of one block added to a[0][] (x) and a[1][] (y): the walk of diag_common.h's block_sum, one register set
+    static __device__ __forceinline__ void block(float (&a)[C][K], const float (&px)[K], const float (&py)[K], float s, ConstF sp,
+                                                 ConstF sg, uint32_t j0, uint32_t j1) {
+        uint32_t j = j0;
+        for (; j + 8 <= j1; j += 8) {
+            const v16f P = cload<v16f>(sp + 2 * (size_t)j);
+            const v8f G = cload<v8f>(sg + j);
+#pragma unroll
+            for (int u = 0; u < 8; u++) pair2(a, px, py, s, P[2 * u], P[2 * u + 1], G[u]);
+        }
+        for (; j < j1; j++) pair2(a, px, py, s, sp[2 * (size_t)j], sp[2 * (size_t)j + 1], sg[j]);
+    }
+    static __device__ __forceinline__ Out result(const double (&sum)[C]) { return make_float2((float)sum[0], (float)sum[1]); }
+    static __device__ __forceinline__ Out nan() { return make_float2(__builtin_nanf(""), __builtin_nanf("")); }
+};
+static_assert(K == 2, "NB_INTERACTION2_ASM is the statement for two samples per lane");
 
 // the K samples of this lane: tile rows lane and lane + 64; tail lanes redo the last sample, their results are dropped
 template <bool MAP>
-__device__ __forceinline__ void load_samples(const FieldParams &p, uint32_t rb, uint32_t lane, float (&px)[K], float (&py)[K]) {
+__device__ __forceinline__ void load_samples(const Params &p, uint32_t rb, uint32_t lane, float (&px)[K], float (&py)[K]) {
 #pragma unroll
     for (int k = 0; k < K; k++) {
         uint32_t i = rb + k * WAVE + lane;
@@ -64,85 +128,109 @@ __device__ __forceinline__ void load_samples(const FieldParams &p, uint32_t rb, 
     }
 }
 
-__device__ __forceinline__ void store_sample(const FieldParams &p, uint32_t i, float x, float y, double sum) {
+template <typename Q>
+__device__ __forceinline__ void store_sample(const Params &p, uint32_t i, float x, float y, const double (&sum)[Q::C]) {
     if (i >= p.n) return;
     const bool finite = nb_render_finite(x) && nb_render_finite(y);
-    p.phi[i] = finite ? (float)-sum : __builtin_nanf("");
+    const typename Q::Out v = Q::result(sum);
+    static_cast<typename Q::Out *>(p.out)[i] = finite ? v : Q::nan();
 }
 
-// 512 threads, at most 64 VGPRs (8 waves per SIMD: four workgroups per CU), as potential_kernel.
-template <bool MAP>
-__global__ __launch_bounds__(WAVE * W, 8) void field_split_kernel(const FieldParams p) {
+// slice w of the W source slices, in whole blocks: [b_lo, b_hi) added to the float64 sums s[][] (from whatever they hold),
+// one fp32 block sum at a time
+template <typename Q>
+__device__ __forceinline__ void slice_sum(double (&s)[Q::C][K], const float (&px)[K], const float (&py)[K], const Params &p, uint32_t w) {
+    const uint32_t nblocks = (p.n_src + BLOCK - 1) / BLOCK;
+    const uint32_t per = (nblocks + W - 1) / W;
+    const uint32_t b_lo = min(w * per, nblocks);
+    const uint32_t b_hi = min(b_lo + per, nblocks);
+    const ConstF sp = (ConstF)(uintptr_t)p.pos, sg = (ConstF)(uintptr_t)p.src_gm;
+    float a[Q::C][K];
+#pragma unroll
+    for (int k = 0; k < K; k++)
+        for (int c = 0; c < Q::C; c++) a[c][k] = 0.0f;
+#pragma unroll 1
+    for (uint32_t b = b_lo; b < b_hi; b++) {
+        const uint32_t j0 = b * BLOCK, j1 = min(j0 + BLOCK, p.n_src);
+        Q::block(a, px, py, p.soft, sp, sg, j0, j1);
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            for (int c = 0; c < Q::C; c++) {
+                s[c][k] += (double)a[c][k];
+                a[c][k] = 0.0f;
+            }
+    }
+}
+
+// 512 threads, at most 64 VGPRs (8 waves per SIMD: four workgroups per CU, 8 KiB of LDS each per component), as
+// potential_kernel.
+template <typename Q, bool MAP>
+__global__ __launch_bounds__(WAVE * W, 8) void sample_split_kernel(const Params p) {
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & (WAVE - 1);
     const uint32_t wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t rb = blockIdx.x * TILE;  // first sample of the tile
 
-    float px[K], py[K], r[K], a[K];
-    uint32_t ri[K];
-    double s[K];
+    float px[K], py[K];
+    double s[Q::C][K];
     load_samples<MAP>(p, rb, lane, px, py);
 #pragma unroll
-    for (int k = 0; k < K; k++) {
-        r[k] = p.soft;
-        ri[k] = 0;       // read by the masked body only
-        a[k] = 0.0f;
-        s[k] = 0.0;
-    }
+    for (int k = 0; k < K; k++)
+        for (int c = 0; c < Q::C; c++) s[c][k] = 0.0;
+    slice_sum<Q>(s, px, py, p, wid);
 
-    // this wave's slice of the sources, in whole blocks
-    const uint32_t nblocks = (p.n_src + BLOCK - 1) / BLOCK;
-    const uint32_t per_wave = (nblocks + W - 1) / W;
-    const uint32_t b_lo = min(wid * per_wave, nblocks);
-    const uint32_t b_hi = min(b_lo + per_wave, nblocks);
-    const ConstF sp = (ConstF)(uintptr_t)p.pos, sg = (ConstF)(uintptr_t)p.src_gm;
-    for (uint32_t b = b_lo; b < b_hi; b++) {
-        const uint32_t j0 = b * BLOCK, j1 = min(j0 + BLOCK, p.n_src);
-        block_sum<false>(a, px, py, r, ri, sp, sg, j0, j1);
+    // the W slices in wave order (float64); thread t of the first two waves holds sample rb + t's coordinates in slot
+    // t / 64 of lane t % 64, which is its own slot k = wid
+    __shared__ double part[Q::C][W][TILE];
 #pragma unroll
-        for (int k = 0; k < K; k++) {
-            s[k] += (double)a[k];
-            a[k] = 0.0f;
-        }
-    }
-
-    // the W slices in wave order (float64), then Phi = -sum; thread t of the first two waves holds sample rb + t's
-    // coordinates in slot t / 64 of lane t % 64, which is its own slot k = wid
-    __shared__ double part[W][TILE];
-#pragma unroll
-    for (int k = 0; k < K; k++) part[wid][k * WAVE + lane] = s[k];
+    for (int k = 0; k < K; k++)
+        for (int c = 0; c < Q::C; c++) part[c][wid][k * WAVE + lane] = s[c][k];
     __syncthreads();
     if (tid < TILE) {
-        double sum = 0.0;
+        double sum[Q::C];
 #pragma unroll
-        for (int w = 0; w < W; w++) sum += part[w][tid];
-        store_sample(p, rb + tid, wid ? px[1] : px[0], wid ? py[1] : py[0], sum);
+        for (int c = 0; c < Q::C; c++) sum[c] = 0.0;
+#pragma unroll
+        for (int w = 0; w < W; w++)
+            for (int c = 0; c < Q::C; c++) sum[c] += part[c][w][tid];
+        store_sample<Q>(p, rb + tid, wid ? px[1] : px[0], wid ? py[1] : py[0], sum);
     }
 }
-static_assert(K == 2, "field_split_kernel's finishing threads pick their sample by wave index 0 / 1");
+static_assert(K == 2, "sample_split_kernel's finishing threads pick their sample by wave index 0 / 1");
 
 // 1..4 waves, one tile each, at most 64 VGPRs.
-template <bool MAP>
-__global__ __launch_bounds__(WAVE * WAVES_MAX, 8) void field_wave_kernel(const FieldParams p) {
+template <typename Q, bool MAP>
+__global__ __launch_bounds__(WAVE * WAVES_MAX, 8) void sample_wave_kernel(const Params p) {
     const uint32_t lane = threadIdx.x & (WAVE - 1);
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t rb = (blockIdx.x * WAVES_MAX + wid) * TILE;   // first sample of this wave's tile
     if (rb >= p.n) return;
 
-    float px[K], py[K], r[K];
-    uint32_t ri[K];
+    float px[K], py[K];
+    double sum[Q::C][K];
     load_samples<MAP>(p, rb, lane, px, py);
 #pragma unroll
-    for (int k = 0; k < K; k++) {
-        r[k] = p.soft;
-        ri[k] = 0;
-    }
-    // the eight source slices of the split kernel's waves, one after another; a tile that starts at M holds no source, so
-    // every block runs unmasked as a whole
-    double sum[K];
-    tile_potential(sum, px, py, r, ri, p.n_src, p.n_src, ScalarSources{(ConstF)(uintptr_t)p.pos, (ConstF)(uintptr_t)p.src_gm});
+    for (int k = 0; k < K; k++)
+        for (int c = 0; c < Q::C; c++) sum[c][k] = 0.0;
+    // the eight source slices of the split kernel's waves, one after another
+#pragma unroll 1
+    for (uint32_t w = 0; w < W; w++) {
+        double s[Q::C][K];
 #pragma unroll
-    for (int k = 0; k < K; k++) store_sample(p, rb + k * WAVE + lane, px[k], py[k], sum[k]);
+        for (int k = 0; k < K; k++)
+            for (int c = 0; c < Q::C; c++) s[c][k] = 0.0;
+        slice_sum<Q>(s, px, py, p, w);
+#pragma unroll
+        for (int k = 0; k < K; k++)
+            for (int c = 0; c < Q::C; c++) sum[c][k] += s[c][k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        double t[Q::C];
+#pragma unroll
+        for (int c = 0; c < Q::C; c++) t[c] = sum[c][k];
+        store_sample<Q>(p, rb + k * WAVE + lane, px[k], py[k], t);
+    }
 }
 
 }  // namespace field
@@ -155,70 +243,100 @@ namespace fd = nb::field;
 
 // The one place that picks the kernel shape.  One wave per tile pays when both hold: the world has at most 2 blocks of 256
 // sources (most of a split workgroup's 8 waves would walk nothing) and there are enough tiles to fill the chip with one
-// wave each.  Measured (tools/field_probe.py, profiles/r12_field_probe.json; wave / split device time): at 1280 x 720
-// (7 200 tiles) 0.51 - 0.55 at 1 block, 0.80 at 2, 1.12 - 1.19 from 4 blocks up; at 256 x 256 (512 tiles, a sixteenth of
-// the chip's 8 192 wave slots) the split is ahead at every M, by 1.05 - 1.06 at 1 block and 1.8 - 3.8 beyond.  3 blocks
-// and tile counts between 512 and 7 200 are not measured: the rule keeps the split there, and puts the tile bound at half
-// the wave slots.
+// wave each.  Measured for the Phi pair (tools/field_probe.py, profiles/r12_field_probe.json; wave / split device time): at
+// 1280 x 720 (7 200 tiles) 0.51 - 0.55 at 1 block, 0.80 at 2, 1.12 - 1.19 from 4 blocks up; at 256 x 256 (512 tiles, a
+// sixteenth of the chip's 8 192 wave slots) the split is ahead at every M, by 1.05 - 1.06 at 1 block and 1.8 - 3.8 beyond.
+// 3 blocks and tile counts between 512 and 7 200 are not measured: the rule keeps the split there, and puts the tile bound
+// at half the wave slots.  The g pair (10 VALU instructions per pair against the Phi pair's 6) inherited both thresholds;
+// measured since (tools/gravity_probe.py, profiles/r13_gravity_probe.json): at 1280 x 720 0.54 - 0.59 at 1 block, 0.85 at 2,
+// 0.97 at 3, 1.11 - 1.16 from 4 blocks up; at 256 x 256 the split is ahead at every M, 1.03 - 1.04 at 1 block and 1.76 - 3.58
+// beyond.  The same crossover, so one pair of thresholds serves both.
 constexpr uint32_t WAVE_SHAPE_BLOCKS_MAX = 2;
 constexpr uint32_t WAVE_SHAPE_TILES_MIN = 4096;
 
-bool pick_wave_shape(const SimPipeline *s, uint32_t tiles) {
-    if (s->field_shape) return s->field_shape == 2;
-    const uint32_t nblocks = (s->data.mass_len + nbd::BLOCK - 1) / nbd::BLOCK;
+bool pick_wave_shape(int shape_knob, uint32_t mass_len, uint32_t tiles) {
+    if (shape_knob) return shape_knob == 2;
+    const uint32_t nblocks = (mass_len + nbd::BLOCK - 1) / nbd::BLOCK;
     return nblocks <= WAVE_SHAPE_BLOCKS_MAX && tiles >= WAVE_SHAPE_TILES_MIN;
 }
 
-template <typename T>
-void grow(SimPipeline *s, T *&buf, size_t &cap, size_t need, const char *what) {
+void grow(SimPipeline *s, float *&buf, size_t &cap, size_t need, const char *noun, const char *what) {
     if (cap >= need && buf) return;
     if (buf) {
-        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the %s", what);
+        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the %s %s", noun, what);
         dev_free(buf);
     }
-    buf = dev_alloc<T>(need);
+    buf = dev_alloc<float>(need);
     cap = need;
 }
 
-template <bool MAP>
-void launch(SimPipeline *s, const fd::FieldParams &p) {
+template <typename Q, bool MAP>
+void launch(SimPipeline *s, const fd::Params &p) {
     const uint32_t tiles = (p.n + nbd::TILE - 1) / nbd::TILE;
-    if (pick_wave_shape(s, tiles))
-        hipLaunchKernelGGL(fd::field_wave_kernel<MAP>, dim3((tiles + fd::WAVES_MAX - 1) / fd::WAVES_MAX), dim3(nbd::WAVE * fd::WAVES_MAX), 0,
-                           s->stream, p);
+    if (pick_wave_shape(s->*Q::SHAPE, p.n_src, tiles))
+        hipLaunchKernelGGL((fd::sample_wave_kernel<Q, MAP>), dim3((tiles + fd::WAVES_MAX - 1) / fd::WAVES_MAX),
+                           dim3(nbd::WAVE * fd::WAVES_MAX), 0, s->stream, p);
     else
-        hipLaunchKernelGGL(fd::field_split_kernel<MAP>, dim3(tiles), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
-    ASSERT_HIP(hipGetLastError(), "field kernel launch (%u samples, %u sources)", p.n, p.n_src);
+        hipLaunchKernelGGL((fd::sample_split_kernel<Q, MAP>), dim3(tiles), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
+    ASSERT_HIP(hipGetLastError(), "%s kernel launch (%u samples, %u sources)", Q::NOUN, p.n, p.n_src);
 }
 
 // upload `in_floats` floats, evaluate n samples, one copy of the result, one sync; `in` stays alive until the sync
-void run_field(SimPipeline *s, bool map, const float *in, size_t in_floats, uint32_t n, uint32_t width, float softening, float *phi) {
+template <typename Q>
+void run(SimPipeline *s, bool map, const float *in, size_t in_floats, uint32_t n, uint32_t width, float softening, typename Q::Out *out) {
     use_device();
-    grow(s, s->field_in, s->field_in_cap, in_floats, "field samples");
-    grow(s, s->field_phi, s->field_phi_cap, (size_t)n, "field result");
-    ASSERT_HIP(hipMemcpyAsync(s->field_in, in, in_floats * sizeof(float), hipMemcpyHostToDevice, s->stream), "H2D of the field samples");
-    fd::FieldParams p{};
+    grow(s, s->sample_in, s->sample_in_cap, in_floats, Q::NOUN, "samples");
+    grow(s, s->sample_out, s->sample_out_cap, (size_t)n * Q::C, Q::NOUN, "result");
+    ASSERT_HIP(hipMemcpyAsync(s->sample_in, in, in_floats * sizeof(float), hipMemcpyHostToDevice, s->stream), "H2D of the %s samples", Q::NOUN);
+    fd::Params p{};
     p.pos = s->pos[s->cur];
     p.src_gm = s->src_gm;
     p.n_src = s->data.mass_len;
-    p.in = s->field_in;
+    p.in = s->sample_in;
     p.n = n;
     p.width = width;
     p.soft = softening;
-    p.phi = s->field_phi;
+    p.out = s->sample_out;
     begin_diag(s);
     if (map)
-        launch<true>(s, p);
+        launch<Q, true>(s, p);
     else
-        launch<false>(s, p);
+        launch<Q, false>(s, p);
     end_diag(s);
-    ASSERT_HIP(hipMemcpyAsync(phi, s->field_phi, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u potentials", n);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after the field kernel");
+    ASSERT_HIP(hipMemcpyAsync(out, s->sample_out, (size_t)n * sizeof(typename Q::Out), hipMemcpyDeviceToHost, s->stream),
+               "D2H of %u %s results", n, Q::NOUN);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after the %s kernel", Q::NOUN);
 }
 
-void check_field(float softening, uint64_t samples) {
+void check(const char *noun, float softening, uint64_t samples) {
     const char *fault = nb_field_fault(softening, samples);
-    NB_ASSERT(fault == nullptr, "invalid field call (softening %g, %llu points): %s", (double)softening, (unsigned long long)samples, fault);
+    NB_ASSERT(fault == nullptr, "invalid %s call (softening %g, %llu points): %s", noun, (double)softening, (unsigned long long)samples, fault);
+}
+
+template <typename Q>
+void sample_at(SimPipeline *s, const char *what, const float *points, uint32_t n, float softening, typename Q::Out *out) {
+    check_diag(s, what);
+    check(Q::NOUN, softening, n);
+    NB_ASSERT((points != nullptr && out != nullptr) || n == 0, "NULL points or result");
+    if (n == 0) {
+        s->diag_timed = false;
+        return;
+    }
+    run<Q>(s, false, points, (size_t)n * 2, n, 0, softening, out);
+}
+
+// a map is the probes product at the view's pixel centres: width column coordinates, then height row coordinates
+template <typename Q>
+void sample_map(SimPipeline *s, const char *what, const RenderView *view, float softening, typename Q::Out *out) {
+    check_diag(s, what);
+    NB_ASSERT(view != nullptr, "NULL RenderView");
+    const char *fault = nb_render_view_fault(view);
+    NB_ASSERT(fault == nullptr, "invalid RenderView (%u x %u, zoom %g): %s", view->width, view->height, (double)view->zoom, fault);
+    check(Q::NOUN, softening, (uint64_t)view->width * view->height);
+    NB_ASSERT(out != nullptr, "NULL %s map", Q::NOUN);
+    std::vector<float> coords((size_t)view->width + view->height);
+    nb_render_pixel_centres(view, coords.data(), coords.data() + view->width);
+    run<Q>(s, true, coords.data(), coords.size(), view->width * view->height, view->width, softening, out);
 }
 
 }  // namespace
@@ -226,10 +344,10 @@ void check_field(float softening, uint64_t samples) {
 namespace nbi {
 
 void field_release(SimPipeline *s) {
-    dev_free(s->field_in);
-    dev_free(s->field_phi);
-    s->field_in = s->field_phi = nullptr;
-    s->field_in_cap = s->field_phi_cap = 0;
+    dev_free(s->sample_in);
+    dev_free(s->sample_out);
+    s->sample_in = s->sample_out = nullptr;
+    s->sample_in_cap = s->sample_out_cap = 0;
 }
 
 }  // namespace nbi
@@ -237,26 +355,19 @@ void field_release(SimPipeline *s) {
 extern "C" {
 
 void nb_hip_potential_at(SimPipeline *s, const float *points, uint32_t n, float softening, float *phi) {
-    check_diag(s, "nb_hip_potential_at");
-    check_field(softening, n);
-    NB_ASSERT((points != nullptr && phi != nullptr) || n == 0, "NULL points or phi");
-    if (n == 0) {
-        s->diag_timed = false;
-        return;
-    }
-    run_field(s, false, points, (size_t)n * 2, n, 0, softening, phi);
+    sample_at<fd::Potential>(s, "nb_hip_potential_at", points, n, softening, phi);
 }
 
 void nb_hip_potential_map(SimPipeline *s, const RenderView *view, float softening, float *phi) {
-    check_diag(s, "nb_hip_potential_map");
-    NB_ASSERT(view != nullptr, "NULL RenderView");
-    const char *fault = nb_render_view_fault(view);
-    NB_ASSERT(fault == nullptr, "invalid RenderView (%u x %u, zoom %g): %s", view->width, view->height, (double)view->zoom, fault);
-    check_field(softening, (uint64_t)view->width * view->height);
-    NB_ASSERT(phi != nullptr, "NULL potential map");
-    std::vector<float> coords((size_t)view->width + view->height);
-    nb_render_pixel_centres(view, coords.data(), coords.data() + view->width);
-    run_field(s, true, coords.data(), coords.size(), view->width * view->height, view->width, softening, phi);
+    sample_map<fd::Potential>(s, "nb_hip_potential_map", view, softening, phi);
+}
+
+void nb_hip_acceleration_at(SimPipeline *s, const float *points, uint32_t n, float softening, float *acc) {
+    sample_at<fd::Acceleration>(s, "nb_hip_acceleration_at", points, n, softening, reinterpret_cast<float2 *>(acc));
+}
+
+void nb_hip_acceleration_map(SimPipeline *s, const RenderView *view, float softening, float *acc) {
+    sample_map<fd::Acceleration>(s, "nb_hip_acceleration_map", view, softening, reinterpret_cast<float2 *>(acc));
 }
 
 }  // extern "C"

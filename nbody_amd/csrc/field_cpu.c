@@ -1,11 +1,13 @@
 /*
- * field_cpu.c -- the host path of include/nbody_field.h: GetWorldPotentialAt / RenderWorldPotential of a World whose
- * particle array holds the newest state (it only ever stepped on the CPU, or stepped on the CPU last).
+ * field_cpu.c -- the host path of include/nbody_field.h and include/nbody_gravity.h: GetWorldPotentialAt /
+ * RenderWorldPotential and GetWorldAccelerationAt / RenderWorldAcceleration of a World whose particle array holds the
+ * newest state (it only ever stepped on the CPU, or stepped on the CPU last).
  *
- * Same definitions as the GPU path (field.hip).  G*m_j is the float32 product the step kernels use; every term and the
+ * Same definitions as the GPU path (field.hip).  G*m_j is the float32 product the step kernels use; every term and every
  * sum are float64 from the stored float32 state, rounded once (diag_cpu.c's convention for the per-particle Phi).  OpenMP
- * splits the samples; every Phi is one sequential sum over j in index order, so the result does not depend on the thread
- * count.  A map is the probes product at the pixel centres of render_common.h: the same function evaluates both.
+ * splits the samples; every Phi and every component of g is one sequential sum over j in index order, so the result does
+ * not depend on the thread count.  A map is the probes product at the pixel centres of render_common.h: the same function
+ * evaluates both.
  * O(samples * M): fine for checks and small worlds; the GPU path is the one to use for a frame of a large world.
  */
 #include <math.h>
@@ -14,9 +16,29 @@
 #include "field_common.h"
 #include "nb_util.h"
 
-static void check_field(float softening, uint64_t samples) {
-    const char *fault = nb_field_fault(softening, samples);
-    NB_CHECK(fault == NULL, "invalid field call (softening %g, %llu points): %s", (double)softening, (unsigned long long)samples, fault);
+static float phi_at(const Particle *ps, const double *gm, uint32_t mass_len, float x, float y, double s) {
+    if (!nb_render_finite(x) || !nb_render_finite(y)) return NAN;
+    const double px = x, py = y;
+    double sum = 0.0;
+    for (uint32_t j = 0; j < mass_len; j++) {
+        const double dx = (double)ps[j].pos.x - px, dy = (double)ps[j].pos.y - py;
+        sum += gm[j] / sqrt(dx * dx + dy * dy + s);
+    }
+    return (float)-sum;
+}
+
+static V2 g_at(const Particle *ps, const double *gm, uint32_t mass_len, float x, float y, double s) {
+    if (!nb_render_finite(x) || !nb_render_finite(y)) return (V2){NAN, NAN};
+    const double px = x, py = y;
+    double ax = 0.0, ay = 0.0;
+    for (uint32_t j = 0; j < mass_len; j++) {
+        const double dx = (double)ps[j].pos.x - px, dy = (double)ps[j].pos.y - py;
+        const double q = dx * dx + dy * dy + s;
+        const double f = gm[j] / (q * sqrt(q));
+        ax += dx * f;
+        ay += dy * f;
+    }
+    return (V2){(float)ax, (float)ay};
 }
 
 /* G*m_j as float64 values of the float32 products, j < mass_len */
@@ -30,41 +52,53 @@ static double *source_gm(const Particle *ps, uint32_t mass_len) {
     return gm;
 }
 
-static float phi_at(const Particle *ps, const double *gm, uint32_t mass_len, float x, float y, double s) {
-    if (!nb_render_finite(x) || !nb_render_finite(y)) return NAN;
-    const double px = x, py = y;
-    double sum = 0.0;
-    for (uint32_t j = 0; j < mass_len; j++) {
-        const double dx = (double)ps[j].pos.x - px, dy = (double)ps[j].pos.y - py;
-        sum += gm[j] / sqrt(dx * dx + dy * dy + s);
-    }
-    return (float)-sum;
-}
-
-void nb_cpu_potential_at(const Particle *ps, uint32_t mass_len, const V2 *points, uint32_t n, float softening, float *phi) {
-    check_field(softening, n);
-    NB_CHECK((points != NULL && phi != NULL) || n == 0, "NULL points or phi");
+/*
+ * The one driver behind the four entry points: n samples into phi[] (the potential) or, where phi is NULL, into acc[].
+ * Probes: sample i is points[i].  A map (points NULL): sample i is pixel (i % width, i / width) at (xs[i % width], ys[i / width]).
+ */
+static void sample(const char *noun, const Particle *ps, uint32_t mass_len, const V2 *points, const float *xs, const float *ys,
+                   uint32_t width, uint64_t n, float softening, float *phi, V2 *acc) {
+    const char *fault = nb_field_fault(softening, n);
+    NB_CHECK(fault == NULL, "invalid %s call (softening %g, %llu points): %s", noun, (double)softening, (unsigned long long)n, fault);
+    NB_CHECK(((points != NULL || xs != NULL) && (phi != NULL || acc != NULL)) || n == 0, "NULL %s points or result", noun);
     if (n == 0) return;
     double *gm = source_gm(ps, mass_len);
 #pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < (int64_t)n; i++) phi[i] = phi_at(ps, gm, mass_len, points[i].x, points[i].y, (double)softening);
+    for (int64_t i = 0; i < (int64_t)n; i++) {
+        const float x = points ? points[i].x : xs[i % width], y = points ? points[i].y : ys[i / width];
+        if (phi)
+            phi[i] = phi_at(ps, gm, mass_len, x, y, (double)softening);
+        else
+            acc[i] = g_at(ps, gm, mass_len, x, y, (double)softening);
+    }
     free(gm);
 }
 
-void nb_cpu_potential_map(const Particle *ps, uint32_t mass_len, const RenderView *view, float softening, float *phi) {
+static void sample_map(const char *noun, const Particle *ps, uint32_t mass_len, const RenderView *view, float softening, float *phi,
+                       V2 *acc) {
     NB_CHECK(view != NULL, "NULL RenderView");
     const char *fault = nb_render_view_fault(view);
     NB_CHECK(fault == NULL, "invalid RenderView (%u x %u, zoom %g): %s", view->width, view->height, (double)view->zoom, fault);
-    check_field(softening, (uint64_t)view->width * view->height);
-    NB_CHECK(phi != NULL, "NULL potential map");
     const uint32_t width = view->width, height = view->height;
     float *xs = NB_NEW((size_t)width + height, float), *ys = xs + width;
     NB_CHECK(xs != NULL, "Failed to alloc %u + %u pixel coordinates", width, height);
     nb_render_pixel_centres(view, xs, ys);
-    double *gm = source_gm(ps, mass_len);
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < (int64_t)width * height; i++)
-        phi[i] = phi_at(ps, gm, mass_len, xs[i % width], ys[i / width], (double)softening);
-    free(gm);
+    sample(noun, ps, mass_len, NULL, xs, ys, width, (uint64_t)width * height, softening, phi, acc);
     free(xs);
+}
+
+void nb_cpu_potential_at(const Particle *ps, uint32_t mass_len, const V2 *points, uint32_t n, float softening, float *phi) {
+    sample("field", ps, mass_len, points, NULL, NULL, 0, n, softening, phi, NULL);
+}
+
+void nb_cpu_potential_map(const Particle *ps, uint32_t mass_len, const RenderView *view, float softening, float *phi) {
+    sample_map("field", ps, mass_len, view, softening, phi, NULL);
+}
+
+void nb_cpu_acceleration_at(const Particle *ps, uint32_t mass_len, const V2 *points, uint32_t n, float softening, V2 *acc) {
+    sample("gravity", ps, mass_len, points, NULL, NULL, 0, n, softening, NULL, acc);
+}
+
+void nb_cpu_acceleration_map(const Particle *ps, uint32_t mass_len, const RenderView *view, float softening, V2 *acc) {
+    sample_map("gravity", ps, mass_len, view, softening, NULL, acc);
 }

@@ -48,7 +48,8 @@ extern "C" {
  *               source split; profiles/r12_field_probe.json), 1 = the source split (8 waves share
  *               a tile of samples, 1/8 of the sources each), 2 = one wave per tile; same bits (tests/test_gpu_field.py)
  *   "gravity_shape" which kernel nb_hip_acceleration_at / nb_hip_acceleration_map run: 0 (default) = auto (the rule of
- *               "field_shape", inherited and not yet measured for this pair body), 1 = the source split, 2 = one wave
+ *               "field_shape": field.hip has one pick_wave_shape and one pair of thresholds; the sweep for this pair body,
+ *               profiles/r13_gravity_probe.json, puts its crossover in the same place), 1 = the source split, 2 = one wave
  *               per tile; same bits (tests/test_gpu_gravity.py)
  *   "zero_copy_upload"  1 (default) = SetSimulationData from the noted, page-locked array lets the split kernel read the
  *               records over PCIe itself; 0 = DMA copy into device staging, then the kernel

@@ -102,7 +102,6 @@ void release_device(SimPipeline *s) {
     s->diag_timed = false;
     render_release(s);
     field_release(s);
-    gravity_release(s);
     dev_free(s->adapt);
     s->adapt = nullptr;
     s->adapt_cap = 0;

@@ -13,8 +13,8 @@
 //   batch_diag.hip   the same for every member of a SimBatch: the kernels behind nb_hip_ensemble_energy / _potential
 //                    (batch_diag.h; the arithmetic both share: diag_common.h)
 //   render.hip       bounds, count image and RGBA frame of the state a pipeline holds (nb_hip_bounds, nb_hip_render_*)
-//   field.hip        the potential at probe points and as a map over a view (nb_hip_potential_at, nb_hip_potential_map)
-//   gravity.hip      the acceleration at probe points and as a map over a view (nb_hip_acceleration_at, nb_hip_acceleration_map)
+//   field.hip        the potential and the acceleration at probe points and as maps over a view (nb_hip_potential_at,
+//                    nb_hip_potential_map, nb_hip_acceleration_at, nb_hip_acceleration_map): one sampler, two pair statements
 //   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
 #pragma once
 
@@ -312,19 +312,14 @@ struct SimPipeline {
     bool render_timed = false, render_detailed = false, bounds_timed = false;
     int render_merge = 1, render_detail = 0;   // tuning hooks (nbody_hip_tuning.h)
 
-    // field.hip (nb_hip_potential_at / nb_hip_potential_map): buffers grown on demand; the event pair is ev_diag
-    float *field_in = nullptr;    // the probes' (x, y) pairs, or a map's width column + height row coordinates
-    size_t field_in_cap = 0;      // floats allocated in field_in
-    float *field_phi = nullptr;   // the device result, one float per sample
-    size_t field_phi_cap = 0;
-    int field_shape = 0;          // tuning hook: 0 auto, 1 source split, 2 one wave per tile
-
-    // gravity.hip (nb_hip_acceleration_at / nb_hip_acceleration_map): buffers grown on demand; the event pair is ev_diag
-    float *gravity_in = nullptr;     // the probes' (x, y) pairs, or a map's width column + height row coordinates
-    size_t gravity_in_cap = 0;       // floats allocated in gravity_in
-    float2 *gravity_acc = nullptr;   // the device result, one float2 per sample
-    size_t gravity_acc_cap = 0;
-    int gravity_shape = 0;           // tuning hook: 0 auto, 1 source split, 2 one wave per tile
+    // field.hip (nb_hip_potential_at / _map, nb_hip_acceleration_at / _map): one pair of buffers grown on demand and shared by
+    // the four calls (each ends in a stream sync, so no two are in flight); the event pair is ev_diag
+    float *sample_in = nullptr;    // the probes' (x, y) pairs, or a map's width column + height row coordinates
+    size_t sample_in_cap = 0;      // floats allocated in sample_in
+    float *sample_out = nullptr;   // the device result: one float (Phi) or two (g) per sample
+    size_t sample_out_cap = 0;     // floats allocated in sample_out
+    int field_shape = 0;           // tuning hooks, Phi and g: 0 auto, 1 source split, 2 one wave per tile
+    int gravity_shape = 0;
 
     // adaptive steps (step_chain.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
     // ADAPT_HEAD bytes of records (the call's AdaptState, the record and result of nb_hip_timestep), then the call's log
@@ -369,11 +364,7 @@ void end_diag(SimPipeline *s);                       // records ev_diag[1]; nb_h
 
 // ---- field.hip -----------------------------------------------------------------------------------------------
 
-void field_release(SimPipeline *s);    // frees the field buffers (release_device)
-
-// ---- gravity.hip ---------------------------------------------------------------------------------------------
-
-void gravity_release(SimPipeline *s);  // frees the gravity buffers (release_device)
+void field_release(SimPipeline *s);    // frees the sample buffers (release_device)
 
 // ---- render.hip ----------------------------------------------------------------------------------------------
 

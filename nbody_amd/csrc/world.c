@@ -24,7 +24,7 @@
  * Extension (include/nbody_field.h): GetWorldPotentialAt / RenderWorldPotential
  * follow the same rule (field.hip on the device, field_cpu.c on the host).
  * Extension (include/nbody_gravity.h): GetWorldAccelerationAt /
- * RenderWorldAcceleration likewise (gravity.hip, gravity_cpu.c).
+ * RenderWorldAcceleration likewise (the same two files).
  * Extension (include/nbody_adaptive.h): adaptive steps.  UpdateWorld_GPU_Adaptive
  * and AdvanceWorld_GPU follow UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Adaptive
  * UpdateWorld_CPU's; GetWorldTimestep follows the diagnostics' (timestep.hip on the
@@ -42,7 +42,6 @@
 
 #include "diag_sums.h"
 #include "field_common.h"
-#include "gravity_common.h"
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"

@@ -1,7 +1,7 @@
 """The acceleration at probe points and as a map (include/nbody_gravity.h) without a GPU: the host path of
 GetWorldAccelerationAt / RenderWorldAcceleration against the float64 numpy restatement (tests/gravity_ref.py), the map =
 probes identity, the argument checks, the header / binding / export agreement, and static checks on the ISA of
-nbody_amd/csrc/gravity.hip.  Every child process hides the devices."""
+nbody_amd/csrc/field.hip.  Every child process hides the devices."""
 import os
 import re
 import subprocess
@@ -217,10 +217,11 @@ def test_header_binding_exports_and_sources_agree():
         assert callable(getattr(nb.SimPipeline, method)) and callable(getattr(nb.World, method))
     csrc = os.path.join(ROOT, "nbody_amd", "csrc")
     make = open(os.path.join(csrc, "Makefile")).read()
-    assert re.search(r"^HIP_TUS\s*:=.*\bgravity\b", make, re.M) and re.search(r"^WORLD_SRCS\s*:=.*\bgravity_cpu\.c", make, re.M)
-    assert re.search(r"^WORLD_HDRS\s*:=(.*\\\n)*.*gravity_common\.h", make, re.M) and make.count("gravity_common.h") >= 2
+    # the acceleration lives in the field sampler's files: field.hip, field_cpu.c, field_common.h
+    assert re.search(r"^HIP_TUS\s*:=.*\bfield\b", make, re.M) and re.search(r"^WORLD_SRCS\s*:=.*\bfield_cpu\.c", make, re.M)
+    assert re.search(r"^WORLD_HDRS\s*:=(.*\\\n)*.*field_common\.h", make, re.M) and make.count("field_common.h") >= 2
     assert make.count("include/nbody_gravity.h") >= 2          # libnbody*.so (WORLD_HDRS) and the HIP objects
-    text = open(os.path.join(csrc, "gravity.hip")).read()
+    text = open(os.path.join(csrc, "field.hip")).read()
     assert '#include "diag_common.h"' in text and '#include "interaction_asm.h"' in text and "NB_INTERACTION2_ASM" in text
     assert '"gravity_shape"' in open(os.path.join(csrc, "nbody_hip_tuning.h")).read()
     for h in ("nbody.h", "galaxy.h", "nbody_diag.h", "nbody_render.h", "nbody_field.h"):
@@ -228,18 +229,22 @@ def test_header_binding_exports_and_sources_agree():
         assert not [f for f in WORLD_FUNCS + HIP_FUNCS if f in text], h
 
 
-# ---- static ISA of gravity.hip -------------------------------------------------------------------------------------------------
+# ---- static ISA of field.hip: the kernels of the Acceleration policy -------------------------------------------------------------
 
-KERNELS = ("gravity_split_kernel", "gravity_wave_kernel")
+KERNELS = ("sample_split_kernel", "sample_wave_kernel")
+
+
+def is_g(name):
+    return "Acceleration" in name
 
 
 @pytest.fixture(scope="module")
 def gravity_isa(tmp_path_factory):
-    return compile_isa(tmp_path_factory.mktemp("gravity_isa"), "gravity.hip")
+    return compile_isa(tmp_path_factory.mktemp("gravity_isa"), "field.hip")
 
 
 def test_gravity_kernels_keep_eight_waves_per_simd_without_scratch(gravity_isa):
-    meta = kernel_meta(gravity_isa)
+    meta = [m for m in kernel_meta(gravity_isa) if is_g(m[0])]
     assert [sum(k in m[0] for m in meta) for k in KERNELS] == [2, 2] and len(meta) == 4, [m[0] for m in meta]
     for name, scratch, sgpr, vgpr in meta:
         print(f"[gravity isa] {name}: scratch {scratch}, {sgpr} SGPRs, {vgpr} VGPRs")
@@ -249,7 +254,7 @@ def test_gravity_kernels_keep_eight_waves_per_simd_without_scratch(gravity_isa):
 
 def test_gravity_kernels_keep_the_wait_state_behind_every_rsq(gravity_isa):
     fns = functions(gravity_isa)
-    names = [n for n in fns if any(k in n for k in KERNELS)]
+    names = [n for n in fns if is_g(n) and any(k in n for k in KERNELS)]
     assert len(names) == 4, sorted(fns)
     for name in names:
         assert check_rsq_wait_states(name, fns[name]) >= 2, name
@@ -268,7 +273,9 @@ def loops(text, symbol):
 
 
 def test_the_unmasked_loop_of_every_kernel_holds_sixteen_rsq_per_eight_sources(gravity_isa):
-    for name, *_ in kernel_meta(gravity_isa):
+    names = [name for name, *_ in kernel_meta(gravity_isa) if is_g(name)]
+    assert len(names) == 4, names
+    for name in names:
         fetch8 = [(lab, ops) for lab, ops in loops(gravity_isa, name) if "s_load_dwordx16" in ops]
         assert len(fetch8) == 1, (name, [lab for lab, _ in fetch8])
         ops = fetch8[0][1]
