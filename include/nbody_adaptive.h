@@ -6,7 +6,7 @@
  * unless marked).  For every particle i < N, massless ones included:
  *
  *   a2  = fmaf(acc.x, acc.x, acc.y * acc.y)             a particle whose a2 is zero or not finite is skipped
- *   q_i = fmaxf(radius_i, 0) / a2                       IEEE division
+ *   q_i = (radius_i > 0 ? radius_i : +0) / a2           IEEE division; a radius of -0, below 0 or NaN counts as +0
  *   q   = min_i q_i                                     taken with `<`; +inf when no particle contributes
  *   dt  = fminf(fmaxf(eta * sqrtf(sqrtf(q)), dt_min), dt_max)
  *

@@ -15,7 +15,8 @@
 //   ensemble_timestep_kernel   one workgroup per member, the same statement, no cross-workgroup stage.
 //
 // Rows at or beyond n (the pad rows of an ensemble's stride) are never read.  The minimum of floats is exact in any order and
-// the tail runs once, so the result does not depend on the grid: tests/test_gpu_adaptive.py holds it to the host path bit for bit.
+// the tail runs once, so the result does not depend on the grid: tests/test_gpu_adaptive.py and test_gpu_adaptive_edges.py hold
+// it to the host path bit for bit.
 #include "timestep.h"
 #include "timestep_common.h"
 

@@ -2,7 +2,7 @@
  * timestep_common.h -- the adaptive step-size criterion of include/nbody_adaptive.h, written once for the device kernels
  * (timestep.hip) and the host path (timestep_cpu.c).  Both sides must give the same bits, so what defines a step size lives
  * here and nowhere else:
- *   nb_timestep_q      one particle's q_i = fmaxf(radius, 0) / fmaf(ax, ax, ay * ay), +inf for a particle that is skipped
+ *   nb_timestep_q      one particle's q_i = (radius > 0 ? radius : +0) / fmaf(ax, ax, ay * ay), +inf for a particle that is skipped
  *   nb_timestep_dt     dt = fminf(fmaxf(eta * sqrtf(sqrtf(q)), dt_min), dt_max) of the minimum q
  *   nb_timestep_clip   the span clip in float64; advances t
  *   nb_timestep_count  the bookkeeping of NbAdaptiveResult for one step
@@ -10,7 +10,9 @@
  * product inside it is rounded on its own.  The division and both square roots are the correctly rounded IEEE operations on
  * both sides: gcc emits divss / sqrtss, and hipcc's default for HIP code (fp32 divide and sqrt correctly rounded, no fast-math
  * flag in HIPFLAGS) expands them to the v_div_scale / v_div_fmas / v_div_fixup and the refined v_sqrt sequences, with fp32
- * denormals kept.  The minimum over the particles is taken with `<` by the callers; +inf never wins and no q_i is a NaN.
+ * denormals kept.  The radius is clamped by a comparison, not by fmaxf: C leaves the sign of fmaxf(-0, +0) open, and a q_i of
+ * -0 would lose the device's minimum (taken on the bits) where it ties the host's.  So every q_i is +0, positive or +inf: the
+ * minimum over the particles is taken with `<` by the callers, +inf never wins and no q_i is a NaN or negative.
  */
 #ifndef NB_TIMESTEP_COMMON_H
 #define NB_TIMESTEP_COMMON_H
@@ -31,7 +33,7 @@
 NB_TS_FN float nb_timestep_q(float ax, float ay, float radius) {
     const float a2 = __builtin_fmaf(ax, ax, ay * ay);
     if (!(a2 > 0.0f && a2 < NB_TS_INF)) return NB_TS_INF; /* zero, NaN or overflowed: skipped */
-    return __builtin_fmaxf(radius, 0.0f) / a2;
+    return (radius > 0.0f ? radius : 0.0f) / a2; /* -0, negative and NaN radii give +0 */
 }
 
 NB_TS_FN float nb_timestep_dt(float q, float eta, float dt_min, float dt_max) {

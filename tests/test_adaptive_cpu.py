@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import nbody_amd as nb
+import timestep_cases as tc
 import timestep_ref as tr
 from isa_common import compile_isa, kernel_meta
 from test_abi import declared_functions, exported
@@ -103,6 +104,56 @@ def test_host_criterion_equals_the_restatement_bit_for_bit(golden):
             assert int(np.argmin(tr.q_all(p))) == j and np.float32(dt_min) < got < np.float32(dt_max), name
         seen += 1
     assert seen == 27
+
+
+def test_case_tables_tell_the_statement_from_its_mutants():
+    """tests/timestep_cases.py: over sweep(4096) + directed() every wrong statement (a)-(d) changes the dt bits of at least 50
+    cases, and the -0.0 and negative-radius cases tell (e) apart in a two-particle world.  This is what keeps the device sweep
+    of tests/test_gpu_adaptive_edges.py from passing vacuously; a seed that misses it is a reason to change the generator."""
+    cases = np.concatenate([tc.sweep(4096), tc.directed()])
+    cfg = dict(eta=1.0, dt_max=3.0e38, dt_min=0.0)
+    want = tc.expected(cases, **cfg)
+    assert bits(tc.mutant_dt(cases, None, **cfg)) == bits(want)          # the vectorised real statement is the restatement
+    counts = {m: int(np.sum(tc.mutant_dt(cases, m, **cfg).view(np.uint32) != want.view(np.uint32))) for m in "abcd"}
+    told = 0
+    for name in ("radius -0", "radius -1", "radius -inf", "radius -smallest subnormal"):
+        pair = np.stack([tc.named(name), tc.named("q = 1")])
+        real, wrong = tc.expected_world(pair, **cfg), tc.mutant_e_world(pair, **cfg)
+        assert bits(real) == bits(0.0) and bits(wrong) == bits(tc.expected(pair[1:], **cfg)[0]) and wrong > 0, (name, real, wrong)
+        told += 1
+    counts["e"] = told
+    print("[timestep cases] cases whose dt bits a mutant changes: " + "  ".join(f"({m}) {c}" for m, c in counts.items()))
+    assert all(counts[m] >= 50 for m in "abcd") and counts["e"] >= 2, counts
+    # what the sweep is stated to contain
+    s = tc.sweep(4096)
+    assert s.dtype == np.float32 and s.tobytes() == tc.sweep(4096).tobytes()
+    ratio = np.abs(s[:, 0].astype(np.float64)) / np.where(s[:, 1] == 0, np.inf, np.abs(s[:, 1].astype(np.float64)))
+    assert 0.10 < np.mean(s[:, 1] == 0) < 0.15 and np.mean((ratio > 0.25) & (ratio < 4)) > 0.125
+    a2 = tr.a2_f32(s[:, 0], s[:, 1])
+    tiny = np.float32(2.0 ** -126)
+    assert np.sum((a2 > 0) & (a2 < tiny)) > 50 and np.sum(np.isinf(a2)) > 10
+    q = tr.q_all(tc.particles(s))
+    assert np.sum((q > 0) & (q < tiny)) > 50 and np.sum(q == 0) > 100 and np.sum(np.isinf(q)) > 100
+    assert np.sum(np.abs(s[:, 2]) < tiny) > 100 and np.sum(s[:, 2] < 0) > 100
+    names = tc.directed_names()
+    assert len(set(names)) == len(names) == tc.directed().shape[0]
+
+
+def test_host_criterion_equals_the_restatement_over_the_case_tables():
+    """GetWorldTimestep of a one-particle CPU World for every directed case and the first 512 sweep cases, under both
+    configurations the device sweep uses, and the two-particle worlds of the device's pair test."""
+    cases = np.concatenate([tc.directed(), tc.sweep(512)])
+    names = tc.directed_names() + [f"sweep {i}" for i in range(512)]
+    for cfg in (dict(eta=1.0, dt_max=3.0e38, dt_min=0.0), dict(eta=0.1, dt_max=10.0, dt_min=1.0e-3)):
+        want = tc.expected(cases, **cfg)
+        for name, c, w in zip(names, cases, want):
+            got = host_dt(tc.particles(c), **cfg)
+            assert bits(got) == bits(w), (name, [hex(b) for b in bits(c)], got, w)
+    for a, b in tc.PAIRS:
+        pair = tc.particles(np.stack([tc.named(a), tc.named(b)]))
+        for p in (pair, pair[::-1]):
+            got, want = host_dt(p, 1.0, 3.0e38), tr.timestep(p, 1.0, 3.0e38)
+            assert bits(got) == bits(want), (a, b, got, want)
 
 
 def test_the_restated_fma_is_the_correctly_rounded_one():
@@ -331,7 +382,9 @@ def test_header_binding_exports_and_sources_agree():
     # the statement is written once: nobody else divides a radius by a squared acceleration
     for name in sorted(os.listdir(csrc)):
         if name.endswith((".hip", ".c", ".h")) and name != "timestep_common.h":
-            assert "__builtin_fmaxf(radius" not in open(os.path.join(csrc, name), errors="replace").read(), name
+            text = open(os.path.join(csrc, name), errors="replace").read()
+            assert "__builtin_fmaxf(radius" not in text and "radius > 0.0f ? radius" not in text, name
+    assert "(radius > 0.0f ? radius : 0.0f) / a2" in open(os.path.join(csrc, "timestep_common.h")).read()
 
 
 def C_sizes():

@@ -19,9 +19,9 @@ F32, F64 = np.float32, np.float64
 
 def a2_f32(ax, ay):
     """fmaf(ax, ax, ay * ay) in float32, exactly; arrays of float32."""
-    ay2 = (ay.astype(F64) * ay.astype(F64)).astype(F32).astype(F64)
-    p = ax.astype(F64) * ax.astype(F64)
-    with np.errstate(invalid="ignore", over="ignore"):
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        ay2 = (ay.astype(F64) * ay.astype(F64)).astype(F32).astype(F64)
+        p = ax.astype(F64) * ax.astype(F64)
         s = p + ay2
         bb = s - p
         err = (p - (s - bb)) + (ay2 - bb)
@@ -35,7 +35,7 @@ def q_all(particles):
     a = np.ascontiguousarray(particles, dtype=F32)
     a2 = a2_f32(a[:, 4], a[:, 5])
     use = (a2 > 0) & np.isfinite(a2)
-    r = np.where(a[:, 7] > 0, a[:, 7], F32(0)).astype(F64)          # fmaxf(radius, 0): NaN -> 0
+    r = np.where(a[:, 7] > 0, a[:, 7], F32(0)).astype(F64)          # radius > 0 ? radius : +0 (-0, < 0, NaN -> +0)
     q = np.full(a.shape[0], np.inf, dtype=F32)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore", under="ignore"):
         q[use] = (r[use] / a2[use].astype(F64)).astype(F32)
