@@ -10,6 +10,7 @@ import pytest
 
 import nbody_amd as nb
 import oracle_binding as ob
+import sequence_driver as sd
 import timestep_ref as tr
 from gpu_common import synth
 
@@ -43,9 +44,11 @@ def world(n, golden):
     return _worlds[n]
 
 
-def pipeline(part, m, warm=True):
-    """warm: True = the two fixed steps; "zero" = one dt = 0 step (acc of exactly this state); False = as uploaded."""
+def pipeline(part, m, warm=True, **knobs):
+    """warm: True = the two fixed steps; "zero" = one dt = 0 step (acc of exactly this state); False = as uploaded.
+    knobs: the launch shape (configure), applied before set_data."""
     s = nb.SimPipeline(part.shape[0], m)
+    s.configure(**knobs)
     s.set_data(part)
     if warm == "zero":
         s.update(1, 0.0)
@@ -62,8 +65,10 @@ def replay(b, log, clock, eta=ETA, dt_max=DT_MAX, dt_min=0.0):
         b.update(1, float(dt))
 
 
-def check_contract(part, m, label, warm=True, **cfg):
-    a, b = pipeline(part, m, warm), pipeline(part, m, warm)
+def check_contract(part, m, label, warm=True, knobs=None, **cfg):
+    """knobs: configure() arguments for BOTH pipelines, the adaptive one and the one that replays."""
+    knobs = knobs or {}
+    a, b = pipeline(part, m, warm, **knobs), pipeline(part, m, warm, **knobs)
     log, res = a.update_adaptive(STEPS, ETA, DT_MAX, **cfg)
     clock = tr.Clock(cfg.get("span", math.inf))
     replay(b, log, clock)
@@ -166,6 +171,71 @@ def test_async_twin_and_timestep_change_nothing(golden):
     a.close()
     b.close()
     assert pa.tobytes() == pb.tobytes()
+
+
+# ---- every launch shape --------------------------------------------------------------------------------------------------------
+# enqueue_adaptive launches its steps through the shape the fixed steps have, so the contract holds on each of them: the
+# rows of tests/sequence_driver.py PIPE_ROWS at their sizes (the smallest at which each route exists).
+
+_shape_worlds = {}
+
+
+def shape_world(n, frac):
+    """(partitioned particles, mass_len, the state after the two fixed steps at the default shape); computed once"""
+    if (n, frac) not in _shape_worlds:
+        part, m = synth(n, frac_massive=frac, seed=n)
+        s = pipeline(part, m)
+        _shape_worlds[(n, frac)] = (part, m, s.get_data())
+        s.close()
+    return _shape_worlds[(n, frac)]
+
+
+def assert_the_row_runs_its_shape(row, part, m, knobs):
+    """What the knobs were set for really happens in an adaptive call: the finish kernel, its absence, the second pass, the LDS
+    variant, the lane split."""
+    s = pipeline(part, m, **knobs)
+    s.update_adaptive(2, ETA, DT_MAX)
+    shape, finish, launches = s.launch_shape(), s.finish_launches(), s.last_step_ms()[1]
+    s.close()
+    if row == "split3-finish-9000":
+        assert shape["split"] == 3 and finish == 2, (shape, finish)
+    elif row == "fused-finish-9000":
+        assert shape["split"] > 1 and finish == 0, (shape, finish)
+    elif row == "passes2-1500":
+        assert launches == 4, launches
+    elif row == "classic-4133-lds":
+        assert shape["variant"] == "lds", shape
+    elif row == "lanes4-w8-900":
+        assert shape["lanes"] == 4 and shape["w"] == 8, shape
+    elif row.startswith("lanes-600"):
+        assert shape["lanes"] > 1, shape
+    elif row.startswith("classic-4133"):
+        assert shape["lanes"] == 1 and shape["variant"] == "smem", shape
+
+
+@pytest.mark.parametrize("row", list(sd.PIPE_ROWS))
+def test_the_contract_holds_on_every_launch_shape(row):
+    n, frac, knobs = sd.PIPE_ROWS[row]
+    part, m, _ = shape_world(n, frac)
+    assert_the_row_runs_its_shape(row, part, m, knobs)
+    log, res = check_contract(part, m, row, knobs=knobs)
+    assert res["steps"] == STEPS and res["idle_steps"] == 0
+    assert np.all(log > 0) and np.all(log < np.float32(DT_MAX)) and len(set(bits(log))) > 1, log
+
+
+@pytest.mark.parametrize("row", ["split3-finish-9000", "passes2-1500"])
+def test_planted_minimum_at_the_last_row_on_split_and_two_pass_shapes(row):
+    """The step size the device chose is read by the finish kernel of a split launch, and by both passes of a two-pass step;
+    the particle that sets it sits at index N - 1."""
+    n, frac, knobs = sd.PIPE_ROWS[row]
+    _, m, warmed = shape_world(n, frac)
+    part = tr.plant(warmed, n - 1, 0)
+    probe = pipeline(part, m, "zero", **knobs)
+    assert int(np.argmin(tr.q_all(probe.get_data()))) == n - 1
+    free = probe.timestep(ETA, DT_MAX)
+    probe.close()
+    log, _ = check_contract(part, m, f"{row} minimum at {n - 1}", warm="zero", knobs=knobs)
+    assert bits(log[0]) == bits(free) and log[0] < 0.1 * tr.timestep(warmed, ETA, DT_MAX)
 
 
 # ---- ensembles -----------------------------------------------------------------------------------------------------------------

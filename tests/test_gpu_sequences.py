@@ -1,0 +1,169 @@
+"""Long-lived pipelines and ensembles against chains of fresh ones (tests/sequence_driver.py), on the MI355X: seeded
+sequences of every kind of call -- fixed and adaptive steps, blocking and async, diagnostics, fields, render, get / set -- on
+ONE object, each output bit for bit what a new object gives for the same call from the same state.  One row per step route
+and launch shape, so that the phase bit, the cached chains, the device-side step size, the adaptive head and the scratch
+buffers are all left behind by one feature and found by another.  The hazards that have a name are also written out in full
+(the directed tests).  The seeds are the ones tests/test_sequence_cpu.py shows to catch every planted fault.  This file
+compares the library with itself; tests/test_gpu_adaptive.py anchors the same launch shapes to the numpy criterion."""
+import time
+
+import numpy as np
+import pytest
+
+import nbody_amd as nb
+import sequence_driver as sd
+from gpu_common import synth
+from test_gpu_ragged import MASS as RAGGED_MASS, SIZES as RAGGED_SIZES, world as ragged_world
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def need_gpu():
+    if nb.device_count() < 1:
+        pytest.skip("needs an MI355X")
+
+
+PIPE_ROWS = sd.PIPE_ROWS
+BATCH_ROWS = {"chain-5x250": (5, 250), "lanes-3x800": (3, 800)}
+
+_points = np.random.default_rng(77).standard_normal((max(sd.POINT_COUNTS), 2)).astype(np.float32) * 1.0e4
+
+
+def second_world(n, m, seed):
+    """a second seeded world with the same N and M: other positions, velocities, masses and radii"""
+    part = synth(n, frac_massive=1.1, seed=seed)[0].copy()
+    part[m:, 6], part[m:, 7] = 0.0, 0.5
+    return part
+
+
+def views(centre):
+    """32 x 18 and the maps: the whole world, every particle a point; 80 x 45: close on one massive particle, so discs."""
+    def view(w, h):
+        if (w, h) == (80, 45):
+            return nb.RenderView.make((float(centre[0]), float(centre[1])), (w / 2, h / 2), 0.5, w, h, 2.0e4)
+        return nb.RenderView.make((0.0, 0.0), (w / 2, h / 2), w / 6.0e4, w, h, 2.0e4)
+    return view
+
+
+_envs = {}
+
+
+def pipe_env(n, frac):
+    """Start and second state of a row, each two fixed steps in (so acc is not zero and the criterion has something to say);
+    computed once per size, shared, never changed."""
+    if (n, frac) not in _envs:
+        part, m = synth(n, frac_massive=frac, seed=n)
+        states = []
+        for p in (part, second_world(n, m, n + 1)):
+            s = nb.SimPipeline(n, m)
+            s.set_data(p)
+            s.update(2, 0.01)
+            states.append(s.get_data())
+            s.close()
+        _envs[(n, frac)] = (sd.Env("pipeline", states[0], states[1], views(states[0][0, 0:2]), lambda k: _points[:k]), m)
+    return _envs[(n, frac)]
+
+
+def pipe_maker(n, m, knobs):
+    def make():
+        s = nb.SimPipeline(n, m)
+        s.configure(**knobs)
+        return s
+    return make
+
+
+def run_row(row, ops, seed=None):
+    n, frac, knobs = PIPE_ROWS[row]
+    env, m = pipe_env(n, frac)
+    t0 = time.perf_counter()
+    compared = sd.check(pipe_maker(n, m, knobs), ops, env, seed)
+    print(f"[sequence] {row} seed {seed}: {len(ops)} operations, {compared} outputs compared, {time.perf_counter() - t0:.2f} s")
+    return compared
+
+
+@pytest.mark.parametrize("seed", sd.SEEDS["pipeline"])
+@pytest.mark.parametrize("row", list(PIPE_ROWS))
+def test_a_long_lived_pipeline_is_a_chain_of_fresh_ones(row, seed):
+    ops = sd.generate("pipeline", seed)
+    assert run_row(row, ops, seed) > len(ops) // 2
+
+
+# ---- ensembles -----------------------------------------------------------------------------------------------------------------
+
+def batch_env(count, n):
+    if (count, n) not in _envs:
+        worlds = [synth(n, frac_massive=0.5, seed=1000 * n + b) for b in range(count)]
+        ms = [m for _, m in worlds]
+        states = []
+        for parts in (np.stack([p for p, _ in worlds]), np.stack([second_world(n, m, 2000 * n + b) for b, m in enumerate(ms)])):
+            s = nb.SimBatch(n, ms)
+            s.set_data(parts)
+            s.update(2, 0.01)
+            states.append(s.get_data())
+            s.close()
+        _envs[(count, n)] = (sd.Env("batch", states[0], states[1], views(states[0][0, 0, 0:2]), None, members=count), ms)
+    return _envs[(count, n)]
+
+
+@pytest.mark.parametrize("seed", sd.SEEDS["batch"])
+@pytest.mark.parametrize("row", list(BATCH_ROWS))
+def test_a_long_lived_ensemble_is_a_chain_of_fresh_ones(row, seed):
+    count, n = BATCH_ROWS[row]
+    env, ms = batch_env(count, n)
+    ops = sd.generate("batch", seed, members=count)
+    t0 = time.perf_counter()
+    compared = sd.check(lambda: nb.SimBatch(n, ms), ops, env, seed)
+    print(f"[sequence] {row} seed {seed}: {len(ops)} operations, {compared} outputs compared, {time.perf_counter() - t0:.2f} s")
+    assert compared > len(ops) // 2
+
+
+@pytest.mark.parametrize("seed", sd.SEEDS["ragged"])
+def test_a_long_lived_ragged_ensemble_is_a_chain_of_fresh_ones(seed):
+    """The ensemble of tests/test_gpu_ragged.py; only the calls include/nbody_batch_ragged.h lists (the driver refuses any
+    other on this kind before it reaches the library)."""
+    members = range(len(RAGGED_SIZES))
+    env = sd.Env("ragged", [ragged_world(b, 0) for b in members], [ragged_world(b, 1) for b in members], None, None,
+                 members=len(RAGGED_SIZES))
+    ops = sd.generate("ragged", seed, members=len(RAGGED_SIZES))
+    t0 = time.perf_counter()
+    compared = sd.check(lambda: nb.SimBatch.ragged(RAGGED_SIZES, RAGGED_MASS), ops, env, seed)
+    print(f"[sequence] ragged seed {seed}: {len(ops)} operations, {compared} outputs compared, {time.perf_counter() - t0:.2f} s")
+    assert compared > len(ops) // 2
+
+
+# ---- directed sequences: the hazards that have a name ----------------------------------------------------------------------------
+
+def op(name, **args):
+    return name, args
+
+
+@pytest.mark.parametrize("graph", [1, 2])
+@pytest.mark.parametrize("n,frac", [(600, 0.5), (4133, 1.0)])
+def test_odd_adaptive_steps_then_the_chain_cached_for_the_other_phase(n, frac, graph):
+    """An odd number of adaptive steps flips the phase bit; the next 20-step call finds the chain that was captured in the
+    other phase, and the step size in device memory is the one the device chose."""
+    env, m = pipe_env(n, frac)
+    ops = [op("update", n=20, dt=0.01), op("update_adaptive", n=3), op("update", n=20, dt=0.01), op("update_adaptive", n=1),
+           op("update", n=20, dt=0.005), op("get_data")]
+    sd.check(pipe_maker(n, m, dict(graph=graph)), ops, env)
+
+
+@pytest.mark.parametrize("row", ["chain-200", "lanes-600", "split3-finish-9000"])
+def test_reads_behind_async_adaptive_steps_see_the_state_after_them(row):
+    ops = [op("update_adaptive_async", n=3), op("potential_map", w=40, h=30), op("render", w=80, h=45), op("energy"),
+           op("adaptive_collect", n=3)]
+    run_row(row, ops)
+
+
+@pytest.mark.parametrize("row", ["chain-200", "classic-4133"])
+def test_energy_after_buffers_that_regrew(row):
+    ops = [op("render", w=80, h=45), op("energy"), op("acceleration_at", count=300), op("potential"), op("render", w=32, h=18),
+           op("energy")]
+    run_row(row, ops)
+
+
+@pytest.mark.parametrize("row", ["chain-200", "classic-4133", "passes2-1500"])
+def test_a_new_state_on_an_armed_adaptive_head(row):
+    ops = [op("update_adaptive", n=2), op("set_data"), op("timestep"), op("update_adaptive", n=2)]
+    run_row(row, ops)
