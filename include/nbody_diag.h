@@ -28,6 +28,13 @@
  * particle array back; otherwise on the host in float64, independent of the OpenMP thread count.  A World that only
  * ever steps on the CPU never touches a GPU.  Neither call changes the World's state.  Sharded Worlds abort: their
  * remote slices are current only inside a step, so a correct sharded energy needs a collective (not supported).
+ *
+ * Non-finite state.  Every field of WorldEnergy and every Phi_i has the class (finite, +inf, -inf, NaN) that the float64
+ * host path gives for the same state, wherever the sums run and whatever M mod 128 is (the device works in tiles of 128
+ * receivers; the idle lanes of the last tile add exact zeros by a select, whatever the particle they read holds): one
+ * massive particle with vel.x = +inf makes kinetic, momentum.x and angular_momentum infinite and leaves the other fields
+ * finite; a NaN anywhere in a massive particle's position makes every Phi_i NaN; a massless particle, whatever it
+ * holds, changes no bit of the energy or of any other particle's Phi.
  */
 #ifndef NBODY_AMD_NBODY_DIAG_H
 #define NBODY_AMD_NBODY_DIAG_H

@@ -74,6 +74,26 @@ void SetSimulationData(SimPipeline *sim, const Particle *ps);
  * Replaces reference sim_gpu.h:36 (sim_gpu.c:258-361): n > 0 steps of size dt,
  * blocking.  Simulation data must have been set.  n == 0 is a no-op here
  * (the reference documents n > 0; world.c:113 never passes 0).
+ *
+ * Non-finite state.  A state that has stopped being finite (a close encounter, a bad initial condition, a step size
+ * too large) is ordinary data to the step kernels, on every launch shape, in a sharded group and in an ensemble:
+ *   - every pos, vel and acc value has the CLASS (finite, +inf, -inf, NaN) that the reference's AVX build gives for the
+ *     same input (sim_cpu.c:156-194): the pair term follows the reference through inf and NaN (dx * 0 = NaN for a source
+ *     at infinity, 0 * inf = NaN for a coincident pair with no softening, dx * inf for G*m = inf), and the sums keep an
+ *     infinite total infinite: the compensation of the block sums is not applied to a total that has left the finite
+ *     range, so +-inf plus finite terms stays +-inf and +inf plus -inf is NaN, as in the reference's plain sums;
+ *   - finite values stay within the stated tolerance.  A pair term whose factor G*m / (r * r^2)
+ *     fp32 cannot hold -- r * r^2 beyond 3.4e38, or the factor below 1.2e-38 -- may come out as anything between 0 and
+ *     its float64 value: the reference's form gives exactly 0 (G*m / inf), G*m * rsq * rsq^2 here gives 0 or a denormal;
+ *   - vel = vel0 + acc * dt and pos = pos0 + vel * dt hold in fp32 wherever the result is not NaN;
+ *   - a particle that is no source (mass <= 0) cannot change a bit of any other particle, whatever it holds: the launch
+ *     shape depends on the counts only, and a receiver's lanes, pads and neighbours are kept apart by selects, never by
+ *     a multiplication with zero;
+ *   - an ensemble member's results -- its steps, its energy and potential (include/nbody_diag.h "Non-finite state" holds
+ *     per member) and its rows of a traced update -- do not depend on what its neighbours hold, non-finite neighbours
+ *     included.
+ * Calls whose termination depends on values (the adaptive ones, include/nbody_adaptive.h) state their own edges.
+ * tests/test_gpu_nonfinite.py holds every route to this; tests/nonfinite_cases.py is the case table.
  */
 void PerformSimUpdate(SimPipeline *sim, uint32_t n, float dt);
 

@@ -190,21 +190,24 @@ __device__ __forceinline__ void tile_potential(double (&sum)[K], const float (&p
 }
 
 // The eight float64 terms of receiver i of a tile, in diag_sums.h order.  A dead lane (past the last receiver) reads
-// particle c = 0 with m = 0 and contributes no Phi term (the 0 * inf of a dead lane must not reach the sum).
+// particle c = 0 and contributes exact zeros, every one of them by a select: particle 0 may hold anything (include/
+// nbody_diag.h "Non-finite state"), and the 0 * inf or 0 * NaN of a dead lane must not reach the sum.  For finite data a
+// product with m = 0 was a zero too, of either sign; the tile rows are added up from +0.0 (reduce_rows), where the sign
+// of a zero term cannot show.
 __device__ __forceinline__ void energy_terms(double (&e)[QTY], bool live, double phi, const float *mass, const float2 *pos,
                                              const float2 *vel, uint32_t i) {
     const uint32_t c = live ? i : 0u;
-    const double m = live ? (double)mass[c] : 0.0;
+    const double m = (double)mass[c];
     const float2 x = pos[c], v = vel[c];
     const double vx = v.x, vy = v.y, xx = x.x, xy = x.y;
     e[0] = live ? m * phi : 0.0;
-    e[1] = m * (vx * vx + vy * vy);
-    e[2] = m;
-    e[3] = m * vx;
-    e[4] = m * vy;
-    e[5] = m * (xx * vy - xy * vx);
-    e[6] = m * xx;
-    e[7] = m * xy;
+    e[1] = live ? m * (vx * vx + vy * vy) : 0.0;
+    e[2] = live ? m : 0.0;
+    e[3] = live ? m * vx : 0.0;
+    e[4] = live ? m * vy : 0.0;
+    e[5] = live ? m * (xx * vy - xy * vx) : 0.0;
+    e[6] = live ? m * xx : 0.0;
+    e[7] = live ? m * xy : 0.0;
 }
 
 // potential_kernel's tree over the 128 rows of a tile held by one wave: half = 64 is rows lane and lane + 64 (the lane's

@@ -77,8 +77,12 @@ struct Receivers {
             // a block that added exactly nothing (zero-mass pad sources of a sharded launch) must leave the
             // state untouched, or padded and unpadded launches would differ in the last bit
             const bool lx = a[k].x != 0.0f, ly = a[k].y != 0.0f;
-            c[k].x = lx ? cn.x : c[k].x;
-            c[k].y = ly ? cn.y : c[k].y;
+            // a total that has left the finite range carries no compensation ((inf - s) - inf is NaN, and the next block
+            // would turn a sum of +-inf into NaN, which the reference's plain sums do not: include/nbody_hip.h "Non-finite
+            // state").  A select on t: +-inf then survives finite blocks, +inf meets -inf as NaN, NaN stays NaN.
+            const bool fx = __builtin_fabsf(t.x) < __builtin_inff(), fy = __builtin_fabsf(t.y) < __builtin_inff();
+            c[k].x = lx ? (fx ? cn.x : 0.0f) : c[k].x;
+            c[k].y = ly ? (fy ? cn.y : 0.0f) : c[k].y;
             s[k].x = lx ? t.x : s[k].x;
             s[k].y = ly ? t.y : s[k].y;
             a[k] = f2v{0.0f, 0.0f};
