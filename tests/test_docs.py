@@ -68,3 +68,9 @@ def test_status_headline_table_is_the_drivers_own_record():
         assert abs(line["ms_per_step"] - float(ms)) < 0.06, (rnd, line["ms_per_step"], ms)
         assert abs(line["value"] / 1e12 - float(rate)) < 0.006, (rnd, line["value"], rate)
         assert abs(line["roofline"]["frac"] - float(frac)) < 0.0006, (rnd, line["roofline"]["frac"], frac)
+
+
+def test_the_summation_table_is_committed_and_cited():
+    """DESIGN.md section 5 states the summation scheme per kernel family and cites one run's table of the witness tests."""
+    assert os.path.exists(os.path.join(ROOT, "profiles", "r14_sum_witness.txt"))
+    assert "profiles/r14_sum_witness.txt" in open(os.path.join(ROOT, "DESIGN.md")).read()

@@ -211,19 +211,25 @@ def test_lds_and_smem_variants_agree_bitwise(golden, k, w):
     assert a.tobytes() == run(part, m, 2, 0.01, variant=0, k=k, w=w, unit=8).tobytes()   # asked for 8: still 64 there
 
 
+# the source counts and knob sets of the two sweeps below; tests/test_gpu_sums.py runs its exactly-once witness at the same ones
+SWEEP_COUNTS = sorted(set(list(range(1, 40)) + [63, 64, 65, 71, 72, 73, 127, 128, 129, 247, 248, 249, 255, 256, 257, 263, 264,
+                                                265, 511, 512, 513, 519, 520, 1023, 1024, 1025, 1031, 2047, 2048, 2049, 2111]))
+SWEEP_KNOBS = (dict(k=1, w=1), dict(k=2, w=16), dict(k=2, w=4, split=3), dict(k=1, w=4, passes=2))
+GRANULE_COUNTS = [1, 7, 8, 9, 15, 16, 17, 31, 33, 63, 64, 65, 100, 127, 129, 250, 255, 256, 257, 263, 511, 520, 1000, 1031, 2049]
+GRANULE_KNOBS = (dict(k=1, w=16), dict(k=2, w=4, split=3), dict(k=1, w=8, split=16), dict(k=2, w=16, passes=2), dict(k=1, w=1))
+
+
 def test_source_count_sweep_both_routes_agree_bitwise():
     """The scalar-cache route walks its slice in pairs of 8-source groups inside 256-source blocks with a ragged tail;
     the LDS route walks 64-source tiles.  Same arithmetic, same order: every source count around those boundaries
     must give the same bits on both routes, for long slices (W = 1), short ones (W = 16) and split/passes."""
-    counts = sorted(set(list(range(1, 40)) + [63, 64, 65, 71, 72, 73, 127, 128, 129, 247, 248, 249, 255, 256, 257, 263, 264,
-                                              265, 511, 512, 513, 519, 520, 1023, 1024, 1025, 1031, 2047, 2048, 2049, 2111]))
-    for m_want in counts:
+    for m_want in SWEEP_COUNTS:
         n = m_want + 37
         part, m = synth(n, 1.0, seed=m_want)
         part[m_want:, 6] = 0.0                       # exactly m_want sources, 37 massless receivers
         part, m = ob.partition(part)
         assert m == m_want
-        for knobs in (dict(k=1, w=1), dict(k=2, w=16), dict(k=2, w=4, split=3), dict(k=1, w=4, passes=2)):
+        for knobs in SWEEP_KNOBS:
             a = run(part, m, 2, 0.01, variant=0, **knobs)
             b = run(part, m, 2, 0.01, variant=1, unit=64, **knobs)   # same granule as the LDS route's whole tiles
             assert a.tobytes() == b.tobytes(), f"routes differ at {m_want} sources, {knobs}"
@@ -236,15 +242,14 @@ def test_fine_source_granules(unit):
     """Latency-bound launches slice the sources in granules of 8 / 16 / 32 instead of 64 (StepParams::unit): every
     source must still be added exactly once whatever the count, the split and the waves per workgroup -- checked against
     float64 at source counts around every granule, tile and block boundary, and against the 64-source granule."""
-    counts = [1, 7, 8, 9, 15, 16, 17, 31, 33, 63, 64, 65, 100, 127, 129, 250, 255, 256, 257, 263, 511, 520, 1000, 1031, 2049]
-    for m_want in counts:
+    for m_want in GRANULE_COUNTS:
         n = m_want + 70
         part, m = synth(n, 1.0, seed=1000 + m_want)
         part[m_want:, 6] = 0.0
         part, m = ob.partition(part)
         assert m == m_want
         coarse = run(part, m, 1, 0.01, k=1, w=1, unit=64)
-        for knobs in (dict(k=1, w=16), dict(k=2, w=4, split=3), dict(k=1, w=8, split=16), dict(k=2, w=16, passes=2), dict(k=1, w=1)):
+        for knobs in GRANULE_KNOBS:
             got = run(part, m, 1, 0.01, unit=unit, **knobs)
             acc64, mag = ob.acc_f64(part, m)
             err = np.abs(got[:, 4:6].astype(np.float64) - acc64)
