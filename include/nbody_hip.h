@@ -85,6 +85,9 @@ void SetSimulationData(SimPipeline *sim, const Particle *ps);
  *   - finite values stay within the stated tolerance.  A pair term whose factor G*m / (r * r^2)
  *     fp32 cannot hold -- r * r^2 beyond 3.4e38, or the factor below 1.2e-38 -- may come out as anything between 0 and
  *     its float64 value: the reference's form gives exactly 0 (G*m / inf), G*m * rsq * rsq^2 here gives 0 or a denormal;
+ *     a pair whose dist^2 + radius is a denormal (below 1.2e-38) is outside as well: v_rsq_f32 takes no denormal input, it
+ *     reads it as zero and returns +inf, so the term has the class of a coincident pair with no softening (tests/pair_cases.py
+ *     draws this line: every intermediate of the statement normal and finite; inside it, DESIGN.md section 5 "The pair term");
  *   - vel = vel0 + acc * dt and pos = pos0 + vel * dt hold in fp32 wherever the result is not NaN;
  *   - a particle that is no source (mass <= 0) cannot change a bit of any other particle, whatever it holds: the launch
  *     shape depends on the counts only, and a receiver's lanes, pads and neighbours are kept apart by selects, never by

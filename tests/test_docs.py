@@ -74,3 +74,14 @@ def test_the_summation_table_is_committed_and_cited():
     """DESIGN.md section 5 states the summation scheme per kernel family and cites one run's table of the witness tests."""
     assert os.path.exists(os.path.join(ROOT, "profiles", "r14_sum_witness.txt"))
     assert "profiles/r14_sum_witness.txt" in open(os.path.join(ROOT, "DESIGN.md")).read()
+
+
+def test_the_pair_budget_is_committed_and_cited():
+    """DESIGN.md section 5 derives the pair term's bound and cites one run's table of the pair tests; the files it promises exist."""
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    assert "**The pair term**" in design and "17u" in design and "5u" in design
+    for name in ("profiles/r15_pair_budget.txt", "tests/pair_cases.py", "tests/test_pair_cpu.py", "tests/test_gpu_pairs.py"):
+        assert os.path.exists(os.path.join(ROOT, name)) and name in design, name
+    assert "r15_pair_budget.txt" in open(os.path.join(ROOT, "profiles", "README.md")).read()
+    assert "test_gpu_pairs.py" in open(os.path.join(ROOT, "README.md")).read()
+    assert "profiles/r15_pair_budget.txt" in open(os.path.join(ROOT, "STATUS.md")).read()
