@@ -49,13 +49,17 @@ extern "C" {
 #define NB_ADAPT_CONTINUE 2u         /* GPU calls: go on from the previous adaptive call of this World / batch -- its clock and
                                         counts are kept on the device, span is measured from the call that started them, and
                                         the result is cumulative (the log is this call's).  Without a previous call: ignored */
+#define NB_ADAPT_LEAPFROG 4u         /* every step is a kick-drift-kick step (include/nbody_leapfrog.h) of the size the criterion
+                                        gives for the CURRENT acc: criterion, span clip, open(dt), force, close(dt).  Implies
+                                        NB_ADAPT_PRIME, which is applied only when acc is not already the state's own; an idle
+                                        step is open(0), force, close(0) */
 #define NB_ADAPT_MAX_STEPS (1u << 20) /* steps of one call */
 
 typedef struct NbAdaptive {
     float eta;      /* accuracy parameter, finite and > 0 */
     float dt_min;   /* 0 <= dt_min <= dt_max */
     float dt_max;   /* finite and > 0 */
-    uint32_t flags; /* NB_ADAPT_PRIME | NB_ADAPT_CONTINUE, or 0 */
+    uint32_t flags; /* NB_ADAPT_PRIME | NB_ADAPT_CONTINUE | NB_ADAPT_LEAPFROG, or 0 */
     double span;    /* time one Update call may cover, > 0; +inf: no clip.  The Advance calls ignore it (they take a span) */
     uint32_t chunk; /* Advance calls only: most steps of one inner call; 0 means 64 */
     uint32_t reserved;

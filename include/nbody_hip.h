@@ -599,6 +599,35 @@ void nb_hip_timestep(SimPipeline *sim, const NbAdaptive *cfg, float *dt);
 void nb_hip_ensemble_adaptive_steps(SimBatch *batch, uint32_t n, const NbAdaptive *cfg, float *dt_log /* [n][count] */,
                                  NbAdaptiveResult *out /* [count] */);
 
+/*
+ * Leapfrog (kick-drift-kick) steps (definitions: include/nbody_leapfrog.h; the statement: nbody_amd/csrc/leapfrog_common.h;
+ * kernels: nbody_amd/csrc/leapfrog.hip).
+ *   nb_hip_leapfrog_steps         n steps of size dt; blocking
+ *   nb_hip_leapfrog_steps_async   the same, enqueue only (nb_hip_sync waits)
+ *   nb_hip_ensemble_leapfrog         n steps of every member of a SimBatch, one dt for all; blocking
+ *   nb_hip_ensemble_leapfrog_dts     the same with dt[count], one step size per member
+ * A step is open(dt), exactly the launches of a one-step PerformSimUpdate(sim, 1, 0) / nb_hip_batch_update(batch, 1, 0), and
+ * close(dt); between two force launches one pass closes the step behind it and opens the next.  The step kernels' own step
+ * size holds 0 during the call and the step size cached on the host is dropped, so the next fixed-step call uploads its own.
+ * The object remembers whether acc is the acceleration of the state it holds: true after a leapfrog call (an adaptive call
+ * with NB_ADAPT_LEAPFROG included), false after SetSimulationData / nb_hip_batch_set_data, any Euler update, traced update or
+ * Euler adaptive call.  A call that finds it false first runs one one-step dt = 0 update, so the first call of a sequence
+ * costs n + 1 force evaluations and every following one n.  The contract: the state afterwards is, bit for bit, what the
+ * caller gets from GetSimulationData -> open in float32 -> SetSimulationData -> PerformSimUpdate(sim, 1, 0) ->
+ * GetSimulationData -> close -> SetSimulationData per step, on every launch route, and n steps in one call have the bits of
+ * the same steps in any split into calls.  The adaptive calls above honour NB_ADAPT_LEAPFROG: per step the criterion on the
+ * current acc, the span clip, open(dt_i), force, close(dt_i); dt_log[i] is the host criterion of the state before step i
+ * and the state that of nb_hip_leapfrog_steps(sim, 1, dt_log[i]) for i = 0 .. n - 1.
+ * Chains of leapfrog steps are plain launches: no hipGraph, no one-workgroup chain.  Abort, before any device is touched,
+ * for a NULL argument, for sharded pipelines and ragged ensembles, and before the first SetSimulationData /
+ * nb_hip_batch_set_data.  n = 0 does nothing.  Added WITHOUT a version bump: detect them by symbol (dlsym
+ * "nb_hip_leapfrog_steps").
+ */
+void nb_hip_leapfrog_steps(SimPipeline *sim, uint32_t n, float dt);
+void nb_hip_leapfrog_steps_async(SimPipeline *sim, uint32_t n, float dt);
+void nb_hip_ensemble_leapfrog(SimBatch *batch, uint32_t n, float dt);
+void nb_hip_ensemble_leapfrog_dts(SimBatch *batch, uint32_t n, const float *dt /* [count] */);
+
 /* Library/ABI version: major*10000 + minor*100 + patch. */
 int nb_hip_version(void);
 

@@ -112,11 +112,12 @@ class NbAdaptiveResult(C.Structure):
 
 NB_ADAPT_PRIME = 1      # include/nbody_adaptive.h
 NB_ADAPT_CONTINUE = 2
+NB_ADAPT_LEAPFROG = 4   # every step a kick-drift-kick step (include/nbody_leapfrog.h)
 
 
-def adaptive_cfg(eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, chunk=0, resume=False):
+def adaptive_cfg(eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, chunk=0, resume=False, leapfrog=False):
     """NbAdaptive from the keyword arguments the adaptive methods share; eta and dt_max have no default."""
-    flags = (NB_ADAPT_PRIME if prime else 0) | (NB_ADAPT_CONTINUE if resume else 0)
+    flags = (NB_ADAPT_PRIME if prime else 0) | (NB_ADAPT_CONTINUE if resume else 0) | (NB_ADAPT_LEAPFROG if leapfrog else 0)
     return NbAdaptive(float(eta), float(dt_min), float(dt_max), flags, float(span), int(chunk), 0)
 
 
@@ -210,6 +211,10 @@ HIP_API = {
     "nb_hip_adaptive_collect": (None, [C.c_void_p, C.c_void_p, C.POINTER(NbAdaptiveResult)]),
     "nb_hip_timestep": (None, [C.c_void_p, C.POINTER(NbAdaptive), C.POINTER(C.c_float)]),
     "nb_hip_ensemble_adaptive_steps": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.c_void_p]),
+    "nb_hip_leapfrog_steps": (None, [C.c_void_p, C.c_uint32, C.c_float]),
+    "nb_hip_leapfrog_steps_async": (None, [C.c_void_p, C.c_uint32, C.c_float]),
+    "nb_hip_ensemble_leapfrog": (None, [C.c_void_p, C.c_uint32, C.c_float]),
+    "nb_hip_ensemble_leapfrog_dts": (None, [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]),
     "nb_hip_version": (C.c_int, []),
 }
 
@@ -231,12 +236,14 @@ TUNE_API = {
     "nb_hip_ensemble_render_mode": (None, [C.c_void_p, C.c_int]),
     "nb_hip_ensemble_last_render_info": (None, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]),
     "nb_hip_ensemble_last_render_ms": (C.c_double, [C.c_void_p]),
+    "nb_hip_last_leapfrog_info": (None, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "nb_hip_ensemble_last_leapfrog_info": (None, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
 }
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
 # include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h +
-# include/nbody_adaptive.h
+# include/nbody_adaptive.h + include/nbody_leapfrog.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -289,6 +296,11 @@ NBODY_API = {
     "AdvanceWorld_GPU": (None, [C.c_void_p, C.c_double, C.POINTER(NbAdaptive), C.c_uint32, C.c_void_p, C.POINTER(NbAdaptiveResult)]),
     "UpdateWorldBatch_GPU_Adaptive": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.c_void_p]),
     "AdvanceWorldBatch_GPU": (None, [C.c_void_p, C.c_double, C.POINTER(NbAdaptive), C.c_uint32, C.c_void_p, C.c_void_p]),
+    # include/nbody_leapfrog.h
+    "UpdateWorld_GPU_Leapfrog": (None, [C.c_void_p, C.c_float, C.c_uint32]),
+    "UpdateWorld_CPU_Leapfrog": (None, [C.c_void_p, C.c_float, C.c_uint32]),
+    "UpdateWorldBatch_GPU_Leapfrog": (None, [C.c_void_p, C.c_float, C.c_uint32]),
+    "UpdateWorldBatch_GPU_Leapfrog_dts": (None, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32]),
 }
 
 _hip = None
@@ -501,16 +513,30 @@ class SimPipeline:
     def step_async(self, n, dt):
         hip_lib().nb_hip_step_async(self._h, n, dt)
 
-    def update_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False):
+    def update_leapfrog(self, n, dt):
+        """nb_hip_leapfrog_steps: blocking n kick-drift-kick steps of size dt (include/nbody_leapfrog.h)."""
+        hip_lib().nb_hip_leapfrog_steps(self._h, n, dt)
+
+    def update_leapfrog_async(self, n, dt):
+        """nb_hip_leapfrog_steps_async: enqueue only; sync() waits."""
+        hip_lib().nb_hip_leapfrog_steps_async(self._h, n, dt)
+
+    def last_leapfrog_info(self):
+        """Tuning hook: (force launches of the last leapfrog call, whether it primed)."""
+        k, primed = C.c_uint32(0), C.c_int(0)
+        hip_lib().nb_hip_last_leapfrog_info(self._h, C.byref(k), C.byref(primed))
+        return int(k.value), bool(primed.value)
+
+    def update_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False, leapfrog=False):
         """nb_hip_adaptive_steps: n steps, each of the size the criterion of include/nbody_adaptive.h gives for the state
         before it, chosen on the device.  Returns (dt_log float32 (n,), result dict)."""
-        cfg, res, log = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume), NbAdaptiveResult(), np.zeros(n, dtype=np.float32)
+        cfg, res, log = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume, leapfrog=leapfrog), NbAdaptiveResult(), np.zeros(n, dtype=np.float32)
         hip_lib().nb_hip_adaptive_steps(self._h, n, C.byref(cfg), log.ctypes.data, C.byref(res))
         return log, res.as_dict()
 
-    def update_adaptive_async(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False):
+    def update_adaptive_async(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False, leapfrog=False):
         """nb_hip_adaptive_steps_async: enqueue only; adaptive_collect(n) fetches the log and the result."""
-        cfg = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume)
+        cfg = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume, leapfrog=leapfrog)
         hip_lib().nb_hip_adaptive_steps_async(self._h, n, C.byref(cfg))
 
     def adaptive_collect(self, n):
@@ -792,10 +818,23 @@ class SimBatch:
     def step_async(self, n, dts):
         hip_lib().nb_hip_batch_step_async(self._h, n, _dt_array(dts, self.count).ctypes.data_as(C.POINTER(C.c_float)))
 
-    def update_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False):
+    def update_leapfrog(self, n, dt):
+        """Blocking n kick-drift-kick steps of every member (include/nbody_leapfrog.h); dt: one step size, or one per member."""
+        if np.ndim(dt) == 0:
+            hip_lib().nb_hip_ensemble_leapfrog(self._h, n, float(dt))
+        else:
+            hip_lib().nb_hip_ensemble_leapfrog_dts(self._h, n, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)))
+
+    def last_leapfrog_info(self):
+        """Tuning hook: (force launches of the last leapfrog call, whether it primed)."""
+        k, primed = C.c_uint32(0), C.c_int(0)
+        hip_lib().nb_hip_ensemble_last_leapfrog_info(self._h, C.byref(k), C.byref(primed))
+        return int(k.value), bool(primed.value)
+
+    def update_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, resume=False, leapfrog=False):
         """nb_hip_ensemble_adaptive_steps: n steps, every member with its own step size at every step, chosen on the device.
         Returns (dt_log float32 (n, B), list of B result dicts)."""
-        cfg, res = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume), (NbAdaptiveResult * self.count)()
+        cfg, res = adaptive_cfg(eta, dt_max, dt_min, span, prime, resume=resume, leapfrog=leapfrog), (NbAdaptiveResult * self.count)()
         log = np.zeros((n, self.count), dtype=np.float32)
         hip_lib().nb_hip_ensemble_adaptive_steps(self._h, n, C.byref(cfg), log.ctypes.data, C.byref(res))
         return log, [r.as_dict() for r in res]
@@ -973,17 +1012,24 @@ class WorldBatch:
         else:
             nbody_lib().UpdateWorldBatch_GPU_dts(self._h, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)), n)
 
-    def update_gpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False):
+    def update_gpu_leapfrog(self, dt, n):
+        """UpdateWorldBatch_GPU_Leapfrog(_dts) (include/nbody_leapfrog.h); dt: one step size, or one per member."""
+        if np.ndim(dt) == 0:
+            nbody_lib().UpdateWorldBatch_GPU_Leapfrog(self._h, float(dt), n)
+        else:
+            nbody_lib().UpdateWorldBatch_GPU_Leapfrog_dts(self._h, _dt_array(dt, self.count).ctypes.data_as(C.POINTER(C.c_float)), n)
+
+    def update_gpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, leapfrog=False):
         """UpdateWorldBatch_GPU_Adaptive (include/nbody_adaptive.h): (dt_log float32 (n, B), list of B result dicts)."""
-        cfg, res = adaptive_cfg(eta, dt_max, dt_min, span, prime), (NbAdaptiveResult * self.count)()
+        cfg, res = adaptive_cfg(eta, dt_max, dt_min, span, prime, leapfrog=leapfrog), (NbAdaptiveResult * self.count)()
         log = np.zeros((n, self.count), dtype=np.float32)
         nbody_lib().UpdateWorldBatch_GPU_Adaptive(self._h, n, C.byref(cfg), log.ctypes.data, C.byref(res))
         return log, [r.as_dict() for r in res]
 
-    def advance_gpu(self, span, eta, dt_max, dt_min=0.0, prime=False, chunk=0, max_steps=4096):
+    def advance_gpu(self, span, eta, dt_max, dt_min=0.0, prime=False, chunk=0, max_steps=4096, leapfrog=False):
         """AdvanceWorldBatch_GPU: every member covers `span` (or max_steps steps are made); (dt_log float32 (steps made, B)
         with the idle steps of members that finished early, list of B result dicts)."""
-        cfg, res = adaptive_cfg(eta, dt_max, dt_min, prime=prime, chunk=chunk), (NbAdaptiveResult * self.count)()
+        cfg, res = adaptive_cfg(eta, dt_max, dt_min, prime=prime, chunk=chunk, leapfrog=leapfrog), (NbAdaptiveResult * self.count)()
         log = np.zeros((max_steps, self.count), dtype=np.float32)
         nbody_lib().AdvanceWorldBatch_GPU(self._h, float(span), C.byref(cfg), max_steps, log.ctypes.data, C.byref(res))
         made = max((r.steps + r.idle_steps for r in res), default=0)
@@ -1130,13 +1176,21 @@ class World:
         fn(self._h, n, C.byref(cfg), log.ctypes.data, C.byref(res))
         return log, res.as_dict()
 
-    def update_gpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False):
-        """UpdateWorld_GPU_Adaptive (include/nbody_adaptive.h): (dt_log float32 (n,), result dict)."""
-        return self._adaptive(nbody_lib().UpdateWorld_GPU_Adaptive, n, adaptive_cfg(eta, dt_max, dt_min, span, prime))
+    def update_gpu_leapfrog(self, dt, n):
+        """UpdateWorld_GPU_Leapfrog (include/nbody_leapfrog.h): n kick-drift-kick steps of size dt on the device."""
+        nbody_lib().UpdateWorld_GPU_Leapfrog(self._h, dt, n)
 
-    def update_cpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False):
+    def update_cpu_leapfrog(self, dt, n):
+        """UpdateWorld_CPU_Leapfrog: the same on the host cores."""
+        nbody_lib().UpdateWorld_CPU_Leapfrog(self._h, dt, n)
+
+    def update_gpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, leapfrog=False):
+        """UpdateWorld_GPU_Adaptive (include/nbody_adaptive.h): (dt_log float32 (n,), result dict)."""
+        return self._adaptive(nbody_lib().UpdateWorld_GPU_Adaptive, n, adaptive_cfg(eta, dt_max, dt_min, span, prime, leapfrog=leapfrog))
+
+    def update_cpu_adaptive(self, n, eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, leapfrog=False):
         """UpdateWorld_CPU_Adaptive: the same on the host cores."""
-        return self._adaptive(nbody_lib().UpdateWorld_CPU_Adaptive, n, adaptive_cfg(eta, dt_max, dt_min, span, prime))
+        return self._adaptive(nbody_lib().UpdateWorld_CPU_Adaptive, n, adaptive_cfg(eta, dt_max, dt_min, span, prime, leapfrog=leapfrog))
 
     def timestep(self, eta, dt_max, dt_min=0.0):
         """GetWorldTimestep: the criterion alone (no span clip) for the newest state; changes nothing."""
@@ -1144,10 +1198,10 @@ class World:
         nbody_lib().GetWorldTimestep(self._h, C.byref(cfg), C.byref(dt))
         return float(dt.value)
 
-    def advance_gpu(self, span, eta, dt_max, dt_min=0.0, prime=False, chunk=0, max_steps=4096):
+    def advance_gpu(self, span, eta, dt_max, dt_min=0.0, prime=False, chunk=0, max_steps=4096, leapfrog=False):
         """AdvanceWorld_GPU: adaptive calls until `span` is covered (or max_steps steps are made); (dt_log float32 of the
         steps made, idle ones included, result dict)."""
-        cfg, res = adaptive_cfg(eta, dt_max, dt_min, prime=prime, chunk=chunk), NbAdaptiveResult()
+        cfg, res = adaptive_cfg(eta, dt_max, dt_min, prime=prime, chunk=chunk, leapfrog=leapfrog), NbAdaptiveResult()
         log = np.zeros(max_steps, dtype=np.float32)
         nbody_lib().AdvanceWorld_GPU(self._h, float(span), C.byref(cfg), max_steps, log.ctypes.data, C.byref(res))
         return log[:res.steps + res.idle_steps].copy(), res.as_dict()

@@ -29,6 +29,7 @@
 #include "batch_diag.h"
 #include "batch_render.h"
 #include "diag_sums.h"
+#include "leapfrog.h"
 #include "nbody_hip_tuning.h"
 #include "render_common.h"
 #include "timestep.h"
@@ -118,6 +119,13 @@ struct SimBatch {
     size_t adapt_bytes = 0;
     bool adapt_armed = false;   // the records hold a call to continue (NB_ADAPT_CONTINUE)
     std::vector<char> adapt_host;
+
+    // leapfrog steps (kernels: leapfrog.hip): the step sizes of the kick / drift passes, [2][count] -- a fixed-step call uses
+    // the first row, an adaptive one alternates so that one launch can close step i - 1 and open step i
+    float *lf_dt = nullptr;
+    bool acc_current = false;        // acc = F(x) of the state held: true after a leapfrog call, false after anything else that moves it
+    uint32_t lf_force_launches = 0;  // force evaluations of the last leapfrog call (nb_hip_ensemble_last_leapfrog_info)
+    bool lf_primed = false;          // ... and whether it had to run one first
 };
 
 namespace {
@@ -282,6 +290,7 @@ void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
     NB_ASSERT(s->has_data, "ensemble update before nb_hip_batch_set_data");
     if (n == 0) return;
     use_device();
+    s->acc_current = false;   // an Euler step leaves the acc of the state before it
     upload_dts(s, dt, uniform);
     nb::BatchParams p = step_params(s);
     ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
@@ -289,6 +298,67 @@ void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
     ASSERT_HIP(hipGetLastError(), "ensemble launch (%u members of %u particles, %u steps)", s->count, s->n, n);
     ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
     s->timed = true;
+}
+
+// ---- leapfrog steps: the passes of leapfrog.hip around the launches of a one-step dt = 0 update ----------------------------
+
+// one pass over every member: close with row `close_row` of lf_dt, open (kick + drift of the latest positions) with `open_row`
+void launch_kicks(SimBatch *s, bool close, bool open, uint32_t close_row, uint32_t open_row) {
+    nb::LeapfrogParams lf;
+    memset(&lf, 0, sizeof lf);
+    lf.pos = s->pos[s->cur];
+    lf.vel = s->vel;
+    lf.acc = s->acc;
+    lf.dt_close = s->lf_dt + (size_t)close_row * s->count;
+    lf.dt_open = s->lf_dt + (size_t)open_row * s->count;
+    lf.n = s->n;
+    lf.stride = s->stride;
+    nb::launch_leapfrog(s->stream, lf, close, open, s->count);
+}
+
+void launch_force(SimBatch *s, nb::BatchParams &p) {
+    launch_steps(s, p, 1);
+    s->lf_force_launches++;
+}
+
+// the step kernels' dt[count] holds 0 for the whole call; one unlogged, uncounted force evaluation first when acc is not
+// known to be the members' own
+void begin_leapfrog(SimBatch *s, nb::BatchParams &p) {
+    if (!s->lf_dt) s->lf_dt = dev_alloc<float>(2 * (size_t)s->count);
+    const float zero = 0.0f;
+    upload_dts(s, &zero, true);
+    s->lf_force_launches = 0;
+    s->lf_primed = !s->acc_current;
+    if (s->lf_primed) launch_force(s, p);
+}
+
+// n kick-drift-kick steps, every member with its own step size: open, force, one close + open pass and a force launch per
+// further step, close
+void enqueue_leapfrog(SimBatch *s, uint32_t n, const float *dt, bool uniform, const char *what) {
+    NB_ASSERT(s != nullptr && dt != nullptr, "%s: NULL argument", what);
+    NB_ASSERT(!s->ragged, "%s: leapfrog steps of ragged ensembles (members of different sizes) are not supported", what);
+    if (n == 0) return;
+    NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
+    use_device();
+    nb::BatchParams p = step_params(s);
+    begin_leapfrog(s, p);
+    if (uniform) {
+        nb::launch_batch_fill(s->stream, s->lf_dt, s->count, dt[0]);
+    } else {
+        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before a per-member step-size upload");
+        ASSERT_HIP(hipMemcpy(s->lf_dt, dt, (size_t)s->count * sizeof(float), hipMemcpyHostToDevice), "H2D of %u step sizes", s->count);
+    }
+    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+    for (uint32_t i = 0; i < n; i++) {
+        launch_kicks(s, i > 0, true, 0, 0);
+        launch_force(s, p);
+    }
+    launch_kicks(s, true, false, 0, 0);
+    ASSERT_HIP(hipGetLastError(), "leapfrog ensemble launches (%u members of %u particles, %u steps)", s->count, s->n, n);
+    ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
+    s->timed = true;
+    s->dt_valid = false;   // the next fixed-step update uploads its own step sizes afresh
+    s->acc_current = true;
 }
 
 void read_back(SimBatch *s, uint32_t first, uint32_t members, Particle *ps) {
@@ -389,7 +459,10 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
     const uint32_t records = nb_hip_ensemble_trace_rows(n, every);
     NB_ASSERT(s->has_data, "traced ensemble update before nb_hip_batch_set_data");
     use_device();
-    if (n > 0) upload_dts(s, dt, uniform);
+    if (n > 0) {
+        upload_dts(s, dt, uniform);
+        s->acc_current = false;   // Euler steps leave the acc of the state before them
+    }
     constexpr size_t Q = NB_DIAG_SUMS;
     const size_t pitch = (size_t)s->count * Q;
     double *rows = grown(s, s->trace, s->trace_cap, (size_t)records * pitch);
@@ -673,6 +746,7 @@ void nb_hip_batch_destroy(SimBatch *s) {
         if (s->render_rgba) dev_free(s->render_rgba);
         if (s->render_discs) dev_free(s->render_discs);
         if (s->adapt) dev_free(s->adapt);
+        if (s->lf_dt) dev_free(s->lf_dt);
         for (auto &e : s->ev_render)
             if (e) ASSERT_HIP(hipEventDestroy(e), "event");
         for (auto &e : s->ev_diag)
@@ -692,6 +766,7 @@ void nb_hip_batch_set_data(SimBatch *s, const Particle *ps) {
     }
     use_device();
     s->cur = 0;
+    s->acc_current = false;   // the uploaded acc is the caller's: a leapfrog call evaluates its own first
     ASSERT_HIP(hipMemcpyAsync(s->aos, ps, (size_t)s->offsets[s->count] * sizeof(Particle), hipMemcpyHostToDevice, s->stream),
                "H2D of %u members' particles (up to %u each)", s->count, s->n);
     if (s->ragged)
@@ -732,6 +807,22 @@ void nb_hip_batch_update(SimBatch *s, uint32_t n, float dt) {
 void nb_hip_batch_update_dts(SimBatch *s, uint32_t n, const float *dt) {
     enqueue(s, n, dt, false);
     nb_hip_batch_sync(s);
+}
+
+void nb_hip_ensemble_leapfrog(SimBatch *s, uint32_t n, float dt) {
+    enqueue_leapfrog(s, n, &dt, true, "nb_hip_ensemble_leapfrog");
+    if (n > 0) nb_hip_batch_sync(s);
+}
+
+void nb_hip_ensemble_leapfrog_dts(SimBatch *s, uint32_t n, const float *dt) {
+    enqueue_leapfrog(s, n, dt, false, "nb_hip_ensemble_leapfrog_dts");
+    if (n > 0) nb_hip_batch_sync(s);
+}
+
+void nb_hip_ensemble_last_leapfrog_info(const SimBatch *s, uint32_t *force_launches, int *primed) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (force_launches) *force_launches = s->lf_force_launches;
+    if (primed) *primed = s->lf_primed ? 1 : 0;
 }
 
 // n adaptive steps of every member: per step the criterion launch (one workgroup per member writes dt[b]), then the launches
@@ -779,16 +870,33 @@ void nb_hip_ensemble_adaptive_steps(SimBatch *s, uint32_t n, const NbAdaptive *c
     nb::BatchParams p = step_params(s);
     if (!(cfg->flags & NB_ADAPT_CONTINUE) || !s->adapt_armed) nb::launch_arm(s->stream, t.state, s->count);
     s->adapt_armed = true;
-    if (cfg->flags & NB_ADAPT_PRIME) {   // one dt = 0 step of the ordinary path: acc becomes the state's own
-        const float zero = 0.0f;
-        upload_dts(s, &zero, true);
-        launch_steps(s, p, 1);
-    }
-    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
-    for (uint32_t i = 0; i < n; i++) {
-        t.log = log ? log + (size_t)i * s->count : nullptr;
-        nb::launch_ensemble_timestep(s->stream, t, s->count);
-        launch_steps(s, p, 1);
+    if (cfg->flags & NB_ADAPT_LEAPFROG) {
+        // per step: the criterion on the members' own acc writes dt_i[count] to one of two alternating rows, one pass closes
+        // step i - 1 with the other row and opens step i with this one, then the force launch; a last pass closes step n - 1
+        begin_leapfrog(s, p);
+        ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+        for (uint32_t i = 0; i < n; i++) {
+            t.log = log ? log + (size_t)i * s->count : nullptr;
+            t.dt_out = s->lf_dt + (size_t)(i & 1) * s->count;
+            nb::launch_ensemble_timestep(s->stream, t, s->count);
+            launch_kicks(s, i > 0, true, (i & 1) ^ 1, i & 1);
+            launch_force(s, p);
+        }
+        launch_kicks(s, true, false, (n - 1) & 1, 0);
+        s->acc_current = true;
+    } else {
+        s->acc_current = false;   // Euler steps leave the acc of the state before them
+        if (cfg->flags & NB_ADAPT_PRIME) {   // one dt = 0 step of the ordinary path: acc becomes the state's own
+            const float zero = 0.0f;
+            upload_dts(s, &zero, true);
+            launch_steps(s, p, 1);
+        }
+        ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+        for (uint32_t i = 0; i < n; i++) {
+            t.log = log ? log + (size_t)i * s->count : nullptr;
+            nb::launch_ensemble_timestep(s->stream, t, s->count);
+            launch_steps(s, p, 1);
+        }
     }
     ASSERT_HIP(hipGetLastError(), "adaptive ensemble launches (%u members of %u particles, %u steps)", s->count, s->n, n);
     ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");

@@ -105,6 +105,12 @@ void nb_hip_ensemble_render_mode(SimBatch *batch, int mode);
 void nb_hip_ensemble_last_render_info(const SimBatch *batch, int *tile_path, uint32_t *launches);
 double nb_hip_ensemble_last_render_ms(SimBatch *batch);
 
+/* The last leapfrog call (nb_hip_leapfrog_steps, an adaptive call with NB_ADAPT_LEAPFROG; nb_hip_ensemble_leapfrog and the
+ * ensemble's adaptive call for a SimBatch): the force evaluations it enqueued -- steps, plus one when it primed -- and
+ * whether it primed, i.e. acc was not known to be the state's own.  Both 0 before the first call; either pointer may be NULL. */
+void nb_hip_last_leapfrog_info(const SimPipeline *sim, uint32_t *force_launches, int *primed);
+void nb_hip_ensemble_last_leapfrog_info(const SimBatch *batch, uint32_t *force_launches, int *primed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -398,6 +398,7 @@ void set_simulation_data(SimPipeline *s, const Particle *ps) {
     hipStream_t st = s->stream;
     s->cur = 0;
     s->host_current = false;
+    s->acc_current = false;   // the uploaded acc is the caller's: a leapfrog call evaluates its own first
     s->updates_since_get = 0;
     zero_tickets(s);   // a new state starts from clean tile tickets whatever the previous launches did
     // The noted, page-locked array is readable from the device: the split kernel pulls the records over PCIe itself
@@ -578,6 +579,25 @@ void nb_hip_timestep(SimPipeline *s, const NbAdaptive *cfg, float *dt) {
                               s->stream),
                "D2H of the step size");
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_timestep");
+}
+
+// ---- leapfrog steps (include/nbody_leapfrog.h; kernels: leapfrog.hip; the launches: step_chain.hip enqueue_leapfrog) ----
+
+void nb_hip_leapfrog_steps_async(SimPipeline *s, uint32_t n, float dt) {
+    check_leapfrog(s, n, "nb_hip_leapfrog_steps_async");
+    enqueue_leapfrog(s, n, dt);
+}
+
+void nb_hip_leapfrog_steps(SimPipeline *s, uint32_t n, float dt) {
+    check_leapfrog(s, n, "nb_hip_leapfrog_steps");
+    enqueue_leapfrog(s, n, dt);
+    if (n > 0) nb_hip_sync(s);
+}
+
+void nb_hip_last_leapfrog_info(const SimPipeline *s, uint32_t *force_launches, int *primed) {
+    NB_ASSERT(s != nullptr, "NULL pipeline");
+    if (force_launches) *force_launches = s->lf_force_launches;
+    if (primed) *primed = s->lf_primed ? 1 : 0;
 }
 
 double nb_hip_last_step_ms(SimPipeline *s, uint32_t *launches) {

@@ -16,6 +16,7 @@
 //   field.hip        the potential and the acceleration at probe points and as maps over a view (nb_hip_potential_at,
 //                    nb_hip_potential_map, nb_hip_acceleration_at, nb_hip_acceleration_map): one sampler, two pair statements
 //   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
+//   leapfrog.hip     the kick / drift passes of a kick-drift-kick step around a dt = 0 force launch (leapfrog.h, leapfrog_common.h)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -328,6 +329,13 @@ struct SimPipeline {
     bool adapt_armed = false;        // the call record holds a call to continue (NB_ADAPT_CONTINUE)
     uint32_t adapt_logged = 0;       // steps of the last adaptive call: what nb_hip_adaptive_collect copies back
     std::vector<char> adapt_host;    // where that copy lands
+
+    // leapfrog steps (step_chain.hip enqueue_leapfrog; kernels: leapfrog.hip).  Their step sizes live in two words of the
+    // adaptive head (LEAPFROG_WORDS): a fixed-step call uses the first, an adaptive one alternates so that one launch can
+    // close step i - 1 and open step i.
+    bool acc_current = false;        // acc = F(x) of the state held: true after a leapfrog call, false after anything else that moves it
+    uint32_t lf_force_launches = 0;  // force evaluations of the last leapfrog call (nb_hip_last_leapfrog_info)
+    bool lf_primed = false;          // ... and whether it had to run one first
 };
 
 namespace nbi {
@@ -351,10 +359,14 @@ void host_allgather(SimPipeline *s, void *dev_base, size_t bytes_per_rank, hipSt
 void enqueue_steps(SimPipeline *s, uint32_t n, float dt);  // what PerformSimUpdate / nb_hip_step_async enqueue
 // adaptive steps (include/nbody_hip.h nb_hip_adaptive_steps): per step the criterion launch, then the launches of a one-step
 // call without its dt upload; enqueue only.  check_adaptive aborts on a bad call before anything touches a device.
-constexpr size_t ADAPT_HEAD = 128;   // bytes: AdaptState of the call at 0, of nb_hip_timestep at 32, its result at 64
+constexpr size_t ADAPT_HEAD = 128;   // bytes: AdaptState of the call at 0, of nb_hip_timestep at 32, its result at 64, leapfrog words at 96
+constexpr size_t LEAPFROG_WORDS = 96;   // offset of the two step-size words of the leapfrog passes in that head
 void check_adaptive(const SimPipeline *s, uint32_t n, const NbAdaptive *cfg, const char *what);
 void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg);
 void enqueue_timestep_peek(SimPipeline *s, const NbAdaptive *cfg);   // the criterion alone into the head's result slot
+// leapfrog steps (include/nbody_hip.h nb_hip_leapfrog_steps): open, a dt = 0 force launch, close per step; enqueue only
+void check_leapfrog(const SimPipeline *s, uint32_t n, const char *what);
+void enqueue_leapfrog(SimPipeline *s, uint32_t n, float dt);
 
 // ---- diagnostics.hip -----------------------------------------------------------------------------------------
 

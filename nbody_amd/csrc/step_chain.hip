@@ -9,6 +9,7 @@
 //   * sharded pipelines add the per-step in-place all-gather of the new source positions (RCCL, a local group, or
 //     a caller-supplied host transport), in-stream or overlapped with the own-shard launch.
 #include "pipeline_internal.h"
+#include "leapfrog.h"
 #include "timestep.h"
 #include "timestep_common.h"
 
@@ -591,6 +592,7 @@ void enqueue_steps(SimPipeline *s, uint32_t n, float dt) {
     s->detail_steps = 0;
     s->fused_steps = 0;
     s->host_current = false;
+    s->acc_current = false;   // an Euler step leaves the acc of the state before it
     upload_dt(s, dt);
     if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_begin, s->stream), "record begin");
     if (!s->sharded)
@@ -645,6 +647,78 @@ nb::TimestepParams timestep_params(const SimPipeline *s, const NbAdaptive *cfg) 
     return p;
 }
 
+// the two step-size words of the leapfrog passes (the head exists: grow_adapt ran)
+float *leapfrog_words(SimPipeline *s) { return reinterpret_cast<float *>(static_cast<char *>(s->adapt) + LEAPFROG_WORDS); }
+
+nb::LeapfrogParams leapfrog_params(const SimPipeline *s) {
+    nb::LeapfrogParams p;
+    memset(&p, 0, sizeof p);
+    // the latest positions; an unsharded pipeline's sources are this array itself (whole_step: src_pos[b] == pos[b]), so the
+    // drift leaves no second copy behind
+    p.pos = s->pos[s->cur];
+    p.vel = s->vel;
+    p.acc = s->acc;
+    p.n = s->n_real;
+    return p;
+}
+
+// what a one-step dt = 0 update launches: the step kernels' dt word holds 0 for the whole call
+void launch_force(SimPipeline *s, nb::LaunchShape sh) {
+    launch_step(s, sh, whole_step(s, s->cur, 0.0f), s->stream);
+    s->cur ^= 1;
+    s->lf_force_launches++;
+}
+
+// the unlogged, uncounted force evaluation a leapfrog call starts with when acc is not the state's own
+void prime_leapfrog(SimPipeline *s, nb::LaunchShape sh) {
+    s->lf_force_launches = 0;
+    s->lf_primed = !s->acc_current;
+    if (s->lf_primed) launch_force(s, sh);
+}
+
+void begin_call(SimPipeline *s) {
+    s->pool.used = 0;
+    s->kernel_iv.clear();
+    s->comm_iv.clear();
+    s->detail_steps = 0;
+    s->fused_steps = 0;
+    s->host_current = false;
+}
+
+void end_timed_call(SimPipeline *s, uint32_t n) {
+    if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_end, s->stream), "record end");
+    s->timed = s->timing != 0;
+    s->timed_launches = n * passes_for(s, whole_step(s, s->cur, 0.0f));
+    s->timed_finish_launches = s->last_shape.split > 1 && !fused_finish_applies(s, s->last_shape) ? s->timed_launches : 0;
+    s->dt_valid = false;   // the next fixed-step call uploads its own step size afresh
+}
+
+// Adaptive leapfrog (NB_ADAPT_LEAPFROG): per step the criterion on the state's own acc writes dt_i to one of two alternating
+// words, one pass closes step i - 1 with the other word and opens step i with this one, then the force launch; a last pass
+// closes step n - 1.
+void enqueue_adaptive_leapfrog(SimPipeline *s, uint32_t n, nb::TimestepParams p, float *log, nb::LaunchShape sh) {
+    float *words = leapfrog_words(s);
+    upload_dt(s, 0.0f);
+    prime_leapfrog(s, sh);
+    if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_begin, s->stream), "record begin");
+    for (uint32_t i = 0; i < n; i++) {
+        p.log = log + i;
+        p.dt_out = words + (i & 1);
+        nb::launch_timestep(s->stream, p);
+        nb::LeapfrogParams lf = leapfrog_params(s);
+        lf.dt_close = words + ((i & 1) ^ 1);
+        lf.dt_open = words + (i & 1);
+        nb::launch_leapfrog(s->stream, lf, i > 0, true, 0);
+        launch_force(s, sh);
+    }
+    nb::LeapfrogParams lf = leapfrog_params(s);
+    lf.dt_close = words + ((n - 1) & 1);
+    nb::launch_leapfrog(s->stream, lf, true, false, 0);
+    ASSERT_HIP(hipGetLastError(), "adaptive leapfrog launches (%u steps, %u particles)", n, s->n_real);
+    end_timed_call(s, n);
+    s->acc_current = true;
+}
+
 }  // namespace
 
 void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg) {
@@ -652,12 +726,7 @@ void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg) {
     if (s->slots == 0 || n == 0) return;
     use_device();
     grow_adapt(s, n);
-    s->pool.used = 0;
-    s->kernel_iv.clear();
-    s->comm_iv.clear();
-    s->detail_steps = 0;
-    s->fused_steps = 0;
-    s->host_current = false;
+    begin_call(s);
     char *head = static_cast<char *>(s->adapt);
     nb::TimestepParams p = timestep_params(s, cfg);
     p.state = reinterpret_cast<nb::AdaptState *>(head);
@@ -667,6 +736,12 @@ void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg) {
     if (!(cfg->flags & NB_ADAPT_CONTINUE) || !s->adapt_armed) nb::launch_arm(s->stream, p.state, 1);
     s->adapt_armed = true;
     const nb::LaunchShape sh = resolve_shape(s);
+    if (cfg->flags & NB_ADAPT_LEAPFROG) {
+        enqueue_adaptive_leapfrog(s, n, p, log, sh);
+        s->adapt_logged = n;
+        return;
+    }
+    s->acc_current = false;   // Euler steps leave the acc of the state before them
     if (cfg->flags & NB_ADAPT_PRIME) {   // one dt = 0 step of the ordinary path: acc becomes the state's own
         upload_dt(s, 0.0f);
         launch_step(s, sh, whole_step(s, s->cur, 0.0f), s->stream);
@@ -680,12 +755,43 @@ void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg) {
         s->cur ^= 1;
     }
     ASSERT_HIP(hipGetLastError(), "adaptive step launches (%u steps, %u particles)", n, s->n_real);
-    if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_end, s->stream), "record end");
-    s->timed = s->timing != 0;
-    s->timed_launches = n * passes_for(s, whole_step(s, s->cur, 0.0f));
-    s->timed_finish_launches = s->last_shape.split > 1 && !fused_finish_applies(s, s->last_shape) ? s->timed_launches : 0;
-    s->dt_valid = false;   // the device chose the last step size: the next fixed-step call uploads its own afresh
+    end_timed_call(s, n);   // the device chose the last step size
     s->adapt_logged = n;
+}
+
+// ---- leapfrog steps --------------------------------------------------------------------------------------------------
+
+void check_leapfrog(const SimPipeline *s, uint32_t n, const char *what) {
+    NB_ASSERT(s != nullptr, "%s: NULL argument", what);
+    NB_ASSERT(!s->sharded, "%s of a sharded pipeline needs a collective over the ranks: not supported", what);
+    NB_ASSERT(n == 0 || s->on_device, "%s before SetSimulationData", what);
+}
+
+// n kick-drift-kick steps of one size: open, force, then one close + open pass and a force launch per further step, close.
+// Everything goes on the pipeline's stream and nothing returns to the host between the steps.
+void enqueue_leapfrog(SimPipeline *s, uint32_t n, float dt) {
+    if (s->slots == 0 || n == 0) return;
+    use_device();
+    grow_adapt(s, 0);
+    begin_call(s);
+    float *word = leapfrog_words(s);
+    nb::launch_set_scalar(s->stream, word, dt);
+    upload_dt(s, 0.0f);
+    const nb::LaunchShape sh = resolve_shape(s);
+    prime_leapfrog(s, sh);
+    if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_begin, s->stream), "record begin");
+    for (uint32_t i = 0; i < n; i++) {
+        nb::LeapfrogParams lf = leapfrog_params(s);
+        lf.dt_close = lf.dt_open = word;
+        nb::launch_leapfrog(s->stream, lf, i > 0, true, 0);
+        launch_force(s, sh);
+    }
+    nb::LeapfrogParams lf = leapfrog_params(s);
+    lf.dt_close = word;
+    nb::launch_leapfrog(s->stream, lf, true, false, 0);
+    ASSERT_HIP(hipGetLastError(), "leapfrog launches (%u steps, %u particles)", n, s->n_real);
+    end_timed_call(s, n);
+    s->acc_current = true;
 }
 
 void enqueue_timestep_peek(SimPipeline *s, const NbAdaptive *cfg) {

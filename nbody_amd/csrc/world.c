@@ -29,6 +29,10 @@
  * and AdvanceWorld_GPU follow UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Adaptive
  * UpdateWorld_CPU's; GetWorldTimestep follows the diagnostics' (timestep.hip on the
  * device, timestep_cpu.c on the host).
+ * Extension (include/nbody_leapfrog.h): kick-drift-kick steps.  UpdateWorld_GPU_Leapfrog
+ * follows UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Leapfrog UpdateWorld_CPU's
+ * (leapfrog.hip on the device, leapfrog_cpu.c around UpdateWorld_CPU(w, 0, 1) on the host);
+ * whether acc belongs to the state is remembered per side, so a transfer primes again.
  */
 #include "nbody.h"
 #include "nbody_adaptive.h"
@@ -36,12 +40,14 @@
 #include "nbody_field.h"
 #include "nbody_gravity.h"
 #include "nbody_hip.h"
+#include "nbody_leapfrog.h"
 #include "nbody_render.h"
 
 #include <stdbool.h>
 
 #include "diag_sums.h"
 #include "field_common.h"
+#include "leapfrog_common.h"
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
@@ -57,7 +63,13 @@ struct World {
     bool host_is_newer;   /* array changed since the device last saw it */
     bool device_is_newer; /* device stepped since the array was last refreshed */
     int nranks;           /* > 1: sharded (the pipeline holds 1/nranks of the receivers) */
+    bool cpu_acc_current; /* the array's acc is F(x) of the array's state: true after a CPU leapfrog call only (the device
+                             side of the same knowledge lives in the pipeline) */
 };
+
+/* leapfrog_cpu.c */
+__attribute__((visibility("hidden"))) void nb_cpu_leapfrog_open(Particle *ps, uint32_t n, float dt);
+__attribute__((visibility("hidden"))) void nb_cpu_leapfrog_close(Particle *ps, uint32_t n, float dt);
 
 /* rank < 0: an ordinary single-GPU World; otherwise the sharded pipeline of include/nbody_hip.h. */
 static World *create_world(const Particle *ps, uint32_t size, int rank, int nranks, const void *unique_id128,
@@ -82,6 +94,7 @@ static World *create_world(const Particle *ps, uint32_t size, int rank, int nran
     w->host_is_newer = true;    /* the device has seen nothing yet */
     w->device_is_newer = false;
     w->nranks = rank < 0 ? 1 : nranks;
+    w->cpu_acc_current = false;
     return w;
 }
 
@@ -131,6 +144,7 @@ static void pull_if_stale(World *w) {
     if (!w->device_is_newer) return;
     GetSimulationData(w->gpu, w->particles);
     w->device_is_newer = false;
+    w->cpu_acc_current = false;
 }
 
 const Particle *GetWorldParticles(World *w, uint32_t *size) {
@@ -143,6 +157,7 @@ void UpdateWorld_CPU(World *w, float dt, uint32_t n) {
     pull_if_stale(w);
     for (uint32_t step = 0; step < n; step++) CpuSimStep(w->cpu, w->particles, w->count, w->massive, dt);
     w->host_is_newer = true;
+    w->cpu_acc_current = false;   /* an Euler step leaves the acc of the state before it */
 }
 
 void UpdateWorld_GPU(World *w, float dt, uint32_t n) {
@@ -252,6 +267,14 @@ static void check_adaptive_world(const World *w, uint32_t n, const NbAdaptive *c
     NB_CHECK(n <= NB_ADAPT_MAX_STEPS, "%s: %u steps > 2^20 in one call", what, n);
 }
 
+/* one kick-drift-kick step of the array, acc being the array's own before and after */
+static void cpu_leapfrog_step(World *w, float dt) {
+    nb_cpu_leapfrog_open(w->particles, w->count, dt);
+    UpdateWorld_CPU(w, 0.0f, 1);
+    nb_cpu_leapfrog_close(w->particles, w->count, dt);
+    w->cpu_acc_current = true;
+}
+
 void GetWorldTimestep(World *w, const NbAdaptive *cfg, float *dt) {
     check_adaptive_world(w, 0, cfg, "GetWorldTimestep");
     NB_CHECK(dt != NULL, "GetWorldTimestep: NULL argument");
@@ -264,13 +287,22 @@ void GetWorldTimestep(World *w, const NbAdaptive *cfg, float *dt) {
 void UpdateWorld_CPU_Adaptive(World *w, uint32_t n, const NbAdaptive *cfg, float *dt_log, NbAdaptiveResult *out) {
     check_adaptive_world(w, n, cfg, "UpdateWorld_CPU_Adaptive");
     NbAdaptiveResult r = {0.0, 0, 0, 0.0f, 0.0f};
-    if (n > 0 && (cfg->flags & NB_ADAPT_PRIME)) UpdateWorld_CPU(w, 0.0f, 1);
+    const bool leapfrog = (cfg->flags & NB_ADAPT_LEAPFROG) != 0;
+    if (n > 0 && leapfrog) {
+        pull_if_stale(w);
+        if (!w->cpu_acc_current) UpdateWorld_CPU(w, 0.0f, 1);
+    } else if (n > 0 && (cfg->flags & NB_ADAPT_PRIME)) {
+        UpdateWorld_CPU(w, 0.0f, 1);
+    }
     for (uint32_t i = 0; i < n; i++) {
         float dt;
         GetWorldTimestep(w, cfg, &dt);
         dt = nb_timestep_clip(dt, cfg->span, &r.elapsed);
         nb_timestep_count(dt, &r.steps, &r.idle_steps, &r.dt_last, &r.dt_smallest);
-        UpdateWorld_CPU(w, dt, 1);
+        if (leapfrog)
+            cpu_leapfrog_step(w, dt);
+        else
+            UpdateWorld_CPU(w, dt, 1);
         if (dt_log) dt_log[i] = dt;
     }
     if (out) *out = r;
@@ -305,4 +337,23 @@ void AdvanceWorld_GPU(World *w, double span, const NbAdaptive *cfg, uint32_t max
         next = left < 1.0 ? 1u : left > (double)chunk ? chunk : (uint32_t)left;
     }
     if (out) *out = total;
+}
+
+/* ---- include/nbody_leapfrog.h ---------------------------------------------------------------------------------------- */
+
+void UpdateWorld_CPU_Leapfrog(World *w, float dt, uint32_t n) {
+    NB_CHECK(w != NULL, "UpdateWorld_CPU_Leapfrog: NULL argument");
+    if (n == 0) return;
+    pull_if_stale(w);
+    if (!w->cpu_acc_current) UpdateWorld_CPU(w, 0.0f, 1);   /* unlogged, uncounted: acc becomes the state's own */
+    for (uint32_t i = 0; i < n; i++) cpu_leapfrog_step(w, dt);
+}
+
+void UpdateWorld_GPU_Leapfrog(World *w, float dt, uint32_t n) {
+    NB_CHECK(w != NULL, "UpdateWorld_GPU_Leapfrog: NULL argument");
+    NB_CHECK(w->nranks <= 1, "UpdateWorld_GPU_Leapfrog of a sharded pipeline needs a collective over the ranks: not supported");
+    if (n == 0) return;
+    push_if_stale(w);
+    nb_hip_leapfrog_steps(w->gpu, n, dt);
+    w->device_is_newer = true;
 }

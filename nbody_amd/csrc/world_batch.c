@@ -16,8 +16,11 @@
  * the case offset[b] = b * size.  The render calls are not wired for such a batch and abort.
  * include/nbody_adaptive.h: UpdateWorldBatch_GPU_Adaptive / AdvanceWorldBatch_GPU are updates whose step sizes the device
  * chooses per member and step: same upload, same coherence; ragged batches abort.
+ * include/nbody_leapfrog.h: UpdateWorldBatch_GPU_Leapfrog(_dts) are updates of kick-drift-kick steps: same upload, same
+ * coherence; ragged batches abort.
  */
 #include "nbody_adaptive.h"
+#include "nbody_leapfrog.h"
 #include "nbody_batch.h"
 #include "nbody_batch_diag.h"
 #include "nbody_batch_ragged.h"
@@ -284,4 +287,24 @@ void AdvanceWorldBatch_GPU(WorldBatch *w, double span, const NbAdaptive *cfg, ui
     }
     if (out) memcpy(out, total, (size_t)w->count * sizeof *out);
     free(total);
+}
+
+/* ---- include/nbody_leapfrog.h ---------------------------------------------------------------------------------------- */
+
+void UpdateWorldBatch_GPU_Leapfrog(WorldBatch *w, float dt, uint32_t n) {
+    NB_CHECK(w != NULL, "UpdateWorldBatch_GPU_Leapfrog: NULL argument");
+    NB_CHECK(!w->ragged, "UpdateWorldBatch_GPU_Leapfrog: leapfrog steps of ragged ensembles (members of different sizes) are not supported");
+    if (n == 0) return;
+    push_once(w);
+    nb_hip_ensemble_leapfrog(w->gpu, n, dt);
+    w->device_is_newer = true;
+}
+
+void UpdateWorldBatch_GPU_Leapfrog_dts(WorldBatch *w, const float *dt, uint32_t n) {
+    NB_CHECK(w != NULL && dt != NULL, "UpdateWorldBatch_GPU_Leapfrog_dts: NULL argument");
+    NB_CHECK(!w->ragged, "UpdateWorldBatch_GPU_Leapfrog_dts: leapfrog steps of ragged ensembles (members of different sizes) are not supported");
+    if (n == 0) return;
+    push_once(w);
+    nb_hip_ensemble_leapfrog_dts(w->gpu, n, dt);
+    w->device_is_newer = true;
 }
