@@ -11,8 +11,8 @@
 // A traced update (nb_hip_ensemble_trace) records every member's energy sums every k steps without returning to the host:
 // on the chain path batch_trace_chain_kernel records from the state it holds in LDS (still one launch per call), on the
 // lane-split path the two diagnostics launches are interleaved with the step launches; one copy and one sync at the end.
-// nb_hip_ensemble_bounds / _render_counts / _render_rgba look at every member without reading it back (kernels:
-// batch_render.hip): a constant number of launches, one copy of the images and one sync for any B.
+// Adaptive and leapfrog updates run step_schedule.h's one launch schedule with every member as its target.  The read-only
+// calls (energy, potential, bounds, renders) are batch_observe.hip.
 // The path is chosen by N alone -- never by B or by the members' source counts -- and the kernels run the very bodies of
 // chain_kernel / lane_split_kernel, so member b's bits are those of the same particles alone in a SimPipeline pinned to
 // that shape (tests/test_gpu_batch.py).  Members share nothing with each other and a SimBatch shares nothing with any
@@ -25,108 +25,14 @@
 // and step (kernels.hip ragged_*_kernel, the same bodies with the receiver count read per member).  Member b's bits are
 // those of the same particles as the only member of a uniform SimBatch of its size.  A uniform SimBatch launches exactly
 // what it launched before ragged ones existed.
-#include "pipeline_internal.h"
-#include "batch_diag.h"
-#include "batch_render.h"
+#include "batch_internal.h"
 #include "diag_sums.h"
 #include "leapfrog.h"
 #include "nbody_hip_tuning.h"
-#include "render_common.h"
+#include "step_schedule.h"
 #include "timestep.h"
-#include "timestep_common.h"
 
 using namespace nbi;
-
-struct SimBatch {
-    uint32_t count = 0;     // members
-    uint32_t n = 0;         // particles per member; ragged: of the largest member
-    uint32_t stride = 0;    // rows per member in the SoA arrays: n rounded up to 64 (256-byte aligned float rows)
-    std::vector<uint32_t> n_len;      // [count] particles of each member
-    std::vector<uint64_t> offsets;    // [count + 1] member b's first record in the packed AoS arrays of the seam
-    bool ragged = false;              // made by nb_hip_ragged_create
-    std::vector<uint32_t> mass_len;   // [count]
-    std::vector<float> dt_host;       // [count]: what dt_dev holds (valid once dt_valid)
-    bool dt_valid = false;
-    uint32_t dt_uploads = 0;
-
-    bool on_device = false;
-    bool has_data = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false;
-    float2 *pos[2] = {nullptr, nullptr};
-    float2 *vel = nullptr, *acc = nullptr;
-    float *radius = nullptr, *mass = nullptr, *gm = nullptr;
-    uint32_t *mass_len_dev = nullptr;
-    float *dt_dev = nullptr;
-    void *aos = nullptr;   // device staging of Set / Get: [count][n] Particle
-    int cur = 0;           // pos[cur] is the latest state (the chain path never moves it)
-
-    // the launch shape, fixed at creation
-    int path = 0;          // 0 chain, 1 lane-split
-    int k = 2, w = 16, lanes = 1;
-    uint32_t tiles = 0;
-    uint32_t workgroups = 0;
-
-    // ragged only: the launch groups, in the order chain, lane-split (8, 8), lane-split (16, 4); those without members are
-    // absent.  path = 1 as soon as one member is lane-split (both position buffers exist, traces interleave).
-    struct Group {
-        int path = 0, k = 2, w = 16, lanes = 1;   // chain: w of the group's largest member
-        uint32_t max_n = 0;                       // its largest member
-        uint32_t workgroups = 0;                  // per launch
-        std::vector<uint32_t> members;            // ascending member indices
-        uint32_t *list = nullptr;                 // the same on the device
-    };
-    std::vector<Group> groups;
-    uint32_t *n_len_dev = nullptr;
-    uint64_t *offsets_dev = nullptr;
-
-    // nb_hip_ensemble_energy / nb_hip_ensemble_potential (kernels: batch_diag.hip): scratch made on first use, an event
-    // pair of their own (ev[] keeps bracketing the last update)
-    double *diag = nullptr;      // float64 slab: [count][tiles of 128][NB_DIAG_SUMS] + the [count][NB_DIAG_SUMS] results
-    size_t diag_cap = 0;         // doubles allocated in diag
-    float *diag_phi = nullptr;   // the potentials on the device: [count][n]
-    size_t diag_phi_cap = 0;
-    std::vector<double> diag_host;   // the results on the host before they become WorldEnergy
-    hipEvent_t ev_diag[2] = {nullptr, nullptr};
-    bool diag_timed = false;
-
-    // nb_hip_ensemble_trace: the rows of the last traced call, on the device and on their way to WorldEnergy
-    double *trace = nullptr;     // [records][count][NB_DIAG_SUMS]
-    size_t trace_cap = 0;
-    std::vector<double> trace_host;
-    int trace_mode = 0;          // tuning hook: 1 = interleaved diagnostics launches also where the chain could record
-    int trace_fused = 0;         // what the last traced call did
-    uint32_t trace_launches = 0;
-
-    // nb_hip_ensemble_bounds / _render_counts / _render_rgba (kernels: batch_render.hip): scratch made on first use, an
-    // event pair of their own
-    RenderView *render_views = nullptr;      // [count]: the views of the last call
-    uint32_t *render_keys = nullptr;         // [count][4]
-    uint32_t *render_counts = nullptr;       // tile path: [count][3][h][w]; global path: the disc cursor behind them
-    size_t render_counts_cap = 0;
-    uint32_t *render_rgba = nullptr;         // [count][h][w]
-    size_t render_rgba_cap = 0;
-    nbr::EnsembleDisc *render_discs = nullptr;   // global path: [count * n]
-    hipEvent_t ev_render[2] = {nullptr, nullptr};
-    bool render_timed = false;
-    int render_mode = 0;                     // tuning hook: 1 = the global path also where the tile path applies
-    int render_tile = 0;                     // what the last render did (a bounds call leaves both alone)
-    uint32_t render_launches = 0;
-
-    // nb_hip_ensemble_adaptive_steps (kernels: timestep.hip): [count] AdaptState, then the call's log [n][count]; grown on demand
-    void *adapt = nullptr;
-    size_t adapt_bytes = 0;
-    bool adapt_armed = false;   // the records hold a call to continue (NB_ADAPT_CONTINUE)
-    std::vector<char> adapt_host;
-
-    // leapfrog steps (kernels: leapfrog.hip): the step sizes of the kick / drift passes, [2][count] -- a fixed-step call uses
-    // the first row, an adaptive one alternates so that one launch can close step i - 1 and open step i
-    float *lf_dt = nullptr;
-    bool acc_current = false;        // acc = F(x) of the state held: true after a leapfrog call, false after anything else that moves it
-    uint32_t lf_force_launches = 0;  // force evaluations of the last leapfrog call (nb_hip_ensemble_last_leapfrog_info)
-    bool lf_primed = false;          // ... and whether it had to run one first
-};
 
 namespace {
 
@@ -300,65 +206,84 @@ void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
     s->timed = true;
 }
 
-// ---- leapfrog steps: the passes of leapfrog.hip around the launches of a one-step dt = 0 update ----------------------------
+// ---- device-chosen and leapfrog steps: every member as the target of step_schedule.h's schedule --------------------------
 
-// one pass over every member: close with row `close_row` of lf_dt, open (kick + drift of the latest positions) with `open_row`
-void launch_kicks(SimBatch *s, bool close, bool open, uint32_t close_row, uint32_t open_row) {
-    nb::LeapfrogParams lf;
-    memset(&lf, 0, sizeof lf);
-    lf.pos = s->pos[s->cur];
-    lf.vel = s->vel;
-    lf.acc = s->acc;
-    lf.dt_close = s->lf_dt + (size_t)close_row * s->count;
-    lf.dt_open = s->lf_dt + (size_t)open_row * s->count;
-    lf.n = s->n;
-    lf.stride = s->stride;
-    nb::launch_leapfrog(s->stream, lf, close, open, s->count);
-}
-
-void launch_force(SimBatch *s, nb::BatchParams &p) {
-    launch_steps(s, p, 1);
-    s->lf_force_launches++;
-}
-
-// the step kernels' dt[count] holds 0 for the whole call; one unlogged, uncounted force evaluation first when acc is not
-// known to be the members' own
-void begin_leapfrog(SimBatch *s, nb::BatchParams &p) {
+// the step sizes of the kick / drift passes, [2][count]
+float *kick_words(SimBatch *s) {
     if (!s->lf_dt) s->lf_dt = dev_alloc<float>(2 * (size_t)s->count);
-    const float zero = 0.0f;
-    upload_dts(s, &zero, true);
-    s->lf_force_launches = 0;
-    s->lf_primed = !s->acc_current;
-    if (s->lf_primed) launch_force(s, p);
+    return s->lf_dt;
 }
 
-// n kick-drift-kick steps, every member with its own step size: open, force, one close + open pass and a force launch per
-// further step, close
+// The step words are dt_dev[count], read by the launches of a one-step update; the kick words are the two rows of lf_dt.
+struct BatchTarget {
+    SimBatch *s;
+    nb::BatchParams p;
+    nb::TimestepParams t;   // adaptive calls only
+    float *log;             // [n][count] on the device, or null
+    uint32_t forces = 0;
+
+    bool acc_current() const { return s->acc_current; }
+    void zero_step_word() {
+        const float zero = 0.0f;
+        upload_dts(s, &zero, true);
+    }
+    void force() {
+        launch_steps(s, p, 1);
+        forces++;
+    }
+    void criterion(uint32_t i, int row) {   // one workgroup per member writes dt[b]
+        t.log = log ? log + (size_t)i * s->count : nullptr;
+        t.dt_out = row < 0 ? s->dt_dev : s->lf_dt + (size_t)row * s->count;
+        nb::launch_ensemble_timestep(s->stream, t, s->count);
+    }
+    // one pass over every member: close with row `close_row` of lf_dt, open (kick + drift of the latest positions) with `open_row`
+    void kicks(bool close, bool open, uint32_t close_row, uint32_t open_row) {
+        nb::LeapfrogParams lf;
+        memset(&lf, 0, sizeof lf);
+        lf.pos = s->pos[s->cur];
+        lf.vel = s->vel;
+        lf.acc = s->acc;
+        lf.dt_close = s->lf_dt + (size_t)close_row * s->count;
+        lf.dt_open = s->lf_dt + (size_t)open_row * s->count;
+        lf.n = s->n;
+        lf.stride = s->stride;
+        nb::launch_leapfrog(s->stream, lf, close, open, s->count);
+    }
+    void begin_mark() { ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record"); }
+    void end_mark() {
+        ASSERT_HIP(hipGetLastError(), "ensemble step launches (%u members of %u particles)", s->count, s->n);
+        ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
+    }
+};
+
+// One call of the schedule and every record it leaves: the only place these fields are set for a device-chosen or leapfrog call.
+void run_call(SimBatch *s, Schedule c, const nb::TimestepParams &t, float *log) {
+    BatchTarget target = {s, step_params(s), t, log};
+    if (c.leapfrog) {
+        kick_words(s);
+        s->lf_primed = !s->acc_current;
+    }
+    run_schedule(target, c);
+    if (c.leapfrog) s->lf_force_launches = target.forces;
+    s->timed = true;
+    s->dt_valid = false;            // dt_dev holds 0 or the device's choices: the next fixed-step update uploads its own afresh
+    s->acc_current = c.leapfrog;    // Euler steps leave the acc of the state before them
+}
+
+// n kick-drift-kick steps, every member with its own step size
 void enqueue_leapfrog(SimBatch *s, uint32_t n, const float *dt, bool uniform, const char *what) {
     NB_ASSERT(s != nullptr && dt != nullptr, "%s: NULL argument", what);
     NB_ASSERT(!s->ragged, "%s: leapfrog steps of ragged ensembles (members of different sizes) are not supported", what);
     if (n == 0) return;
     NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
     use_device();
-    nb::BatchParams p = step_params(s);
-    begin_leapfrog(s, p);
     if (uniform) {
-        nb::launch_batch_fill(s->stream, s->lf_dt, s->count, dt[0]);
-    } else {
+        nb::launch_batch_fill(s->stream, kick_words(s), s->count, dt[0]);
+    } else {   // before anything of this call is queued: the blocking copy drains what earlier calls left, not this one
         ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before a per-member step-size upload");
-        ASSERT_HIP(hipMemcpy(s->lf_dt, dt, (size_t)s->count * sizeof(float), hipMemcpyHostToDevice), "H2D of %u step sizes", s->count);
+        ASSERT_HIP(hipMemcpy(kick_words(s), dt, (size_t)s->count * sizeof(float), hipMemcpyHostToDevice), "H2D of %u step sizes", s->count);
     }
-    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
-    for (uint32_t i = 0; i < n; i++) {
-        launch_kicks(s, i > 0, true, 0, 0);
-        launch_force(s, p);
-    }
-    launch_kicks(s, true, false, 0, 0);
-    ASSERT_HIP(hipGetLastError(), "leapfrog ensemble launches (%u members of %u particles, %u steps)", s->count, s->n, n);
-    ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
-    s->timed = true;
-    s->dt_valid = false;   // the next fixed-step update uploads its own step sizes afresh
-    s->acc_current = true;
+    run_call(s, {n, true, false, false}, nb::TimestepParams{}, nullptr);
 }
 
 void read_back(SimBatch *s, uint32_t first, uint32_t members, Particle *ps) {
@@ -375,76 +300,6 @@ void read_back(SimBatch *s, uint32_t first, uint32_t members, Particle *ps) {
                               s->stream),
                "D2H of %u members", members);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after an ensemble read-back");
-}
-
-// ---- diagnostics: the state every member holds, without reading the particles back ----------------------------------
-
-void check_diag(SimBatch *s, const void *out, const char *what) {
-    NB_ASSERT(s != nullptr, "NULL ensemble");
-    NB_ASSERT(out != nullptr, "%s: NULL result array", what);
-    NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
-}
-
-// the three render calls are not wired for ragged ensembles: said before anything touches the device
-void check_not_ragged(const SimBatch *s, const char *what) {
-    NB_ASSERT(s != nullptr, "NULL ensemble");
-    NB_ASSERT(!s->ragged, "%s: rendering of ragged ensembles (members of different sizes) is not supported", what);
-}
-
-nbd::EnsembleDiagParams diag_params(const SimBatch *s) {   // of the latest state
-    nbd::EnsembleDiagParams p{};
-    p.pos = s->pos[s->cur];
-    p.vel = s->vel;
-    p.radius = s->radius;
-    p.mass = s->mass;
-    p.gm = s->gm;
-    p.mass_len = s->mass_len_dev;
-    p.n = s->n;
-    p.stride = s->stride;
-    return p;
-}
-
-nbd::EnsembleDiagParams begin_diag(SimBatch *s) {
-    use_device();
-    if (!s->ev_diag[0]) {
-        for (auto &e : s->ev_diag) ASSERT_HIP(hipEventCreate(&e), "event");
-    }
-    ASSERT_HIP(hipEventRecord(s->ev_diag[0], s->stream), "record diagnostics begin");
-    return diag_params(s);
-}
-
-void end_diag(SimBatch *s) {
-    ASSERT_HIP(hipEventRecord(s->ev_diag[1], s->stream), "record diagnostics end");
-    s->diag_timed = true;
-}
-
-template <typename T>
-T *grown(SimBatch *s, T *&buf, size_t &cap, size_t need) {
-    if (cap < need) {
-        if (buf) {
-            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing a diagnostics buffer");
-            dev_free(buf);
-        }
-        buf = dev_alloc<T>(need);
-        cap = need;
-    }
-    return buf;
-}
-
-// The two launches of an energy diagnostic of the latest state: every member's eight sums -> res[count][NB_DIAG_SUMS].
-void launch_energy_sums(SimBatch *s, double *res) {
-    const uint32_t tiles = nbd::ensemble_tiles(s->n);
-    nbd::EnsembleDiagParams p = diag_params(s);
-    p.slab = s->diag;
-    nbd::launch_ensemble_potential(s->stream, p, s->count);
-    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (energy, %u members of %u)", s->count, s->n);
-    nbd::launch_ensemble_reduce(s->stream, s->diag, s->mass_len_dev, tiles, s->count, res);
-    ASSERT_HIP(hipGetLastError(), "ensemble_reduce_kernel launch (%u members)", s->count);
-}
-
-// The slab of per-tile rows, with room for one call's results behind it.
-double *energy_slab(SimBatch *s) {
-    return grown(s, s->diag, s->diag_cap, (size_t)s->count * (nbd::ensemble_tiles(s->n) + 1) * NB_DIAG_SUMS);
 }
 
 constexpr uint64_t TRACE_MAX_ROWS = 1ull << 24;   // rows of 64 bytes: 1 GiB
@@ -465,7 +320,7 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
     }
     constexpr size_t Q = NB_DIAG_SUMS;
     const size_t pitch = (size_t)s->count * Q;
-    double *rows = grown(s, s->trace, s->trace_cap, (size_t)records * pitch);
+    double *rows = grown(s->stream, s->trace, s->trace_cap, (size_t)records * pitch);
     const bool fused = s->path == 0 && s->trace_mode == 0;
     if (!fused) energy_slab(s);
     nb::BatchParams p = step_params(s);
@@ -511,72 +366,6 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
                "D2H of %u x %u energy rows", records, s->count);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after a traced ensemble update");
     for (size_t i = 0; i < (size_t)records * s->count; i++) nb_energy_from_sums(s->trace_host.data() + i * Q, out + i);
-}
-
-// ---- rendering: bounds, count tiles and frames of every member, without reading the particles back ------------------
-
-void begin_render(SimBatch *s) {
-    use_device();
-    if (!s->ev_render[0]) {
-        for (auto &e : s->ev_render) ASSERT_HIP(hipEventCreate(&e), "event");
-    }
-    ASSERT_HIP(hipEventRecord(s->ev_render[0], s->stream), "record render begin");
-}
-
-void end_render(SimBatch *s) {
-    ASSERT_HIP(hipEventRecord(s->ev_render[1], s->stream), "record render end");
-    s->render_timed = true;
-}
-
-void check_views(const SimBatch *s, const RenderView *views, const char *what) {
-    NB_ASSERT(views != nullptr, "%s: NULL RenderView array", what);
-    uint32_t member = 0;
-    const char *fault = nb_render_views_fault(views, s->count, &member);
-    NB_ASSERT(fault == nullptr, "%s: invalid RenderView of member %u of %u (%u x %u, zoom %g): %s", what, member, s->count,
-              views[member].width, views[member].height, (double)views[member].zoom, fault);
-}
-
-// The count images of the latest state on the stream: the tile kernel (straight to the frame when a palette is given) or
-// clear + splat + disc pass (+ shade); *launches = what was enqueued.
-void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint32_t *launches) {
-    const uint32_t width = views[0].width, height = views[0].height;
-    const size_t plane = (size_t)width * height;
-    const bool tile = nbr::tile_fits(width, height) && s->render_mode == 0;
-    if (!s->render_views) s->render_views = dev_alloc<RenderView>(s->count);
-    if (palette) grown(s, s->render_rgba, s->render_rgba_cap, (size_t)s->count * plane);
-    if (!tile || !palette) grown(s, s->render_counts, s->render_counts_cap, nbr::global_count_words(s->count, width, height));
-    if (!tile && !s->render_discs) s->render_discs = dev_alloc<nbr::EnsembleDisc>((size_t)s->count * s->n);
-    ASSERT_HIP(hipMemcpyAsync(s->render_views, views, (size_t)s->count * sizeof(RenderView), hipMemcpyHostToDevice, s->stream),
-               "H2D of %u views", s->count);
-    begin_render(s);
-    nbr::EnsembleRenderParams p{};
-    p.pos = s->pos[s->cur];
-    p.mass = s->mass;
-    p.radius = s->radius;
-    p.n = s->n;
-    p.stride = s->stride;
-    p.count = s->count;
-    p.width = width;
-    p.height = height;
-    p.views = s->render_views;
-    if (tile) {
-        nbr::launch_ensemble_tile(s->stream, p, s->render_counts, palette, s->render_rgba);
-        *launches = 1;
-    } else {
-        ASSERT_HIP(hipMemsetAsync(s->render_counts, 0, nbr::global_count_words(s->count, width, height) * sizeof(uint32_t), s->stream),
-                   "clear %u count images and the disc cursor", s->count);
-        nbr::launch_ensemble_global(s->stream, p, s->render_counts, s->render_discs);
-        *launches = 3;
-        if (palette) {
-            nbr::launch_ensemble_shade(s->stream, s->render_counts, s->count, (uint32_t)plane, *palette, s->render_rgba);
-            *launches = 4;
-        }
-    }
-    ASSERT_HIP(hipGetLastError(), "ensemble render launch (%u members of %u particles, %u x %u, %s path)", s->count, s->n, width, height,
-               tile ? "tile" : "global");
-    end_render(s);
-    s->render_tile = tile;
-    s->render_launches = *launches;
 }
 
 }  // namespace
@@ -825,15 +614,10 @@ void nb_hip_ensemble_last_leapfrog_info(const SimBatch *s, uint32_t *force_launc
     if (primed) *primed = s->lf_primed ? 1 : 0;
 }
 
-// n adaptive steps of every member: per step the criterion launch (one workgroup per member writes dt[b]), then the launches
-// of a one-step update reading the same dt[count]; nothing returns to the host until the one copy at the end.
+// n adaptive steps of every member; nothing returns to the host until the one copy at the end.
 void nb_hip_ensemble_adaptive_steps(SimBatch *s, uint32_t n, const NbAdaptive *cfg, float *dt_log, NbAdaptiveResult *out) {
     const char *what = "nb_hip_ensemble_adaptive_steps";
-    NB_ASSERT(s != nullptr && cfg != nullptr, "%s: NULL argument", what);
-    const char *fault = nb_timestep_cfg_fault(cfg);
-    NB_ASSERT(fault == nullptr, "%s: %s (eta %g, dt_min %g, dt_max %g, span %g)", what, fault, (double)cfg->eta, (double)cfg->dt_min,
-              (double)cfg->dt_max, cfg->span);
-    NB_ASSERT(n <= NB_ADAPT_MAX_STEPS, "%s: %u steps > 2^20 in one call", what, n);
+    check_adaptive_cfg(s, n, cfg, what);
     NB_ASSERT(!s->ragged, "%s: adaptive steps of ragged ensembles (members of different sizes) are not supported", what);
     if (n == 0) {
         if (out) memset(out, 0, (size_t)s->count * sizeof *out);
@@ -843,74 +627,23 @@ void nb_hip_ensemble_adaptive_steps(SimBatch *s, uint32_t n, const NbAdaptive *c
     use_device();
     const size_t head = (size_t)s->count * sizeof(nb::AdaptState);
     const size_t log_bytes = dt_log ? (size_t)n * s->count * sizeof(float) : 0;
-    if (s->adapt_bytes < head + log_bytes) {   // a regrow carries the records over: a continued call goes on from them
-        void *old = s->adapt;
-        s->adapt = dev_alloc_bytes(head + log_bytes);
+    if (s->adapt_bytes < head + log_bytes) {
+        regrow_carrying(s->stream, s->adapt, head + log_bytes, head);
         s->adapt_bytes = head + log_bytes;
-        if (old) {
-            ASSERT_HIP(hipMemcpyAsync(s->adapt, old, head, hipMemcpyDeviceToDevice, s->stream), "carry the adaptive-step records over");
-            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before freeing the old adaptive-step buffer");
-            dev_free(old);
-        }
     }
-    nb::TimestepParams t;
-    memset(&t, 0, sizeof t);
-    t.acc = s->acc;
-    t.radius = s->radius;
-    t.n = s->n;
-    t.stride = s->stride;
-    t.eta = cfg->eta;
-    t.dt_min = cfg->dt_min;
-    t.dt_max = cfg->dt_max;
-    t.span = cfg->span;
+    nb::TimestepParams t = nb::timestep_params(s->acc, s->radius, s->n, s->stride, *cfg);
     t.state = static_cast<nb::AdaptState *>(s->adapt);
-    t.dt_out = s->dt_dev;
     t.commit = 1;
-    float *log = dt_log ? reinterpret_cast<float *>(static_cast<char *>(s->adapt) + head) : nullptr;
-    nb::BatchParams p = step_params(s);
     if (!(cfg->flags & NB_ADAPT_CONTINUE) || !s->adapt_armed) nb::launch_arm(s->stream, t.state, s->count);
     s->adapt_armed = true;
-    if (cfg->flags & NB_ADAPT_LEAPFROG) {
-        // per step: the criterion on the members' own acc writes dt_i[count] to one of two alternating rows, one pass closes
-        // step i - 1 with the other row and opens step i with this one, then the force launch; a last pass closes step n - 1
-        begin_leapfrog(s, p);
-        ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
-        for (uint32_t i = 0; i < n; i++) {
-            t.log = log ? log + (size_t)i * s->count : nullptr;
-            t.dt_out = s->lf_dt + (size_t)(i & 1) * s->count;
-            nb::launch_ensemble_timestep(s->stream, t, s->count);
-            launch_kicks(s, i > 0, true, (i & 1) ^ 1, i & 1);
-            launch_force(s, p);
-        }
-        launch_kicks(s, true, false, (n - 1) & 1, 0);
-        s->acc_current = true;
-    } else {
-        s->acc_current = false;   // Euler steps leave the acc of the state before them
-        if (cfg->flags & NB_ADAPT_PRIME) {   // one dt = 0 step of the ordinary path: acc becomes the state's own
-            const float zero = 0.0f;
-            upload_dts(s, &zero, true);
-            launch_steps(s, p, 1);
-        }
-        ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
-        for (uint32_t i = 0; i < n; i++) {
-            t.log = log ? log + (size_t)i * s->count : nullptr;
-            nb::launch_ensemble_timestep(s->stream, t, s->count);
-            launch_steps(s, p, 1);
-        }
-    }
-    ASSERT_HIP(hipGetLastError(), "adaptive ensemble launches (%u members of %u particles, %u steps)", s->count, s->n, n);
-    ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
-    s->timed = true;
-    s->dt_valid = false;   // the device chose the step sizes: the next fixed-step update uploads its own afresh
+    const bool leapfrog = (cfg->flags & NB_ADAPT_LEAPFROG) != 0;
+    run_call(s, {n, leapfrog, true, !leapfrog && (cfg->flags & NB_ADAPT_PRIME) != 0}, t,
+             dt_log ? reinterpret_cast<float *>(static_cast<char *>(s->adapt) + head) : nullptr);
     s->adapt_host.resize(head + log_bytes);
     ASSERT_HIP(hipMemcpyAsync(s->adapt_host.data(), s->adapt, head + log_bytes, hipMemcpyDeviceToHost, s->stream),
                "D2H of %u x %u step sizes and the results", n, s->count);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after an adaptive ensemble update");
-    for (uint32_t b = 0; out && b < s->count; b++) {
-        nb::AdaptState st;
-        memcpy(&st, s->adapt_host.data() + (size_t)b * sizeof st, sizeof st);
-        out[b] = NbAdaptiveResult{st.t, st.steps, st.idle_steps, st.dt_last, st.dt_smallest};
-    }
+    for (uint32_t b = 0; out && b < s->count; b++) out[b] = nb::adaptive_result(s->adapt_host.data() + (size_t)b * sizeof(nb::AdaptState));
     if (dt_log) memcpy(dt_log, s->adapt_host.data() + head, log_bytes);
 }
 
@@ -918,56 +651,12 @@ double nb_hip_batch_last_ms(SimBatch *s) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
     if (!s->timed) return 0.0;
     use_device();
-    ASSERT_HIP(hipEventSynchronize(s->ev[1]), "event sync");
-    float ms = 0.0f;
-    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]), "elapsed time");
-    return (double)ms;
+    return elapsed_ms(s->ev[0], s->ev[1]);
 }
 
 uint32_t nb_hip_batch_dt_uploads(const SimBatch *s) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
     return s->dt_uploads;
-}
-
-void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
-    check_diag(s, out, "nb_hip_ensemble_energy");
-    constexpr size_t Q = NB_DIAG_SUMS;
-    begin_diag(s);
-    double *res = energy_slab(s) + (size_t)s->count * nbd::ensemble_tiles(s->n) * Q;
-    launch_energy_sums(s, res);
-    end_diag(s);
-    s->diag_host.resize((size_t)s->count * Q);
-    ASSERT_HIP(hipMemcpyAsync(s->diag_host.data(), res, (size_t)s->count * Q * sizeof(double), hipMemcpyDeviceToHost, s->stream),
-               "D2H of %u members' energy sums", s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_energy");
-    for (uint32_t b = 0; b < s->count; b++) nb_energy_from_sums(s->diag_host.data() + (size_t)b * Q, out + b);
-}
-
-void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
-    check_diag(s, phi, "nb_hip_ensemble_potential");
-    nbd::EnsembleDiagParams p = begin_diag(s);
-    const size_t total = (size_t)s->offsets[s->count];
-    p.phi = grown(s, s->diag_phi, s->diag_phi_cap, total);
-    if (s->ragged)
-        nbd::launch_ragged_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
-    else
-        nbd::launch_ensemble_potential(s->stream, p, s->count);
-    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
-    end_diag(s);
-    ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u members' potentials",
-               s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_potential");
-}
-
-// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_ensemble_energy / _potential
-double nb_hip_ensemble_last_diag_ms(SimBatch *s) {
-    NB_ASSERT(s != nullptr, "NULL ensemble");
-    if (!s->diag_timed) return 0.0;
-    use_device();
-    ASSERT_HIP(hipEventSynchronize(s->ev_diag[1]), "diagnostics end event");
-    float ms = 0.0f;
-    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev_diag[0], s->ev_diag[1]), "diagnostics elapsed time");
-    return (double)ms;
 }
 
 uint32_t nb_hip_ensemble_trace_rows(uint32_t n, uint32_t every) {
@@ -992,70 +681,6 @@ void nb_hip_ensemble_last_trace_info(const SimBatch *s, int *fused, uint32_t *la
     NB_ASSERT(s != nullptr, "NULL ensemble");
     if (fused) *fused = s->trace_fused;
     if (launches) *launches = s->trace_launches;
-}
-
-void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {
-    check_not_ragged(s, "nb_hip_ensemble_bounds");
-    check_diag(s, bounds, "nb_hip_ensemble_bounds");
-    begin_render(s);
-    if (!s->render_keys) s->render_keys = dev_alloc<uint32_t>((size_t)s->count * 4);
-    nbr::launch_ensemble_bounds(s->stream, s->pos[s->cur], s->n, s->stride, s->count, s->render_keys);
-    ASSERT_HIP(hipGetLastError(), "ensemble_bounds_kernel launch (%u members of %u)", s->count, s->n);
-    end_render(s);   // the event pair is shared with the renders; render_tile / render_launches speak of renders only
-    std::vector<uint32_t> keys((size_t)s->count * 4);
-    ASSERT_HIP(hipMemcpyAsync(keys.data(), s->render_keys, keys.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream),
-               "D2H of %u members' bounds", s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_bounds");
-    for (uint32_t b = 0; b < s->count; b++) nb_render_bounds_from_keys(keys.data() + (size_t)b * 4, bounds + (size_t)b * 4);
-}
-
-void nb_hip_ensemble_render_counts(SimBatch *s, const RenderView *views, uint32_t *counts) {
-    check_not_ragged(s, "nb_hip_ensemble_render_counts");
-    check_diag(s, counts, "nb_hip_ensemble_render_counts");
-    check_views(s, views, "nb_hip_ensemble_render_counts");
-    use_device();
-    uint32_t launches = 0;
-    enqueue_render(s, views, nullptr, &launches);
-    const size_t bytes = (size_t)s->count * NB_RENDER_CLASSES * views[0].width * views[0].height * sizeof(uint32_t);
-    ASSERT_HIP(hipMemcpyAsync(counts, s->render_counts, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u count images", s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_render_counts");
-}
-
-void nb_hip_ensemble_render_rgba(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint8_t *rgba) {
-    check_not_ragged(s, "nb_hip_ensemble_render_rgba");
-    check_diag(s, rgba, "nb_hip_ensemble_render_rgba");
-    check_views(s, views, "nb_hip_ensemble_render_rgba");
-    NB_ASSERT(palette != nullptr, "nb_hip_ensemble_render_rgba: NULL RenderPalette");
-    NB_ASSERT(palette->saturation >= 1u, "RenderPalette saturation must be at least 1");
-    use_device();
-    uint32_t launches = 0;
-    enqueue_render(s, views, palette, &launches);
-    const size_t bytes = (size_t)s->count * views[0].width * views[0].height * sizeof(uint32_t);
-    ASSERT_HIP(hipMemcpyAsync(rgba, s->render_rgba, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u frames", s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_render_rgba");
-}
-
-// tuning hooks (nbody_hip_tuning.h)
-void nb_hip_ensemble_render_mode(SimBatch *s, int mode) {
-    NB_ASSERT(s != nullptr, "NULL ensemble");
-    NB_ASSERT(mode == 0 || mode == 1, "render mode %d (0 = auto, 1 = global path)", mode);
-    s->render_mode = mode;
-}
-
-void nb_hip_ensemble_last_render_info(const SimBatch *s, int *tile_path, uint32_t *launches) {
-    NB_ASSERT(s != nullptr, "NULL ensemble");
-    if (tile_path) *tile_path = s->render_tile;
-    if (launches) *launches = s->render_launches;
-}
-
-double nb_hip_ensemble_last_render_ms(SimBatch *s) {
-    NB_ASSERT(s != nullptr, "NULL ensemble");
-    if (!s->render_timed) return 0.0;
-    use_device();
-    ASSERT_HIP(hipEventSynchronize(s->ev_render[1]), "render end event");
-    float ms = 0.0f;
-    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev_render[0], s->ev_render[1]), "render elapsed time");
-    return (double)ms;
 }
 
 void nb_hip_batch_launch_shape(const SimBatch *s, int *path, int *k, int *w, int *lanes, uint32_t *workgroups) {

@@ -1,4 +1,4 @@
-// batch_diag.h -- what batch.hip (the SimBatch and its C-ABI) needs of batch_diag.hip (the ensemble's diagnostics kernels).
+// batch_diag.h -- what batch_observe.hip and batch.hip (the SimBatch and its C-ABI) need of batch_diag.hip (the ensemble's diagnostics kernels).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // batch_diag.hip -- energy, momentum and per-particle potential of every member of an ensemble (SimBatch), in one pass
 // over all members (include/nbody_hip.h nb_hip_ensemble_energy / nb_hip_ensemble_potential; the entry points sit in
-// batch.hip beside the SimBatch they read).
+// batch_observe.hip).
 //
 // The definitions and the arithmetic are those of diagnostics.hip, through diag_common.h: member b's result is, bit for
 // bit, what nb_hip_energy / nb_hip_potential give for the same particles alone in a SimPipeline.  That is possible because

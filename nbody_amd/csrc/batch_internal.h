@@ -1,0 +1,106 @@
+// batch_internal.h -- struct SimBatch and what batch.hip (life cycle, stepping, traces) and batch_observe.hip (the read-only
+// calls) share.  C++, not part of the C-ABI.
+#pragma once
+
+#include "pipeline_internal.h"
+#include "batch_render.h"
+
+struct SimBatch {
+    uint32_t count = 0;     // members
+    uint32_t n = 0;         // particles per member; ragged: of the largest member
+    uint32_t stride = 0;    // rows per member in the SoA arrays: n rounded up to 64 (256-byte aligned float rows)
+    std::vector<uint32_t> n_len;      // [count] particles of each member
+    std::vector<uint64_t> offsets;    // [count + 1] member b's first record in the packed AoS arrays of the seam
+    bool ragged = false;              // made by nb_hip_ragged_create
+    std::vector<uint32_t> mass_len;   // [count]
+    std::vector<float> dt_host;       // [count]: what dt_dev holds (valid once dt_valid)
+    bool dt_valid = false;
+    uint32_t dt_uploads = 0;
+
+    bool on_device = false;
+    bool has_data = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool timed = false;
+    float2 *pos[2] = {nullptr, nullptr};
+    float2 *vel = nullptr, *acc = nullptr;
+    float *radius = nullptr, *mass = nullptr, *gm = nullptr;
+    uint32_t *mass_len_dev = nullptr;
+    float *dt_dev = nullptr;
+    void *aos = nullptr;   // device staging of Set / Get: [count][n] Particle
+    int cur = 0;           // pos[cur] is the latest state (the chain path never moves it)
+
+    // the launch shape, fixed at creation
+    int path = 0;          // 0 chain, 1 lane-split
+    int k = 2, w = 16, lanes = 1;
+    uint32_t tiles = 0;
+    uint32_t workgroups = 0;
+
+    // ragged only: the launch groups, in the order chain, lane-split (8, 8), lane-split (16, 4); those without members are
+    // absent.  path = 1 as soon as one member is lane-split (both position buffers exist, traces interleave).
+    struct Group {
+        int path = 0, k = 2, w = 16, lanes = 1;   // chain: w of the group's largest member
+        uint32_t max_n = 0;                       // its largest member
+        uint32_t workgroups = 0;                  // per launch
+        std::vector<uint32_t> members;            // ascending member indices
+        uint32_t *list = nullptr;                 // the same on the device
+    };
+    std::vector<Group> groups;
+    uint32_t *n_len_dev = nullptr;
+    uint64_t *offsets_dev = nullptr;
+
+    // nb_hip_ensemble_energy / nb_hip_ensemble_potential (kernels: batch_diag.hip): scratch made on first use, an event
+    // pair of their own (ev[] keeps bracketing the last update)
+    double *diag = nullptr;      // float64 slab: [count][tiles of 128][NB_DIAG_SUMS] + the [count][NB_DIAG_SUMS] results
+    size_t diag_cap = 0;         // doubles allocated in diag
+    float *diag_phi = nullptr;   // the potentials on the device: [count][n]
+    size_t diag_phi_cap = 0;
+    std::vector<double> diag_host;   // the results on the host before they become WorldEnergy
+    hipEvent_t ev_diag[2] = {nullptr, nullptr};
+    bool diag_timed = false;
+
+    // nb_hip_ensemble_trace: the rows of the last traced call, on the device and on their way to WorldEnergy
+    double *trace = nullptr;     // [records][count][NB_DIAG_SUMS]
+    size_t trace_cap = 0;
+    std::vector<double> trace_host;
+    int trace_mode = 0;          // tuning hook: 1 = interleaved diagnostics launches also where the chain could record
+    int trace_fused = 0;         // what the last traced call did
+    uint32_t trace_launches = 0;
+
+    // nb_hip_ensemble_bounds / _render_counts / _render_rgba (kernels: batch_render.hip): scratch made on first use, an
+    // event pair of their own
+    RenderView *render_views = nullptr;      // [count]: the views of the last call
+    uint32_t *render_keys = nullptr;         // [count][4]
+    uint32_t *render_counts = nullptr;       // tile path: [count][3][h][w]; global path: the disc cursor behind them
+    size_t render_counts_cap = 0;
+    uint32_t *render_rgba = nullptr;         // [count][h][w]
+    size_t render_rgba_cap = 0;
+    nbr::EnsembleDisc *render_discs = nullptr;   // global path: [count * n]
+    hipEvent_t ev_render[2] = {nullptr, nullptr};
+    bool render_timed = false;
+    int render_mode = 0;                     // tuning hook: 1 = the global path also where the tile path applies
+    int render_tile = 0;                     // what the last render did (a bounds call leaves both alone)
+    uint32_t render_launches = 0;
+
+    // nb_hip_ensemble_adaptive_steps (kernels: timestep.hip): [count] AdaptState, then the call's log [n][count]; grown on demand
+    void *adapt = nullptr;
+    size_t adapt_bytes = 0;
+    bool adapt_armed = false;   // the records hold a call to continue (NB_ADAPT_CONTINUE)
+    std::vector<char> adapt_host;
+
+    // leapfrog steps (kernels: leapfrog.hip): the step sizes of the kick / drift passes, [2][count] -- a fixed-step call uses
+    // the first row, an adaptive one alternates so that one launch can close step i - 1 and open step i
+    float *lf_dt = nullptr;
+    bool acc_current = false;        // acc = F(x) of the state held: true after a leapfrog call, false after anything else that moves it
+    uint32_t lf_force_launches = 0;  // force evaluations of the last leapfrog call (nb_hip_ensemble_last_leapfrog_info)
+    bool lf_primed = false;          // ... and whether it had to run one first
+};
+
+namespace nbi {
+
+// batch_observe.hip, used by traces too: the slab of per-tile rows with room for one call's results behind it, and the two
+// launches of an energy diagnostic of the latest state: every member's eight sums -> res[count][NB_DIAG_SUMS]
+double *energy_slab(SimBatch *s);
+void launch_energy_sums(SimBatch *s, double *res);
+
+}  // namespace nbi

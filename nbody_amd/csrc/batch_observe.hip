@@ -1,0 +1,246 @@
+// batch_observe.hip -- the read-only calls on a SimBatch: energy and potential of every member (kernels: batch_diag.hip,
+// ragged_diag.hip), bounds, count images and frames (kernels: batch_render.hip), with their tuning hooks and timers.  Each
+// looks at the latest state without reading the particles back: a constant number of launches, one copy, one sync for any B.
+#include "batch_internal.h"
+#include "batch_diag.h"
+#include "diag_sums.h"
+#include "nbody_hip_tuning.h"
+#include "render_common.h"
+
+using namespace nbi;
+
+namespace {
+
+// ---- diagnostics: the state every member holds, without reading the particles back ----------------------------------
+
+void check_diag(SimBatch *s, const void *out, const char *what) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(out != nullptr, "%s: NULL result array", what);
+    NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
+}
+
+// the three render calls are not wired for ragged ensembles: said before anything touches the device
+void check_not_ragged(const SimBatch *s, const char *what) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(!s->ragged, "%s: rendering of ragged ensembles (members of different sizes) is not supported", what);
+}
+
+nbd::EnsembleDiagParams diag_params(const SimBatch *s) {   // of the latest state
+    nbd::EnsembleDiagParams p{};
+    p.pos = s->pos[s->cur];
+    p.vel = s->vel;
+    p.radius = s->radius;
+    p.mass = s->mass;
+    p.gm = s->gm;
+    p.mass_len = s->mass_len_dev;
+    p.n = s->n;
+    p.stride = s->stride;
+    return p;
+}
+
+nbd::EnsembleDiagParams begin_diag(SimBatch *s) {
+    use_device();
+    if (!s->ev_diag[0]) {
+        for (auto &e : s->ev_diag) ASSERT_HIP(hipEventCreate(&e), "event");
+    }
+    ASSERT_HIP(hipEventRecord(s->ev_diag[0], s->stream), "record diagnostics begin");
+    return diag_params(s);
+}
+
+void end_diag(SimBatch *s) {
+    ASSERT_HIP(hipEventRecord(s->ev_diag[1], s->stream), "record diagnostics end");
+    s->diag_timed = true;
+}
+
+}  // namespace
+
+namespace nbi {
+
+void launch_energy_sums(SimBatch *s, double *res) {
+    const uint32_t tiles = nbd::ensemble_tiles(s->n);
+    nbd::EnsembleDiagParams p = diag_params(s);
+    p.slab = s->diag;
+    nbd::launch_ensemble_potential(s->stream, p, s->count);
+    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (energy, %u members of %u)", s->count, s->n);
+    nbd::launch_ensemble_reduce(s->stream, s->diag, s->mass_len_dev, tiles, s->count, res);
+    ASSERT_HIP(hipGetLastError(), "ensemble_reduce_kernel launch (%u members)", s->count);
+}
+
+double *energy_slab(SimBatch *s) {
+    return grown(s->stream, s->diag, s->diag_cap, (size_t)s->count * (nbd::ensemble_tiles(s->n) + 1) * NB_DIAG_SUMS);
+}
+
+}  // namespace nbi
+
+namespace {
+
+// ---- rendering: bounds, count tiles and frames of every member, without reading the particles back ------------------
+
+void begin_render(SimBatch *s) {
+    use_device();
+    if (!s->ev_render[0]) {
+        for (auto &e : s->ev_render) ASSERT_HIP(hipEventCreate(&e), "event");
+    }
+    ASSERT_HIP(hipEventRecord(s->ev_render[0], s->stream), "record render begin");
+}
+
+void end_render(SimBatch *s) {
+    ASSERT_HIP(hipEventRecord(s->ev_render[1], s->stream), "record render end");
+    s->render_timed = true;
+}
+
+void check_views(const SimBatch *s, const RenderView *views, const char *what) {
+    NB_ASSERT(views != nullptr, "%s: NULL RenderView array", what);
+    uint32_t member = 0;
+    const char *fault = nb_render_views_fault(views, s->count, &member);
+    NB_ASSERT(fault == nullptr, "%s: invalid RenderView of member %u of %u (%u x %u, zoom %g): %s", what, member, s->count,
+              views[member].width, views[member].height, (double)views[member].zoom, fault);
+}
+
+// The count images of the latest state on the stream: the tile kernel (straight to the frame when a palette is given) or
+// clear + splat + disc pass (+ shade); *launches = what was enqueued.
+void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint32_t *launches) {
+    const uint32_t width = views[0].width, height = views[0].height;
+    const size_t plane = (size_t)width * height;
+    const bool tile = nbr::tile_fits(width, height) && s->render_mode == 0;
+    if (!s->render_views) s->render_views = dev_alloc<RenderView>(s->count);
+    if (palette) grown(s->stream, s->render_rgba, s->render_rgba_cap, (size_t)s->count * plane);
+    if (!tile || !palette) grown(s->stream, s->render_counts, s->render_counts_cap, nbr::global_count_words(s->count, width, height));
+    if (!tile && !s->render_discs) s->render_discs = dev_alloc<nbr::EnsembleDisc>((size_t)s->count * s->n);
+    ASSERT_HIP(hipMemcpyAsync(s->render_views, views, (size_t)s->count * sizeof(RenderView), hipMemcpyHostToDevice, s->stream),
+               "H2D of %u views", s->count);
+    begin_render(s);
+    nbr::EnsembleRenderParams p{};
+    p.pos = s->pos[s->cur];
+    p.mass = s->mass;
+    p.radius = s->radius;
+    p.n = s->n;
+    p.stride = s->stride;
+    p.count = s->count;
+    p.width = width;
+    p.height = height;
+    p.views = s->render_views;
+    if (tile) {
+        nbr::launch_ensemble_tile(s->stream, p, s->render_counts, palette, s->render_rgba);
+        *launches = 1;
+    } else {
+        ASSERT_HIP(hipMemsetAsync(s->render_counts, 0, nbr::global_count_words(s->count, width, height) * sizeof(uint32_t), s->stream),
+                   "clear %u count images and the disc cursor", s->count);
+        nbr::launch_ensemble_global(s->stream, p, s->render_counts, s->render_discs);
+        *launches = 3;
+        if (palette) {
+            nbr::launch_ensemble_shade(s->stream, s->render_counts, s->count, (uint32_t)plane, *palette, s->render_rgba);
+            *launches = 4;
+        }
+    }
+    ASSERT_HIP(hipGetLastError(), "ensemble render launch (%u members of %u particles, %u x %u, %s path)", s->count, s->n, width, height,
+               tile ? "tile" : "global");
+    end_render(s);
+    s->render_tile = tile;
+    s->render_launches = *launches;
+}
+
+}  // namespace
+
+extern "C" {
+
+void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
+    check_diag(s, out, "nb_hip_ensemble_energy");
+    constexpr size_t Q = NB_DIAG_SUMS;
+    begin_diag(s);
+    double *res = energy_slab(s) + (size_t)s->count * nbd::ensemble_tiles(s->n) * Q;
+    launch_energy_sums(s, res);
+    end_diag(s);
+    s->diag_host.resize((size_t)s->count * Q);
+    ASSERT_HIP(hipMemcpyAsync(s->diag_host.data(), res, (size_t)s->count * Q * sizeof(double), hipMemcpyDeviceToHost, s->stream),
+               "D2H of %u members' energy sums", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_energy");
+    for (uint32_t b = 0; b < s->count; b++) nb_energy_from_sums(s->diag_host.data() + (size_t)b * Q, out + b);
+}
+
+void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
+    check_diag(s, phi, "nb_hip_ensemble_potential");
+    nbd::EnsembleDiagParams p = begin_diag(s);
+    const size_t total = (size_t)s->offsets[s->count];
+    p.phi = grown(s->stream, s->diag_phi, s->diag_phi_cap, total);
+    if (s->ragged)
+        nbd::launch_ragged_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
+    else
+        nbd::launch_ensemble_potential(s->stream, p, s->count);
+    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
+    end_diag(s);
+    ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u members' potentials",
+               s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_potential");
+}
+
+// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_ensemble_energy / _potential
+double nb_hip_ensemble_last_diag_ms(SimBatch *s) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (!s->diag_timed) return 0.0;
+    use_device();
+    return elapsed_ms(s->ev_diag[0], s->ev_diag[1]);
+}
+
+void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {
+    check_not_ragged(s, "nb_hip_ensemble_bounds");
+    check_diag(s, bounds, "nb_hip_ensemble_bounds");
+    begin_render(s);
+    if (!s->render_keys) s->render_keys = dev_alloc<uint32_t>((size_t)s->count * 4);
+    nbr::launch_ensemble_bounds(s->stream, s->pos[s->cur], s->n, s->stride, s->count, s->render_keys);
+    ASSERT_HIP(hipGetLastError(), "ensemble_bounds_kernel launch (%u members of %u)", s->count, s->n);
+    end_render(s);   // the event pair is shared with the renders; render_tile / render_launches speak of renders only
+    std::vector<uint32_t> keys((size_t)s->count * 4);
+    ASSERT_HIP(hipMemcpyAsync(keys.data(), s->render_keys, keys.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream),
+               "D2H of %u members' bounds", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_bounds");
+    for (uint32_t b = 0; b < s->count; b++) nb_render_bounds_from_keys(keys.data() + (size_t)b * 4, bounds + (size_t)b * 4);
+}
+
+void nb_hip_ensemble_render_counts(SimBatch *s, const RenderView *views, uint32_t *counts) {
+    check_not_ragged(s, "nb_hip_ensemble_render_counts");
+    check_diag(s, counts, "nb_hip_ensemble_render_counts");
+    check_views(s, views, "nb_hip_ensemble_render_counts");
+    use_device();
+    uint32_t launches = 0;
+    enqueue_render(s, views, nullptr, &launches);
+    const size_t bytes = (size_t)s->count * NB_RENDER_CLASSES * views[0].width * views[0].height * sizeof(uint32_t);
+    ASSERT_HIP(hipMemcpyAsync(counts, s->render_counts, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u count images", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_render_counts");
+}
+
+void nb_hip_ensemble_render_rgba(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint8_t *rgba) {
+    check_not_ragged(s, "nb_hip_ensemble_render_rgba");
+    check_diag(s, rgba, "nb_hip_ensemble_render_rgba");
+    check_views(s, views, "nb_hip_ensemble_render_rgba");
+    NB_ASSERT(palette != nullptr, "nb_hip_ensemble_render_rgba: NULL RenderPalette");
+    NB_ASSERT(palette->saturation >= 1u, "RenderPalette saturation must be at least 1");
+    use_device();
+    uint32_t launches = 0;
+    enqueue_render(s, views, palette, &launches);
+    const size_t bytes = (size_t)s->count * views[0].width * views[0].height * sizeof(uint32_t);
+    ASSERT_HIP(hipMemcpyAsync(rgba, s->render_rgba, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u frames", s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_render_rgba");
+}
+
+// tuning hooks (nbody_hip_tuning.h)
+void nb_hip_ensemble_render_mode(SimBatch *s, int mode) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(mode == 0 || mode == 1, "render mode %d (0 = auto, 1 = global path)", mode);
+    s->render_mode = mode;
+}
+
+void nb_hip_ensemble_last_render_info(const SimBatch *s, int *tile_path, uint32_t *launches) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (tile_path) *tile_path = s->render_tile;
+    if (launches) *launches = s->render_launches;
+}
+
+double nb_hip_ensemble_last_render_ms(SimBatch *s) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    if (!s->render_timed) return 0.0;
+    use_device();
+    return elapsed_ms(s->ev_render[0], s->ev_render[1]);
+}
+
+}  // extern "C"

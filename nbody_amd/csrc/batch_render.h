@@ -1,4 +1,4 @@
-// batch_render.h -- what batch.hip (the SimBatch and its C-ABI) needs of batch_render.hip (the ensemble's render kernels).
+// batch_render.h -- what batch_observe.hip and batch.hip (the SimBatch and its C-ABI) need of batch_render.hip (the ensemble's render kernels).
 #pragma once
 
 #include <hip/hip_runtime.h>

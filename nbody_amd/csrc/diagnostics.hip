@@ -148,16 +148,7 @@ nbd::DiagParams diag_params(SimPipeline *s, uint32_t n_recv) {
 
 // the pipeline's float64 scratch: QTY per workgroup + QTY results, grown on demand
 double *diag_scratch(SimPipeline *s, uint32_t rows) {
-    const size_t need = (size_t)(rows + 1) * QTY;
-    if (s->diag_cap < need) {
-        if (s->diag) {
-            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the diagnostics slab");
-            dev_free(s->diag);
-        }
-        s->diag = dev_alloc<double>(need);
-        s->diag_cap = need;
-    }
-    return s->diag;
+    return grown(s->stream, s->diag, s->diag_cap, (size_t)(rows + 1) * QTY);
 }
 
 }  // namespace
@@ -223,14 +214,7 @@ void nb_hip_potential(SimPipeline *s, float *phi) {
         return;
     }
     begin_diag(s);
-    if (s->diag_phi_cap < N) {
-        if (s->diag_phi) {
-            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the potential buffer");
-            dev_free(s->diag_phi);
-        }
-        s->diag_phi = dev_alloc<float>(N);
-        s->diag_phi_cap = N;
-    }
+    grown(s->stream, s->diag_phi, s->diag_phi_cap, N);
     nbd::DiagParams p = diag_params(s, N);
     p.phi = s->diag_phi;
     hipLaunchKernelGGL(nbd::potential_kernel, dim3((N + nbd::TILE - 1) / nbd::TILE), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
@@ -245,10 +229,7 @@ double nb_hip_last_diag_ms(SimPipeline *s) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
     if (!s->diag_timed) return 0.0;
     use_device();
-    ASSERT_HIP(hipEventSynchronize(s->ev_diag[1]), "diagnostics end event");
-    float ms = 0.0f;
-    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev_diag[0], s->ev_diag[1]), "diagnostics elapsed time");
-    return ms;
+    return elapsed_ms(s->ev_diag[0], s->ev_diag[1]);
 }
 
 }  // extern "C"

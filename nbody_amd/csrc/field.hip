@@ -260,16 +260,6 @@ bool pick_wave_shape(int shape_knob, uint32_t mass_len, uint32_t tiles) {
     return nblocks <= WAVE_SHAPE_BLOCKS_MAX && tiles >= WAVE_SHAPE_TILES_MIN;
 }
 
-void grow(SimPipeline *s, float *&buf, size_t &cap, size_t need, const char *noun, const char *what) {
-    if (cap >= need && buf) return;
-    if (buf) {
-        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the %s %s", noun, what);
-        dev_free(buf);
-    }
-    buf = dev_alloc<float>(need);
-    cap = need;
-}
-
 template <typename Q, bool MAP>
 void launch(SimPipeline *s, const fd::Params &p) {
     const uint32_t tiles = (p.n + nbd::TILE - 1) / nbd::TILE;
@@ -285,8 +275,8 @@ void launch(SimPipeline *s, const fd::Params &p) {
 template <typename Q>
 void run(SimPipeline *s, bool map, const float *in, size_t in_floats, uint32_t n, uint32_t width, float softening, typename Q::Out *out) {
     use_device();
-    grow(s, s->sample_in, s->sample_in_cap, in_floats, Q::NOUN, "samples");
-    grow(s, s->sample_out, s->sample_out_cap, (size_t)n * Q::C, Q::NOUN, "result");
+    grown(s->stream, s->sample_in, s->sample_in_cap, in_floats);
+    grown(s->stream, s->sample_out, s->sample_out_cap, (size_t)n * Q::C);
     ASSERT_HIP(hipMemcpyAsync(s->sample_in, in, in_floats * sizeof(float), hipMemcpyHostToDevice, s->stream), "H2D of the %s samples", Q::NOUN);
     fd::Params p{};
     p.pos = s->pos[s->cur];

@@ -5,12 +5,12 @@
 //   * SoA in HBM (float2 pos/vel/acc, float radius/mass, float G*m) instead of 32-byte AoS records;
 //   * device-to-host copy only when GetSimulationData asks (the reference copies after every call, sim_gpu.c:336-341);
 //   * nothing is created on the GPU until SetSimulationData, so CPU-only worlds never touch a device.
-// The rest of the seam lives next door: device_ctx.hip (device pick), step_chain.hip (what a step call enqueues),
+// The rest of the seam lives next door: device_ctx.hip (device pick), step_chain.hip (what a fixed-step call enqueues),
+// shard_exchange.hip (the sharded step), step_schedule.hip (device-chosen and leapfrog steps),
 // rccl_bind.hip + shard_plan.hip (the sharded pipeline's communicator and ownership plan), kernels.hip (gfx950 force
 // kernels), launch_shape.hip (launch policy), convert.hip (AoS <-> SoA).
 #include "pipeline_internal.h"
 #include "nbody_hip_tuning.h"
-#include "timestep.h"
 
 using namespace nbi;
 
@@ -309,53 +309,6 @@ int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units) 
     return nb::choose_shape({.lanes = 1}, n_recv, n_src, compute_units).unit;
 }
 
-int nb_hip_local_group_create(WorldData data, int nranks, SimPipeline **out) {
-    NB_ASSERT(nranks >= 1 && out != nullptr, "bad local group request");
-    use_device();
-    LocalGroup *g = new LocalGroup();
-    ASSERT_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking), "group stream");
-    for (int r = 0; r < nranks; r++) {
-        SimPipeline *s = CreateSimPipeline(data);
-        s->rank = r;
-        s->nranks = nranks;
-        s->sharded = true;
-        s->group = g;
-        s->plan = nb_hip_shard_plan(data.total_len, data.mass_len, r, nranks);
-        g->members.push_back(s);
-        out[r] = s;
-    }
-    return nranks;
-}
-
-void nb_hip_local_group_step(SimPipeline **sims, int nranks, uint32_t n, float dt) {
-    NB_ASSERT(sims != nullptr && nranks >= 1 && sims[0]->group != nullptr, "not a local group");
-    LocalGroup *g = sims[0]->group;
-    NB_ASSERT((int)g->members.size() == nranks, "group has %zu members, %d passed", g->members.size(), nranks);
-    for (int r = 0; r < nranks; r++) NB_ASSERT(sims[r]->on_device, "member %d has no data", r);
-    use_device();
-    for (int r = 0; r < nranks; r++) {
-        SimPipeline *s = sims[r];
-        s->pool.used = 0;
-        s->kernel_iv.clear();
-        s->comm_iv.clear();
-        s->detail_steps = 0;
-        upload_dt(s, dt);
-    }
-    // with the "timing" knob every member's kernels and pushes get their own event pairs, so that
-    // nb_hip_last_step_breakdown(member) says what ONE rank's shard step costs (bench.py S2 / S4 / S8)
-    for (uint32_t i = 0; i < n; i++)
-        for (int r = 0; r < nranks; r++) {
-            SimPipeline *s = sims[r];
-            sharded_step(s, resolve_shape(s), dt, g->stream, s->timing != 0 && i < DETAIL_STEPS_MAX);
-        }
-    for (int r = 0; r < nranks; r++) {
-        SimPipeline *s = sims[r];
-        s->detail_steps = s->timing ? (n < DETAIL_STEPS_MAX ? n : DETAIL_STEPS_MAX) : 0;
-        s->timed = false;   // no whole-chain event pair for group members; the breakdown has its own
-    }
-    ASSERT_HIP(hipStreamSynchronize(g->stream), "group sync");
-}
-
 void DestroySimPipeline(SimPipeline *sim) {
     if (sim == nullptr) return;
     release_device(sim);
@@ -538,77 +491,12 @@ void PerformSimUpdate(SimPipeline *s, uint32_t n, float dt) {
     nb_hip_sync(s);
 }
 
-// ---- adaptive steps (include/nbody_adaptive.h; kernels: timestep.hip; the launches: step_chain.hip enqueue_adaptive) ----
-
-void nb_hip_adaptive_steps_async(SimPipeline *s, uint32_t n, const NbAdaptive *cfg) {
-    check_adaptive(s, n, cfg, "nb_hip_adaptive_steps_async");
-    enqueue_adaptive(s, n, cfg);
-}
-
-void nb_hip_adaptive_collect(SimPipeline *s, float *dt_log, NbAdaptiveResult *out) {
-    NB_ASSERT(s != nullptr, "nb_hip_adaptive_collect: NULL pipeline");
-    if (out) memset(out, 0, sizeof *out);
-    const uint32_t n = s->adapt_logged;
-    if (n == 0 || !s->on_device) return;
-    use_device();
-    const size_t bytes = ADAPT_HEAD + (dt_log ? (size_t)n * sizeof(float) : 0);
-    s->adapt_host.resize(bytes);
-    ASSERT_HIP(hipMemcpyAsync(s->adapt_host.data(), s->adapt, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u step sizes and the result", n);
-    nb_hip_sync(s);
-    nb::AdaptState st;
-    memcpy(&st, s->adapt_host.data(), sizeof st);
-    if (out) *out = NbAdaptiveResult{st.t, st.steps, st.idle_steps, st.dt_last, st.dt_smallest};
-    if (dt_log) memcpy(dt_log, s->adapt_host.data() + ADAPT_HEAD, (size_t)n * sizeof(float));
-}
-
-void nb_hip_adaptive_steps(SimPipeline *s, uint32_t n, const NbAdaptive *cfg, float *dt_log, NbAdaptiveResult *out) {
-    check_adaptive(s, n, cfg, "nb_hip_adaptive_steps");
-    enqueue_adaptive(s, n, cfg);
-    nb_hip_adaptive_collect(s, dt_log, out);
-}
-
-void nb_hip_timestep(SimPipeline *s, const NbAdaptive *cfg, float *dt) {
-    check_adaptive(s, 1, cfg, "nb_hip_timestep");
-    NB_ASSERT(dt != nullptr, "nb_hip_timestep: NULL result");
-    if (s->slots == 0) {
-        *dt = cfg->dt_max;
-        return;
-    }
-    enqueue_timestep_peek(s, cfg);
-    ASSERT_HIP(hipMemcpyAsync(dt, static_cast<const char *>(s->adapt) + 2 * sizeof(nb::AdaptState), sizeof(float), hipMemcpyDeviceToHost,
-                              s->stream),
-               "D2H of the step size");
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_timestep");
-}
-
-// ---- leapfrog steps (include/nbody_leapfrog.h; kernels: leapfrog.hip; the launches: step_chain.hip enqueue_leapfrog) ----
-
-void nb_hip_leapfrog_steps_async(SimPipeline *s, uint32_t n, float dt) {
-    check_leapfrog(s, n, "nb_hip_leapfrog_steps_async");
-    enqueue_leapfrog(s, n, dt);
-}
-
-void nb_hip_leapfrog_steps(SimPipeline *s, uint32_t n, float dt) {
-    check_leapfrog(s, n, "nb_hip_leapfrog_steps");
-    enqueue_leapfrog(s, n, dt);
-    if (n > 0) nb_hip_sync(s);
-}
-
-void nb_hip_last_leapfrog_info(const SimPipeline *s, uint32_t *force_launches, int *primed) {
-    NB_ASSERT(s != nullptr, "NULL pipeline");
-    if (force_launches) *force_launches = s->lf_force_launches;
-    if (primed) *primed = s->lf_primed ? 1 : 0;
-}
-
 double nb_hip_last_step_ms(SimPipeline *s, uint32_t *launches) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
     if (launches) *launches = 0;
     if (!s->on_device || !s->timed) return 0.0;
-    ASSERT_HIP(hipEventSynchronize(s->ev_end), "event sync");
-    float ms = 0.0f;
-    ASSERT_HIP(hipEventElapsedTime(&ms, s->ev_begin, s->ev_end), "hipEventElapsedTime");
     if (launches) *launches = s->timed_launches;
-    return (double)ms;
+    return elapsed_ms(s->ev_begin, s->ev_end);
 }
 
 uint32_t nb_hip_last_finish_launches(const SimPipeline *s) {
@@ -626,11 +514,7 @@ uint32_t nb_hip_last_step_breakdown(SimPipeline *s, double *kernel_ms, double *c
     if (s->comm_stream) ASSERT_HIP(hipStreamSynchronize(s->comm_stream), "comm stream sync");
     auto total = [](const std::vector<std::pair<hipEvent_t, hipEvent_t>> &iv) {
         double sum = 0.0;
-        for (const auto &p : iv) {
-            float ms = 0.0f;
-            ASSERT_HIP(hipEventElapsedTime(&ms, p.first, p.second), "hipEventElapsedTime");
-            sum += (double)ms;
-        }
+        for (const auto &p : iv) sum += elapsed_ms(p.first, p.second);
         return sum;
     };
     if (kernel_ms) *kernel_ms = total(s->kernel_iv);

@@ -3,12 +3,16 @@
 //   device_ctx.hip   the process-wide device context (the reference keeps one global vulkan_ctx, vulkan_ctx.c:11)
 //   rccl_bind.hip    RCCL bound lazily with dlopen, the communicator of a sharded pipeline, the watchdog
 //   shard_plan.hip   nb_hip_shard_plan: who owns which receivers and sources (pure host arithmetic)
-//   step_chain.hip   one step / n steps as launches, cached hipGraph chains, the sharded step with its all-gather
+//   step_chain.hip   one step / n fixed Euler steps as launches: the launch plan, cached hipGraph chains, the one-workgroup chain
+//   shard_exchange.hip  the sharded step: the four transports of its in-place all-gather, captured sharded chains
+//   step_schedule.hip   device-chosen and leapfrog steps of a pipeline: the target of step_schedule.h's one launch schedule
 //   pipeline.hip     SimPipeline life cycle and the C-ABI entry points (Create/Destroy/Set/Get/PerformSimUpdate, knobs)
 //   kernels.hip      the gfx950 force kernels and their entry points (kernels.h)
 //   launch_shape.hip the host-side launch policy: shape, grid, LDS of a launch (launch_shape.h)
 //   convert.hip      AoS <-> SoA converters, pads, G*m, fills (convert.h)
-//   batch.hip        SimBatch: ensembles of small worlds stepped by one launch (nb_hip_batch_*)
+//   batch.hip        SimBatch (batch_internal.h): ensembles of small worlds stepped by one launch (nb_hip_batch_*), their
+//                    traced, adaptive and leapfrog updates (the ensemble's target of step_schedule.h)
+//   batch_observe.hip  the read-only calls on a SimBatch: energy, potential, bounds, count images and frames
 //   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
 //   batch_diag.hip   the same for every member of a SimBatch: the kernels behind nb_hip_ensemble_energy / _potential
 //                    (batch_diag.h; the arithmetic both share: diag_common.h)
@@ -136,6 +140,40 @@ T *dev_alloc(size_t count) {
 }
 
 inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
+
+// A scratch buffer grown on demand: at least `need` elements afterwards.  The old contents go (work queued on `st` may
+// still read them: it is drained first).
+template <typename T>
+T *grown(hipStream_t st, T *&buf, size_t &cap, size_t need) {
+    if (cap < need || !buf) {
+        if (buf) {
+            ASSERT_HIP(hipStreamSynchronize(st), "sync before regrowing a scratch buffer");
+            dev_free(buf);
+        }
+        buf = dev_alloc<T>(need);
+        cap = need;
+    }
+    return buf;
+}
+
+// The same for a buffer whose first `head` bytes are records a continued call goes on from: they are carried over.
+inline void regrow_carrying(hipStream_t st, void *&buf, size_t bytes, size_t head) {
+    void *old = buf;
+    buf = dev_alloc_bytes(bytes);
+    if (old) {
+        ASSERT_HIP(hipMemcpyAsync(buf, old, head, hipMemcpyDeviceToDevice, st), "carry the adaptive-step records over");
+        ASSERT_HIP(hipStreamSynchronize(st), "sync before freeing the old adaptive-step buffer");
+        dev_free(old);
+    }
+}
+
+// device time between two recorded events, once the later one has completed
+inline double elapsed_ms(hipEvent_t ev0, hipEvent_t ev1) {
+    ASSERT_HIP(hipEventSynchronize(ev1), "end event");
+    float ms = 0.0f;
+    ASSERT_HIP(hipEventElapsedTime(&ms, ev0, ev1), "elapsed time");
+    return (double)ms;
+}
 
 // ---- rccl_bind.hip -------------------------------------------------------------------------------------------
 
@@ -297,7 +335,7 @@ struct SimPipeline {
     double *diag = nullptr;      // float64 slab: NB_DIAG_SUMS per workgroup + the NB_DIAG_SUMS results
     size_t diag_cap = 0;         // doubles allocated in diag
     float *diag_phi = nullptr;   // nb_hip_potential's device result
-    uint32_t diag_phi_cap = 0;
+    size_t diag_phi_cap = 0;
     hipEvent_t ev_diag[2] = {nullptr, nullptr};
     bool diag_timed = false;
 
@@ -322,7 +360,7 @@ struct SimPipeline {
     int field_shape = 0;           // tuning hooks, Phi and g: 0 auto, 1 source split, 2 one wave per tile
     int gravity_shape = 0;
 
-    // adaptive steps (step_chain.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
+    // adaptive steps (step_schedule.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
     // ADAPT_HEAD bytes of records (the call's AdaptState, the record and result of nb_hip_timestep), then the call's log
     void *adapt = nullptr;
     size_t adapt_cap = 0;            // log floats allocated behind the head
@@ -330,7 +368,7 @@ struct SimPipeline {
     uint32_t adapt_logged = 0;       // steps of the last adaptive call: what nb_hip_adaptive_collect copies back
     std::vector<char> adapt_host;    // where that copy lands
 
-    // leapfrog steps (step_chain.hip enqueue_leapfrog; kernels: leapfrog.hip).  Their step sizes live in two words of the
+    // leapfrog steps (step_schedule.hip enqueue_leapfrog; kernels: leapfrog.hip).  Their step sizes live in two words of the
     // adaptive head (LEAPFROG_WORDS): a fixed-step call uses the first, an adaptive one alternates so that one launch can
     // close step i - 1 and open step i.
     bool acc_current = false;        // acc = F(x) of the state held: true after a leapfrog call, false after anything else that moves it
@@ -349,24 +387,33 @@ constexpr uint32_t DETAIL_STEPS_MAX = 256;  // steps per call whose kernels / ga
 void destroy_graph(StepGraph &g);
 nb::LaunchShape resolve_shape(SimPipeline *s);
 bool wants_canonical(const SimPipeline *s);
+StepGraph *find_graph(SimPipeline *s, uint32_t n, uint32_t passes, nb::LaunchShape sh, int phase);
 StepGraph *find_or_build_graph(SimPipeline *s, uint32_t n, float dt, nb::LaunchShape sh);
+void evict_for_one_more(SimPipeline *s);   // the least recently used cached chain goes once the cache is full
+constexpr uint32_t GRAPH_CHAIN_MAX = 64;   // longer requests replay an even-length chain
+// the single-kernel step that reads phase `in` and writes phase `in ^ 1`; its source passes; its launches
+nb::StepParams whole_step(const SimPipeline *s, int in, float dt);
+uint32_t passes_for(const SimPipeline *s, const nb::StepParams &p);
+void launch_step(SimPipeline *s, nb::LaunchShape sh, const nb::StepParams &p, hipStream_t st);
 void upload_dt(SimPipeline *s, float dt);
 void zero_tickets(SimPipeline *s);   // fused finish: all tile tickets back to 0, in stream order
+// what every step call starts and ends with: the per-call records cleared; ev_end and the launch counts of the timed interval
+void begin_call(SimPipeline *s);
+void end_call(SimPipeline *s, uint32_t launches);
+void enqueue_steps(SimPipeline *s, uint32_t n, float dt);  // what PerformSimUpdate / nb_hip_step_async enqueue
+
+// ---- shard_exchange.hip --------------------------------------------------------------------------------------
+
 // one sharded step of one rank; `cs` carries the gather (the comm stream with RCCL; the group stream locally)
 void sharded_step(SimPipeline *s, nb::LaunchShape sh, float dt, hipStream_t cs, bool detail = false);
 // in-place all-gather of a device array of nranks slots through the caller's host transport
 void host_allgather(SimPipeline *s, void *dev_base, size_t bytes_per_rank, hipStream_t st);
-void enqueue_steps(SimPipeline *s, uint32_t n, float dt);  // what PerformSimUpdate / nb_hip_step_async enqueue
-// adaptive steps (include/nbody_hip.h nb_hip_adaptive_steps): per step the criterion launch, then the launches of a one-step
-// call without its dt upload; enqueue only.  check_adaptive aborts on a bad call before anything touches a device.
-constexpr size_t ADAPT_HEAD = 128;   // bytes: AdaptState of the call at 0, of nb_hip_timestep at 32, its result at 64, leapfrog words at 96
-constexpr size_t LEAPFROG_WORDS = 96;   // offset of the two step-size words of the leapfrog passes in that head
-void check_adaptive(const SimPipeline *s, uint32_t n, const NbAdaptive *cfg, const char *what);
-void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg);
-void enqueue_timestep_peek(SimPipeline *s, const NbAdaptive *cfg);   // the criterion alone into the head's result slot
-// leapfrog steps (include/nbody_hip.h nb_hip_leapfrog_steps): open, a dt = 0 force launch, close per step; enqueue only
-void check_leapfrog(const SimPipeline *s, uint32_t n, const char *what);
-void enqueue_leapfrog(SimPipeline *s, uint32_t n, float dt);
+void enqueue_sharded(SimPipeline *s, uint32_t n, float dt);
+
+// ---- step_schedule.hip ---------------------------------------------------------------------------------------
+
+// the part of an adaptive call's checks a pipeline and an ensemble share: NULL arguments, the NbAdaptive's fault, the step count
+void check_adaptive_cfg(const void *s, uint32_t n, const NbAdaptive *cfg, const char *what);
 
 // ---- diagnostics.hip -----------------------------------------------------------------------------------------
 

@@ -233,17 +233,6 @@ void check_view(const RenderView *view) {
     NB_ASSERT(fault == nullptr, "invalid RenderView (%u x %u, zoom %g): %s", view->width, view->height, (double)view->zoom, fault);
 }
 
-template <typename T>
-void grow(SimPipeline *s, T *&buf, size_t &cap, size_t need, const char *what) {
-    if (cap >= need && buf) return;
-    if (buf) {
-        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before regrowing the %s", what);
-        dev_free(buf);
-    }
-    buf = dev_alloc<T>(need);
-    cap = need;
-}
-
 void ensure_words(SimPipeline *s) {
     if (!s->render_words) s->render_words = dev_alloc<uint32_t>(8);
 }
@@ -258,7 +247,7 @@ void enqueue_counts(SimPipeline *s, const RenderView *view) {
     use_device();
     const uint32_t N = s->data.total_len;
     const size_t plane = (size_t)view->width * view->height;
-    grow(s, s->render_counts, s->render_counts_cap, plane * NB_RENDER_CLASSES, "count image");
+    grown(s->stream, s->render_counts, s->render_counts_cap, plane * NB_RENDER_CLASSES);
     ensure_words(s);
     if (!s->render_discs) s->render_discs = dev_alloc<NbSplat>(N);
     const bool detail = s->render_detail != 0;
@@ -292,12 +281,6 @@ void enqueue_counts(SimPipeline *s, const RenderView *view) {
 void end_render(SimPipeline *s) {
     record(s, s->ev_render[3]);
     s->render_timed = true;
-}
-
-double elapsed(hipEvent_t a, hipEvent_t b) {
-    float ms = 0.0f;
-    ASSERT_HIP(hipEventElapsedTime(&ms, a, b), "render elapsed time");
-    return ms;
 }
 
 }  // namespace
@@ -371,7 +354,7 @@ void nb_hip_render_rgba(SimPipeline *s, const RenderView *view, const RenderPale
     NB_ASSERT(palette->saturation >= 1u, "RenderPalette saturation must be at least 1");
     const uint32_t plane = view->width * view->height;
     enqueue_counts(s, view);
-    grow(s, s->render_rgba, s->render_rgba_cap, (size_t)plane, "frame");
+    grown(s->stream, s->render_rgba, s->render_rgba_cap, (size_t)plane);
     hipLaunchKernelGGL(rd::shade_kernel, dim3((plane + rd::THREADS - 1) / rd::THREADS), dim3(rd::THREADS), 0, s->stream,
                        s->render_counts, plane, *palette, s->render_rgba);
     ASSERT_HIP(hipGetLastError(), "shade_kernel launch (%u pixels)", plane);
@@ -386,18 +369,15 @@ double nb_hip_last_render_ms(SimPipeline *s, double *parts) {
     if (parts) parts[0] = parts[1] = parts[2] = parts[3] = 0.0;
     if (!s->render_timed && !s->bounds_timed) return 0.0;
     use_device();
-    if (parts && s->bounds_timed) {
-        ASSERT_HIP(hipEventSynchronize(s->ev_bounds[1]), "bounds end event");
-        parts[0] = elapsed(s->ev_bounds[0], s->ev_bounds[1]);
-    }
+    if (parts && s->bounds_timed) parts[0] = elapsed_ms(s->ev_bounds[0], s->ev_bounds[1]);
     if (!s->render_timed) return 0.0;
-    ASSERT_HIP(hipEventSynchronize(s->ev_render[3]), "render end event");
+    const double whole = elapsed_ms(s->ev_render[0], s->ev_render[3]);   // waits for the last event: the ones between are done
     if (parts && s->render_detailed) {
-        parts[1] = elapsed(s->ev_render[0], s->ev_render[1]);
-        parts[2] = elapsed(s->ev_render[1], s->ev_render[2]);
-        parts[3] = elapsed(s->ev_render[2], s->ev_render[3]);
+        parts[1] = elapsed_ms(s->ev_render[0], s->ev_render[1]);
+        parts[2] = elapsed_ms(s->ev_render[1], s->ev_render[2]);
+        parts[3] = elapsed_ms(s->ev_render[2], s->ev_render[3]);
     }
-    return elapsed(s->ev_render[0], s->ev_render[3]);
+    return whole;
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "nbody_adaptive.h"
 
@@ -36,6 +37,28 @@ struct TimestepParams {
     float *log;            // this step's slot (ensemble: this step's row of [count]); may be null
     uint32_t commit;       // 1: advance t, count, log; 0: the criterion alone (dt_out only, no clip)
 };
+
+// what a call reports of a record copied back from the device
+inline NbAdaptiveResult adaptive_result(const void *record) {
+    AdaptState st;
+    memcpy(&st, record, sizeof st);
+    return NbAdaptiveResult{st.t, st.steps, st.idle_steps, st.dt_last, st.dt_smallest};
+}
+
+// the fields a world and an ensemble fill alike; state, dt_out, log and commit are the caller's
+inline TimestepParams timestep_params(const float2 *acc, const float *radius, uint32_t n, uint32_t stride, const NbAdaptive &cfg) {
+    TimestepParams p;
+    memset(&p, 0, sizeof p);
+    p.acc = acc;
+    p.radius = radius;
+    p.n = n;
+    p.stride = stride;
+    p.eta = cfg.eta;
+    p.dt_min = cfg.dt_min;
+    p.dt_max = cfg.dt_max;
+    p.span = cfg.span;
+    return p;
+}
 
 constexpr uint32_t TIMESTEP_THREADS = 256;
 constexpr uint32_t TIMESTEP_MAX_GROUPS = 32;   // four per XCD: a grid-stride read of 12 bytes per particle needs no more

@@ -377,7 +377,7 @@ def test_header_binding_exports_and_sources_agree():
     make = open(os.path.join(csrc, "Makefile")).read()
     assert re.search(r"^HIP_TUS\s*:=.*\btimestep\b", make, re.M) and re.search(r"^WORLD_SRCS\s*:=.*\btimestep_cpu\.c", make, re.M)
     assert make.count("timestep_common.h") >= 2 and make.count("include/nbody_adaptive.h") >= 2
-    for src in ("timestep.hip", "timestep_cpu.c", "step_chain.hip", "batch.hip", "world.c", "world_batch.c"):
+    for src in ("timestep.hip", "timestep_cpu.c", "step_schedule.hip", "world.c", "world_batch.c"):
         assert '#include "timestep_common.h"' in open(os.path.join(csrc, src)).read(), src
     # the statement is written once: nobody else divides a radius by a squared acceleration
     for name in sorted(os.listdir(csrc)):

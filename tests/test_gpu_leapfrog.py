@@ -230,6 +230,58 @@ def test_ensemble_members_are_the_composition_and_do_not_depend_on_their_neighbo
     assert lr.same_bits(got[1, :, 0:4], idle[1, :, 0:4])
 
 
+# The ensemble twins of the two pipeline tests above: what a call leaves behind (acc_current, dt_valid) is kept by the same
+# code for a world and for an ensemble.  250 particles x 3 members on the chain path, 600 x 2 on the lane-split path.
+BATCH_SHAPES = [(250, 3, "chain"), (600, 2, "lanes")]
+
+
+@pytest.mark.parametrize("what", ["update", "set_data", "euler adaptive", "trace"])
+@pytest.mark.parametrize("n,count,path", BATCH_SHAPES)
+def test_the_next_ensemble_call_primes_again_after(n, count, path, what):
+    parts, ms = members(n, count)
+    s = batch(parts, ms)
+    assert s.launch_shape()["path"] == path
+    s.update_leapfrog(2, DT)
+    if what == "update":
+        s.update(1, DT)
+    elif what == "set_data":
+        s.set_data(s.get_data())
+    elif what == "euler adaptive":
+        s.update_adaptive(1, ETA, DT_MAX)
+    else:
+        s.trace(1, DT, 1)
+    mid = s.get_data()
+    s.update_leapfrog(2, DT)
+    got, info = s.get_data(), s.last_leapfrog_info()
+    s.update_leapfrog(1, DT)
+    again = s.last_leapfrog_info()
+    s.close()
+    assert info == (3, True) and again == (1, False)
+    r = nb.SimBatch(n, ms)
+    want = lr.compose(batch_force_of(r), mid, [DT] * 2, prime=True)
+    r.close()
+    assert lr.same_bits(got, want), (n, count, what, lr.differing(got, want))
+
+
+@pytest.mark.parametrize("per_member", [False, True])
+@pytest.mark.parametrize("n,count,path", BATCH_SHAPES)
+def test_a_fixed_step_ensemble_update_after_a_leapfrog_call_uploads_its_own_step_sizes(n, count, path, per_member):
+    parts, ms = members(n, count)
+    dt = np.array([DT * (b + 1) for b in range(count)], dtype=np.float32) if per_member else DT
+    a = batch(parts, ms)
+    assert a.launch_shape()["path"] == path
+    a.update(1, dt)                 # the step kernels' words hold dt, and the host knows it
+    a.update_leapfrog(2, dt)        # ... now they hold 0
+    mid = a.get_data()
+    a.update(3, dt)
+    b = batch(mid, ms)
+    b.update(3, dt)
+    got, want = a.get_data(), b.get_data()
+    a.close()
+    b.close()
+    assert got.tobytes() == want.tobytes() and np.any(got[:, :, 0:2] != mid[:, :, 0:2])
+
+
 # ---- adaptive leapfrog -------------------------------------------------------------------------------------------------------
 
 STEPS = 6
