@@ -23,10 +23,16 @@
 // members fall into up to three launch GROUPS by their own size alone -- chain (N <= 512), lane-split (8, 8), lane-split
 // (16, 4) -- each with a device list of its member indices: one chain launch per call and one lane-split launch per group
 // and step (kernels.hip ragged_*_kernel, the same bodies with the receiver count read per member).  Member b's bits are
-// those of the same particles as the only member of a uniform SimBatch of its size.  A uniform SimBatch launches exactly
-// what it launched before ragged ones existed.
+// those of the same particles as the only member of a uniform SimBatch of its size.
+// The host has ONE representation and ONE launch walk for both: create() below makes every SimBatch with its groups -- a
+// uniform one has exactly one, of all members, without a device list -- and every fixed Euler step goes through
+// ensemble_walk.h's walk_ensemble with StepTarget as its target, so a uniform SimBatch launches exactly what it launched
+// before ragged ones existed.  `ragged` only picks the kernel family that addresses the members (batch_* by block index,
+// ragged_* through n_len and the lists): StepTarget, TraceTarget, split_members, merge_members, batch_observe.hip's
+// launch_potential, and materialize's upload of the tables the ragged family reads.
 #include "batch_internal.h"
 #include "diag_sums.h"
+#include "ensemble_walk.h"
 #include "leapfrog.h"
 #include "nbody_hip_tuning.h"
 #include "step_schedule.h"
@@ -43,7 +49,7 @@ void materialize(SimBatch *s) {
     for (auto &e : s->ev) ASSERT_HIP(hipEventCreate(&e), "event");
     const size_t rows = (size_t)s->count * s->stride;
     for (int b = 0; b < 2; b++) {
-        if (b == 1 && s->path == 0) break;   // the chain updates positions in place
+        if (b == 1 && !s->lane_split()) break;   // the chain updates positions in place
         s->pos[b] = dev_alloc<float2>(rows);
         ASSERT_HIP(hipMemsetAsync(s->pos[b], 0, rows * sizeof(float2), s->stream), "clear positions");
     }
@@ -114,81 +120,79 @@ nb::BatchParams step_params(const SimBatch *s) {
     p.dt = s->dt_dev;
     p.n_recv = s->n;
     p.stride = s->stride;
-    p.tiles = s->tiles;
     return p;
 }
 
-// n lane-split steps, one launch each
-void launch_lane_steps(SimBatch *s, nb::BatchParams &p, uint32_t n) {
-    const void *fn = nb::batch_lane_split_fn(s->w, s->lanes);
-    const nb::LaunchShape sh = {.k = 1, .w = s->w, .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = s->lanes};
-    dim3 grid = nb::step_grid(sh, s->n);
-    grid.y = s->count;
-    for (uint32_t i = 0; i < n; i++) {
-        p.pos_in = s->pos[s->cur];
-        p.pos_out = s->pos[s->cur ^ 1];
-        void *args[] = {&p};
-        ASSERT_HIP(hipLaunchKernel(fn, grid, nb::step_block(sh), args, nb::step_lds_bytes(sh, s->n), s->stream),
-                   "ensemble lane-split launch (w=%d lanes=%d, %u members of %u)", s->w, s->lanes, s->count, s->n);
-        s->cur ^= 1;
-    }
-}
+// What the launches of walk_ensemble are.  Each picks the kernel family: the uniform kernels take the BatchParams and index
+// the members by block, the ragged ones take it with the member sizes and the group's list.
+struct StepTarget {
+    SimBatch *s;
+    nb::BatchParams p;   // step_params(s)
 
-// n steps of a ragged ensemble: per step one launch for every lane-split group (all of them flip the ping-pong phase
-// together), then the chain group's whole call in place in the buffer it started from -- and, when the phase moved, one
-// copy of the chain members' position rows into the buffer that is now the latest, so that every reader (read-back,
-// diagnostics, the next call) finds all members in pos[cur].  Returns the launches made.
-uint32_t launch_ragged_steps(SimBatch *s, const nb::BatchParams &p0, uint32_t n) {
-    uint32_t launches = 0;
-    const int cur0 = s->cur;
-    for (uint32_t i = 0; i < n && s->path != 0; i++) {
-        for (const auto &g : s->groups) {
-            if (g.path == 0) continue;
-            nb::RaggedParams rp = {p0, s->n_len_dev, g.list};
-            rp.b.pos_in = s->pos[s->cur];
-            rp.b.pos_out = s->pos[s->cur ^ 1];
-            const nb::LaunchShape sh = {.k = 1, .w = g.w, .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = g.lanes};
-            dim3 grid = nb::step_grid(sh, g.max_n);
-            grid.y = (uint32_t)g.members.size();
-            void *args[] = {&rp};
-            ASSERT_HIP(hipLaunchKernel(nb::ragged_lane_split_fn(g.w, g.lanes), grid, nb::step_block(sh), args,
-                                       nb::step_lds_bytes(sh, g.max_n), s->stream),
-                       "ragged lane-split launch (w=%d lanes=%d, %zu members of up to %u)", g.w, g.lanes, g.members.size(), g.max_n);
-            launches++;
-        }
-        s->cur ^= 1;
+    nb::RaggedParams params(const SimBatch::Group &g, int in, int out, uint32_t steps) const {
+        nb::RaggedParams rp = {p, s->n_len_dev, g.list};
+        rp.b.pos_in = s->pos[in];
+        rp.b.pos_out = s->pos[out];
+        rp.b.steps = steps;
+        rp.b.tiles = g.tiles;
+        return rp;
     }
-    for (const auto &g : s->groups) {
-        if (g.path != 0) continue;
-        nb::RaggedParams rp = {p0, s->n_len_dev, g.list};
-        rp.b.pos_in = rp.b.pos_out = s->pos[cur0];
-        for (uint32_t left = n; left > 0; left -= rp.b.steps, launches++) {
-            rp.b.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
+    void lanes(const SimBatch::Group &g, int in) {
+        nb::RaggedParams rp = params(g, in, in ^ 1, 0);
+        void *args[] = {s->ragged ? (void *)&rp : (void *)&rp.b};
+        ASSERT_HIP(hipLaunchKernel(g.fn, g.grid, g.block, args, g.lds, s->stream),
+                   "ensemble lane-split launch (w=%d lanes=%d, %zu members of up to %u)", g.w, g.lanes, g.members.size(), g.max_n);
+    }
+    void chain(const SimBatch::Group &g, int buf, uint32_t steps) {
+        const nb::RaggedParams rp = params(g, buf, buf, steps);
+        if (s->ragged)
             nb::launch_ragged_chain(s->stream, rp, (uint32_t)g.members.size());
-        }
-        if (s->cur != cur0 && n > 0) {
-            nb::launch_ragged_copy_rows(s->stream, g.list, s->n_len_dev, (uint32_t)g.members.size(), g.max_n, s->stride, s->pos[cur0],
-                                        s->pos[s->cur]);
-            launches++;
-        }
+        else
+            nb::launch_batch_chain(s->stream, rp.b, s->count);
     }
-    return launches;
+    void copy(const SimBatch::Group &g, int from, int to) {
+        NB_ASSERT(s->ragged, "a uniform ensemble is one group: its chain never meets a phase that moved");
+        nb::launch_ragged_copy_rows(s->stream, g.list, s->n_len_dev, (uint32_t)g.members.size(), g.max_n, s->stride, s->pos[from],
+                                    s->pos[to]);
+    }
+};
+
+// The chain that records from the state it holds in LDS: t.done carries the record index across the launches of a call.
+struct TraceTarget : StepTarget {
+    nb::BatchTraceParams t;
+
+    void chain(const SimBatch::Group &g, int buf, uint32_t steps) {
+        t.b = params(g, buf, buf, steps).b;
+        if (s->ragged)
+            nb::launch_ragged_trace_chain(s->stream, nb::RaggedTraceParams{t, s->n_len_dev, g.list}, (uint32_t)g.members.size());
+        else
+            nb::launch_batch_trace_chain(s->stream, t);
+        t.done += steps;
+    }
+};
+
+// n steps, no record; returns the launches made
+uint32_t launch_steps(SimBatch *s, const nb::BatchParams &p, uint32_t n) {
+    StepTarget target = {s, p};
+    return walk_ensemble(target, s->groups, s->cur, n, CHAIN_MAX_STEPS_PER_LAUNCH);
 }
 
-// n steps, no record: whole chain launches or lane-split launches; returns the launches made
-uint32_t launch_steps(SimBatch *s, nb::BatchParams &p, uint32_t n) {
-    if (s->ragged) return launch_ragged_steps(s, p, n);
-    if (s->path != 0) {
-        launch_lane_steps(s, p, n);
-        return n;
-    }
-    uint32_t launches = 0;
-    p.pos_in = p.pos_out = s->pos[s->cur];
-    for (uint32_t left = n; left > 0; left -= p.steps, launches++) {
-        p.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
-        nb::launch_batch_chain(s->stream, p, s->count);
-    }
-    return launches;
+// the seam's converters, same pick: staged AoS records -> SoA rows of buffer 0 and G*m; the latest rows -> AoS records
+void split_members(SimBatch *s) {
+    if (s->ragged)
+        nb::launch_ragged_split(s->stream, s->aos, s->offsets_dev, s->n_len_dev, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0],
+                                s->vel, s->acc, s->radius, s->mass, s->gm, NB_G);
+    else
+        nb::launch_batch_split(s->stream, s->aos, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0], s->vel, s->acc, s->radius,
+                               s->mass, s->gm, NB_G);
+}
+
+void merge_members(SimBatch *s, uint32_t first, uint32_t members) {
+    if (s->ragged)
+        nb::launch_ragged_merge(s->stream, s->aos, s->offsets_dev, s->n_len_dev, first, members, s->n, s->stride, s->pos[s->cur], s->vel,
+                                s->acc, s->radius, s->mass);
+    else
+        nb::launch_batch_merge(s->stream, s->aos, first, members, s->n, s->stride, s->pos[s->cur], s->vel, s->acc, s->radius, s->mass);
 }
 
 void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
@@ -290,11 +294,7 @@ void read_back(SimBatch *s, uint32_t first, uint32_t members, Particle *ps) {
     NB_ASSERT(s != nullptr && ps != nullptr, "NULL argument");
     NB_ASSERT(s->has_data, "ensemble read-back before nb_hip_batch_set_data");
     use_device();
-    if (s->ragged)
-        nb::launch_ragged_merge(s->stream, s->aos, s->offsets_dev, s->n_len_dev, first, members, s->n, s->stride, s->pos[s->cur], s->vel,
-                                s->acc, s->radius, s->mass);
-    else
-        nb::launch_batch_merge(s->stream, s->aos, first, members, s->n, s->stride, s->pos[s->cur], s->vel, s->acc, s->radius, s->mass);
+    merge_members(s, first, members);
     ASSERT_HIP(hipMemcpyAsync(ps, static_cast<const Particle *>(s->aos) + s->offsets[first],
                               (size_t)(s->offsets[first + members] - s->offsets[first]) * sizeof(Particle), hipMemcpyDeviceToHost,
                               s->stream),
@@ -321,30 +321,15 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
     constexpr size_t Q = NB_DIAG_SUMS;
     const size_t pitch = (size_t)s->count * Q;
     double *rows = grown(s->stream, s->trace, s->trace_cap, (size_t)records * pitch);
-    const bool fused = s->path == 0 && s->trace_mode == 0;
+    const bool fused = !s->lane_split() && s->trace_mode == 0;   // every member is in the one chain group
     if (!fused) energy_slab(s);
-    nb::BatchParams p = step_params(s);
+    const nb::BatchParams p = step_params(s);
     uint32_t launches = 0;
     ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
     if (fused) {
-        nb::BatchTraceParams t;
-        memset(&t, 0, sizeof t);
-        t.mass = s->mass;
-        t.rows = rows;
-        t.count = s->count;
-        t.every = every;
-        p.pos_in = p.pos_out = s->pos[s->cur];
-        do {   // n = 0 is one launch of no steps: the record on entry
-            const uint32_t left = n - t.done;
-            p.steps = left > CHAIN_MAX_STEPS_PER_LAUNCH ? CHAIN_MAX_STEPS_PER_LAUNCH : left;
-            t.b = p;
-            if (s->ragged)   // fused means every member is in the chain group: its list is 0 .. count - 1
-                nb::launch_ragged_trace_chain(s->stream, nb::RaggedTraceParams{t, s->n_len_dev, s->groups[0].list}, s->count);
-            else
-                nb::launch_batch_trace_chain(s->stream, t);
-            t.done += p.steps;
-            launches++;
-        } while (t.done < n);
+        TraceTarget target = {{s, p}, {.mass = s->mass, .rows = rows, .count = s->count, .every = every}};
+        if (n == 0) target.chain(s->groups[0], s->cur, 0);   // one launch of no steps: the record on entry
+        launches = n == 0 ? 1 : walk_ensemble(target, s->groups, s->cur, n, CHAIN_MAX_STEPS_PER_LAUNCH);
     } else {
         launch_energy_sums(s, rows);
         launches += 2;
@@ -368,6 +353,61 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
     for (size_t i = 0; i < (size_t)records * s->count; i++) nb_energy_from_sums(s->trace_host.data() + i * Q, out + i);
 }
 
+// The launch shape of a member of n particles, a function of n alone: the chain while it fits (k = 2, 16 waves over its
+// tiles), the lane-split shape above that.  slot: 0 chain, 1 lane-split (8, 8), 2 lane-split (16, 4).
+struct MemberShape { int slot, k, w, lanes; };
+MemberShape member_shape(uint32_t n) {
+    if (const uint32_t tiles = nb::chain_tiles(n)) return {0, 2, (int)(16u / tiles), 1};
+    int w = 16;
+    const int lanes = nb::batch_lane_shape(n, &w);
+    return {lanes == 8 ? 1 : 2, 1, w, lanes};
+}
+
+// Every SimBatch is made here, from the checked sizes its entry point put into n_len: offsets, stride, and the groups with
+// all that their launches need.
+SimBatch *create(SimBatch *s, const uint32_t *mass_len, bool ragged) {
+    const uint32_t count = (uint32_t)s->n_len.size();
+    s->ragged = ragged;
+    s->count = count;
+    s->mass_len.assign(mass_len, mass_len + count);
+    s->dt_host.assign(count, 0.0f);
+    s->offsets.resize((size_t)count + 1);   // offsets[0] = 0
+    SimBatch::Group slot[3];
+    for (uint32_t b = 0; b < count; b++) {
+        const uint32_t n = s->n_len[b];
+        s->offsets[b + 1] = s->offsets[b] + n;
+        s->n = n > s->n ? n : s->n;
+        const MemberShape m = member_shape(n);
+        SimBatch::Group &g = slot[m.slot];
+        g.path = m.slot != 0;
+        g.k = m.k;
+        g.lanes = m.lanes;
+        if (n > g.max_n) {   // chain: w of the group's largest member
+            g.max_n = n;
+            g.w = m.w;
+        }
+        g.members.push_back(b);
+    }
+    s->stride = round_up(s->n, 64);
+    for (auto &g : slot) {
+        if (g.members.empty()) continue;
+        g.tiles = nb::chain_tiles(g.max_n);
+        g.workgroups = (uint32_t)g.members.size();
+        if (g.path) {
+            const nb::LaunchShape sh = {.k = 1, .w = g.w, .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = g.lanes};
+            g.fn = ragged ? nb::ragged_lane_split_fn(g.w, g.lanes) : nb::batch_lane_split_fn(g.w, g.lanes);
+            NB_ASSERT(g.lanes > 1 && g.fn != nullptr, "no ensemble kernel for w=%d lanes=%d", g.w, g.lanes);
+            g.grid = nb::step_grid(sh, g.max_n);
+            g.workgroups *= g.grid.x;
+            g.grid.y = (uint32_t)g.members.size();
+            g.block = nb::step_block(sh);
+            g.lds = nb::step_lds_bytes(sh, g.max_n);
+        }
+        s->groups.push_back(g);
+    }
+    return s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -382,30 +422,8 @@ SimBatch *nb_hip_batch_create(uint32_t count, uint32_t total_len, const uint32_t
     for (uint32_t b = 0; b < count; b++)
         NB_ASSERT(mass_len[b] <= total_len, "member %u: mass_len %u > total_len %u", b, mass_len[b], total_len);
     SimBatch *s = new SimBatch();
-    s->count = count;
-    s->n = total_len;
-    s->stride = round_up(total_len, 64);
-    s->mass_len.assign(mass_len, mass_len + count);
-    s->dt_host.assign(count, 0.0f);
     s->n_len.assign(count, total_len);
-    s->offsets.resize((size_t)count + 1);
-    for (uint32_t b = 0; b <= count; b++) s->offsets[b] = (uint64_t)b * total_len;
-    s->tiles = nb::chain_tiles(total_len);
-    if (s->tiles) {
-        s->path = 0;
-        s->k = 2;
-        s->w = (int)(16u / s->tiles);
-        s->lanes = 1;
-        s->workgroups = count;
-    } else {
-        s->path = 1;
-        s->k = 1;
-        s->lanes = nb::batch_lane_shape(total_len, &s->w);
-        NB_ASSERT(s->lanes > 1 && nb::batch_lane_split_fn(s->w, s->lanes) != nullptr, "no ensemble kernel for w=%d lanes=%d", s->w,
-                  s->lanes);
-        s->workgroups = count * ((total_len + 64u / (uint32_t)s->lanes - 1) / (64u / (uint32_t)s->lanes));
-    }
-    return s;
+    return create(s, mass_len, false);
 }
 
 SimBatch *nb_hip_ragged_create(uint32_t count, const uint32_t *total_len, const uint32_t *mass_len) {
@@ -419,46 +437,8 @@ SimBatch *nb_hip_ragged_create(uint32_t count, const uint32_t *total_len, const 
         NB_ASSERT(mass_len[b] <= total_len[b], "member %u: mass_len %u > total_len %u", b, mass_len[b], total_len[b]);
     }
     SimBatch *s = new SimBatch();
-    s->ragged = true;
-    s->count = count;
-    s->mass_len.assign(mass_len, mass_len + count);
     s->n_len.assign(total_len, total_len + count);
-    s->dt_host.assign(count, 0.0f);
-    s->offsets.resize((size_t)count + 1);
-    s->offsets[0] = 0;
-    SimBatch::Group slot[3];   // chain, lane-split (8, 8), lane-split (16, 4)
-    for (uint32_t b = 0; b < count; b++) {
-        const uint32_t n = total_len[b];
-        s->offsets[b + 1] = s->offsets[b] + n;
-        s->n = n > s->n ? n : s->n;
-        int which = 0, w = 16, lanes = 1;
-        if (nb::chain_tiles(n) == 0) {
-            lanes = nb::batch_lane_shape(n, &w);
-            NB_ASSERT(lanes > 1 && nb::ragged_lane_split_fn(w, lanes) != nullptr, "member %u: no ensemble kernel for w=%d lanes=%d", b, w,
-                      lanes);
-            which = lanes == 8 ? 1 : 2;
-        }
-        SimBatch::Group &g = slot[which];
-        g.path = which != 0;
-        g.k = which ? 1 : 2;
-        g.lanes = lanes;
-        g.max_n = n > g.max_n ? n : g.max_n;
-        g.w = which ? w : (int)(16u / nb::chain_tiles(g.max_n));
-        g.members.push_back(b);
-    }
-    s->stride = round_up(s->n, 64);
-    for (auto &g : slot) {
-        if (g.members.empty()) continue;
-        const uint32_t per = g.path ? (g.max_n + 64u / (uint32_t)g.lanes - 1) / (64u / (uint32_t)g.lanes) : 1u;
-        g.workgroups = (uint32_t)g.members.size() * per;
-        s->workgroups += g.workgroups;
-        if (g.path) s->path = 1;
-        s->groups.push_back(g);
-    }
-    s->k = s->groups[0].k;
-    s->w = s->groups[0].w;
-    s->lanes = s->groups[0].lanes;
-    return s;
+    return create(s, mass_len, true);
 }
 
 void nb_hip_ragged_layout(const SimBatch *s, uint32_t *sizes, uint64_t *offsets) {
@@ -470,22 +450,14 @@ void nb_hip_ragged_layout(const SimBatch *s, uint32_t *sizes, uint64_t *offsets)
 uint32_t nb_hip_ragged_launch_shape(const SimBatch *s, uint32_t group, int *path, int *k, int *w, int *lanes, uint32_t *members,
                                     uint32_t *workgroups) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
-    const uint32_t groups = s->ragged ? (uint32_t)s->groups.size() : 1u;
+    const uint32_t groups = (uint32_t)s->groups.size();
     NB_ASSERT(group < groups, "launch group %u of %u", group, groups);
-    SimBatch::Group uniform;   // a uniform ensemble is one group of all members
-    if (!s->ragged) {
-        uniform.path = s->path;
-        uniform.k = s->k;
-        uniform.w = s->w;
-        uniform.lanes = s->lanes;
-        uniform.workgroups = s->workgroups;
-    }
-    const SimBatch::Group &g = s->ragged ? s->groups[group] : uniform;
+    const SimBatch::Group &g = s->groups[group];
     if (path) *path = g.path;
     if (k) *k = g.k;
     if (w) *w = g.w;
     if (lanes) *lanes = g.lanes;
-    if (members) *members = s->ragged ? (uint32_t)g.members.size() : s->count;
+    if (members) *members = (uint32_t)g.members.size();
     if (workgroups) *workgroups = g.workgroups;
     return groups;
 }
@@ -493,19 +465,14 @@ uint32_t nb_hip_ragged_launch_shape(const SimBatch *s, uint32_t group, int *path
 void nb_hip_ragged_member_shape(const SimBatch *s, uint32_t member, uint32_t *group, int *k, int *w, int *lanes) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
     NB_ASSERT(member < s->count, "member %u of %u", member, s->count);
-    const uint32_t n = s->n_len[member], tiles = nb::chain_tiles(n);
-    int mw = 16, ml = 1;
-    if (tiles)
-        mw = (int)(16u / tiles);
-    else
-        ml = nb::batch_lane_shape(n, &mw);
-    uint32_t gi = 0;
-    for (uint32_t i = 0; s->ragged && i < s->groups.size(); i++)
-        if (s->groups[i].path == (tiles ? 0 : 1) && (tiles || s->groups[i].lanes == ml)) gi = i;
+    const MemberShape m = member_shape(s->n_len[member]);
+    uint32_t gi = 0;   // the lanes tell the groups apart: 1, 8, 4
+    for (uint32_t i = 0; i < s->groups.size(); i++)
+        if (s->groups[i].lanes == m.lanes) gi = i;
     if (group) *group = gi;
-    if (k) *k = tiles ? 2 : 1;
-    if (w) *w = mw;
-    if (lanes) *lanes = ml;
+    if (k) *k = m.k;
+    if (w) *w = m.w;
+    if (lanes) *lanes = m.lanes;
 }
 
 void nb_hip_batch_destroy(SimBatch *s) {
@@ -513,29 +480,12 @@ void nb_hip_batch_destroy(SimBatch *s) {
     if (s->on_device) {
         use_device();
         ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before destroying an ensemble");
-        for (auto &p : s->pos) dev_free(p);
-        dev_free(s->vel);
-        dev_free(s->acc);
-        dev_free(s->radius);
-        dev_free(s->mass);
-        dev_free(s->gm);
-        dev_free(s->mass_len_dev);
-        dev_free(s->dt_dev);
-        dev_free(s->aos);
-        if (s->n_len_dev) dev_free(s->n_len_dev);
-        if (s->offsets_dev) dev_free(s->offsets_dev);
-        for (auto &g : s->groups)
-            if (g.list) dev_free(g.list);
-        if (s->diag) dev_free(s->diag);
-        if (s->diag_phi) dev_free(s->diag_phi);
-        if (s->trace) dev_free(s->trace);
-        if (s->render_views) dev_free(s->render_views);
-        if (s->render_keys) dev_free(s->render_keys);
-        if (s->render_counts) dev_free(s->render_counts);
-        if (s->render_rgba) dev_free(s->render_rgba);
-        if (s->render_discs) dev_free(s->render_discs);
-        if (s->adapt) dev_free(s->adapt);
-        if (s->lf_dt) dev_free(s->lf_dt);
+        for (void *p : std::initializer_list<void *>{   // dev_free takes null: what was never made
+                 s->pos[0], s->pos[1], s->vel, s->acc, s->radius, s->mass, s->gm, s->mass_len_dev, s->dt_dev, s->aos, s->n_len_dev,
+                 s->offsets_dev, s->diag, s->diag_phi, s->trace, s->render_views, s->render_keys, s->render_counts, s->render_rgba,
+                 s->render_discs, s->adapt, s->lf_dt})
+            dev_free(p);
+        for (auto &g : s->groups) dev_free(g.list);
         for (auto &e : s->ev_render)
             if (e) ASSERT_HIP(hipEventDestroy(e), "event");
         for (auto &e : s->ev_diag)
@@ -558,12 +508,7 @@ void nb_hip_batch_set_data(SimBatch *s, const Particle *ps) {
     s->acc_current = false;   // the uploaded acc is the caller's: a leapfrog call evaluates its own first
     ASSERT_HIP(hipMemcpyAsync(s->aos, ps, (size_t)s->offsets[s->count] * sizeof(Particle), hipMemcpyHostToDevice, s->stream),
                "H2D of %u members' particles (up to %u each)", s->count, s->n);
-    if (s->ragged)
-        nb::launch_ragged_split(s->stream, s->aos, s->offsets_dev, s->n_len_dev, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0],
-                                s->vel, s->acc, s->radius, s->mass, s->gm, NB_G);
-    else
-        nb::launch_batch_split(s->stream, s->aos, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0], s->vel, s->acc, s->radius,
-                               s->mass, s->gm, NB_G);
+    split_members(s);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_batch_set_data");
     s->has_data = true;
 }
@@ -685,11 +630,14 @@ void nb_hip_ensemble_last_trace_info(const SimBatch *s, int *fused, uint32_t *la
 
 void nb_hip_batch_launch_shape(const SimBatch *s, int *path, int *k, int *w, int *lanes, uint32_t *workgroups) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
-    if (path) *path = s->path;
-    if (k) *k = s->k;
-    if (w) *w = s->w;
-    if (lanes) *lanes = s->lanes;
-    if (workgroups) *workgroups = s->workgroups;
+    const SimBatch::Group &first = s->groups[0];
+    uint32_t total = 0;
+    for (const auto &g : s->groups) total += g.workgroups;
+    if (path) *path = s->lane_split() ? 1 : 0;
+    if (k) *k = first.k;
+    if (w) *w = first.w;
+    if (lanes) *lanes = first.lanes;
+    if (workgroups) *workgroups = total;
 }
 
 }  // extern "C"

@@ -30,23 +30,24 @@ struct SimBatch {
     void *aos = nullptr;   // device staging of Set / Get: [count][n] Particle
     int cur = 0;           // pos[cur] is the latest state (the chain path never moves it)
 
-    // the launch shape, fixed at creation
-    int path = 0;          // 0 chain, 1 lane-split
-    int k = 2, w = 16, lanes = 1;
-    uint32_t tiles = 0;
-    uint32_t workgroups = 0;
-
-    // ragged only: the launch groups, in the order chain, lane-split (8, 8), lane-split (16, 4); those without members are
-    // absent.  path = 1 as soon as one member is lane-split (both position buffers exist, traces interleave).
+    // The launch shape, fixed at creation: the launch groups, in the order chain, lane-split (8, 8), lane-split (16, 4); those
+    // without members are absent.  A uniform ensemble is one group of all members.  `ragged` says only which kernel family
+    // addresses the members: by block index, or through n_len_dev and the groups' lists.
     struct Group {
-        int path = 0, k = 2, w = 16, lanes = 1;   // chain: w of the group's largest member
+        int path = 0, k = 2, w = 16, lanes = 1;   // path: 0 chain, 1 lane-split; chain: w of the group's largest member
+        uint32_t tiles = 0;                       // chain: chain_tiles(max_n)
         uint32_t max_n = 0;                       // its largest member
         uint32_t workgroups = 0;                  // per launch
         std::vector<uint32_t> members;            // ascending member indices
-        uint32_t *list = nullptr;                 // the same on the device
+        uint32_t *list = nullptr;                 // ragged: the same on the device
+        const void *fn = nullptr;                 // lane-split: the kernel, the grid, the block and the LDS bytes of a launch
+        dim3 grid, block;
+        size_t lds = 0;
     };
     std::vector<Group> groups;
-    uint32_t *n_len_dev = nullptr;
+    // some group is lane-split (the chain group comes first): both position buffers exist, traces interleave
+    bool lane_split() const { return groups.back().path != 0; }
+    uint32_t *n_len_dev = nullptr;     // ragged only, like offsets_dev
     uint64_t *offsets_dev = nullptr;
 
     // nb_hip_ensemble_energy / nb_hip_ensemble_potential (kernels: batch_diag.hip): scratch made on first use, an event

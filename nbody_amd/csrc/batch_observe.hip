@@ -52,6 +52,14 @@ void end_diag(SimBatch *s) {
     s->diag_timed = true;
 }
 
+// Phi of every particle to p.phi, packed member after member: the pick of the kernel family, as batch.hip's StepTarget makes it
+void launch_potential(SimBatch *s, const nbd::EnsembleDiagParams &p) {
+    if (s->ragged)
+        nbd::launch_ragged_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
+    else
+        nbd::launch_ensemble_potential(s->stream, p, s->count);
+}
+
 }  // namespace
 
 namespace nbi {
@@ -163,10 +171,7 @@ void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
     nbd::EnsembleDiagParams p = begin_diag(s);
     const size_t total = (size_t)s->offsets[s->count];
     p.phi = grown(s->stream, s->diag_phi, s->diag_phi_cap, total);
-    if (s->ragged)
-        nbd::launch_ragged_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
-    else
-        nbd::launch_ensemble_potential(s->stream, p, s->count);
+    launch_potential(s, p);
     ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
     end_diag(s);
     ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u members' potentials",

@@ -10,8 +10,10 @@
 //   kernels.hip      the gfx950 force kernels and their entry points (kernels.h)
 //   launch_shape.hip the host-side launch policy: shape, grid, LDS of a launch (launch_shape.h)
 //   convert.hip      AoS <-> SoA converters, pads, G*m, fills (convert.h)
-//   batch.hip        SimBatch (batch_internal.h): ensembles of small worlds stepped by one launch (nb_hip_batch_*), their
-//                    traced, adaptive and leapfrog updates (the ensemble's target of step_schedule.h)
+//   batch.hip        SimBatch (batch_internal.h): ensembles of small worlds, uniform or ragged, stepped by one launch
+//                    (nb_hip_batch_*, nb_hip_ragged_*): one constructor, and the target of ensemble_walk.h's one launch walk
+//                    (host only, no HIP) for every fixed step; their traced, adaptive and leapfrog updates (the ensemble's
+//                    target of step_schedule.h)
 //   batch_observe.hip  the read-only calls on a SimBatch: energy, potential, bounds, count images and frames
 //   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
 //   batch_diag.hip   the same for every member of a SimBatch: the kernels behind nb_hip_ensemble_energy / _potential

@@ -170,6 +170,35 @@ def test_traced_updates_record_the_energy_of_separately_stepped_states(mixed, ev
         t.close()
 
 
+@pytest.mark.parametrize("n", [129, 513, 1582], ids=["chain-2-tiles", "lanes-8x8", "lanes-16x4"])
+def test_a_ragged_ensemble_of_equal_sizes_is_the_uniform_ensemble(n):
+    """Both come out of one constructor and one launch walk: the same launches through the other kernel family.  B = 3 with
+    M = (N, 0, 77) and a step size per member; update(3), update(2), trace(5, every=2): everything observable is bitwise equal."""
+    mass, steps = [n, 0, 77], [0.01, 0.013, 0.007]
+    members = []
+    for b, m in enumerate(mass):
+        part = synth(n, frac_massive=1.1, seed=9100 + n + b)[0].copy()
+        part[m:, 6] = 0.0
+        part[m:, 7] = 0.5
+        members.append(part)
+    u, r = nb.SimBatch(n, mass), nb.SimBatch.ragged([n] * 3, mass)
+    u.set_data(np.stack(members))
+    r.set_data(members)
+    seen = []
+    for batch in (u, r):
+        batch.update(3, steps)
+        batch.update(2, steps)
+        rows = batch.trace(5, steps, 2)
+        seen.append((b"".join(np.asarray(a).tobytes() for a in batch.get_data()), b"".join(ebits(e) for e in batch.energy()),
+                     b"".join(np.asarray(p).tobytes() for p in batch.potential()), rows.shape, rows.tobytes(),
+                     batch.last_trace_info(), batch.dt_uploads()))
+        batch.close()
+    for name, a, b in zip(("get_data", "energy", "potential", "trace shape", "trace rows", "last_trace_info", "dt_uploads"), *seen):
+        assert a == b, name
+    assert seen[0][3] == (3, 3, 8) and seen[0][6] == 1 and seen[0][5]["fused"] == (1 if n <= 512 else 0)
+    assert seen[0][0] != np.stack(members).tobytes()          # it did move
+
+
 @pytest.mark.parametrize("keep", [0, 2, 8, 11])
 def test_a_member_does_not_see_its_neighbours(keep):
     r = ragged(seed=0, others_seed=1, keep=keep)   # every other member holds different particles

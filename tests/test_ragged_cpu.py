@@ -3,6 +3,7 @@ include/nbody_batch_ragged.h), creation and its launch groups, the argument chec
 diagnostics, and the static ISA of the new kernels (kernels.hip ragged_chain_kernel / ragged_trace_chain_kernel /
 ragged_lane_split_kernel, ragged_diag.hip ragged_phi_kernel, convert.hip ragged_split_kernel / ragged_merge_kernel /
 ragged_copy_rows_kernel)."""
+import ctypes as C
 import os
 import re
 import subprocess
@@ -94,6 +95,38 @@ def test_layout_offsets_are_the_running_sum_also_for_a_uniform_ensemble():
     got_sizes, offsets = u.layout()
     assert list(got_sizes) == [250] * 3 and list(offsets) == [0, 250, 500, 750]
     u.close()
+
+
+def _group(batch, i):
+    """nb_hip_ragged_launch_shape of group i, called on the handle whatever made it: (groups, path, k, w, lanes, members, workgroups)."""
+    path, k, w, lanes, members, wgs = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_uint32(), C.c_uint32()
+    total = nb.hip_lib().nb_hip_ragged_launch_shape(batch._h, i, C.byref(path), C.byref(k), C.byref(w), C.byref(lanes), C.byref(members),
+                                                    C.byref(wgs))
+    return (int(total), path.value, k.value, w.value, lanes.value, members.value, wgs.value)
+
+
+def _member(batch, b):
+    grp, k, w, lanes = C.c_uint32(), C.c_int(), C.c_int(), C.c_int()
+    nb.hip_lib().nb_hip_ragged_member_shape(batch._h, b, C.byref(grp), C.byref(k), C.byref(w), C.byref(lanes))
+    return (grp.value, k.value, w.value, lanes.value)
+
+
+@pytest.mark.parametrize("n", [1, 128, 129, 256, 257, 512, 513, 1581, 1582, 3000])
+def test_a_uniform_ensemble_is_the_one_group_case_of_a_ragged_one(n):
+    """SimBatch(N, [N, 0]) and SimBatch.ragged([N, N], [N, 0]) come out of one constructor: one group of 2 members with the
+    shape nb_hip_batch_launch_shape reports, the same member shapes, the same layout.  Creation touches no device."""
+    u, r = nb.SimBatch(n, [n, 0]), nb.SimBatch.ragged([n, n], [n, 0])
+    s = u.launch_shape()
+    total, path, k, w, lanes, members, wgs = _group(u, 0)
+    assert (total, members) == (1, 2)
+    assert ("lanes" if path else "chain", k, w, lanes, wgs) == (s["path"], s["k"], s["w"], s["lanes"], s["workgroups"])
+    assert _group(r, 0) == _group(u, 0)
+    assert r.launch_shape()["groups"] == [dict(s, members=2)]
+    assert [_member(u, b) for b in range(2)] == [_member(r, b) for b in range(2)] == [(0, k, w, lanes)] * 2
+    (us, uo), (rs, ro) = u.layout(), r.layout()
+    assert list(us) == list(rs) == [n, n] and list(uo) == list(ro) == [0, n, 2 * n]
+    u.close()
+    r.close()
 
 
 # ---- argument checks ---------------------------------------------------------------------------------------------------
