@@ -238,6 +238,7 @@ TUNE_API = {
     "nb_hip_ensemble_last_render_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_last_leapfrog_info": (None, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "nb_hip_ensemble_last_leapfrog_info": (None, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
+    "nb_hip_live_resources": (None, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb_hip_configure; everything else is a tuning hook
 
@@ -365,6 +366,13 @@ def as_points(points):
 
 def device_count():
     return int(hip_lib().nb_hip_device_count())
+
+
+def live_resources():
+    """nb_hip_live_resources (tuning hook): (device allocations, events) the library holds right now; needs no GPU."""
+    buffers, events = C.c_uint32(0), C.c_uint32(0)
+    hip_lib().nb_hip_live_resources(C.byref(buffers), C.byref(events))
+    return int(buffers.value), int(events.value)
 
 
 def device_info():

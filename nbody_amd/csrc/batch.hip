@@ -46,21 +46,20 @@ void materialize(SimBatch *s) {
     use_device();
     if (s->on_device) return;
     ASSERT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "stream");
-    for (auto &e : s->ev) ASSERT_HIP(hipEventCreate(&e), "event");
     const size_t rows = (size_t)s->count * s->stride;
     for (int b = 0; b < 2; b++) {
         if (b == 1 && !s->lane_split()) break;   // the chain updates positions in place
-        s->pos[b] = dev_alloc<float2>(rows);
+        s->pos[b].alloc(rows);
         ASSERT_HIP(hipMemsetAsync(s->pos[b], 0, rows * sizeof(float2), s->stream), "clear positions");
     }
-    s->vel = dev_alloc<float2>(rows);
-    s->acc = dev_alloc<float2>(rows);
-    s->radius = dev_alloc<float>(rows);
-    s->mass = dev_alloc<float>(rows);
-    s->gm = dev_alloc<float>(rows);
-    s->mass_len_dev = dev_alloc<uint32_t>(s->count);
-    s->dt_dev = dev_alloc<float>(s->count);
-    s->aos = dev_alloc<Particle>((size_t)s->offsets[s->count]);
+    s->vel.alloc(rows);
+    s->acc.alloc(rows);
+    s->radius.alloc(rows);
+    s->mass.alloc(rows);
+    s->gm.alloc(rows);
+    s->mass_len_dev.alloc(s->count);
+    s->dt_dev.alloc(s->count);
+    s->aos.alloc((size_t)s->offsets[s->count]);
     if (s->ragged) {
         // pad rows stay zero for the life of the ensemble: no kernel writes a row at or beyond n_len[b]
         ASSERT_HIP(hipMemsetAsync(s->vel, 0, rows * sizeof(float2), s->stream), "clear velocities");
@@ -68,15 +67,15 @@ void materialize(SimBatch *s) {
         ASSERT_HIP(hipMemsetAsync(s->radius, 0, rows * sizeof(float), s->stream), "clear radii");
         ASSERT_HIP(hipMemsetAsync(s->mass, 0, rows * sizeof(float), s->stream), "clear masses");
         ASSERT_HIP(hipMemsetAsync(s->gm, 0, rows * sizeof(float), s->stream), "clear G*m");
-        s->n_len_dev = dev_alloc<uint32_t>(s->count);
-        s->offsets_dev = dev_alloc<uint64_t>((size_t)s->count + 1);
+        s->n_len_dev.alloc(s->count);
+        s->offsets_dev.alloc((size_t)s->count + 1);
         ASSERT_HIP(hipMemcpyAsync(s->n_len_dev, s->n_len.data(), (size_t)s->count * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream),
                    "H2D of %u member sizes", s->count);
         ASSERT_HIP(hipMemcpyAsync(s->offsets_dev, s->offsets.data(), ((size_t)s->count + 1) * sizeof(uint64_t), hipMemcpyHostToDevice,
                                   s->stream),
                    "H2D of %u member offsets", s->count);
         for (auto &g : s->groups) {
-            g.list = dev_alloc<uint32_t>(g.members.size());
+            g.list.alloc(g.members.size());
             ASSERT_HIP(hipMemcpyAsync(g.list, g.members.data(), g.members.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream),
                        "H2D of a launch group's %zu members", g.members.size());
         }
@@ -203,18 +202,17 @@ void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
     s->acc_current = false;   // an Euler step leaves the acc of the state before it
     upload_dts(s, dt, uniform);
     nb::BatchParams p = step_params(s);
-    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+    s->step_iv.begin(s->stream);
     launch_steps(s, p, n);
     ASSERT_HIP(hipGetLastError(), "ensemble launch (%u members of %u particles, %u steps)", s->count, s->n, n);
-    ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
-    s->timed = true;
+    s->step_iv.end(s->stream);
 }
 
 // ---- device-chosen and leapfrog steps: every member as the target of step_schedule.h's schedule --------------------------
 
 // the step sizes of the kick / drift passes, [2][count]
 float *kick_words(SimBatch *s) {
-    if (!s->lf_dt) s->lf_dt = dev_alloc<float>(2 * (size_t)s->count);
+    if (!s->lf_dt) s->lf_dt.alloc(2 * (size_t)s->count);
     return s->lf_dt;
 }
 
@@ -253,10 +251,10 @@ struct BatchTarget {
         lf.stride = s->stride;
         nb::launch_leapfrog(s->stream, lf, close, open, s->count);
     }
-    void begin_mark() { ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record"); }
+    void begin_mark() { s->step_iv.begin(s->stream); }
     void end_mark() {
         ASSERT_HIP(hipGetLastError(), "ensemble step launches (%u members of %u particles)", s->count, s->n);
-        ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
+        s->step_iv.end(s->stream);
     }
 };
 
@@ -269,7 +267,6 @@ void run_call(SimBatch *s, Schedule c, const nb::TimestepParams &t, float *log) 
     }
     run_schedule(target, c);
     if (c.leapfrog) s->lf_force_launches = target.forces;
-    s->timed = true;
     s->dt_valid = false;            // dt_dev holds 0 or the device's choices: the next fixed-step update uploads its own afresh
     s->acc_current = c.leapfrog;    // Euler steps leave the acc of the state before them
 }
@@ -295,7 +292,7 @@ void read_back(SimBatch *s, uint32_t first, uint32_t members, Particle *ps) {
     NB_ASSERT(s->has_data, "ensemble read-back before nb_hip_batch_set_data");
     use_device();
     merge_members(s, first, members);
-    ASSERT_HIP(hipMemcpyAsync(ps, static_cast<const Particle *>(s->aos) + s->offsets[first],
+    ASSERT_HIP(hipMemcpyAsync(ps, s->aos + s->offsets[first],
                               (size_t)(s->offsets[first + members] - s->offsets[first]) * sizeof(Particle), hipMemcpyDeviceToHost,
                               s->stream),
                "D2H of %u members", members);
@@ -320,12 +317,13 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
     }
     constexpr size_t Q = NB_DIAG_SUMS;
     const size_t pitch = (size_t)s->count * Q;
-    double *rows = grown(s->stream, s->trace, s->trace_cap, (size_t)records * pitch);
+    s->trace.grown(s->stream, (size_t)records * pitch);
+    double *rows = s->trace;
     const bool fused = !s->lane_split() && s->trace_mode == 0;   // every member is in the one chain group
     if (!fused) energy_slab(s);
     const nb::BatchParams p = step_params(s);
     uint32_t launches = 0;
-    ASSERT_HIP(hipEventRecord(s->ev[0], s->stream), "event record");
+    s->step_iv.begin(s->stream);
     if (fused) {
         TraceTarget target = {{s, p}, {.mass = s->mass, .rows = rows, .count = s->count, .every = every}};
         if (n == 0) target.chain(s->groups[0], s->cur, 0);   // one launch of no steps: the record on entry
@@ -342,8 +340,7 @@ void trace(SimBatch *s, uint32_t n, const float *dt, bool uniform, uint32_t ever
     }
     ASSERT_HIP(hipGetLastError(), "traced ensemble launch (%u members of %u particles, %u steps, a record every %u)", s->count, s->n,
                n, every);
-    ASSERT_HIP(hipEventRecord(s->ev[1], s->stream), "event record");
-    s->timed = true;
+    s->step_iv.end(s->stream);
     s->trace_fused = fused;
     s->trace_launches = launches;
     s->trace_host.resize((size_t)records * pitch);
@@ -403,7 +400,7 @@ SimBatch *create(SimBatch *s, const uint32_t *mass_len, bool ragged) {
             g.block = nb::step_block(sh);
             g.lds = nb::step_lds_bytes(sh, g.max_n);
         }
-        s->groups.push_back(g);
+        s->groups.push_back(std::move(g));
     }
     return s;
 }
@@ -480,20 +477,9 @@ void nb_hip_batch_destroy(SimBatch *s) {
     if (s->on_device) {
         use_device();
         ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before destroying an ensemble");
-        for (void *p : std::initializer_list<void *>{   // dev_free takes null: what was never made
-                 s->pos[0], s->pos[1], s->vel, s->acc, s->radius, s->mass, s->gm, s->mass_len_dev, s->dt_dev, s->aos, s->n_len_dev,
-                 s->offsets_dev, s->diag, s->diag_phi, s->trace, s->render_views, s->render_keys, s->render_counts, s->render_rgba,
-                 s->render_discs, s->adapt, s->lf_dt})
-            dev_free(p);
-        for (auto &g : s->groups) dev_free(g.list);
-        for (auto &e : s->ev_render)
-            if (e) ASSERT_HIP(hipEventDestroy(e), "event");
-        for (auto &e : s->ev_diag)
-            if (e) ASSERT_HIP(hipEventDestroy(e), "event");
-        for (auto &e : s->ev) ASSERT_HIP(hipEventDestroy(e), "event");
         ASSERT_HIP(hipStreamDestroy(s->stream), "stream");
     }
-    delete s;
+    delete s;   // its device arrays and events go with their owners
 }
 
 void nb_hip_batch_set_data(SimBatch *s, const Particle *ps) {
@@ -572,18 +558,16 @@ void nb_hip_ensemble_adaptive_steps(SimBatch *s, uint32_t n, const NbAdaptive *c
     use_device();
     const size_t head = (size_t)s->count * sizeof(nb::AdaptState);
     const size_t log_bytes = dt_log ? (size_t)n * s->count * sizeof(float) : 0;
-    if (s->adapt_bytes < head + log_bytes) {
-        regrow_carrying(s->stream, s->adapt, head + log_bytes, head);
-        s->adapt_bytes = head + log_bytes;
-    }
+    s->adapt.grown_carrying(s->stream, head + log_bytes, head);
     nb::TimestepParams t = nb::timestep_params(s->acc, s->radius, s->n, s->stride, *cfg);
-    t.state = static_cast<nb::AdaptState *>(s->adapt);
+    char *records = s->adapt;
+    t.state = reinterpret_cast<nb::AdaptState *>(records);
     t.commit = 1;
     if (!(cfg->flags & NB_ADAPT_CONTINUE) || !s->adapt_armed) nb::launch_arm(s->stream, t.state, s->count);
     s->adapt_armed = true;
     const bool leapfrog = (cfg->flags & NB_ADAPT_LEAPFROG) != 0;
     run_call(s, {n, leapfrog, true, !leapfrog && (cfg->flags & NB_ADAPT_PRIME) != 0}, t,
-             dt_log ? reinterpret_cast<float *>(static_cast<char *>(s->adapt) + head) : nullptr);
+             dt_log ? reinterpret_cast<float *>(records + head) : nullptr);
     s->adapt_host.resize(head + log_bytes);
     ASSERT_HIP(hipMemcpyAsync(s->adapt_host.data(), s->adapt, head + log_bytes, hipMemcpyDeviceToHost, s->stream),
                "D2H of %u x %u step sizes and the results", n, s->count);
@@ -594,9 +578,9 @@ void nb_hip_ensemble_adaptive_steps(SimBatch *s, uint32_t n, const NbAdaptive *c
 
 double nb_hip_batch_last_ms(SimBatch *s) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
-    if (!s->timed) return 0.0;
+    if (!s->step_iv.valid()) return 0.0;
     use_device();
-    return elapsed_ms(s->ev[0], s->ev[1]);
+    return s->step_iv.ms();
 }
 
 uint32_t nb_hip_batch_dt_uploads(const SimBatch *s) {

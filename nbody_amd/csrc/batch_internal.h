@@ -1,5 +1,9 @@
 // batch_internal.h -- struct SimBatch and what batch.hip (life cycle, stepping, traces) and batch_observe.hip (the read-only
 // calls) share.  C++, not part of the C-ABI.
+//
+// Every device array and event of a SimBatch is a member of an owner type (pipeline_internal.h DevBuf / Interval): made by
+// materialize or on a call's first use, released by the member's destructor when nb_hip_batch_destroy deletes the struct,
+// after it has drained the stream.  nb_hip_batch_destroy itself only syncs and destroys the stream.
 #pragma once
 
 #include "pipeline_internal.h"
@@ -20,14 +24,13 @@ struct SimBatch {
     bool on_device = false;
     bool has_data = false;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool timed = false;
-    float2 *pos[2] = {nullptr, nullptr};
-    float2 *vel = nullptr, *acc = nullptr;
-    float *radius = nullptr, *mass = nullptr, *gm = nullptr;
-    uint32_t *mass_len_dev = nullptr;
-    float *dt_dev = nullptr;
-    void *aos = nullptr;   // device staging of Set / Get: [count][n] Particle
+    nbi::Interval step_iv;   // around the launches of the last update
+    nbi::DevBuf<float2> pos[2];
+    nbi::DevBuf<float2> vel, acc;
+    nbi::DevBuf<float> radius, mass, gm;
+    nbi::DevBuf<uint32_t> mass_len_dev;
+    nbi::DevBuf<float> dt_dev;
+    nbi::DevBuf<Particle> aos;   // device staging of Set / Get: [count][n] Particle
     int cur = 0;           // pos[cur] is the latest state (the chain path never moves it)
 
     // The launch shape, fixed at creation: the launch groups, in the order chain, lane-split (8, 8), lane-split (16, 4); those
@@ -39,7 +42,7 @@ struct SimBatch {
         uint32_t max_n = 0;                       // its largest member
         uint32_t workgroups = 0;                  // per launch
         std::vector<uint32_t> members;            // ascending member indices
-        uint32_t *list = nullptr;                 // ragged: the same on the device
+        nbi::DevBuf<uint32_t> list;               // ragged: the same on the device
         const void *fn = nullptr;                 // lane-split: the kernel, the grid, the block and the LDS bytes of a launch
         dim3 grid, block;
         size_t lds = 0;
@@ -47,51 +50,43 @@ struct SimBatch {
     std::vector<Group> groups;
     // some group is lane-split (the chain group comes first): both position buffers exist, traces interleave
     bool lane_split() const { return groups.back().path != 0; }
-    uint32_t *n_len_dev = nullptr;     // ragged only, like offsets_dev
-    uint64_t *offsets_dev = nullptr;
+    nbi::DevBuf<uint32_t> n_len_dev;     // ragged only, like offsets_dev
+    nbi::DevBuf<uint64_t> offsets_dev;
 
-    // nb_hip_ensemble_energy / nb_hip_ensemble_potential (kernels: batch_diag.hip): scratch made on first use, an event
-    // pair of their own (ev[] keeps bracketing the last update)
-    double *diag = nullptr;      // float64 slab: [count][tiles of 128][NB_DIAG_SUMS] + the [count][NB_DIAG_SUMS] results
-    size_t diag_cap = 0;         // doubles allocated in diag
-    float *diag_phi = nullptr;   // the potentials on the device: [count][n]
-    size_t diag_phi_cap = 0;
+    // nb_hip_ensemble_energy / nb_hip_ensemble_potential (kernels: batch_diag.hip): scratch made on first use, an interval
+    // of their own (step_iv keeps bracketing the last update)
+    nbi::DevBuf<double> diag;      // float64 slab: [count][tiles of 128][NB_DIAG_SUMS] + the [count][NB_DIAG_SUMS] results
+    nbi::DevBuf<float> diag_phi;   // the potentials on the device: [count][n]
     std::vector<double> diag_host;   // the results on the host before they become WorldEnergy
-    hipEvent_t ev_diag[2] = {nullptr, nullptr};
-    bool diag_timed = false;
+    nbi::Interval diag_iv;
 
     // nb_hip_ensemble_trace: the rows of the last traced call, on the device and on their way to WorldEnergy
-    double *trace = nullptr;     // [records][count][NB_DIAG_SUMS]
-    size_t trace_cap = 0;
+    nbi::DevBuf<double> trace;     // [records][count][NB_DIAG_SUMS]
     std::vector<double> trace_host;
     int trace_mode = 0;          // tuning hook: 1 = interleaved diagnostics launches also where the chain could record
     int trace_fused = 0;         // what the last traced call did
     uint32_t trace_launches = 0;
 
     // nb_hip_ensemble_bounds / _render_counts / _render_rgba (kernels: batch_render.hip): scratch made on first use, an
-    // event pair of their own
-    RenderView *render_views = nullptr;      // [count]: the views of the last call
-    uint32_t *render_keys = nullptr;         // [count][4]
-    uint32_t *render_counts = nullptr;       // tile path: [count][3][h][w]; global path: the disc cursor behind them
-    size_t render_counts_cap = 0;
-    uint32_t *render_rgba = nullptr;         // [count][h][w]
-    size_t render_rgba_cap = 0;
-    nbr::EnsembleDisc *render_discs = nullptr;   // global path: [count * n]
-    hipEvent_t ev_render[2] = {nullptr, nullptr};
-    bool render_timed = false;
+    // interval of their own
+    nbi::DevBuf<RenderView> render_views;      // [count]: the views of the last call
+    nbi::DevBuf<uint32_t> render_keys;         // [count][4]
+    nbi::DevBuf<uint32_t> render_counts;       // tile path: [count][3][h][w]; global path: the disc cursor behind them
+    nbi::DevBuf<uint32_t> render_rgba;         // [count][h][w]
+    nbi::DevBuf<nbr::EnsembleDisc> render_discs;   // global path: [count * n]
+    nbi::Interval render_iv;
     int render_mode = 0;                     // tuning hook: 1 = the global path also where the tile path applies
     int render_tile = 0;                     // what the last render did (a bounds call leaves both alone)
     uint32_t render_launches = 0;
 
     // nb_hip_ensemble_adaptive_steps (kernels: timestep.hip): [count] AdaptState, then the call's log [n][count]; grown on demand
-    void *adapt = nullptr;
-    size_t adapt_bytes = 0;
+    nbi::DevBuf<char> adapt;
     bool adapt_armed = false;   // the records hold a call to continue (NB_ADAPT_CONTINUE)
     std::vector<char> adapt_host;
 
     // leapfrog steps (kernels: leapfrog.hip): the step sizes of the kick / drift passes, [2][count] -- a fixed-step call uses
     // the first row, an adaptive one alternates so that one launch can close step i - 1 and open step i
-    float *lf_dt = nullptr;
+    nbi::DevBuf<float> lf_dt;
     bool acc_current = false;        // acc = F(x) of the state held: true after a leapfrog call, false after anything else that moves it
     uint32_t lf_force_launches = 0;  // force evaluations of the last leapfrog call (nb_hip_ensemble_last_leapfrog_info)
     bool lf_primed = false;          // ... and whether it had to run one first

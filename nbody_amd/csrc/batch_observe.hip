@@ -38,20 +38,6 @@ nbd::EnsembleDiagParams diag_params(const SimBatch *s) {   // of the latest stat
     return p;
 }
 
-nbd::EnsembleDiagParams begin_diag(SimBatch *s) {
-    use_device();
-    if (!s->ev_diag[0]) {
-        for (auto &e : s->ev_diag) ASSERT_HIP(hipEventCreate(&e), "event");
-    }
-    ASSERT_HIP(hipEventRecord(s->ev_diag[0], s->stream), "record diagnostics begin");
-    return diag_params(s);
-}
-
-void end_diag(SimBatch *s) {
-    ASSERT_HIP(hipEventRecord(s->ev_diag[1], s->stream), "record diagnostics end");
-    s->diag_timed = true;
-}
-
 // Phi of every particle to p.phi, packed member after member: the pick of the kernel family, as batch.hip's StepTarget makes it
 void launch_potential(SimBatch *s, const nbd::EnsembleDiagParams &p) {
     if (s->ragged)
@@ -75,7 +61,8 @@ void launch_energy_sums(SimBatch *s, double *res) {
 }
 
 double *energy_slab(SimBatch *s) {
-    return grown(s->stream, s->diag, s->diag_cap, (size_t)s->count * (nbd::ensemble_tiles(s->n) + 1) * NB_DIAG_SUMS);
+    s->diag.grown(s->stream, (size_t)s->count * (nbd::ensemble_tiles(s->n) + 1) * NB_DIAG_SUMS);
+    return s->diag;
 }
 
 }  // namespace nbi
@@ -83,19 +70,6 @@ double *energy_slab(SimBatch *s) {
 namespace {
 
 // ---- rendering: bounds, count tiles and frames of every member, without reading the particles back ------------------
-
-void begin_render(SimBatch *s) {
-    use_device();
-    if (!s->ev_render[0]) {
-        for (auto &e : s->ev_render) ASSERT_HIP(hipEventCreate(&e), "event");
-    }
-    ASSERT_HIP(hipEventRecord(s->ev_render[0], s->stream), "record render begin");
-}
-
-void end_render(SimBatch *s) {
-    ASSERT_HIP(hipEventRecord(s->ev_render[1], s->stream), "record render end");
-    s->render_timed = true;
-}
 
 void check_views(const SimBatch *s, const RenderView *views, const char *what) {
     NB_ASSERT(views != nullptr, "%s: NULL RenderView array", what);
@@ -111,13 +85,13 @@ void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *p
     const uint32_t width = views[0].width, height = views[0].height;
     const size_t plane = (size_t)width * height;
     const bool tile = nbr::tile_fits(width, height) && s->render_mode == 0;
-    if (!s->render_views) s->render_views = dev_alloc<RenderView>(s->count);
-    if (palette) grown(s->stream, s->render_rgba, s->render_rgba_cap, (size_t)s->count * plane);
-    if (!tile || !palette) grown(s->stream, s->render_counts, s->render_counts_cap, nbr::global_count_words(s->count, width, height));
-    if (!tile && !s->render_discs) s->render_discs = dev_alloc<nbr::EnsembleDisc>((size_t)s->count * s->n);
+    if (!s->render_views) s->render_views.alloc(s->count);
+    if (palette) s->render_rgba.grown(s->stream, (size_t)s->count * plane);
+    if (!tile || !palette) s->render_counts.grown(s->stream, nbr::global_count_words(s->count, width, height));
+    if (!tile && !s->render_discs) s->render_discs.alloc((size_t)s->count * s->n);
     ASSERT_HIP(hipMemcpyAsync(s->render_views, views, (size_t)s->count * sizeof(RenderView), hipMemcpyHostToDevice, s->stream),
                "H2D of %u views", s->count);
-    begin_render(s);
+    s->render_iv.begin(s->stream);
     nbr::EnsembleRenderParams p{};
     p.pos = s->pos[s->cur];
     p.mass = s->mass;
@@ -143,7 +117,7 @@ void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *p
     }
     ASSERT_HIP(hipGetLastError(), "ensemble render launch (%u members of %u particles, %u x %u, %s path)", s->count, s->n, width, height,
                tile ? "tile" : "global");
-    end_render(s);
+    s->render_iv.end(s->stream);
     s->render_tile = tile;
     s->render_launches = *launches;
 }
@@ -155,10 +129,11 @@ extern "C" {
 void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
     check_diag(s, out, "nb_hip_ensemble_energy");
     constexpr size_t Q = NB_DIAG_SUMS;
-    begin_diag(s);
+    use_device();
+    s->diag_iv.begin(s->stream);
     double *res = energy_slab(s) + (size_t)s->count * nbd::ensemble_tiles(s->n) * Q;
     launch_energy_sums(s, res);
-    end_diag(s);
+    s->diag_iv.end(s->stream);
     s->diag_host.resize((size_t)s->count * Q);
     ASSERT_HIP(hipMemcpyAsync(s->diag_host.data(), res, (size_t)s->count * Q * sizeof(double), hipMemcpyDeviceToHost, s->stream),
                "D2H of %u members' energy sums", s->count);
@@ -168,12 +143,15 @@ void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
 
 void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
     check_diag(s, phi, "nb_hip_ensemble_potential");
-    nbd::EnsembleDiagParams p = begin_diag(s);
+    use_device();
+    s->diag_iv.begin(s->stream);
+    nbd::EnsembleDiagParams p = diag_params(s);
     const size_t total = (size_t)s->offsets[s->count];
-    p.phi = grown(s->stream, s->diag_phi, s->diag_phi_cap, total);
+    s->diag_phi.grown(s->stream, total);
+    p.phi = s->diag_phi;
     launch_potential(s, p);
     ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
-    end_diag(s);
+    s->diag_iv.end(s->stream);
     ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u members' potentials",
                s->count);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_potential");
@@ -182,19 +160,20 @@ void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
 // tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_ensemble_energy / _potential
 double nb_hip_ensemble_last_diag_ms(SimBatch *s) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
-    if (!s->diag_timed) return 0.0;
+    if (!s->diag_iv.valid()) return 0.0;
     use_device();
-    return elapsed_ms(s->ev_diag[0], s->ev_diag[1]);
+    return s->diag_iv.ms();
 }
 
 void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {
     check_not_ragged(s, "nb_hip_ensemble_bounds");
     check_diag(s, bounds, "nb_hip_ensemble_bounds");
-    begin_render(s);
-    if (!s->render_keys) s->render_keys = dev_alloc<uint32_t>((size_t)s->count * 4);
+    use_device();
+    s->render_iv.begin(s->stream);
+    if (!s->render_keys) s->render_keys.alloc((size_t)s->count * 4);
     nbr::launch_ensemble_bounds(s->stream, s->pos[s->cur], s->n, s->stride, s->count, s->render_keys);
     ASSERT_HIP(hipGetLastError(), "ensemble_bounds_kernel launch (%u members of %u)", s->count, s->n);
-    end_render(s);   // the event pair is shared with the renders; render_tile / render_launches speak of renders only
+    s->render_iv.end(s->stream);   // the interval is shared with the renders; render_tile / render_launches speak of renders only
     std::vector<uint32_t> keys((size_t)s->count * 4);
     ASSERT_HIP(hipMemcpyAsync(keys.data(), s->render_keys, keys.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream),
                "D2H of %u members' bounds", s->count);
@@ -243,9 +222,9 @@ void nb_hip_ensemble_last_render_info(const SimBatch *s, int *tile_path, uint32_
 
 double nb_hip_ensemble_last_render_ms(SimBatch *s) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
-    if (!s->render_timed) return 0.0;
+    if (!s->render_iv.valid()) return 0.0;
     use_device();
-    return elapsed_ms(s->ev_render[0], s->ev_render[1]);
+    return s->render_iv.ms();
 }
 
 }  // extern "C"

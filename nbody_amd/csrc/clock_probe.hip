@@ -123,22 +123,22 @@ __global__ __launch_bounds__(64) void clock_sampler_kernel(SamplerPair *__restri
 constexpr int SAMPLER_WAVES = 8;
 
 struct Sampler {
-    bool running = false;
     hipStream_t stream = nullptr;
-    SamplerPair *out = nullptr;
-    uint32_t *count = nullptr, *xcc = nullptr;
+    nbi::DevBuf<SamplerPair> out;
+    nbi::DevBuf<uint32_t> count, xcc;
     uint32_t *stop = nullptr;   // page-locked host word, read by the waves with system scope
     uint32_t max_samples = 0;
     int wall_khz = 100000;
-} g_sampler;
+};
+Sampler *g_sampler = nullptr;   // alive from nb_hip_clock_sampler_begin to _end
 
 }  // namespace
 
 extern "C" int nb_hip_clock_sampler_begin(double period_ms, double max_ms) {
     using namespace nbi;
     use_device();
-    Sampler &S = g_sampler;
-    NB_ASSERT(!S.running, "clock sampler already running");
+    NB_ASSERT(g_sampler == nullptr, "clock sampler already running");
+    Sampler &S = *(g_sampler = new Sampler());
     // a measurement aid must not take the process down over its own bound: out-of-range requests are clamped (the waves
     // leave by themselves after max_ms, so a leg longer than the bound is simply sampled over its first 20 s)
     if (!(period_ms >= 0.05)) period_ms = 0.05;
@@ -149,9 +149,9 @@ extern "C" int nb_hip_clock_sampler_begin(double period_ms, double max_ms) {
         S.wall_khz = 100000;
     }
     S.max_samples = (uint32_t)(max_ms / period_ms) + 2;
-    S.out = dev_alloc<SamplerPair>((size_t)SAMPLER_WAVES * S.max_samples);
-    S.count = dev_alloc<uint32_t>(SAMPLER_WAVES);
-    S.xcc = dev_alloc<uint32_t>(SAMPLER_WAVES);
+    S.out.alloc((size_t)SAMPLER_WAVES * S.max_samples);
+    S.count.alloc(SAMPLER_WAVES);
+    S.xcc.alloc(SAMPLER_WAVES);
     ASSERT_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.stop), sizeof(uint32_t), hipHostMallocDefault), "sampler stop word");
     *S.stop = 0u;
     ASSERT_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking), "sampler stream");
@@ -159,7 +159,6 @@ extern "C" int nb_hip_clock_sampler_begin(double period_ms, double max_ms) {
     const uint32_t period_ticks = (uint32_t)(period_ms * (double)S.wall_khz);
     hipLaunchKernelGGL(clock_sampler_kernel, dim3(SAMPLER_WAVES), dim3(64), 0, S.stream, S.out, S.count, S.xcc, S.stop, S.max_samples, period_ticks);
     ASSERT_HIP(hipGetLastError(), "clock sampler launch");
-    S.running = true;
     return SAMPLER_WAVES;
 }
 
@@ -167,11 +166,11 @@ extern "C" int nb_hip_clock_sampler_end(double *clock_ghz, double *clock_ghz_min
                                         double *profile10, double *span_ms, uint32_t *dropped_intervals) {
     using namespace nbi;
     use_device();
-    Sampler &S = g_sampler;
-    NB_ASSERT(S.running, "clock sampler not running");
+    NB_ASSERT(g_sampler != nullptr, "clock sampler not running");
+    Sampler &S = *g_sampler;
     __atomic_store_n(S.stop, 1u, __ATOMIC_RELEASE);
     ASSERT_HIP(hipStreamSynchronize(S.stream), "sampler sync");
-    const size_t stride = S.max_samples;
+    const size_t stride = S.max_samples;   // by value: the sampler goes below
     const double khz = (double)S.wall_khz;   // ticks of s_memrealtime per millisecond
     std::vector<SamplerPair> host((size_t)SAMPLER_WAVES * stride);
     uint32_t count[SAMPLER_WAVES], xcc[SAMPLER_WAVES];
@@ -179,11 +178,9 @@ extern "C" int nb_hip_clock_sampler_end(double *clock_ghz, double *clock_ghz_min
     ASSERT_HIP(hipMemcpy(count, S.count, sizeof count, hipMemcpyDeviceToHost), "sampler counts");
     ASSERT_HIP(hipMemcpy(xcc, S.xcc, sizeof xcc, hipMemcpyDeviceToHost), "sampler xcc ids");
     ASSERT_HIP(hipStreamDestroy(S.stream), "sampler stream");
-    dev_free(S.out);
-    dev_free(S.count);
-    dev_free(S.xcc);
     ASSERT_HIP(hipHostFree(S.stop), "sampler stop word");
-    S = Sampler();
+    delete g_sampler;
+    g_sampler = nullptr;
 
     std::vector<double> all, by_xcd[8];
     double span = 0.0;
@@ -263,30 +260,24 @@ extern "C" int nb_hip_probe_clock(double target_ms, double *clock_ghz, double *c
         host_src[2 * u + 1] = -7.0f * (float)u;
         host_src[16 + u] = 1.0e4f + (float)u;
     }
-    float *src = dev_alloc<float>(24);
-    float *sink = dev_alloc<float>(64 * PROBE_WAVES);
-    ProbeStamp *stamps = dev_alloc<ProbeStamp>(waves);
+    DevBuf<float> src, sink;
+    DevBuf<ProbeStamp> stamps;
+    src.alloc(24);
+    sink.alloc(64 * PROBE_WAVES);
+    stamps.alloc(waves);
     hipStream_t st;
-    hipEvent_t e0, e1;
+    Interval iv;
     ASSERT_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "probe stream");
-    ASSERT_HIP(hipEventCreate(&e0), "event");
-    ASSERT_HIP(hipEventCreate(&e1), "event");
     ASSERT_HIP(hipMemcpyAsync(src, host_src, sizeof host_src, hipMemcpyHostToDevice, st), "probe sources");
-    ASSERT_HIP(hipEventRecord(e0, st), "record");
+    iv.begin(st);
     hipLaunchKernelGGL(clock_probe_kernel, dim3(groups), dim3(64 * PROBE_WAVES), 0, st, src, iters, stamps, sink);
     ASSERT_HIP(hipGetLastError(), "clock probe launch (%d workgroups, %u trips)", groups, iters);
-    ASSERT_HIP(hipEventRecord(e1, st), "record");
+    iv.end(st);
     std::vector<ProbeStamp> host(waves);
     ASSERT_HIP(hipMemcpyAsync(host.data(), stamps, waves * sizeof(ProbeStamp), hipMemcpyDeviceToHost, st), "probe stamps");
     ASSERT_HIP(hipStreamSynchronize(st), "probe sync");
-    float ms = 0.0f;
-    ASSERT_HIP(hipEventElapsedTime(&ms, e0, e1), "elapsed");
-    ASSERT_HIP(hipEventDestroy(e0), "event");
-    ASSERT_HIP(hipEventDestroy(e1), "event");
+    const double ms = iv.ms();
     ASSERT_HIP(hipStreamDestroy(st), "probe stream");
-    dev_free(src);
-    dev_free(sink);
-    dev_free(stamps);
 
     // The SIMD's arbiter favours its oldest wave, so the eight waves of a SIMD do not finish together: the oldest leaves
     // after about an eighth of the launch, the youngest spans all of it (measured: median lifetime 0.56 of the launch).
@@ -308,6 +299,6 @@ extern "C" int nb_hip_probe_clock(double target_ms, double *clock_ghz, double *c
     if (clock_ghz_min) *clock_ghz_min = ghz_all.front();
     if (clock_ghz_max) *clock_ghz_max = ghz_all.back();
     if (cycles_per_wave_interaction) *cycles_per_wave_interaction = (double)longest / PROBE_WAVES_PER_SIMD / ((double)iters * 16.0);
-    if (elapsed_ms) *elapsed_ms = (double)ms;
+    if (elapsed_ms) *elapsed_ms = ms;
     return (int)ghz_all.size();
 }

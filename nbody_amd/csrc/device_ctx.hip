@@ -7,6 +7,7 @@
 #include <chrono>
 
 #include "pipeline_internal.h"
+#include "nbody_hip_tuning.h"
 
 #define NB_HIP_VERSION 400  // 0.4.0: + nb_hip_energy / nb_hip_potential (0.3.1: + nb_hip_preflight_* / nb_hip_comm_bringup)
 
@@ -57,19 +58,29 @@ void use_device() {
     ASSERT_HIP(hipSetDevice(g_dev.ordinal), "hipSetDevice(%d)", g_dev.ordinal);
 }
 
+std::atomic<uint32_t> g_live_buffers{0}, g_live_events{0};
+
 void *dev_alloc_bytes(size_t bytes) {
     void *p = nullptr;
     ASSERT_HIP(hipMalloc(&p, bytes ? bytes : 1), "hipMalloc of %zu bytes", bytes);
+    g_live_buffers++;
     return p;
 }
 
 void dev_free(void *p) {
-    if (p) ASSERT_HIP(hipFree(p), "hipFree");
+    if (!p) return;
+    ASSERT_HIP(hipFree(p), "hipFree");
+    g_live_buffers--;
 }
 
 }  // namespace nbi
 
 extern "C" {
+
+void nb_hip_live_resources(uint32_t *buffers, uint32_t *events) {
+    if (buffers) *buffers = nbi::g_live_buffers.load();
+    if (events) *events = nbi::g_live_events.load();
+}
 
 int nb_hip_version(void) { return NB_HIP_VERSION; }
 

@@ -146,34 +146,15 @@ nbd::DiagParams diag_params(SimPipeline *s, uint32_t n_recv) {
     return p;
 }
 
-// the pipeline's float64 scratch: QTY per workgroup + QTY results, grown on demand
-double *diag_scratch(SimPipeline *s, uint32_t rows) {
-    return grown(s->stream, s->diag, s->diag_cap, (size_t)(rows + 1) * QTY);
-}
-
 }  // namespace
 
 namespace nbi {
 
-// shared with field.hip (pipeline_internal.h): the checks and the event pair of every diagnostic of one pipeline
+// shared with field.hip (pipeline_internal.h): the checks of every diagnostic of one pipeline
 void check_diag(SimPipeline *s, const char *what) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
     NB_ASSERT(!s->sharded, "%s of a sharded pipeline needs a collective over the ranks: not supported", what);
     NB_ASSERT(s->on_device, "%s before SetSimulationData", what);
-}
-
-void begin_diag(SimPipeline *s) {
-    use_device();
-    if (!s->ev_diag[0]) {
-        ASSERT_HIP(hipEventCreate(&s->ev_diag[0]), "event");
-        ASSERT_HIP(hipEventCreate(&s->ev_diag[1]), "event");
-    }
-    ASSERT_HIP(hipEventRecord(s->ev_diag[0], s->stream), "record diagnostics begin");
-}
-
-void end_diag(SimPipeline *s) {
-    ASSERT_HIP(hipEventRecord(s->ev_diag[1], s->stream), "record diagnostics end");
-    s->diag_timed = true;
 }
 
 }  // namespace nbi
@@ -186,9 +167,11 @@ void nb_hip_energy(SimPipeline *s, WorldEnergy *out) {
     const uint32_t M = s->data.mass_len;
     double q[QTY] = {0};
     if (M > 0) {
-        begin_diag(s);
+        use_device();
+        s->diag_iv.begin(s->stream);
         const uint32_t rows = (M + nbd::TILE - 1) / nbd::TILE;
-        double *slab = diag_scratch(s, rows);
+        s->diag.grown(s->stream, (size_t)(rows + 1) * QTY);   // QTY per workgroup + QTY results
+        double *slab = s->diag;
         nbd::DiagParams p = diag_params(s, M);
         p.slab = slab;
         hipLaunchKernelGGL(nbd::potential_kernel, dim3(rows), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
@@ -196,11 +179,11 @@ void nb_hip_energy(SimPipeline *s, WorldEnergy *out) {
         double *res = slab + (size_t)rows * QTY;
         hipLaunchKernelGGL(nbd::energy_reduce_kernel, dim3(1), dim3(nbd::REDUCE_THREADS), 0, s->stream, slab, rows, res);
         ASSERT_HIP(hipGetLastError(), "energy_reduce_kernel launch");
-        end_diag(s);
+        s->diag_iv.end(s->stream);
         ASSERT_HIP(hipMemcpyAsync(q, res, sizeof(q), hipMemcpyDeviceToHost, s->stream), "D2H of the energy sums");
         ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_energy");
     } else {
-        s->diag_timed = false;
+        s->diag_iv.clear();
     }
     nb_energy_from_sums(q, out);
 }
@@ -210,16 +193,17 @@ void nb_hip_potential(SimPipeline *s, float *phi) {
     const uint32_t N = s->data.total_len;
     NB_ASSERT(phi != nullptr || N == 0, "NULL phi");
     if (N == 0) {
-        s->diag_timed = false;
+        s->diag_iv.clear();
         return;
     }
-    begin_diag(s);
-    grown(s->stream, s->diag_phi, s->diag_phi_cap, N);
+    use_device();
+    s->diag_iv.begin(s->stream);
+    s->diag_phi.grown(s->stream, N);
     nbd::DiagParams p = diag_params(s, N);
     p.phi = s->diag_phi;
     hipLaunchKernelGGL(nbd::potential_kernel, dim3((N + nbd::TILE - 1) / nbd::TILE), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
     ASSERT_HIP(hipGetLastError(), "potential_kernel launch (%u receivers)", N);
-    end_diag(s);
+    s->diag_iv.end(s->stream);
     ASSERT_HIP(hipMemcpyAsync(phi, s->diag_phi, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u potentials", N);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_potential");
 }
@@ -227,9 +211,9 @@ void nb_hip_potential(SimPipeline *s, float *phi) {
 // tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_energy / nb_hip_potential
 double nb_hip_last_diag_ms(SimPipeline *s) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
-    if (!s->diag_timed) return 0.0;
+    if (!s->diag_iv.valid()) return 0.0;
     use_device();
-    return elapsed_ms(s->ev_diag[0], s->ev_diag[1]);
+    return s->diag_iv.ms();
 }
 
 }  // extern "C"

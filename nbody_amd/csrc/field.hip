@@ -275,8 +275,8 @@ void launch(SimPipeline *s, const fd::Params &p) {
 template <typename Q>
 void run(SimPipeline *s, bool map, const float *in, size_t in_floats, uint32_t n, uint32_t width, float softening, typename Q::Out *out) {
     use_device();
-    grown(s->stream, s->sample_in, s->sample_in_cap, in_floats);
-    grown(s->stream, s->sample_out, s->sample_out_cap, (size_t)n * Q::C);
+    s->sample_in.grown(s->stream, in_floats);
+    s->sample_out.grown(s->stream, (size_t)n * Q::C);
     ASSERT_HIP(hipMemcpyAsync(s->sample_in, in, in_floats * sizeof(float), hipMemcpyHostToDevice, s->stream), "H2D of the %s samples", Q::NOUN);
     fd::Params p{};
     p.pos = s->pos[s->cur];
@@ -287,12 +287,12 @@ void run(SimPipeline *s, bool map, const float *in, size_t in_floats, uint32_t n
     p.width = width;
     p.soft = softening;
     p.out = s->sample_out;
-    begin_diag(s);
+    s->diag_iv.begin(s->stream);
     if (map)
         launch<Q, true>(s, p);
     else
         launch<Q, false>(s, p);
-    end_diag(s);
+    s->diag_iv.end(s->stream);
     ASSERT_HIP(hipMemcpyAsync(out, s->sample_out, (size_t)n * sizeof(typename Q::Out), hipMemcpyDeviceToHost, s->stream),
                "D2H of %u %s results", n, Q::NOUN);
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after the %s kernel", Q::NOUN);
@@ -309,7 +309,7 @@ void sample_at(SimPipeline *s, const char *what, const float *points, uint32_t n
     check(Q::NOUN, softening, n);
     NB_ASSERT((points != nullptr && out != nullptr) || n == 0, "NULL points or result");
     if (n == 0) {
-        s->diag_timed = false;
+        s->diag_iv.clear();
         return;
     }
     run<Q>(s, false, points, (size_t)n * 2, n, 0, softening, out);
@@ -330,17 +330,6 @@ void sample_map(SimPipeline *s, const char *what, const RenderView *view, float 
 }
 
 }  // namespace
-
-namespace nbi {
-
-void field_release(SimPipeline *s) {
-    dev_free(s->sample_in);
-    dev_free(s->sample_out);
-    s->sample_in = s->sample_out = nullptr;
-    s->sample_in_cap = s->sample_out_cap = 0;
-}
-
-}  // namespace nbi
 
 extern "C" {
 

@@ -111,6 +111,12 @@ double nb_hip_ensemble_last_render_ms(SimBatch *batch);
 void nb_hip_last_leapfrog_info(const SimPipeline *sim, uint32_t *force_launches, int *primed);
 void nb_hip_ensemble_last_leapfrog_info(const SimBatch *batch, uint32_t *force_launches, int *primed);
 
+/* Device allocations and events the library holds at this moment, process-wide: every allocation goes through one seam
+ * (device_ctx.hip dev_alloc_bytes / dev_free) and every event through one owner type (pipeline_internal.h), and both count
+ * there.  Plain host counters: no HIP call, works without a GPU.  An object that is destroyed gives back exactly what it
+ * took (the GPU suite holds each kind of object to that).  Either pointer may be NULL. */
+void nb_hip_live_resources(uint32_t *buffers, uint32_t *events);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,8 @@ void pin_host(SimPipeline *s) {
     }
 }
 
+// What is neither device memory nor an event: those are members of owner types and go with `delete sim`, directly after
+// this -- on this thread, with the streams drained, and for a direct pipeline after the second barrier below.
 void release_device(SimPipeline *s) {
     if (!s->on_device) return;
     use_device();
@@ -47,78 +49,26 @@ void release_device(SimPipeline *s) {
     if (s->comm_stream) ASSERT_HIP(hipStreamSynchronize(s->comm_stream), "sync before release");
     if (s->direct) {
         // every rank has finished writing into its peers before anyone unmaps or frees (DestroySimPipeline is collective
-        // for direct pipelines); then the mappings go, then -- below -- the memory they pointed at
+        // for direct pipelines); then the mappings go, then -- in the destructor -- the memory they pointed at
         uint64_t tag[64] = {0};
         tag[s->rank < 64 ? s->rank : 0] = ~0ull;
         s->host_gather(s->host_gather_ctx, tag, sizeof(uint64_t), s->rank, s->nranks);
-        for (int b = 0; b < 2; b++) {
+        for (int b = 0; b < 2; b++)
             for (int q = 0; q < (int)s->peer_src[b].size(); q++)
                 if (q != s->rank && s->peer_src[b][q]) ASSERT_HIP(hipIpcCloseMemHandle(s->peer_src[b][q]), "hipIpcCloseMemHandle(rank %d)", q);
-            s->peer_src[b].clear();
-        }
         tag[s->rank < 64 ? s->rank : 0] = ~1ull;
         s->host_gather(s->host_gather_ctx, tag, sizeof(uint64_t), s->rank, s->nranks);
     }
-    s->pool.destroy();
-    s->kernel_iv.clear();
-    s->comm_iv.clear();
     unpin_host(s);
     for (auto &g : s->graphs) destroy_graph(g);
-    s->graphs.clear();
-    for (int b = 0; b < 2; b++) {
-        dev_free(s->pos[b]);
-        if (s->sharded) dev_free(s->src_pos[b]);
-        s->pos[b] = s->src_pos[b] = nullptr;
-    }
-    dev_free(s->vel);
-    dev_free(s->acc);
-    dev_free(s->radius);
-    dev_free(s->mass);
-    dev_free(s->src_gm);
-    dev_free(s->dt_dev);
-    s->dt_dev = nullptr;
-    s->dt_valid = false;
-    dev_free(s->aos);
-    dev_free(s->aos_shard);
     if (s->stage) ASSERT_HIP(hipHostFree(s->stage), "hipHostFree staging");
-    s->stage = nullptr;
-    s->stage_bytes = 0;
-    dev_free(s->parts);
-    s->parts = nullptr;
-    s->parts_cap = 0;
-    dev_free(s->tickets);
-    s->tickets = nullptr;
-    s->tickets_len = 0;
-    dev_free(s->diag);
-    s->diag = nullptr;
-    s->diag_cap = 0;
-    dev_free(s->diag_phi);
-    s->diag_phi = nullptr;
-    s->diag_phi_cap = 0;
-    for (auto &e : s->ev_diag) {
-        if (e) ASSERT_HIP(hipEventDestroy(e), "event");
-        e = nullptr;
-    }
-    s->diag_timed = false;
-    render_release(s);
-    field_release(s);
-    dev_free(s->adapt);
-    s->adapt = nullptr;
-    s->adapt_cap = 0;
-    s->adapt_armed = false;
-    s->adapt_logged = 0;
-    ASSERT_HIP(hipEventDestroy(s->ev_begin), "event");
-    ASSERT_HIP(hipEventDestroy(s->ev_end), "event");
-    ASSERT_HIP(hipEventDestroy(s->ev_local), "event");
-    ASSERT_HIP(hipEventDestroy(s->ev_gather), "event");
     if (s->comm_stream) ASSERT_HIP(hipStreamDestroy(s->comm_stream), "stream");
     if (!s->group) ASSERT_HIP(hipStreamDestroy(s->stream), "stream");
-    s->on_device = false;
 }
 
 void set_simulation_data(SimPipeline *s, const Particle *ps);
 
-// First touch of the GPU for this pipeline: stream, events, HBM buffers.
+// First touch of the GPU for this pipeline: stream, HBM buffers (events are made when first recorded).
 void materialize(SimPipeline *s) {
     use_device();
     if (s->on_device) return;
@@ -126,10 +76,6 @@ void materialize(SimPipeline *s) {
         s->stream = s->group->stream;
     else
         ASSERT_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking), "stream");
-    ASSERT_HIP(hipEventCreate(&s->ev_begin), "event");
-    ASSERT_HIP(hipEventCreate(&s->ev_end), "event");
-    ASSERT_HIP(hipEventCreateWithFlags(&s->ev_local, hipEventDisableTiming), "event");
-    ASSERT_HIP(hipEventCreateWithFlags(&s->ev_gather, hipEventDisableTiming), "event");
 
     const uint32_t N = s->data.total_len, M = s->data.mass_len;
     if (!s->sharded) {
@@ -143,21 +89,21 @@ void materialize(SimPipeline *s) {
         s->n_src = s->plan.src_padded;
     }
     const uint32_t cap = s->slots ? s->slots : 1;
-    for (int b = 0; b < 2; b++) s->pos[b] = dev_alloc<float2>(cap);
-    s->vel = dev_alloc<float2>(cap);
-    s->acc = dev_alloc<float2>(cap);
-    s->radius = dev_alloc<float>(cap);
-    s->mass = dev_alloc<float>(cap);
-    s->src_gm = dev_alloc<float>(s->n_src);
-    s->dt_dev = dev_alloc<float>(1);
-    s->aos = dev_alloc<Particle>(N);
+    for (int b = 0; b < 2; b++) s->pos[b].alloc(cap);
+    s->vel.alloc(cap);
+    s->acc.alloc(cap);
+    s->radius.alloc(cap);
+    s->mass.alloc(cap);
+    s->src_gm.alloc(s->n_src);
+    s->dt_dev.alloc(1);
+    s->aos.alloc(N);
     if (!s->sharded) {
         // the first mass_len receivers ARE the sources: no separate source array
         s->src_pos[0] = s->pos[0];
         s->src_pos[1] = s->pos[1];
     } else {
-        for (int b = 0; b < 2; b++) s->src_pos[b] = dev_alloc<float2>(s->n_src);
-        s->aos_shard = dev_alloc<Particle>((size_t)s->slots * (size_t)s->nranks);
+        for (int b = 0; b < 2; b++) s->src_pos[b] = s->gathered[b].alloc(s->n_src);
+        s->aos_shard.alloc((size_t)s->slots * (size_t)s->nranks);
         if (s->host_gather) {
             const size_t a = (size_t)s->n_src * sizeof(float2), b = (size_t)s->slots * (size_t)s->nranks * sizeof(Particle);
             s->stage_bytes = a > b ? a : b;
@@ -373,7 +319,7 @@ void set_simulation_data(SimPipeline *s, const Particle *ps) {
         // sources: every rank holds the whole world in `aos`, so the first gathered array and the static
         // G*m need no communication: rank q's slice is aos[q*Mc ..) padded
         nb::launch_split_sources(st, s->aos, M, s->n_src, s->src_pos[0], s->src_pos[1], s->src_gm, NB_G);
-        if (s->overlap) ASSERT_HIP(hipEventRecord(s->ev_gather, s->group ? s->stream : s->comm_stream), "prime gather event");
+        if (s->overlap) s->ev_gather.record(s->group ? s->stream : s->comm_stream);   // primed
     }
     ASSERT_HIP(hipStreamSynchronize(st), "sync after SetSimulationData");
     if (s->direct) {
@@ -417,7 +363,7 @@ void GetSimulationData(const SimPipeline *cs, Particle *ps) {
         // every rank merges its slots, the slices are all-gathered (uniform size), then unpacked into
         // partitioned order: massive slices first, massless slices after them
         const NbShardPlan &pl = s->plan;
-        Particle *shard = static_cast<Particle *>(s->aos_shard);
+        Particle *shard = s->aos_shard;
         Particle *mine = shard + (size_t)s->rank * s->slots;
         if (s->group) {
             for (SimPipeline *q : s->group->members)
@@ -435,11 +381,11 @@ void GetSimulationData(const SimPipeline *cs, Particle *ps) {
             const NbShardPlan pq = nb_hip_shard_plan(N, s->data.mass_len, q, s->nranks);
             const Particle *from = shard + (size_t)q * s->slots;
             if (pq.mass_count)
-                ASSERT_HIP(hipMemcpyAsync(static_cast<Particle *>(s->aos) + pq.mass_begin, from,
+                ASSERT_HIP(hipMemcpyAsync(s->aos + pq.mass_begin, from,
                                           (size_t)pq.mass_count * sizeof(Particle), hipMemcpyDeviceToDevice, st),
                            "unpack massive slice of rank %d", q);
             if (pq.zero_count)
-                ASSERT_HIP(hipMemcpyAsync(static_cast<Particle *>(s->aos) + pq.zero_begin, from + pl.mass_chunk,
+                ASSERT_HIP(hipMemcpyAsync(s->aos + pq.zero_begin, from + pl.mass_chunk,
                                           (size_t)pq.zero_count * sizeof(Particle), hipMemcpyDeviceToDevice, st),
                            "unpack massless slice of rank %d", q);
         }
@@ -494,21 +440,21 @@ void PerformSimUpdate(SimPipeline *s, uint32_t n, float dt) {
 double nb_hip_last_step_ms(SimPipeline *s, uint32_t *launches) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
     if (launches) *launches = 0;
-    if (!s->on_device || !s->timed) return 0.0;
+    if (!s->on_device || !s->step_iv.valid()) return 0.0;
     if (launches) *launches = s->timed_launches;
-    return elapsed_ms(s->ev_begin, s->ev_end);
+    return s->step_iv.ms();
 }
 
 uint32_t nb_hip_last_finish_launches(const SimPipeline *s) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
-    return s->timed ? s->timed_finish_launches : 0;
+    return s->step_iv.valid() ? s->timed_finish_launches : 0;
 }
 
 uint32_t nb_hip_last_step_breakdown(SimPipeline *s, double *kernel_ms, double *comm_ms) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
     if (kernel_ms) *kernel_ms = 0.0;
     if (comm_ms) *comm_ms = 0.0;
-    if (!s->on_device || (!s->timed && !s->group) || s->detail_steps == 0) return 0;
+    if (!s->on_device || (!s->step_iv.valid() && !s->group) || s->detail_steps == 0) return 0;
     use_device();
     ASSERT_HIP(hipStreamSynchronize(s->stream), "stream sync");
     if (s->comm_stream) ASSERT_HIP(hipStreamSynchronize(s->comm_stream), "comm stream sync");
@@ -575,7 +521,7 @@ int nb_hip_configure(SimPipeline *s, const char *key, int value) {
         if (s->on_device && s->sharded) nb_hip_sync(s);
         s->overlap = value ? 1 : 0;
         if (s->on_device && s->overlap && s->sharded)
-            ASSERT_HIP(hipEventRecord(s->ev_gather, s->group ? s->stream : s->comm_stream), "prime gather event");
+            s->ev_gather.record(s->group ? s->stream : s->comm_stream);   // primed
     } else {
         NB_FAIL("unknown knob \"%s\" (include/nbody_hip.h lists the knobs; launch-shape hooks: nbody_hip_tuning.h)", key);
     }

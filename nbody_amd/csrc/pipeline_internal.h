@@ -1,12 +1,17 @@
 // pipeline_internal.h -- what the translation units behind include/nbody_hip.h share (C++, not part of the C-ABI):
 //
-//   device_ctx.hip   the process-wide device context (the reference keeps one global vulkan_ctx, vulkan_ctx.c:11)
+//   this header      besides the two structs' shared declarations: DevBuf<T>, DevEvent and Interval, the owner types every
+//                    device array, event and timed interval of a SimPipeline / SimBatch is a member of.  Nothing in these files
+//                    frees device memory or destroys an event by hand: the member's destructor does, when the struct is deleted
+//   device_ctx.hip   the process-wide device context (the reference keeps one global vulkan_ctx, vulkan_ctx.c:11); the one
+//                    allocation seam (dev_alloc_bytes / dev_free) and the counters behind nb_hip_live_resources
 //   rccl_bind.hip    RCCL bound lazily with dlopen, the communicator of a sharded pipeline, the watchdog
 //   shard_plan.hip   nb_hip_shard_plan: who owns which receivers and sources (pure host arithmetic)
 //   step_chain.hip   one step / n fixed Euler steps as launches: the launch plan, cached hipGraph chains, the one-workgroup chain
 //   shard_exchange.hip  the sharded step: the four transports of its in-place all-gather, captured sharded chains
 //   step_schedule.hip   device-chosen and leapfrog steps of a pipeline: the target of step_schedule.h's one launch schedule
-//   pipeline.hip     SimPipeline life cycle and the C-ABI entry points (Create/Destroy/Set/Get/PerformSimUpdate, knobs)
+//   pipeline.hip     SimPipeline life cycle and the C-ABI entry points (Create/Destroy/Set/Get/PerformSimUpdate, knobs);
+//                    release_device ends what no owner type holds: streams, cached graphs, IPC mappings, pinned host memory
 //   kernels.hip      the gfx950 force kernels and their entry points (kernels.h)
 //   launch_shape.hip the host-side launch policy: shape, grid, LDS of a launch (launch_shape.h)
 //   convert.hip      AoS <-> SoA converters, pads, G*m, fills (convert.h)
@@ -32,6 +37,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -68,7 +74,10 @@
         }                                                                                               \
     } while (0)
 
+#define NB_HIDDEN __attribute__((visibility("hidden")))   // not among the library's exported symbols
+
 typedef struct ncclComm *ncclComm_t;  // opaque; rccl_bind.hip holds the rest of the binding
+struct NbSplat;                       // render_common.h: an entry of the pipeline's disc list
 
 namespace nbi {
 
@@ -86,7 +95,9 @@ extern int g_requested_ordinal;
 void ensure_device();  // first touch of the GPU by this process; aborts unless a gfx950 device answers (no CPU fallback)
 void use_device();     // ensure_device + hipSetDevice on the calling thread (HIP's current device is per THREAD)
 void *dev_alloc_bytes(size_t bytes);
-void dev_free(void *p);
+void dev_free(void *p);   // NULL: no HIP call
+// what nb_hip_live_resources reports: device allocations and events alive in the process (plain host counters)
+extern NB_HIDDEN std::atomic<uint32_t> g_live_buffers, g_live_events;
 
 // libc's rand() stream belongs to the caller: the reference harness seeds it ONCE and draws every universe of its table
 // from it (src/bench.c:42,53), between GPU calls.  The HIP runtime's first stream / allocation / code-object set-up
@@ -143,31 +154,81 @@ T *dev_alloc(size_t count) {
 
 inline uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 
-// A scratch buffer grown on demand: at least `need` elements afterwards.  The old contents go (work queued on `st` may
-// still read them: it is drained first).
-template <typename T>
-T *grown(hipStream_t st, T *&buf, size_t &cap, size_t need) {
-    if (cap < need || !buf) {
-        if (buf) {
-            ASSERT_HIP(hipStreamSynchronize(st), "sync before regrowing a scratch buffer");
-            dev_free(buf);
-        }
-        buf = dev_alloc<T>(need);
-        cap = need;
-    }
-    return buf;
-}
+// ---- the owners: every device buffer and every event of the seam is a member of one of these three types, and is released
+// by that member's destructor -- once, when its SimPipeline / SimBatch / calling function goes, after whoever deletes the
+// owner has drained its streams.  One that was never made makes no HIP call when it goes.
 
-// The same for a buffer whose first `head` bytes are records a continued call goes on from: they are carried over.
-inline void regrow_carrying(hipStream_t st, void *&buf, size_t bytes, size_t head) {
-    void *old = buf;
-    buf = dev_alloc_bytes(bytes);
-    if (old) {
-        ASSERT_HIP(hipMemcpyAsync(buf, old, head, hipMemcpyDeviceToDevice, st), "carry the adaptive-step records over");
-        ASSERT_HIP(hipStreamSynchronize(st), "sync before freeing the old adaptive-step buffer");
-        dev_free(old);
+// A device array: a pointer and an element count.  Reads as a plain T * wherever a parameter block is filled.
+template <typename T>
+class NB_HIDDEN DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { dev_free(p_); }
+
+    operator T *() const { return p_; }
+    size_t count() const { return n_; }   // elements asked for (0 before alloc)
+
+    T *alloc(size_t count) {   // once
+        NB_ASSERT(p_ == nullptr, "device array made twice");
+        n_ = count;
+        return p_ = dev_alloc<T>(count);
     }
-}
+    // Scratch grown on demand: at least `need` elements afterwards, exactly `need` when it had to be made anew.  The old
+    // contents go (work queued on `st` may still read them: it is drained first).  True when the array moved.
+    bool grown(hipStream_t st, size_t need) { return regrow(st, need, 0); }
+    // The same for an array whose first `head` bytes are records a continued call goes on from: they are carried over.
+    bool grown_carrying(hipStream_t st, size_t need, size_t head) { return regrow(st, need, head); }
+
+  private:
+    bool regrow(hipStream_t st, size_t need, size_t head) {
+        if (p_ && n_ >= need) return false;
+        T *old = p_;
+        p_ = nullptr;
+        if (old && head == 0) {
+            ASSERT_HIP(hipStreamSynchronize(st), "sync before regrowing a scratch buffer");
+            dev_free(old);
+            old = nullptr;
+        }
+        alloc(need);
+        if (old) {
+            ASSERT_HIP(hipMemcpyAsync(p_, old, head, hipMemcpyDeviceToDevice, st), "carry the head of a regrown buffer over");
+            ASSERT_HIP(hipStreamSynchronize(st), "sync before freeing the old buffer");
+            dev_free(old);
+        }
+        return true;
+    }
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// An event, created on first use with the flags given.
+class NB_HIDDEN DevEvent {
+  public:
+    explicit DevEvent(unsigned flags = hipEventDefault) : flags_(flags) {}
+    DevEvent(DevEvent &&o) noexcept : ev_(o.ev_), flags_(o.flags_) { o.ev_ = nullptr; }
+    DevEvent(const DevEvent &) = delete;
+    DevEvent &operator=(const DevEvent &) = delete;
+    ~DevEvent() {
+        if (!ev_) return;
+        ASSERT_HIP(hipEventDestroy(ev_), "event");
+        g_live_events--;
+    }
+    hipEvent_t get() {
+        if (!ev_) {
+            ASSERT_HIP(hipEventCreateWithFlags(&ev_, flags_), "event");
+            g_live_events++;
+        }
+        return ev_;
+    }
+    void record(hipStream_t st) { ASSERT_HIP(hipEventRecord(get(), st), "event record"); }
+
+  private:
+    hipEvent_t ev_ = nullptr;
+    unsigned flags_;
+};
 
 // device time between two recorded events, once the later one has completed
 inline double elapsed_ms(hipEvent_t ev0, hipEvent_t ev1) {
@@ -176,6 +237,23 @@ inline double elapsed_ms(hipEvent_t ev0, hipEvent_t ev1) {
     ASSERT_HIP(hipEventElapsedTime(&ms, ev0, ev1), "elapsed time");
     return (double)ms;
 }
+
+// A timed interval of stream work: two events and whether the pair was recorded by the last call that could have.
+class NB_HIDDEN Interval {
+  public:
+    void begin(hipStream_t st) { first.record(st); }
+    void end(hipStream_t st) {
+        last.record(st);
+        valid_ = true;
+    }
+    void clear() { valid_ = false; }   // the last call had nothing to time
+    bool valid() const { return valid_; }
+    double ms() { return valid_ ? elapsed_ms(first.get(), last.get()) : 0.0; }
+    DevEvent first, last;
+
+  private:
+    bool valid_ = false;
+};
 
 // ---- rccl_bind.hip -------------------------------------------------------------------------------------------
 
@@ -221,10 +299,12 @@ struct StepGraph {
 // Event pairs around the kernels and the gathers of a sharded chain (the plain-launch path, "timing" knob on), so that
 // a multi-GPU run can say how much of a step was the all-gather.  Grown on demand, reused by every call.
 struct EventPool {
-    std::vector<hipEvent_t> ev;
+    std::vector<DevEvent> ev;
     size_t used = 0;
-    hipEvent_t next();
-    void destroy();
+    hipEvent_t next() {
+        if (used == ev.size()) ev.emplace_back();
+        return ev[used++].get();
+    }
 };
 
 }  // namespace nbi
@@ -262,22 +342,23 @@ struct SimPipeline {
     uint32_t n_src = 0;      // sources every receiver sees (mass_len, or the padded gathered length)
 
     // SoA streams (DESIGN.md "Layout in HBM")
-    float2 *pos[2] = {nullptr, nullptr};
-    float2 *vel = nullptr;
-    float2 *acc = nullptr;
-    float *radius = nullptr;
-    float *mass = nullptr;
-    float2 *src_pos[2] = {nullptr, nullptr};  // sharded only: gathered source positions (ping-pong)
-    float *src_gm = nullptr;
+    nbi::DevBuf<float2> pos[2];
+    nbi::DevBuf<float2> vel, acc;
+    nbi::DevBuf<float> radius, mass;
+    // the sources of a step (ping-pong): a view of pos[] when unsharded (the first mass_len receivers ARE the sources), of
+    // the gathered source positions when sharded
+    float2 *src_pos[2] = {nullptr, nullptr};
+    nbi::DevBuf<float2> gathered[2];
+    nbi::DevBuf<float> src_gm;
     // the step size lives in device memory, like the reference's uniform block (sim_gpu.h:8-12): kernels read it
     // through StepParams::dt, a new value is written in stream order when PerformSimUpdate's dt differs from the last
     // one enqueued (the reference's re-upload, sim_gpu.c:268-284), and no cached hipGraph ever needs re-patching
-    float *dt_dev = nullptr;
+    nbi::DevBuf<float> dt_dev;
     float dt_enqueued = 0.0f;
     bool dt_valid = false;
     uint32_t dt_uploads = 0;
-    void *aos = nullptr;     // device AoS staging for Set/Get (whole world)
-    void *aos_shard = nullptr;  // sharded only: this rank's slice, uniform size
+    nbi::DevBuf<Particle> aos;        // device AoS staging for Set/Get (whole world)
+    nbi::DevBuf<Particle> aos_shard;  // sharded only: every rank's slice, uniform size
     void *host_array = nullptr;  // caller's long-lived particle array (nb_hip_note_host_array), page-locked lazily
     size_t host_bytes = 0;
     bool host_pinned = false;
@@ -290,24 +371,22 @@ struct SimPipeline {
     int zero_copy_upload = 1;     // SetSimulationData from the noted array: the split kernel reads host memory directly
     bool host_current = false;    // the noted array already holds the device's latest state
     uint32_t updates_since_get = 0, frame_streak = 0;
-    // record the ev_begin / ev_end pair around every chain (nb_hip_last_step_ms) and, on the sharded plain-launch path,
+    // record the step interval around every chain (nb_hip_last_step_ms) and, on the sharded plain-launch path,
     // the per-step kernel / gather event pairs (nb_hip_last_step_breakdown).  Off unless asked for: the records cost an
     // interactive caller 3-7 us per call (profiles/r02_frame_loop_latency.txt).
     int timing = 0;
-    float2 *parts = nullptr;    // split steps only: [split][n_real] partial sums
-    uint32_t parts_cap = 0;     // float2 elements allocated in parts
-    uint32_t *tickets = nullptr;  // fused finish: one arrival counter per receiver tile, zero between launches (re-zeroed at every upload
-    uint32_t tickets_len = 0;     // and before a chain is built: a launch that ended part-way must not leave a tile unfinished for ever)
+    nbi::DevBuf<float2> parts;      // split steps only: [split][n_real] partial sums
+    nbi::DevBuf<uint32_t> tickets;  // fused finish: one arrival counter per receiver tile, zero between launches (re-zeroed at every upload
+                                    // and before a chain is built: a launch that ended part-way must not leave a tile unfinished for ever)
     int fused_finish = 2;         // 0: step kernel + finish kernel; 1: the last workgroup of a tile finishes it, whenever
                                   // the shape allows; 2 (default): auto (launch_shape.hip fused_finish_rule)
     int cur = 0;             // pos[cur] is the latest state
 
     hipStream_t stream = nullptr;
     hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    hipEvent_t ev_local = nullptr, ev_gather = nullptr;
-    bool timed = false;
-    uint32_t timed_launches = 0;         // step-kernel launches between ev_begin and ev_end
+    nbi::Interval step_iv;   // around the last chain, when the "timing" knob was on
+    nbi::DevEvent ev_local{hipEventDisableTiming}, ev_gather{hipEventDisableTiming};   // sharded: what orders stream and comm stream
+    uint32_t timed_launches = 0;         // step-kernel launches inside step_iv
     uint32_t timed_finish_launches = 0;  // finish-kernel launches in the same interval (split shapes only)
     // sharded plain-launch chains: [begin, end) event pairs of each step's kernels and of each gather
     nbi::EventPool pool;
@@ -332,40 +411,32 @@ struct SimPipeline {
 
     std::vector<nbi::StepGraph> graphs;
 
-    // diagnostics.hip (nb_hip_energy / nb_hip_potential): scratch grown on demand, an event pair of their own (the step's
-    // ev_begin / ev_end keep bracketing the last step)
-    double *diag = nullptr;      // float64 slab: NB_DIAG_SUMS per workgroup + the NB_DIAG_SUMS results
-    size_t diag_cap = 0;         // doubles allocated in diag
-    float *diag_phi = nullptr;   // nb_hip_potential's device result
-    size_t diag_phi_cap = 0;
-    hipEvent_t ev_diag[2] = {nullptr, nullptr};
-    bool diag_timed = false;
+    // diagnostics.hip (nb_hip_energy / nb_hip_potential): scratch grown on demand, an interval of their own (step_iv keeps
+    // bracketing the last step)
+    nbi::DevBuf<double> diag;      // float64 slab: NB_DIAG_SUMS per workgroup + the NB_DIAG_SUMS results
+    nbi::DevBuf<float> diag_phi;   // nb_hip_potential's device result
+    nbi::Interval diag_iv;
 
     // render.hip (nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba): buffers grown on demand, events of their own
-    uint32_t *render_counts = nullptr;   // count image [3][height][width]
-    size_t render_counts_cap = 0;        // uint32 allocated in render_counts
-    void *render_discs = nullptr;        // compact disc list, total_len entries
-    uint32_t *render_words = nullptr;    // [0] discs appended by the last splat, [4..7] the bounds' ordered keys
-    uint32_t *render_rgba = nullptr;     // frame, one packed RGBA word per pixel
-    size_t render_rgba_cap = 0;          // pixels allocated in render_rgba
-    hipEvent_t ev_render[4] = {nullptr, nullptr, nullptr, nullptr};   // begin, after splat, after disc, end
-    hipEvent_t ev_bounds[2] = {nullptr, nullptr};
-    bool render_timed = false, render_detailed = false, bounds_timed = false;
+    nbi::DevBuf<uint32_t> render_counts;   // count image [3][height][width]
+    nbi::DevBuf<NbSplat> render_discs;     // compact disc list, total_len entries
+    nbi::DevBuf<uint32_t> render_words;    // [0] discs appended by the last splat, [4..7] the bounds' ordered keys
+    nbi::DevBuf<uint32_t> render_rgba;     // frame, one packed RGBA word per pixel
+    nbi::Interval render_iv, bounds_iv;
+    nbi::DevEvent ev_splat, ev_disc;       // inside render_iv: after the splat, after the disc pass ("render_detail")
+    bool render_detailed = false;          // the last render recorded those two
     int render_merge = 1, render_detail = 0;   // tuning hooks (nbody_hip_tuning.h)
 
     // field.hip (nb_hip_potential_at / _map, nb_hip_acceleration_at / _map): one pair of buffers grown on demand and shared by
-    // the four calls (each ends in a stream sync, so no two are in flight); the event pair is ev_diag
-    float *sample_in = nullptr;    // the probes' (x, y) pairs, or a map's width column + height row coordinates
-    size_t sample_in_cap = 0;      // floats allocated in sample_in
-    float *sample_out = nullptr;   // the device result: one float (Phi) or two (g) per sample
-    size_t sample_out_cap = 0;     // floats allocated in sample_out
+    // the four calls (each ends in a stream sync, so no two are in flight); the interval is diag_iv
+    nbi::DevBuf<float> sample_in;    // the probes' (x, y) pairs, or a map's width column + height row coordinates
+    nbi::DevBuf<float> sample_out;   // the device result: one float (Phi) or two (g) per sample
     int field_shape = 0;           // tuning hooks, Phi and g: 0 auto, 1 source split, 2 one wave per tile
     int gravity_shape = 0;
 
     // adaptive steps (step_schedule.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
     // ADAPT_HEAD bytes of records (the call's AdaptState, the record and result of nb_hip_timestep), then the call's log
-    void *adapt = nullptr;
-    size_t adapt_cap = 0;            // log floats allocated behind the head
+    nbi::DevBuf<char> adapt;
     bool adapt_armed = false;        // the call record holds a call to continue (NB_ADAPT_CONTINUE)
     uint32_t adapt_logged = 0;       // steps of the last adaptive call: what nb_hip_adaptive_collect copies back
     std::vector<char> adapt_host;    // where that copy lands
@@ -399,7 +470,7 @@ uint32_t passes_for(const SimPipeline *s, const nb::StepParams &p);
 void launch_step(SimPipeline *s, nb::LaunchShape sh, const nb::StepParams &p, hipStream_t st);
 void upload_dt(SimPipeline *s, float dt);
 void zero_tickets(SimPipeline *s);   // fused finish: all tile tickets back to 0, in stream order
-// what every step call starts and ends with: the per-call records cleared; ev_end and the launch counts of the timed interval
+// what every step call starts and ends with: the per-call records cleared; the end of step_iv and the launch counts of the timed interval
 void begin_call(SimPipeline *s);
 void end_call(SimPipeline *s, uint32_t launches);
 void enqueue_steps(SimPipeline *s, uint32_t n, float dt);  // what PerformSimUpdate / nb_hip_step_async enqueue
@@ -420,15 +491,5 @@ void check_adaptive_cfg(const void *s, uint32_t n, const NbAdaptive *cfg, const 
 // ---- diagnostics.hip -----------------------------------------------------------------------------------------
 
 void check_diag(SimPipeline *s, const char *what);   // aborts on NULL, on a sharded pipeline and before SetSimulationData
-void begin_diag(SimPipeline *s);                     // records ev_diag[0] on the stream (creates the pair on first use)
-void end_diag(SimPipeline *s);                       // records ev_diag[1]; nb_hip_last_diag_ms then reports the interval
-
-// ---- field.hip -----------------------------------------------------------------------------------------------
-
-void field_release(SimPipeline *s);    // frees the sample buffers (release_device)
-
-// ---- render.hip ----------------------------------------------------------------------------------------------
-
-void render_release(SimPipeline *s);   // frees the render buffers and events (release_device)
 
 }  // namespace nbi

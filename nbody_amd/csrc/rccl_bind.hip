@@ -200,41 +200,34 @@ void comm_create(SimPipeline *s, const void *unique_id128) {
     // lazy channel setup here instead of inside the first timed step.
     Watchdog dog("the first ncclAllGather", rank, nranks);
     const size_t per = 64;
-    float *probe = dev_alloc<float>(per * (size_t)nranks);
+    DevBuf<float> probe;
+    probe.alloc(per * (size_t)nranks);
     std::vector<float> host(per * (size_t)nranks, 0.0f);
     for (size_t i = 0; i < per; i++) host[(size_t)rank * per + i] = (float)(rank + 1);
     hipStream_t st;
     ASSERT_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "probe stream");
     ASSERT_HIP(hipMemcpyAsync(probe, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, st), "probe H2D");
-    hipEvent_t e0, e1;
-    ASSERT_HIP(hipEventCreate(&e0), "event");
-    ASSERT_HIP(hipEventCreate(&e1), "event");
-    ASSERT_HIP(hipEventRecord(e0, st), "record");
+    Interval iv;
+    iv.begin(st);
     ASSERT_NCCL(rccl().AllGather(probe + (size_t)rank * per, probe, per, NCCL_FLOAT32, s->comm, st), "first ncclAllGather");
-    ASSERT_HIP(hipEventRecord(e1, st), "record");
+    iv.end(st);
     ASSERT_HIP(hipMemcpyAsync(host.data(), probe, host.size() * sizeof(float), hipMemcpyDeviceToHost, st), "probe D2H");
     ASSERT_HIP(hipStreamSynchronize(st), "probe sync");
     for (int q = 0; q < nranks; q++)
         for (size_t i = 0; i < per; i++)
             NB_ASSERT(host[(size_t)q * per + i] == (float)(q + 1), "first all-gather: slot of rank %d holds %g", q,
                       (double)host[(size_t)q * per + i]);
-    float ms = 0.0f;
-    ASSERT_HIP(hipEventElapsedTime(&ms, e0, e1), "elapsed");
-    s->first_gather_ms = (double)ms;
+    s->first_gather_ms = iv.ms();
     // ... and what a WARM small all-gather costs in-stream: 16 back-to-back 8-byte-per-rank gathers between one event pair.
     // This is the fixed cost of the per-step gather -- the one term of the scaling curve a single-GPU box cannot measure.
     const int reps = 16;
-    ASSERT_HIP(hipEventRecord(e0, st), "record");
+    iv.begin(st);
     for (int i = 0; i < reps; i++)
         ASSERT_NCCL(rccl().AllGather(probe + (size_t)rank * 2, probe, 2, NCCL_FLOAT32, s->comm, st), "8-byte ncclAllGather");
-    ASSERT_HIP(hipEventRecord(e1, st), "record");
+    iv.end(st);
     ASSERT_HIP(hipStreamSynchronize(st), "8-byte gathers");
-    ASSERT_HIP(hipEventElapsedTime(&ms, e0, e1), "elapsed");
-    s->small_gather_us = (double)ms * 1e3 / reps;
-    ASSERT_HIP(hipEventDestroy(e0), "event");
-    ASSERT_HIP(hipEventDestroy(e1), "event");
+    s->small_gather_us = iv.ms() * 1e3 / reps;
     ASSERT_HIP(hipStreamDestroy(st), "probe stream");
-    dev_free(probe);
 }
 
 void comm_destroy(SimPipeline *s) {

@@ -234,12 +234,7 @@ void check_view(const RenderView *view) {
 }
 
 void ensure_words(SimPipeline *s) {
-    if (!s->render_words) s->render_words = dev_alloc<uint32_t>(8);
-}
-
-void record(SimPipeline *s, hipEvent_t &e) {
-    if (!e) ASSERT_HIP(hipEventCreate(&e), "event");
-    ASSERT_HIP(hipEventRecord(e, s->stream), "record render event");
+    if (!s->render_words) s->render_words.alloc(8);
 }
 
 // clear + splat + disc on the stream: the count image of the current state is in s->render_counts afterwards
@@ -247,11 +242,11 @@ void enqueue_counts(SimPipeline *s, const RenderView *view) {
     use_device();
     const uint32_t N = s->data.total_len;
     const size_t plane = (size_t)view->width * view->height;
-    grown(s->stream, s->render_counts, s->render_counts_cap, plane * NB_RENDER_CLASSES);
+    s->render_counts.grown(s->stream, plane * NB_RENDER_CLASSES);
     ensure_words(s);
-    if (!s->render_discs) s->render_discs = dev_alloc<NbSplat>(N);
+    if (!s->render_discs) s->render_discs.alloc(N);
     const bool detail = s->render_detail != 0;
-    record(s, s->ev_render[0]);
+    s->render_iv.begin(s->stream);
     ASSERT_HIP(hipMemsetAsync(s->render_counts, 0, plane * NB_RENDER_CLASSES * sizeof(uint32_t), s->stream), "clear the count image");
     if (N > 0) {
         ASSERT_HIP(hipMemsetAsync(s->render_words, 0, sizeof(uint32_t), s->stream), "clear the disc count");
@@ -259,54 +254,25 @@ void enqueue_counts(SimPipeline *s, const RenderView *view) {
                                   view->zoom,      view->core_mass, view->width,     view->height};
         const uint32_t per_group = rd::THREADS * rd::PER_LANE;
         const dim3 grid((N + per_group - 1) / per_group), block(rd::THREADS);
-        NbSplat *discs = static_cast<NbSplat *>(s->render_discs);
         if (s->render_merge)
             hipLaunchKernelGGL(rd::splat_kernel<true>, grid, block, 0, s->stream, s->pos[s->cur], s->mass, s->radius, N, v,
-                               s->render_counts, discs, s->render_words);
+                               s->render_counts, s->render_discs, s->render_words);
         else
             hipLaunchKernelGGL(rd::splat_kernel<false>, grid, block, 0, s->stream, s->pos[s->cur], s->mass, s->radius, N, v,
-                               s->render_counts, discs, s->render_words);
+                               s->render_counts, s->render_discs, s->render_words);
         ASSERT_HIP(hipGetLastError(), "splat_kernel launch (%u particles)", N);
     }
-    if (detail) record(s, s->ev_render[1]);
+    if (detail) s->ev_splat.record(s->stream);
     if (N > 0) {
-        hipLaunchKernelGGL(rd::disc_kernel, dim3(rd::DISC_GROUPS), dim3(rd::THREADS), 0, s->stream,
-                           static_cast<const NbSplat *>(s->render_discs), s->render_words, view->width, view->height, s->render_counts);
+        hipLaunchKernelGGL(rd::disc_kernel, dim3(rd::DISC_GROUPS), dim3(rd::THREADS), 0, s->stream, s->render_discs, s->render_words,
+                           view->width, view->height, s->render_counts);
         ASSERT_HIP(hipGetLastError(), "disc_kernel launch");
     }
-    if (detail) record(s, s->ev_render[2]);
+    if (detail) s->ev_disc.record(s->stream);
     s->render_detailed = detail;
 }
 
-void end_render(SimPipeline *s) {
-    record(s, s->ev_render[3]);
-    s->render_timed = true;
-}
-
 }  // namespace
-
-namespace nbi {
-
-void render_release(SimPipeline *s) {
-    dev_free(s->render_counts);
-    dev_free(s->render_discs);
-    dev_free(s->render_words);
-    dev_free(s->render_rgba);
-    s->render_counts = s->render_words = s->render_rgba = nullptr;
-    s->render_discs = nullptr;
-    s->render_counts_cap = s->render_rgba_cap = 0;
-    for (auto &e : s->ev_render) {
-        if (e) ASSERT_HIP(hipEventDestroy(e), "event");
-        e = nullptr;
-    }
-    for (auto &e : s->ev_bounds) {
-        if (e) ASSERT_HIP(hipEventDestroy(e), "event");
-        e = nullptr;
-    }
-    s->render_timed = s->render_detailed = s->bounds_timed = false;
-}
-
-}  // namespace nbi
 
 extern "C" {
 
@@ -319,19 +285,18 @@ void nb_hip_bounds(SimPipeline *s, float *bounds) {
         use_device();
         ensure_words(s);
         uint32_t *keys = s->render_words + 4;
-        record(s, s->ev_bounds[0]);
+        s->bounds_iv.begin(s->stream);
         ASSERT_HIP(hipMemsetAsync(keys, 0xff, 2 * sizeof(uint32_t), s->stream), "identity of the min keys");
         ASSERT_HIP(hipMemsetAsync(keys + 2, 0, 2 * sizeof(uint32_t), s->stream), "identity of the max keys");
         const uint32_t groups = (N + rd::THREADS - 1) / rd::THREADS;
         hipLaunchKernelGGL(rd::bounds_kernel, dim3(groups < rd::BOUNDS_GROUPS_MAX ? groups : rd::BOUNDS_GROUPS_MAX), dim3(rd::THREADS), 0,
                            s->stream, s->pos[s->cur], N, keys);
         ASSERT_HIP(hipGetLastError(), "bounds_kernel launch (%u particles)", N);
-        record(s, s->ev_bounds[1]);
-        s->bounds_timed = true;
+        s->bounds_iv.end(s->stream);
         ASSERT_HIP(hipMemcpyAsync(key, keys, sizeof(key), hipMemcpyDeviceToHost, s->stream), "D2H of the bounds");
         ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_bounds");
     } else {
-        s->bounds_timed = false;
+        s->bounds_iv.clear();
     }
     nb_render_bounds_from_keys(key, bounds);
 }
@@ -341,7 +306,7 @@ void nb_hip_render_counts(SimPipeline *s, const RenderView *view, uint32_t *coun
     check_view(view);
     NB_ASSERT(counts != nullptr, "NULL count image");
     enqueue_counts(s, view);
-    end_render(s);
+    s->render_iv.end(s->stream);
     const size_t bytes = (size_t)view->width * view->height * NB_RENDER_CLASSES * sizeof(uint32_t);
     ASSERT_HIP(hipMemcpyAsync(counts, s->render_counts, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of the count image");
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_render_counts");
@@ -354,11 +319,11 @@ void nb_hip_render_rgba(SimPipeline *s, const RenderView *view, const RenderPale
     NB_ASSERT(palette->saturation >= 1u, "RenderPalette saturation must be at least 1");
     const uint32_t plane = view->width * view->height;
     enqueue_counts(s, view);
-    grown(s->stream, s->render_rgba, s->render_rgba_cap, (size_t)plane);
+    s->render_rgba.grown(s->stream, (size_t)plane);
     hipLaunchKernelGGL(rd::shade_kernel, dim3((plane + rd::THREADS - 1) / rd::THREADS), dim3(rd::THREADS), 0, s->stream,
                        s->render_counts, plane, *palette, s->render_rgba);
     ASSERT_HIP(hipGetLastError(), "shade_kernel launch (%u pixels)", plane);
-    end_render(s);
+    s->render_iv.end(s->stream);
     ASSERT_HIP(hipMemcpyAsync(rgba, s->render_rgba, (size_t)plane * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream), "D2H of the frame");
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_render_rgba");
 }
@@ -367,15 +332,14 @@ void nb_hip_render_rgba(SimPipeline *s, const RenderView *view, const RenderPale
 double nb_hip_last_render_ms(SimPipeline *s, double *parts) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
     if (parts) parts[0] = parts[1] = parts[2] = parts[3] = 0.0;
-    if (!s->render_timed && !s->bounds_timed) return 0.0;
+    if (!s->render_iv.valid() && !s->bounds_iv.valid()) return 0.0;
     use_device();
-    if (parts && s->bounds_timed) parts[0] = elapsed_ms(s->ev_bounds[0], s->ev_bounds[1]);
-    if (!s->render_timed) return 0.0;
-    const double whole = elapsed_ms(s->ev_render[0], s->ev_render[3]);   // waits for the last event: the ones between are done
-    if (parts && s->render_detailed) {
-        parts[1] = elapsed_ms(s->ev_render[0], s->ev_render[1]);
-        parts[2] = elapsed_ms(s->ev_render[1], s->ev_render[2]);
-        parts[3] = elapsed_ms(s->ev_render[2], s->ev_render[3]);
+    if (parts) parts[0] = s->bounds_iv.ms();
+    const double whole = s->render_iv.ms();   // waits for the last event: the ones between are done
+    if (parts && s->render_iv.valid() && s->render_detailed) {
+        parts[1] = elapsed_ms(s->render_iv.first.get(), s->ev_splat.get());
+        parts[2] = elapsed_ms(s->ev_splat.get(), s->ev_disc.get());
+        parts[3] = elapsed_ms(s->ev_disc.get(), s->render_iv.last.get());
     }
     return whole;
 }

@@ -131,7 +131,7 @@ void sharded_step(SimPipeline *s, nb::LaunchShape sh, float dt, hipStream_t cs, 
         const hipEvent_t a0 = mark(s->stream);
         launch_step(s, sh, a, s->stream);
         const hipEvent_t a1 = mark(s->stream);
-        ASSERT_HIP(hipStreamWaitEvent(s->stream, s->ev_gather, 0), "wait gather");
+        ASSERT_HIP(hipStreamWaitEvent(s->stream, s->ev_gather.get(), 0), "wait gather");
         const hipEvent_t b0 = mark(s->stream);  // stamped once the previous step's gather has landed
         nb::StepParams b = whole_step(s, in, dt);
         b.src_begin[0] = 0;
@@ -141,12 +141,12 @@ void sharded_step(SimPipeline *s, nb::LaunchShape sh, float dt, hipStream_t cs, 
         b.flags = nb::STEP_ACC_IN;
         launch_step(s, sh, b, s->stream);
         const hipEvent_t b1 = mark(s->stream);
-        ASSERT_HIP(hipEventRecord(s->ev_local, s->stream), "record local");
-        ASSERT_HIP(hipStreamWaitEvent(cs, s->ev_local, 0), "comm waits for the new slice");
+        s->ev_local.record(s->stream);
+        ASSERT_HIP(hipStreamWaitEvent(cs, s->ev_local.get(), 0), "comm waits for the new slice");
         const hipEvent_t g0 = mark(cs);
         allgather_sources(s, in ^ 1, cs);
         const hipEvent_t g1 = mark(cs);
-        ASSERT_HIP(hipEventRecord(s->ev_gather, cs), "record gather");
+        s->ev_gather.record(cs);
         if (detail) {
             s->kernel_iv.emplace_back(a0, a1);
             s->kernel_iv.emplace_back(b0, b1);
@@ -200,7 +200,7 @@ void enqueue_sharded(SimPipeline *s, uint32_t n, float dt) {
     // per-step event pairs only when the caller asked for timing: up to ~1000 hipEventRecord per call otherwise for nothing
     for (uint32_t i = 0; i < n; i++) sharded_step(s, sh, dt, s->comm_stream, s->timing != 0 && i < DETAIL_STEPS_MAX);
     s->detail_steps = s->timing ? (n < DETAIL_STEPS_MAX ? n : DETAIL_STEPS_MAX) : 0;
-    if (s->overlap) ASSERT_HIP(hipStreamWaitEvent(s->stream, s->ev_gather, 0), "join comm stream");
+    if (s->overlap) ASSERT_HIP(hipStreamWaitEvent(s->stream, s->ev_gather.get(), 0), "join comm stream");
 }
 
 }  // namespace nbi
@@ -251,7 +251,7 @@ void nb_hip_local_group_step(SimPipeline **sims, int nranks, uint32_t n, float d
     for (int r = 0; r < nranks; r++) {
         SimPipeline *s = sims[r];
         s->detail_steps = s->timing ? (n < DETAIL_STEPS_MAX ? n : DETAIL_STEPS_MAX) : 0;
-        s->timed = false;   // no whole-chain event pair for group members; the breakdown has its own
+        s->step_iv.clear();   // no whole-chain event pair for group members; the breakdown has its own
     }
     ASSERT_HIP(hipStreamSynchronize(g->stream), "group sync");
 }

@@ -11,21 +11,6 @@
 
 namespace nbi {
 
-hipEvent_t EventPool::next() {
-    if (used == ev.size()) {
-        hipEvent_t e;
-        ASSERT_HIP(hipEventCreate(&e), "event");
-        ev.push_back(e);
-    }
-    return ev[used++];
-}
-
-void EventPool::destroy() {
-    for (hipEvent_t e : ev) ASSERT_HIP(hipEventDestroy(e), "event");
-    ev.clear();
-    used = 0;
-}
-
 constexpr size_t GRAPH_CACHE_MAX = 8;     // cached chains per pipeline; the least recently used one is evicted
 // graph = 2 (auto): chains shorter than this stay plain launches.  A hipGraphLaunch costs the host ~12 us more than
 // a few plain launches and a replayed node saves 1-2 us, so a graph pays from a dozen steps on
@@ -65,22 +50,14 @@ nb::LaunchShape resolve_shape(SimPipeline *s) {
     if (s->sharded || passes != 1 || s->n_src > nb::LANE_SPLIT_MAX_SRC || s->n_src == 0) want.lanes = 1;   // never, not "auto"
     nb::LaunchShape sh = nb::choose_shape(want, s->n_real, (s->n_src + passes - 1) / passes, g_dev.compute_units);
     NB_ASSERT(nb::step_kernel_fn(sh) != nullptr, "no step kernel for k=%d w=%d variant=%d", sh.k, sh.w, sh.variant);
-    if (sh.split > 1) {
-        const size_t need = (size_t)sh.split * s->n_real;
-        if (need > s->parts_cap) {
-            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before growing the parts buffer");
-            dev_free(s->parts);
-            s->parts = dev_alloc<float2>(need);
-            s->parts_cap = (uint32_t)need;
-            if (!s->tickets) {
-                s->tickets_len = (uint32_t)((size_t)s->n_real / 64 + 2);
-                s->tickets = dev_alloc<uint32_t>(s->tickets_len);
-                zero_tickets(s);
-                ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after zeroing the tickets");
-            }
-            for (auto &g : s->graphs) destroy_graph(g);  // cached nodes point at the old buffer
-            s->graphs.clear();
+    if (sh.split > 1 && s->n_real > 0 && s->parts.grown(s->stream, (size_t)sh.split * s->n_real)) {
+        if (!s->tickets) {
+            s->tickets.alloc((size_t)s->n_real / 64 + 2);
+            zero_tickets(s);
+            ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after zeroing the tickets");
         }
+        for (auto &g : s->graphs) destroy_graph(g);  // cached nodes point at the old buffer
+        s->graphs.clear();
     }
     s->last_shape = sh;
     s->last_groups = nb::step_grid(sh, s->n_real).x * nb::step_grid(sh, s->n_real).y;
@@ -110,7 +87,7 @@ nb::StepParams whole_step(const SimPipeline *s, int in, float dt) {
 // N = 10 000 + 300 random shapes, 0 differences).  What it buys, and from which size on it is the default:
 // launch_shape.hip fused_finish_rule.
 bool fused_finish_applies(const SimPipeline *s, nb::LaunchShape sh) {
-    if (s->fused_finish == 0 || s->sharded || sh.split <= 1 || sh.lanes > 1 || s->tickets == nullptr) return false;
+    if (s->fused_finish == 0 || s->sharded || sh.split <= 1 || sh.lanes > 1 || !s->tickets) return false;
     if (nb::step_kernel_fused_fn(sh) == nullptr) return false;   // scalar-cache route, W >= 4
     return s->fused_finish == 1 || nb::fused_finish_rule(s->n_real, s->n_src);
 }
@@ -177,8 +154,7 @@ void launch_step(SimPipeline *s, nb::LaunchShape sh, const nb::StepParams &p, hi
 // survived) would leave non-zero tickets, and every later step would silently skip that tile's integration: so the tickets
 // are re-zeroed, in stream order, whenever a new state is uploaded and before a chain is built.
 void zero_tickets(SimPipeline *s) {
-    if (s->tickets && s->tickets_len)
-        ASSERT_HIP(hipMemsetAsync(s->tickets, 0, (size_t)s->tickets_len * sizeof(uint32_t), s->stream), "zero the tile tickets");
+    if (s->tickets) ASSERT_HIP(hipMemsetAsync(s->tickets, 0, s->tickets.count() * sizeof(uint32_t), s->stream), "zero the tile tickets");
 }
 
 // The step size of everything enqueued from here on.  Written in stream order, so steps already queued keep theirs.
@@ -387,8 +363,10 @@ void begin_call(SimPipeline *s) {
 }
 
 void end_call(SimPipeline *s, uint32_t launches) {
-    if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_end, s->stream), "record end");
-    s->timed = s->timing != 0;
+    if (s->timing)
+        s->step_iv.end(s->stream);
+    else
+        s->step_iv.clear();
     s->timed_launches = launches;
     s->timed_finish_launches = s->last_shape.split > 1 && !fused_finish_applies(s, s->last_shape) ? s->timed_launches : 0;
 }
@@ -400,7 +378,7 @@ void enqueue_steps(SimPipeline *s, uint32_t n, float dt) {
     begin_call(s);
     s->acc_current = false;   // an Euler step leaves the acc of the state before it
     upload_dt(s, dt);
-    if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_begin, s->stream), "record begin");
+    if (s->timing) s->step_iv.begin(s->stream);
     if (!s->sharded)
         enqueue_single(s, n, dt);
     else

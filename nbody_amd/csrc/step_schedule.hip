@@ -41,9 +41,7 @@ void check_leapfrog(const SimPipeline *s, uint32_t n, const char *what) {
 
 // the head and room for `log` step sizes; a regrow carries the head over (a continued call goes on from its records)
 void grow_adapt(SimPipeline *s, size_t log) {
-    if (s->adapt != nullptr && s->adapt_cap >= log) return;
-    s->adapt_cap = log < 64 ? 64 : log;
-    regrow_carrying(s->stream, s->adapt, ADAPT_HEAD + s->adapt_cap * sizeof(float), ADAPT_HEAD);
+    s->adapt.grown_carrying(s->stream, ADAPT_HEAD + (log < 64 ? 64 : log) * sizeof(float), ADAPT_HEAD);
 }
 
 // One world as the schedule's target.  The step word is dt_dev; the two kick words sit in the adaptive head.
@@ -82,14 +80,14 @@ struct PipelineTarget {
         nb::launch_leapfrog(s->stream, lf, close, open, 0);
     }
     void begin_mark() {
-        if (s->timing) ASSERT_HIP(hipEventRecord(s->ev_begin, s->stream), "record begin");
+        if (s->timing) s->step_iv.begin(s->stream);
     }
     void end_mark() { ASSERT_HIP(hipGetLastError(), "step launches (%u particles)", s->n_real); }
 };
 
 // One call of the schedule and every record it leaves: the only place these fields are set for a device-chosen or leapfrog call.
 void run_call(SimPipeline *s, Schedule c, const nb::TimestepParams &p, float *log) {
-    PipelineTarget t = {s, resolve_shape(s), p, log, reinterpret_cast<float *>(static_cast<char *>(s->adapt) + LEAPFROG_WORDS)};
+    PipelineTarget t = {s, resolve_shape(s), p, log, reinterpret_cast<float *>(s->adapt + LEAPFROG_WORDS)};
     if (c.leapfrog) s->lf_primed = !s->acc_current;
     run_schedule(t, c);
     if (c.leapfrog) s->lf_force_launches = t.forces;
@@ -105,7 +103,7 @@ void enqueue_adaptive(SimPipeline *s, uint32_t n, const NbAdaptive *cfg) {
     use_device();
     grow_adapt(s, n);
     begin_call(s);
-    char *head = static_cast<char *>(s->adapt);
+    char *head = s->adapt;
     nb::TimestepParams p = nb::timestep_params(s->acc, s->radius, s->n_real, 0, *cfg);
     p.state = reinterpret_cast<nb::AdaptState *>(head);
     p.commit = 1;
@@ -122,14 +120,14 @@ void enqueue_leapfrog(SimPipeline *s, uint32_t n, float dt) {
     use_device();
     grow_adapt(s, 0);
     begin_call(s);
-    nb::launch_set_scalar(s->stream, reinterpret_cast<float *>(static_cast<char *>(s->adapt) + LEAPFROG_WORDS), dt);
+    nb::launch_set_scalar(s->stream, reinterpret_cast<float *>(s->adapt + LEAPFROG_WORDS), dt);
     run_call(s, {n, true, false, false}, nb::TimestepParams{}, nullptr);
 }
 
 void enqueue_timestep_peek(SimPipeline *s, const NbAdaptive *cfg) {
     use_device();
     grow_adapt(s, 0);
-    char *head = static_cast<char *>(s->adapt);
+    char *head = s->adapt;
     nb::TimestepParams p = nb::timestep_params(s->acc, s->radius, s->n_real, 0, *cfg);
     p.state = reinterpret_cast<nb::AdaptState *>(head + sizeof(nb::AdaptState));
     p.dt_out = reinterpret_cast<float *>(head + 2 * sizeof(nb::AdaptState));
@@ -182,7 +180,7 @@ void nb_hip_timestep(SimPipeline *s, const NbAdaptive *cfg, float *dt) {
         return;
     }
     enqueue_timestep_peek(s, cfg);
-    ASSERT_HIP(hipMemcpyAsync(dt, static_cast<const char *>(s->adapt) + 2 * sizeof(nb::AdaptState), sizeof(float), hipMemcpyDeviceToHost,
+    ASSERT_HIP(hipMemcpyAsync(dt, s->adapt + 2 * sizeof(nb::AdaptState), sizeof(float), hipMemcpyDeviceToHost,
                               s->stream),
                "D2H of the step size");
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_timestep");

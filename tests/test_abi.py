@@ -107,6 +107,21 @@ def test_pipeline_create_destroy_needs_no_gpu():
     L.DestroySimPipeline(None)   # NULL accepted, reference sim_gpu.c:224
 
 
+def test_live_resources_are_even_across_create_destroy_without_a_gpu():
+    """nb_hip_live_resources counts what the owner types hold: an object that never reached the device takes nothing and
+    gives nothing back, and deleting it makes no HIP call (this runs with no device present)."""
+    L = nb.hip_lib()
+    base = nb.live_resources()
+    L.DestroySimPipeline(L.CreateSimPipeline(nb.WorldData(1000, 400, 0.0)))
+    assert nb.live_resources() == base
+    mass = (C.c_uint32 * 3)(120, 0, 250)
+    L.nb_hip_batch_destroy(L.nb_hip_batch_create(3, 250, mass))
+    assert nb.live_resources() == base
+    sizes, mass = (C.c_uint32 * 3)(100, 600, 2000), (C.c_uint32 * 3)(50, 300, 1000)   # one member per launch group
+    L.nb_hip_batch_destroy(L.nb_hip_ragged_create(3, sizes, mass))
+    assert nb.live_resources() == base
+
+
 @pytest.mark.parametrize("N,M,P", [(1 << 20, 523884, 8), (1 << 20, 523884, 2), (4096, 1989, 4), (333, 150, 8),
                                    (100, 0, 3), (100, 100, 3), (65, 1, 2), (0, 0, 2), (1 << 22, 2100000, 8)])
 def test_shard_plan_covers_everything_once(N, M, P):
