@@ -22,14 +22,15 @@
 // stride (the largest member rounded up to 64 rows), the AoS side of the seam is packed (member b at offsets[b]), and the
 // members fall into up to three launch GROUPS by their own size alone -- chain (N <= 512), lane-split (8, 8), lane-split
 // (16, 4) -- each with a device list of its member indices: one chain launch per call and one lane-split launch per group
-// and step (kernels.hip ragged_*_kernel, the same bodies with the receiver count read per member).  Member b's bits are
+// and step (the same kernels instantiated for RaggedParams: the receiver count read per member).  Member b's bits are
 // those of the same particles as the only member of a uniform SimBatch of its size.
 // The host has ONE representation and ONE launch walk for both: create() below makes every SimBatch with its groups -- a
 // uniform one has exactly one, of all members, without a device list -- and every fixed Euler step goes through
 // ensemble_walk.h's walk_ensemble with StepTarget as its target, so a uniform SimBatch launches exactly what it launched
-// before ragged ones existed.  `ragged` only picks the kernel family that addresses the members (batch_* by block index,
-// ragged_* through n_len and the lists): StepTarget, TraceTarget, split_members, merge_members, batch_observe.hip's
-// launch_potential, and materialize's upload of the tables the ragged family reads.
+// before ragged ones existed.  How a launch finds its members (by block index, or through n_len and the lists) is decided
+// on the device side of the seam (kernels.h, convert.h, batch_diag.h): every launch here hands over the tables, which a
+// uniform ensemble does not have.  `ragged` itself is read by materialize's upload of those tables, by create()'s lookup of
+// the lane-split kernel, by StepTarget::copy's assertion, and by the calls that are not wired for ragged ensembles.
 #include "batch_internal.h"
 #include "diag_sums.h"
 #include "ensemble_walk.h"
@@ -122,32 +123,28 @@ nb::BatchParams step_params(const SimBatch *s) {
     return p;
 }
 
-// What the launches of walk_ensemble are.  Each picks the kernel family: the uniform kernels take the BatchParams and index
-// the members by block, the ragged ones take it with the member sizes and the group's list.
+// What the launches of walk_ensemble are.  Every launch gets the full block: the BatchParams, the member sizes and the
+// group's list -- the last two null in a uniform ensemble, whose kernels read only the BatchParams at its head.
 struct StepTarget {
     SimBatch *s;
     nb::BatchParams p;   // step_params(s)
 
     nb::RaggedParams params(const SimBatch::Group &g, int in, int out, uint32_t steps) const {
         nb::RaggedParams rp = {p, s->n_len_dev, g.list};
-        rp.b.pos_in = s->pos[in];
-        rp.b.pos_out = s->pos[out];
-        rp.b.steps = steps;
-        rp.b.tiles = g.tiles;
+        rp.pos_in = s->pos[in];
+        rp.pos_out = s->pos[out];
+        rp.steps = steps;
+        rp.tiles = g.tiles;
         return rp;
     }
     void lanes(const SimBatch::Group &g, int in) {
         nb::RaggedParams rp = params(g, in, in ^ 1, 0);
-        void *args[] = {s->ragged ? (void *)&rp : (void *)&rp.b};
+        void *args[] = {&rp};   // g.fn takes the whole of it or its head
         ASSERT_HIP(hipLaunchKernel(g.fn, g.grid, g.block, args, g.lds, s->stream),
                    "ensemble lane-split launch (w=%d lanes=%d, %zu members of up to %u)", g.w, g.lanes, g.members.size(), g.max_n);
     }
     void chain(const SimBatch::Group &g, int buf, uint32_t steps) {
-        const nb::RaggedParams rp = params(g, buf, buf, steps);
-        if (s->ragged)
-            nb::launch_ragged_chain(s->stream, rp, (uint32_t)g.members.size());
-        else
-            nb::launch_batch_chain(s->stream, rp.b, s->count);
+        nb::launch_batch_chain(s->stream, params(g, buf, buf, steps), (uint32_t)g.members.size());
     }
     void copy(const SimBatch::Group &g, int from, int to) {
         NB_ASSERT(s->ragged, "a uniform ensemble is one group: its chain never meets a phase that moved");
@@ -158,14 +155,10 @@ struct StepTarget {
 
 // The chain that records from the state it holds in LDS: t.done carries the record index across the launches of a call.
 struct TraceTarget : StepTarget {
-    nb::BatchTraceParams t;
+    nb::TraceParams t;
 
     void chain(const SimBatch::Group &g, int buf, uint32_t steps) {
-        t.b = params(g, buf, buf, steps).b;
-        if (s->ragged)
-            nb::launch_ragged_trace_chain(s->stream, nb::RaggedTraceParams{t, s->n_len_dev, g.list}, (uint32_t)g.members.size());
-        else
-            nb::launch_batch_trace_chain(s->stream, t);
+        nb::launch_batch_trace_chain(s->stream, params(g, buf, buf, steps), t, (uint32_t)g.members.size());
         t.done += steps;
     }
 };
@@ -176,22 +169,16 @@ uint32_t launch_steps(SimBatch *s, const nb::BatchParams &p, uint32_t n) {
     return walk_ensemble(target, s->groups, s->cur, n, CHAIN_MAX_STEPS_PER_LAUNCH);
 }
 
-// the seam's converters, same pick: staged AoS records -> SoA rows of buffer 0 and G*m; the latest rows -> AoS records
+// the seam's converters: staged AoS records -> SoA rows of buffer 0 and G*m; the latest rows -> AoS records (the offsets
+// and member sizes on the device are null in a uniform ensemble, like the lists)
 void split_members(SimBatch *s) {
-    if (s->ragged)
-        nb::launch_ragged_split(s->stream, s->aos, s->offsets_dev, s->n_len_dev, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0],
-                                s->vel, s->acc, s->radius, s->mass, s->gm, NB_G);
-    else
-        nb::launch_batch_split(s->stream, s->aos, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0], s->vel, s->acc, s->radius,
-                               s->mass, s->gm, NB_G);
+    nb::launch_batch_split(s->stream, s->aos, s->offsets_dev, s->n_len_dev, s->mass_len_dev, s->count, s->n, s->stride, s->pos[0], s->vel,
+                           s->acc, s->radius, s->mass, s->gm, NB_G);
 }
 
 void merge_members(SimBatch *s, uint32_t first, uint32_t members) {
-    if (s->ragged)
-        nb::launch_ragged_merge(s->stream, s->aos, s->offsets_dev, s->n_len_dev, first, members, s->n, s->stride, s->pos[s->cur], s->vel,
-                                s->acc, s->radius, s->mass);
-    else
-        nb::launch_batch_merge(s->stream, s->aos, first, members, s->n, s->stride, s->pos[s->cur], s->vel, s->acc, s->radius, s->mass);
+    nb::launch_batch_merge(s->stream, s->aos, s->offsets_dev, s->n_len_dev, first, members, s->n, s->stride, s->pos[s->cur], s->vel, s->acc,
+                           s->radius, s->mass);
 }
 
 void enqueue(SimBatch *s, uint32_t n, const float *dt, bool uniform) {
@@ -392,7 +379,7 @@ SimBatch *create(SimBatch *s, const uint32_t *mass_len, bool ragged) {
         g.workgroups = (uint32_t)g.members.size();
         if (g.path) {
             const nb::LaunchShape sh = {.k = 1, .w = g.w, .variant = nb::VARIANT_LDS, .split = 1, .unit = 8, .lanes = g.lanes};
-            g.fn = ragged ? nb::ragged_lane_split_fn(g.w, g.lanes) : nb::batch_lane_split_fn(g.w, g.lanes);
+            g.fn = nb::batch_lane_split_fn(g.w, g.lanes, ragged);
             NB_ASSERT(g.lanes > 1 && g.fn != nullptr, "no ensemble kernel for w=%d lanes=%d", g.w, g.lanes);
             g.grid = nb::step_grid(sh, g.max_n);
             g.workgroups *= g.grid.x;

@@ -7,7 +7,7 @@
 
 namespace nbd {
 
-// The SoA arrays of a SimBatch: member b's rows start at b * stride.
+// The SoA arrays of a SimBatch: member b's rows start at b * stride.  Members are found by block index: each has n particles.
 struct EnsembleDiagParams {
     const float2 *pos;         // pos[cur]: the latest state
     const float2 *vel;
@@ -23,15 +23,21 @@ struct EnsembleDiagParams {
     double *slab;              // energy: [count][tiles][8]; else NULL
 };
 
+// The potential of a ragged ensemble: member b has n_len[b] particles (n = the largest member) and its values go to
+// phi + offsets[b]; both arrays on the device.  The kernel is one template over the two parameter types.
+struct RaggedDiagParams : EnsembleDiagParams {
+    const uint32_t *n_len;     // [count]
+    const uint64_t *offsets;   // [count]
+};
+
 uint32_t ensemble_tiles(uint32_t n);   // 128-receiver tiles of one member
-// Phi of every particle of every member (p.phi) or the per-tile energy rows of every member's M_b massive receivers (p.slab)
-void launch_ensemble_potential(hipStream_t stream, EnsembleDiagParams p, uint32_t count);
+// Phi of every particle of every member (p.phi) or the per-tile energy rows of every member's M_b massive receivers (p.slab).
+// With n_len (and offsets) the members are those of a ragged ensemble, p.phi only; the energy rows of a ragged ensemble are
+// launched without: they are sized by p.n = the largest member.
+void launch_ensemble_potential(hipStream_t stream, EnsembleDiagParams p, uint32_t count, const uint32_t *n_len = nullptr,
+                               const uint64_t *offsets = nullptr);
 // out[b][8] = member b's rows added in the fixed order of energy_reduce_kernel
 void launch_ensemble_reduce(hipStream_t stream, const double *slab, const uint32_t *mass_len, uint32_t tiles, uint32_t count,
                             double *out);
-
-// ragged ensembles (ragged_diag.hip): Phi of member b's n_len[b] particles to p.phi + offsets[b]; p.n = the largest
-// member, n_len and offsets on the device.  The energy rows of a ragged ensemble are launch_ensemble_potential's.
-void launch_ragged_potential(hipStream_t stream, EnsembleDiagParams p, uint32_t count, const uint32_t *n_len, const uint64_t *offsets);
 
 }  // namespace nbd

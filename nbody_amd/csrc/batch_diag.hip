@@ -19,8 +19,16 @@
 // half = 64, 32, .. 1, dead lanes 0 -- where the first level adds the lane's own two receivers and the other six move
 // through the cross-lane network; lane 0 stores the row.  ensemble_reduce_kernel, one workgroup per member, then adds the
 // member's ceil(M_b / 128) rows exactly as energy_reduce_kernel does.  No float atomics, vector stores only.
+//
+// A RAGGED ensemble (members of different N) needs nothing new for its energy sums: they run over a member's mass_len[b]
+// massive receivers, read from the device already, and the slab rows only have to be sized by the largest member.  Its
+// potential runs over ALL of a member's particles and is stored packed, so the receiver count and the output offset are per
+// member: ensemble_phi_kernel<RaggedDiagParams> reads both from device arrays and is otherwise the same statements, so
+// member b's values are the bits nb_hip_ensemble_potential gives the same particles in a uniform ensemble.
 #include "batch_diag.h"
 #include "diag_common.h"
+
+#include <type_traits>
 
 namespace nbd {
 namespace {
@@ -32,13 +40,24 @@ __device__ __forceinline__ T uniform_load(const T *p) {   // wave-uniform addres
     return *(const T __attribute__((address_space(4))) *)(uintptr_t)p;
 }
 
-__global__ __launch_bounds__(WAVE * WAVES_MAX) void ensemble_phi_kernel(const EnsembleDiagParams p) {
+// One body for both ways of addressing the members (batch_diag.h; the step kernels' member_of, kernels.hip, mirrored).
+// What depends on it is how many receivers member b has in this launch and where its potentials start in p.phi: by block
+// index p.n and b * p.n, by list (LISTED) both read from the device.  LISTED computes the potential only: nothing of the
+// slab is compiled into it.  (The two answers are spelled in the body, not in functions of p: a reference to the
+// by-value kernel argument costs the stores of the slab rows their global address space.)
+template <class P>
+__global__ __launch_bounds__(WAVE * WAVES_MAX) void ensemble_phi_kernel(const P p) {
+    constexpr bool LISTED = std::is_same_v<P, RaggedDiagParams>;
     const uint32_t lane = threadIdx.x & (WAVE - 1);
     const uint32_t wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t member = blockIdx.y;
     const uint32_t tile = blockIdx.x * p.waves + wid;
     const uint32_t n_src = uniform_load(p.mass_len + member);
-    const uint32_t n_recv = p.slab ? n_src : p.n;   // the energy sums run over the massive receivers only
+    uint32_t n_recv;
+    if constexpr (LISTED)
+        n_recv = uniform_load(p.n_len + member);
+    else
+        n_recv = p.slab ? n_src : p.n;   // the energy sums run over the massive receivers only
     const uint32_t rb = tile * TILE;                // first receiver of this wave's tile, member-local
     if (rb >= n_recv) return;
     const size_t base = (size_t)member * p.stride;
@@ -62,23 +81,28 @@ __global__ __launch_bounds__(WAVE * WAVES_MAX) void ensemble_phi_kernel(const En
     tile_potential(sum, px, py, r, ri, rb, n_src, ScalarSources{(ConstF)(uintptr_t)pos, (ConstF)(uintptr_t)(p.gm + base)});
 
     // Phi_i = -sum; the eight terms of the lane's two receivers (tile rows lane and lane + 64)
+    size_t packed_at = 0;
+    if constexpr (LISTED) packed_at = uniform_load(p.offsets + member);
     double e[K][QTY];
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const double phi = -sum[k];
         const uint32_t i = rb + k * WAVE + lane;
         const bool live = i < n_recv;
-        if (live && p.phi) p.phi[(size_t)member * p.n + i] = (float)phi;
-        if (p.slab) energy_terms(e[k], live, phi, p.mass + base, pos, p.vel + base, i);
+        if (live && (LISTED || p.phi)) p.phi[(LISTED ? packed_at : (size_t)member * p.n) + i] = (float)phi;
+        if constexpr (!LISTED)
+            if (p.slab) energy_terms(e[k], live, phi, p.mass + base, pos, p.vel + base, i);
     }
-    if (!p.slab) return;
-    // potential_kernel's tree over the 128 rows of the tile: half = 64 is rows lane and lane + 64, the rest crosses lanes
-    double t[QTY];
-    tile_tree(t, e);
-    if (lane == 0) {
-        double *row = p.slab + ((size_t)member * p.tiles + tile) * QTY;
+    if constexpr (!LISTED) {
+        if (!p.slab) return;
+        // potential_kernel's tree over the 128 rows of the tile: half = 64 is rows lane and lane + 64, the rest crosses lanes
+        double t[QTY];
+        tile_tree(t, e);
+        if (lane == 0) {
+            double *row = p.slab + ((size_t)member * p.tiles + tile) * QTY;
 #pragma unroll
-        for (int q = 0; q < QTY; q++) row[q] = t[q];
+            for (int q = 0; q < QTY; q++) row[q] = t[q];
+        }
     }
 }
 
@@ -95,11 +119,16 @@ __global__ __launch_bounds__(REDUCE_THREADS) void ensemble_reduce_kernel(const d
 
 uint32_t ensemble_tiles(uint32_t n) { return (n + TILE - 1) / TILE; }
 
-void launch_ensemble_potential(hipStream_t stream, EnsembleDiagParams p, uint32_t count) {
+void launch_ensemble_potential(hipStream_t stream, EnsembleDiagParams p, uint32_t count, const uint32_t *n_len, const uint64_t *offsets) {
     p.tiles = ensemble_tiles(p.n);
     p.waves = p.tiles < (uint32_t)WAVES_MAX ? p.tiles : (uint32_t)WAVES_MAX;
     const dim3 grid((p.tiles + p.waves - 1) / p.waves, count);
-    hipLaunchKernelGGL(ensemble_phi_kernel, grid, dim3(WAVE * p.waves), 0, stream, p);
+    if (n_len) {
+        const RaggedDiagParams rp = {p, n_len, offsets};
+        hipLaunchKernelGGL(ensemble_phi_kernel<RaggedDiagParams>, grid, dim3(WAVE * p.waves), 0, stream, rp);
+    } else {
+        hipLaunchKernelGGL(ensemble_phi_kernel<EnsembleDiagParams>, grid, dim3(WAVE * p.waves), 0, stream, p);
+    }
 }
 
 void launch_ensemble_reduce(hipStream_t stream, const double *slab, const uint32_t *mass_len, uint32_t tiles, uint32_t count,

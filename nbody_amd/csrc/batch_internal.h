@@ -34,8 +34,8 @@ struct SimBatch {
     int cur = 0;           // pos[cur] is the latest state (the chain path never moves it)
 
     // The launch shape, fixed at creation: the launch groups, in the order chain, lane-split (8, 8), lane-split (16, 4); those
-    // without members are absent.  A uniform ensemble is one group of all members.  `ragged` says only which kernel family
-    // addresses the members: by block index, or through n_len_dev and the groups' lists.
+    // without members are absent.  A uniform ensemble is one group of all members.  `ragged` says only how the launches
+    // find the members: by block index, or through n_len_dev and the groups' lists (null in a uniform ensemble).
     struct Group {
         int path = 0, k = 2, w = 16, lanes = 1;   // path: 0 chain, 1 lane-split; chain: w of the group's largest member
         uint32_t tiles = 0;                       // chain: chain_tiles(max_n)

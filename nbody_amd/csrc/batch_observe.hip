@@ -1,5 +1,5 @@
-// batch_observe.hip -- the read-only calls on a SimBatch: energy and potential of every member (kernels: batch_diag.hip,
-// ragged_diag.hip), bounds, count images and frames (kernels: batch_render.hip), with their tuning hooks and timers.  Each
+// batch_observe.hip -- the read-only calls on a SimBatch: energy and potential of every member (kernels: batch_diag.hip),
+// bounds, count images and frames (kernels: batch_render.hip), with their tuning hooks and timers.  Each
 // looks at the latest state without reading the particles back: a constant number of launches, one copy, one sync for any B.
 #include "batch_internal.h"
 #include "batch_diag.h"
@@ -36,14 +36,6 @@ nbd::EnsembleDiagParams diag_params(const SimBatch *s) {   // of the latest stat
     p.n = s->n;
     p.stride = s->stride;
     return p;
-}
-
-// Phi of every particle to p.phi, packed member after member: the pick of the kernel family, as batch.hip's StepTarget makes it
-void launch_potential(SimBatch *s, const nbd::EnsembleDiagParams &p) {
-    if (s->ragged)
-        nbd::launch_ragged_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
-    else
-        nbd::launch_ensemble_potential(s->stream, p, s->count);
 }
 
 }  // namespace
@@ -149,7 +141,8 @@ void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
     const size_t total = (size_t)s->offsets[s->count];
     s->diag_phi.grown(s->stream, total);
     p.phi = s->diag_phi;
-    launch_potential(s, p);
+    // packed member after member; the member sizes and offsets on the device are null in a uniform ensemble
+    nbd::launch_ensemble_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
     ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
     s->diag_iv.end(s->stream);
     ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u members' potentials",

@@ -7,23 +7,18 @@
 
 namespace nb {
 
-// whole-ensemble converters: member-major AoS [count][n] <-> SoA [count][stride]; split also writes G*m
-void launch_batch_split(hipStream_t st, const void *aos, const uint32_t *mass_len, uint32_t count, uint32_t n, uint32_t stride,
-                        float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g);
-void launch_batch_merge(hipStream_t st, void *aos, uint32_t first, uint32_t count, uint32_t n, uint32_t stride, const float2 *pos,
-                        const float2 *vel, const float2 *acc, const float *radius, const float *mass);
+// whole-ensemble converters: member-major AoS <-> SoA [count][stride] (member b's rows at b * stride); split also writes
+// G*m.  Without n_len every member has n records, member b's at aos[b * n]; with it (a ragged ensemble) member b's
+// n_len[b] records sit packed at aos[offsets[b]] and n is the largest member.  offsets, n_len and mass_len are device arrays.
+void launch_batch_split(hipStream_t st, const void *aos, const uint64_t *offsets, const uint32_t *n_len, const uint32_t *mass_len,
+                        uint32_t count, uint32_t n, uint32_t stride, float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass,
+                        float *gm, float g);
+void launch_batch_merge(hipStream_t st, void *aos, const uint64_t *offsets, const uint32_t *n_len, uint32_t first, uint32_t count,
+                        uint32_t n, uint32_t stride, const float2 *pos, const float2 *vel, const float2 *acc, const float *radius,
+                        const float *mass);
 void launch_batch_fill(hipStream_t st, float *dst, uint32_t count, float value);   // dst[0 .. count) = value, in stream order
 
-// ragged ensembles: member b's n_len[b] records sit packed at aos[offsets[b]], its SoA rows at b * stride; offsets, n_len
-// and mass_len are device arrays, max_n = the largest member.  split is two launches: the records (gm = the sources'
-// masses), then launch_make_gm in place -- the G*m rounding stays written once.
-void launch_ragged_split(hipStream_t st, const void *aos, const uint64_t *offsets, const uint32_t *n_len, const uint32_t *mass_len,
-                         uint32_t count, uint32_t max_n, uint32_t stride, float2 *pos, float2 *vel, float2 *acc, float *radius,
-                         float *mass, float *gm, float g);
-void launch_ragged_merge(hipStream_t st, void *aos, const uint64_t *offsets, const uint32_t *n_len, uint32_t first, uint32_t count,
-                         uint32_t max_n, uint32_t stride, const float2 *pos, const float2 *vel, const float2 *acc,
-                         const float *radius, const float *mass);
-// to[rows of members[0 .. count)] = from[the same rows]: position rows across the two ping-pong buffers
+// ragged ensembles: to[rows of members[0 .. count)] = from[the same rows]: position rows across the two ping-pong buffers
 void launch_ragged_copy_rows(hipStream_t st, const uint32_t *members, const uint32_t *n_len, uint32_t count, uint32_t max_n,
                              uint32_t stride, const float2 *from, float2 *to);
 

@@ -92,45 +92,47 @@ __global__ void split_sources_kernel(const ParticleRec *aos, uint32_t mass_len, 
     gm[i] = g_times_m(s.mass, g);
 }
 
+// Where member b's AoS records are and how many it has: all that the converters of a uniform and of a ragged ensemble
+// differ in (the step kernels' member_of, kernels.hip, mirrored).  Each converter is one template over the two.
+struct UniformRecords {   // every member has n records, member b's at b * n
+    uint32_t n;
+};
+
+struct RaggedRecords {    // member b has n_len[b] records, packed at offsets[b]; both arrays on the device
+    const uint64_t *offsets;
+    const uint32_t *n_len;
+};
+
+struct Records {
+    uint32_t n;
+    size_t first;
+};
+
+__device__ __forceinline__ Records records_of(const UniformRecords &u, uint32_t b) { return {u.n, (size_t)b * u.n}; }
+__device__ __forceinline__ Records records_of(const RaggedRecords &r, uint32_t b) { return {r.n_len[b], r.offsets[b]}; }
+
 // Ensemble upload: member blockIdx.y's AoS records into its SoA rows, and G*m of its sources (rows past mass_len[b]
 // hold no source and get 0).  One launch for the whole ensemble.
-__global__ void batch_split_kernel(const ParticleRec *aos, const uint32_t *mass_len, uint32_t n, uint32_t stride, float2 *pos,
+template <class A>
+__global__ void batch_split_kernel(const ParticleRec *aos, const uint32_t *mass_len, const A where, uint32_t stride, float2 *pos,
                                    float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (i >= n) return;
-    const Soa s = unpack(aos[(size_t)b * n + i]);
+    const Records rec = records_of(where, b);
+    if (i >= rec.n) return;
+    const Soa s = unpack(aos[rec.first + i]);
     const size_t o = (size_t)b * stride + i;
     store_soa(s, o, pos, vel, acc, radius, mass);
     gm[o] = i < mass_len[b] ? g_times_m(s.mass, g) : 0.0f;
 }
 
 // Ensemble read-back: members [first, first + gridDim.y) back into their AoS records.
-__global__ void batch_merge_kernel(ParticleRec *aos, uint32_t first, uint32_t n, uint32_t stride, const float2 *pos,
+template <class A>
+__global__ void batch_merge_kernel(ParticleRec *aos, uint32_t first, const A where, uint32_t stride, const float2 *pos,
                                    const float2 *vel, const float2 *acc, const float *radius, const float *mass) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = first + blockIdx.y;
-    if (i >= n) return;
-    aos[(size_t)b * n + i] = pack(load_soa((size_t)b * stride + i, pos, vel, acc, radius, mass));
-}
-
-// Ragged ensemble upload: member blockIdx.y's n_len[b] records, packed at offsets[b], into its SoA rows.  gm receives
-// the MASS of the member's sources (0 in rows that are none); make_gm_kernel over the same array then turns it into G*m
-// with the one rounding rule, so a source's G*m has the bits batch_split_kernel gives it.
-__global__ void ragged_split_kernel(const ParticleRec *aos, const uint64_t *offsets, const uint32_t *n_len, const uint32_t *mass_len,
-                                    uint32_t stride, float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (i >= n_len[b]) return;
-    const Soa s = unpack(aos[offsets[b] + i]);
-    const size_t o = (size_t)b * stride + i;
-    store_soa(s, o, pos, vel, acc, radius, mass);
-    gm[o] = i < mass_len[b] ? s.mass : 0.0f;
-}
-
-// Ragged ensemble read-back: members [first, first + gridDim.y) back into their packed AoS records.
-__global__ void ragged_merge_kernel(ParticleRec *aos, const uint64_t *offsets, const uint32_t *n_len, uint32_t first, uint32_t stride,
-                                    const float2 *pos, const float2 *vel, const float2 *acc, const float *radius, const float *mass) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, b = first + blockIdx.y;
-    if (i >= n_len[b]) return;
-    aos[offsets[b] + i] = pack(load_soa((size_t)b * stride + i, pos, vel, acc, radius, mass));
+    const Records rec = records_of(where, b);
+    if (i >= rec.n) return;
+    aos[rec.first + i] = pack(load_soa((size_t)b * stride + i, pos, vel, acc, radius, mass));
 }
 
 // The position rows of the listed members from one ping-pong buffer to the other (ragged ensembles: the chain group's
@@ -146,36 +148,38 @@ inline dim3 grid1d(uint32_t count, uint32_t rows = 1) { return dim3((count + 255
 
 }  // namespace
 
-void launch_ragged_split(hipStream_t st, const void *aos, const uint64_t *offsets, const uint32_t *n_len, const uint32_t *mass_len,
-                         uint32_t count, uint32_t max_n, uint32_t stride, float2 *pos, float2 *vel, float2 *acc, float *radius,
-                         float *mass, float *gm, float g) {
-    hipLaunchKernelGGL(ragged_split_kernel, grid1d(max_n, count), dim3(256), 0, st, static_cast<const ParticleRec *>(aos), offsets,
-                       n_len, mass_len, stride, pos, vel, acc, radius, mass, gm);
-    launch_make_gm(st, gm, gm, count * stride, g);   // in place: every thread reads and writes its own row
-}
-
-void launch_ragged_merge(hipStream_t st, void *aos, const uint64_t *offsets, const uint32_t *n_len, uint32_t first, uint32_t count,
-                         uint32_t max_n, uint32_t stride, const float2 *pos, const float2 *vel, const float2 *acc,
-                         const float *radius, const float *mass) {
-    if (count) hipLaunchKernelGGL(ragged_merge_kernel, grid1d(max_n, count), dim3(256), 0, st, static_cast<ParticleRec *>(aos), offsets,
-                       n_len, first, stride, pos, vel, acc, radius, mass);
-}
-
 void launch_ragged_copy_rows(hipStream_t st, const uint32_t *members, const uint32_t *n_len, uint32_t count, uint32_t max_n,
                              uint32_t stride, const float2 *from, float2 *to) {
     if (count) hipLaunchKernelGGL(ragged_copy_rows_kernel, grid1d(max_n, count), dim3(256), 0, st, members, n_len, stride, from, to);
 }
 
-void launch_batch_split(hipStream_t st, const void *aos, const uint32_t *mass_len, uint32_t count, uint32_t n, uint32_t stride,
-                        float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass, float *gm, float g) {
-    hipLaunchKernelGGL(batch_split_kernel, grid1d(n, count), dim3(256), 0, st, static_cast<const ParticleRec *>(aos),
-                       mass_len, n, stride, pos, vel, acc, radius, mass, gm, g);
+void launch_batch_split(hipStream_t st, const void *aos, const uint64_t *offsets, const uint32_t *n_len, const uint32_t *mass_len,
+                        uint32_t count, uint32_t n, uint32_t stride, float2 *pos, float2 *vel, float2 *acc, float *radius, float *mass,
+                        float *gm, float g) {
+    const ParticleRec *recs = static_cast<const ParticleRec *>(aos);
+    const UniformRecords uniform = {n};
+    const RaggedRecords ragged = {offsets, n_len};
+    if (n_len)
+        hipLaunchKernelGGL(batch_split_kernel<RaggedRecords>, grid1d(n, count), dim3(256), 0, st, recs, mass_len, ragged, stride, pos, vel,
+                           acc, radius, mass, gm, g);
+    else
+        hipLaunchKernelGGL(batch_split_kernel<UniformRecords>, grid1d(n, count), dim3(256), 0, st, recs, mass_len, uniform, stride, pos,
+                           vel, acc, radius, mass, gm, g);
 }
 
-void launch_batch_merge(hipStream_t st, void *aos, uint32_t first, uint32_t count, uint32_t n, uint32_t stride, const float2 *pos,
-                        const float2 *vel, const float2 *acc, const float *radius, const float *mass) {
-    if (count) hipLaunchKernelGGL(batch_merge_kernel, grid1d(n, count), dim3(256), 0, st, static_cast<ParticleRec *>(aos), first, n,
-                       stride, pos, vel, acc, radius, mass);
+void launch_batch_merge(hipStream_t st, void *aos, const uint64_t *offsets, const uint32_t *n_len, uint32_t first, uint32_t count,
+                        uint32_t n, uint32_t stride, const float2 *pos, const float2 *vel, const float2 *acc, const float *radius,
+                        const float *mass) {
+    if (count == 0) return;
+    ParticleRec *recs = static_cast<ParticleRec *>(aos);
+    const UniformRecords uniform = {n};
+    const RaggedRecords ragged = {offsets, n_len};
+    if (n_len)
+        hipLaunchKernelGGL(batch_merge_kernel<RaggedRecords>, grid1d(n, count), dim3(256), 0, st, recs, first, ragged, stride, pos, vel, acc,
+                           radius, mass);
+    else
+        hipLaunchKernelGGL(batch_merge_kernel<UniformRecords>, grid1d(n, count), dim3(256), 0, st, recs, first, uniform, stride, pos, vel,
+                           acc, radius, mass);
 }
 
 void launch_batch_fill(hipStream_t st, float *dst, uint32_t count, float value) {

@@ -95,10 +95,17 @@ struct ChainParams {
 constexpr uint32_t CHAIN_K = 2;            // receivers per lane of the chain
 constexpr uint32_t CHAIN_MAX_RECV = 512;   // 4 tiles of 128 receivers (K = 2)
 
-// An ensemble of `count` independent worlds with the same particle count, stepped by one launch (batch_chain_kernel: one
-// workgroup per member runs the whole chain; batch_lane_split_kernel: gridDim.y = count, one launch per step).  Member-major
-// SoA: every array is [count][stride], stride >= n_recv and a multiple of 64, so each member's rows stay 256-byte aligned.
+// An ensemble of `count` independent worlds stepped by one launch (batch_chain_kernel: one workgroup per member runs the
+// whole chain; batch_lane_split_kernel: gridDim.y = members, one launch per step).  Member-major SoA: every array is
+// [count][stride], stride >= the largest member and a multiple of 64, so each member's rows stay 256-byte aligned.
 // Member b's sources are its first mass_len[b] particles; its step size is dt[b].  Both are read from device memory.
+//
+// A launch finds its member in one of two ways, and the parameter type says which (kernels.hip member_of):
+//   BatchParams    by block index: workgroup g steps member g, every member has n_recv particles;
+//   RaggedParams   by list: workgroup g steps member members[g] of n_len[members[g]] particles -- a ragged ensemble, whose
+//                  launch covers one GROUP of members that share a launch shape.  n_recv and tiles are not read: both
+//                  come from n_len, so a member's shape is a function of its own size alone.
+// Each ensemble kernel is one template over the two; nothing else of a kernel depends on the addressing.
 struct BatchParams {
     float2 *pos_in;       // state before the step (chain: before the call, updated in place)
     float2 *pos_out;      // lane-split: state after the step; chain: unused
@@ -114,35 +121,22 @@ struct BatchParams {
     uint32_t tiles;       // chain only: chain_tiles(n_recv)
 };
 
-// A traced ensemble chain (batch_trace_chain_kernel): the steps of BatchParams, and every `every`-th step of the CALL
-// the member's eight float64 energy sums (diag_sums.h order, the bits of ensemble_phi_kernel + ensemble_reduce_kernel for
-// that state) go to rows[record][member][8].  A call longer than one launch carries its record index across launches
-// through `done`; the launch with done = 0 also records the state on entry (record 0), and may have steps = 0.
-struct BatchTraceParams {
-    BatchParams b;
-    const float *mass;    // [count][stride], like gm
-    double *rows;         // [records][count][8]
-    uint32_t count;       // members (the row pitch)
-    uint32_t every;       // >= 1
-    uint32_t done;        // steps of this call that earlier launches ran
-};
-
-// A ragged ensemble: the members differ in their particle counts.  The arrays keep ONE stride (the largest member rounded
-// up to 64 rows), member m holds n_len[m] particles in its first rows, and a launch covers one GROUP of members that
-// share a launch shape: workgroup (chain: blockIdx.x, lane-split: blockIdx.y) g steps member members[g].  b.n_recv and
-// b.tiles are not read: both come from n_len[m], so a member's shape is a function of its own size alone.
-struct RaggedParams {
-    BatchParams b;
+struct RaggedParams : BatchParams {
     const uint32_t *n_len;     // [count] particles per member
     const uint32_t *members;   // [workgroups of the group] member indices
 };
 
-// The traced chain of a ragged ensemble whose members all fit the chain: rows are addressed by the member's own index,
-// so t.count stays the row pitch (the ensemble's member count).
-struct RaggedTraceParams {
-    BatchTraceParams t;
-    const uint32_t *n_len;
-    const uint32_t *members;
+// What a traced ensemble chain (batch_trace_chain_kernel) takes besides its steps: every `every`-th step of the CALL the
+// member's eight float64 energy sums (diag_sums.h order, the bits of ensemble_phi_kernel + ensemble_reduce_kernel for that
+// state) go to rows[record][member][8], whichever way the launch finds its members.  A call longer than one launch carries
+// its record index across launches through `done`; the launch with done = 0 also records the state on entry (record 0), and
+// may have steps = 0.
+struct TraceParams {
+    const float *mass;    // [count][stride], like gm
+    double *rows;         // [records][count][8]
+    uint32_t count;       // members of the ensemble (the row pitch)
+    uint32_t every;       // >= 1
+    uint32_t done;        // steps of this call that earlier launches ran
 };
 
 constexpr int MAX_SPLIT = 16;
@@ -158,14 +152,12 @@ const void *finish_kernel_fn();
 // the one-workgroup chain: 1024 threads, one block; tiles from chain_tiles(n_recv)
 void launch_chain(hipStream_t st, const ChainParams &p);
 
-// ensembles: the kernel of a lane-split shape (nullptr when not instantiated), and the chain launch
-const void *batch_lane_split_fn(int w, int lanes);
-void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count);
-void launch_batch_trace_chain(hipStream_t st, const BatchTraceParams &p);
-
-// ragged ensembles: one launch per group of `members` members
-const void *ragged_lane_split_fn(int w, int lanes);
-void launch_ragged_chain(hipStream_t st, const RaggedParams &p, uint32_t members);
-void launch_ragged_trace_chain(hipStream_t st, const RaggedTraceParams &p, uint32_t members);
+// ensembles: the kernel of a lane-split shape (nullptr when not instantiated; `listed`: the RaggedParams instantiation), and
+// the chain launches of `workgroups` members.  Both take the full block and pick the instantiation themselves: by list
+// when p.members is set, else by block index (a kernel argument that points at a RaggedParams serves either way: the
+// BatchParams is its head).
+const void *batch_lane_split_fn(int w, int lanes, bool listed);
+void launch_batch_chain(hipStream_t st, const RaggedParams &p, uint32_t workgroups);
+void launch_batch_trace_chain(hipStream_t st, const RaggedParams &p, const TraceParams &t, uint32_t workgroups);
 
 }  // namespace nb

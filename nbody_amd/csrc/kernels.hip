@@ -38,6 +38,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace nb {
 namespace {
 
@@ -859,110 +861,81 @@ __device__ __forceinline__ void chain_body(const ChainParams &p, const ChainTrac
 
 __global__ __launch_bounds__(1024) void chain_kernel(const ChainParams p) { chain_body<false>(p, ChainTrace{}); }
 
-// ---- world ensembles: B independent worlds of the same N in one launch -------------------------------------------
+// ---- world ensembles: B independent worlds, of one N or of different ones, in one launch ---------------------------
 //
 // A single world of N <= 3 000 keeps one (chain) or a handful (lane-split) of the chip's 256 compute units busy; the
-// others can only be used by MORE WORLDS.  The two kernels below run the bodies above once per member: nothing is
+// others can only be used by MORE WORLDS.  The kernels below run the bodies above once per member: nothing is
 // copied, so member b's bits are those of the same world alone in chain_kernel / lane_split_kernel<W, H>, whatever B,
 // its index or its neighbours are.  Layout: member-major SoA, every array [B][stride]; a member's source count and step
 // size come from device memory (mass_len[b], dt[b]), so neither is baked into a launch.
+//
+// A launch finds its members by block index or through a list (kernels.h BatchParams / RaggedParams), and that is ALL the
+// two differ in: which member a workgroup steps, how many particles the member has, and how many chain tiles those make.
+// member_of answers the three once per parameter type and every kernel below is one template over it.  By list, a launch
+// covers one group of a ragged ensemble -- the chain group (N <= 512) or one of the two lane-split shapes; everything a
+// body branches on (n_recv, tiles, n_src) stays wave-uniform, so member m runs the instructions and the summation order of
+// the same particles as the only member of a uniform ensemble of its size.
 __device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
-__device__ __forceinline__ ChainParams member_chain(const BatchParams &bp) {   // member blockIdx.x of an ensemble
-    const size_t base = (size_t)blockIdx.x * bp.stride;
+struct Member {
+    uint32_t index, n, tiles;   // tiles: of the chain (chain_tiles(n), n <= CHAIN_MAX_RECV)
+};
+
+// `block`: the workgroup's index among the launch's members (chain: blockIdx.x, lane-split: blockIdx.y)
+__device__ __forceinline__ Member member_of(const BatchParams &bp, uint32_t block) { return {block, bp.n_recv, bp.tiles}; }
+
+__device__ __forceinline__ Member member_of(const RaggedParams &rp, uint32_t block) {
+    const uint32_t index = uniform_u32(rp.members[block]);
+    const uint32_t n = uniform_u32(rp.n_len[index]);
+    return {index, n, n <= WAVE * CHAIN_K ? 1u : n <= 2 * WAVE * CHAIN_K ? 2u : 4u};
+}
+
+__device__ __forceinline__ ChainParams member_chain(const BatchParams &bp, const Member &m) {
+    const size_t base = (size_t)m.index * bp.stride;
     ChainParams p;
     p.pos = bp.pos_in + base;   // updated in place, like the single chain
     p.vel = bp.vel + base;
     p.acc = bp.acc + base;
     p.radius = bp.radius + base;
     p.src_gm = bp.gm + base;
-    p.n_recv = bp.n_recv;
-    p.n_src = uniform_u32(bp.mass_len[blockIdx.x]);
+    p.n_recv = m.n;
+    p.n_src = uniform_u32(bp.mass_len[m.index]);
     p.steps = bp.steps;
-    p.tiles = bp.tiles;
-    p.dt = bp.dt + blockIdx.x;
+    p.tiles = m.tiles;
+    p.dt = bp.dt + m.index;
     return p;
 }
 
-__global__ __launch_bounds__(1024) void batch_chain_kernel(const BatchParams bp) {
-    chain_body<false>(member_chain(bp), ChainTrace{});
+template <class P>
+__global__ __launch_bounds__(1024) void batch_chain_kernel(const P bp) {
+    chain_body<false>(member_chain(bp, member_of(bp, blockIdx.x)), ChainTrace{});
 }
 
-// (not a "batch_chain_kernel" by name: tests/test_batch_cpu.py counts those)
-__global__ __launch_bounds__(1024) void batch_trace_chain_kernel(const BatchTraceParams tp) {
-    const uint32_t member = blockIdx.x;
+template <class P>
+__global__ __launch_bounds__(1024) void batch_trace_chain_kernel(const P bp, const TraceParams tp) {
+    const Member m = member_of(bp, blockIdx.x);
     ChainTrace tr;
-    tr.mass = tp.mass + (size_t)member * tp.b.stride;
+    tr.mass = tp.mass + (size_t)m.index * bp.stride;
     tr.pitch = (size_t)tp.count * nbd::QTY;
     tr.entry = tp.done == 0;
     tr.every = tp.every;
     tr.until = tp.every - tp.done % tp.every;
-    // records made before this launch: the one on entry and one per `every` steps done
-    tr.row = tp.rows + ((size_t)(tp.done == 0 ? 0u : 1u + tp.done / tp.every) * tp.count + member) * nbd::QTY;
-    chain_body<true>(member_chain(tp.b), tr);
+    // records made before this launch: the one on entry and one per `every` steps done; a row is the member's own index
+    tr.row = tp.rows + ((size_t)(tp.done == 0 ? 0u : 1u + tp.done / tp.every) * tp.count + m.index) * nbd::QTY;
+    chain_body<true>(member_chain(bp, m), tr);
 }
 
-template <int W, int H>
-__global__ __launch_bounds__(WAVE *W) void batch_lane_split_kernel(const BatchParams bp) {
-    const size_t base = (size_t)blockIdx.y * bp.stride;
+template <int W, int H, class P>
+__global__ __launch_bounds__(WAVE *W) void batch_lane_split_kernel(const P bp) {
+    const Member m = member_of(bp, blockIdx.y);
+    // By list, gridDim.x covers the group's largest member: the workgroups past a smaller member's last receiver leave before
+    // the first barrier (blockIdx and n are uniform over the workgroup, so all of it leaves).
+    if constexpr (std::is_same_v<P, RaggedParams>)
+        if (blockIdx.x * (WAVE / H) >= m.n) return;
+    const size_t base = (size_t)m.index * bp.stride;
     // the first mass_len[b] receivers of a member ARE its sources
-    const StepParams p = plain_step(bp.pos_in + base, bp.gm + base, uniform_u32(bp.mass_len[blockIdx.y]), bp.pos_in + base,
-                                    bp.pos_out + base, bp.vel + base, bp.acc + base, bp.radius + base, bp.n_recv,
-                                    bp.dt + blockIdx.y, 8);
-    lane_split_body<W, H>(p);
-}
-
-// ---- ragged ensembles: members of different N in one launch ---------------------------------------------------------
-//
-// The same bodies once more, with the receiver count read per member (kernels.h RaggedParams): a launch covers one group
-// of members -- the chain group (N <= 512) or one of the two lane-split shapes -- and finds its member through the
-// group's list.  Everything a body branches on (n_recv, tiles, n_src) is wave-uniform, so member m runs the instructions
-// and the summation order of the same particles as the only member of a uniform ensemble of its size.
-__device__ __forceinline__ ChainParams ragged_member_chain(const BatchParams &bp, uint32_t member, uint32_t n) {
-    const size_t base = (size_t)member * bp.stride;
-    ChainParams p;
-    p.pos = bp.pos_in + base;
-    p.vel = bp.vel + base;
-    p.acc = bp.acc + base;
-    p.radius = bp.radius + base;
-    p.src_gm = bp.gm + base;
-    p.n_recv = n;
-    p.n_src = uniform_u32(bp.mass_len[member]);
-    p.steps = bp.steps;
-    p.tiles = n <= WAVE * CHAIN_K ? 1u : n <= 2 * WAVE * CHAIN_K ? 2u : 4u;   // chain_tiles(n), n <= CHAIN_MAX_RECV
-    p.dt = bp.dt + member;
-    return p;
-}
-
-__global__ __launch_bounds__(1024) void ragged_chain_kernel(const RaggedParams rp) {
-    const uint32_t member = uniform_u32(rp.members[blockIdx.x]);
-    chain_body<false>(ragged_member_chain(rp.b, member, uniform_u32(rp.n_len[member])), ChainTrace{});
-}
-
-__global__ __launch_bounds__(1024) void ragged_trace_chain_kernel(const RaggedTraceParams rp) {
-    const BatchTraceParams &tp = rp.t;
-    const uint32_t member = uniform_u32(rp.members[blockIdx.x]);
-    ChainTrace tr;
-    tr.mass = tp.mass + (size_t)member * tp.b.stride;
-    tr.pitch = (size_t)tp.count * nbd::QTY;
-    tr.entry = tp.done == 0;
-    tr.every = tp.every;
-    tr.until = tp.every - tp.done % tp.every;
-    tr.row = tp.rows + ((size_t)(tp.done == 0 ? 0u : 1u + tp.done / tp.every) * tp.count + member) * nbd::QTY;
-    chain_body<true>(ragged_member_chain(tp.b, member, uniform_u32(rp.n_len[member])), tr);
-}
-
-// gridDim.x covers the group's largest member: the workgroups past a smaller member's last receiver leave before the
-// first barrier (blockIdx and n are uniform over the workgroup, so all of it leaves).
-template <int W, int H>
-__global__ __launch_bounds__(WAVE *W) void ragged_lane_split_kernel(const RaggedParams rp) {
-    const uint32_t member = uniform_u32(rp.members[blockIdx.y]);
-    const uint32_t n = uniform_u32(rp.n_len[member]);
-    if (blockIdx.x * (WAVE / H) >= n) return;
-    const BatchParams &bp = rp.b;
-    const size_t base = (size_t)member * bp.stride;
-    const StepParams p = plain_step(bp.pos_in + base, bp.gm + base, uniform_u32(bp.mass_len[member]), bp.pos_in + base,
-                                    bp.pos_out + base, bp.vel + base, bp.acc + base, bp.radius + base, n, bp.dt + member, 8);
+    const StepParams p = plain_step(bp.pos_in + base, bp.gm + base, uniform_u32(bp.mass_len[m.index]), bp.pos_in + base,
+                                    bp.pos_out + base, bp.vel + base, bp.acc + base, bp.radius + base, m.n, bp.dt + m.index, 8);
     lane_split_body<W, H>(p);
 }
 
@@ -1011,14 +984,13 @@ const void *step_kernel_fused_fn(LaunchShape s) {
 
 const void *finish_kernel_fn() { return reinterpret_cast<const void *>(&finish_kernel); }
 
-const void *batch_lane_split_fn(int a, int b) {   // (w, lanes)
-    // the two shapes batch_lane_shape reaches for 512 < N <= 3 000
-    NB_CASE(batch_lane_split_kernel, 8, 8) NB_CASE(batch_lane_split_kernel, 16, 4)
-    return nullptr;
-}
-
-const void *ragged_lane_split_fn(int a, int b) {   // (w, lanes): the same two shapes
-    NB_CASE(ragged_lane_split_kernel, 8, 8) NB_CASE(ragged_lane_split_kernel, 16, 4)
+const void *batch_lane_split_fn(int a, int b, bool listed) {   // (w, lanes)
+    // the two shapes batch_lane_shape reaches for 512 < N <= 3 000, for either way of finding the members
+    if (listed) {
+        NB_CASE(batch_lane_split_kernel, 8, 8, RaggedParams) NB_CASE(batch_lane_split_kernel, 16, 4, RaggedParams)
+    } else {
+        NB_CASE(batch_lane_split_kernel, 8, 8, BatchParams) NB_CASE(batch_lane_split_kernel, 16, 4, BatchParams)
+    }
     return nullptr;
 }
 #undef NB_CASE
@@ -1027,20 +999,18 @@ void launch_chain(hipStream_t st, const ChainParams &p) {
     hipLaunchKernelGGL(chain_kernel, dim3(1), dim3(1024), 0, st, p);
 }
 
-void launch_batch_chain(hipStream_t st, const BatchParams &p, uint32_t count) {
-    hipLaunchKernelGGL(batch_chain_kernel, dim3(count), dim3(1024), 0, st, p);
+void launch_batch_chain(hipStream_t st, const RaggedParams &p, uint32_t workgroups) {
+    if (p.members)
+        hipLaunchKernelGGL(batch_chain_kernel<RaggedParams>, dim3(workgroups), dim3(1024), 0, st, p);
+    else
+        hipLaunchKernelGGL(batch_chain_kernel<BatchParams>, dim3(workgroups), dim3(1024), 0, st, static_cast<const BatchParams &>(p));
 }
 
-void launch_batch_trace_chain(hipStream_t st, const BatchTraceParams &p) {
-    hipLaunchKernelGGL(batch_trace_chain_kernel, dim3(p.count), dim3(1024), 0, st, p);
-}
-
-void launch_ragged_chain(hipStream_t st, const RaggedParams &p, uint32_t members) {
-    hipLaunchKernelGGL(ragged_chain_kernel, dim3(members), dim3(1024), 0, st, p);
-}
-
-void launch_ragged_trace_chain(hipStream_t st, const RaggedTraceParams &p, uint32_t members) {
-    hipLaunchKernelGGL(ragged_trace_chain_kernel, dim3(members), dim3(1024), 0, st, p);
+void launch_batch_trace_chain(hipStream_t st, const RaggedParams &p, const TraceParams &t, uint32_t workgroups) {
+    if (p.members)
+        hipLaunchKernelGGL(batch_trace_chain_kernel<RaggedParams>, dim3(workgroups), dim3(1024), 0, st, p, t);
+    else
+        hipLaunchKernelGGL(batch_trace_chain_kernel<BatchParams>, dim3(workgroups), dim3(1024), 0, st, static_cast<const BatchParams &>(p), t);
 }
 
 }  // namespace nb

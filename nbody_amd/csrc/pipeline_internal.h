@@ -12,7 +12,8 @@
 //   step_schedule.hip   device-chosen and leapfrog steps of a pipeline: the target of step_schedule.h's one launch schedule
 //   pipeline.hip     SimPipeline life cycle and the C-ABI entry points (Create/Destroy/Set/Get/PerformSimUpdate, knobs);
 //                    release_device ends what no owner type holds: streams, cached graphs, IPC mappings, pinned host memory
-//   kernels.hip      the gfx950 force kernels and their entry points (kernels.h)
+//   kernels.hip      the gfx950 force kernels and their entry points (kernels.h); each ensemble kernel once, instantiated
+//                    for the two ways a launch finds its members (by block index / through a ragged ensemble's tables)
 //   launch_shape.hip the host-side launch policy: shape, grid, LDS of a launch (launch_shape.h)
 //   convert.hip      AoS <-> SoA converters, pads, G*m, fills (convert.h)
 //   batch.hip        SimBatch (batch_internal.h): ensembles of small worlds, uniform or ragged, stepped by one launch
@@ -21,7 +22,7 @@
 //                    target of step_schedule.h)
 //   batch_observe.hip  the read-only calls on a SimBatch: energy, potential, bounds, count images and frames
 //   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
-//   batch_diag.hip   the same for every member of a SimBatch: the kernels behind nb_hip_ensemble_energy / _potential
+//   batch_diag.hip   the same for every member of a SimBatch, uniform or ragged: the kernels behind nb_hip_ensemble_energy / _potential
 //                    (batch_diag.h; the arithmetic both share: diag_common.h)
 //   render.hip       bounds, count image and RGBA frame of the state a pipeline holds (nb_hip_bounds, nb_hip_render_*)
 //   field.hip        the potential and the acceleration at probe points and as maps over a view (nb_hip_potential_at,

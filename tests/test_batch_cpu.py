@@ -1,6 +1,7 @@
 """World ensembles without a GPU: the declared surface (include/nbody_hip.h nb_hip_batch_*, include/nbody_batch.h), its
 argument checks, the per-member partition of CreateWorldBatch, and the static ISA of the ensemble kernels
-(nbody_amd/csrc/kernels.hip batch_chain_kernel, batch_lane_split_kernel)."""
+(nbody_amd/csrc/kernels.hip batch_chain_kernel, batch_lane_split_kernel: their instantiations for nb::BatchParams, the members
+addressed by block index; tests/test_ragged_cpu.py holds the ones for nb::RaggedParams)."""
 import os
 import re
 import subprocess
@@ -176,7 +177,8 @@ def isa(tmp_path_factory):
 
 
 def _batch(names):
-    return [n for n in names if "batch_chain_kernel" in n or "batch_lane_split_kernel" in n]
+    """the untraced step kernels whose (mangled) parameter type is nb::BatchParams"""
+    return [n for n in names if ("batch_chain_kernel" in n or "batch_lane_split_kernel" in n) and "BatchParams" in n]
 
 
 def test_ensemble_kernels_keep_the_wait_state_behind_every_rsq(isa):

@@ -209,19 +209,20 @@ def check_ensemble(label, members, ragged, paths):
 
 
 def test_range_on_a_uniform_ensemble_of_one_workgroup_worlds():
-    """126 members of 490 particles: batch_chain_kernel, and ensemble_phi_kernel for SimBatch.potential()"""
+    """126 members of 490 particles: batch_chain_kernel<BatchParams>, and ensemble_phi_kernel<EnsembleDiagParams> for SimBatch.potential()"""
     check_ensemble("range | SimBatch N=490 (chain path) + SimBatch.potential()",
                    [(kind, gi, rows) for kind, gi in pc.WORLDS for rows in slices_for("chain")], False, ["chain"])
 
 
 def test_range_on_a_uniform_ensemble_of_lane_split_worlds():
-    """18 members of 2 650 particles: batch_lane_split_kernel"""
+    """18 members of 2 650 particles: batch_lane_split_kernel<16, 4, BatchParams>"""
     check_ensemble("range | SimBatch N=2650 (lanes path) + SimBatch.potential()",
                    [(kind, gi, slice(0, pc.ROWS)) for kind, gi in pc.WORLDS], False, ["lanes"])
 
 
 def test_range_on_a_ragged_ensemble():
-    """per world one member of 490 and two of 1 210 particles: both ragged kernels in one launch group each"""
+    """per world one member of 490 and two of 1 210 particles: batch_chain_kernel and batch_lane_split_kernel<8, 8> for RaggedParams,
+    one launch group each, and ensemble_phi_kernel<RaggedDiagParams>"""
     cuts = (slice(0, 360), slice(360, 1440), slice(1440, pc.ROWS))
     check_ensemble("range | SimBatch.ragged N in (490, 1210, 1210) + potential()",
                    [(kind, gi, rows) for kind, gi in pc.WORLDS for rows in cuts], True, ["chain", "lanes"])

@@ -270,7 +270,8 @@ def check_member(label, got, m, n):
 
 @pytest.mark.parametrize("n,pairs", [(512, [(1, 63), (64, 65), (255, 256), (257, 511)]), (1300, [(513, 1000)]), (3000, [(1000, 2999)])])
 def test_uniform_ensembles_add_every_source_exactly_once(n, pairs):
-    """N <= 512: batch_chain_kernel (chain_body, the one-workgroup chain); above: batch_lane_split_kernel<8, 8> / <16, 4>."""
+    """N <= 512: batch_chain_kernel (chain_body, the one-workgroup chain); above: batch_lane_split_kernel<8, 8> / <16, 4>; the
+    members found by block index (BatchParams)."""
     worst = 0.0
     for ms in pairs:
         b = nb.SimBatch(n, list(ms))
@@ -284,6 +285,7 @@ def test_uniform_ensembles_add_every_source_exactly_once(n, pairs):
 
 
 def test_a_ragged_ensemble_adds_every_source_exactly_once():
+    """the same three kernels, the members found through the lists (RaggedParams)"""
     sizes = [(63, 100), (257, 300), (511, 512), (513, 600), (1000, 1300), (2999, 3000)]
     r = nb.SimBatch.ragged([n for _, n in sizes], [m for m, _ in sizes])
     r.set_data([member(m, n) for m, n in sizes])

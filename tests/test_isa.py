@@ -102,7 +102,8 @@ def test_the_gravitational_constant_is_written_down_once(convert_isa):
     fns = functions(convert_isa)
     multiply = {n for n, b in fns.items() if any(ins.startswith(("v_mul_f32", "v_pk_mul_f32")) for ins in b)}
     users = {n: b for n, b in fns.items() if any(c in n for c in callers)}
-    assert len(users) == 3 and set(users) == multiply, (sorted(users), sorted(multiply))
+    # batch_split_kernel is built twice: for the members of a uniform and of a ragged ensemble
+    assert len(users) == 4 and sum("batch_split_kernel" in n for n in users) == 2 and set(users) == multiply, (sorted(users), sorted(multiply))
     for name, body in users.items():
         assert any(ins.startswith("v_mul_f32") for ins in body), name
         assert not any(literal in ins.lower() or re.search(r"\b10\.0\b", ins) for ins in body), (name, literal)

@@ -1,8 +1,9 @@
 """Ragged world ensembles without a GPU: the declared surface (include/nbody_hip.h nb_hip_ragged_*,
 include/nbody_batch_ragged.h), creation and its launch groups, the argument checks, the World layer's partition and host
-diagnostics, and the static ISA of the new kernels (kernels.hip ragged_chain_kernel / ragged_trace_chain_kernel /
-ragged_lane_split_kernel, ragged_diag.hip ragged_phi_kernel, convert.hip ragged_split_kernel / ragged_merge_kernel /
-ragged_copy_rows_kernel)."""
+diagnostics, and the static ISA of the kernels that find their members through the ragged tables: the instantiations for
+nb::RaggedParams of kernels.hip batch_chain_kernel / batch_trace_chain_kernel / batch_lane_split_kernel, for
+nbd::RaggedDiagParams of batch_diag.hip ensemble_phi_kernel, for RaggedRecords of convert.hip batch_split_kernel /
+batch_merge_kernel, and convert.hip ragged_copy_rows_kernel."""
 import ctypes as C
 import os
 import re
@@ -14,7 +15,7 @@ import pytest
 import nbody_amd as nb
 from isa_common import check_rsq_wait_states, compile_isa, functions, kernel_meta
 from test_abi import declared_functions, exported
-from test_batch_cpu import BATCH_HIP, BATCH_WORLD
+from test_batch_cpu import BATCH_HIP, BATCH_WORLD, _batch
 
 ROOT = nb.ROOT
 RAGGED_HIP = ["nb_hip_ragged_create", "nb_hip_ragged_layout", "nb_hip_ragged_launch_shape", "nb_hip_ragged_member_shape"]
@@ -202,21 +203,37 @@ print("OK")
 @pytest.fixture(scope="module")
 def isa(tmp_path_factory):
     d = tmp_path_factory.mktemp("ragged_isa")
-    return {src: compile_isa(d, src) for src in ("kernels.hip", "ragged_diag.hip", "convert.hip")}
+    return {src: compile_isa(d, src) for src in ("kernels.hip", "batch_diag.hip", "convert.hip")}
+
+
+def _ragged(name):
+    """by the parameter type in the mangled name (RaggedParams, RaggedDiagParams, RaggedRecords), or ragged_copy_rows_kernel"""
+    return "ragged" in name.lower()
 
 
 def _meta(text):
-    return {n: (scratch, sgpr, vgpr) for n, scratch, sgpr, vgpr in kernel_meta(text) if "ragged" in n}
+    return {n: (scratch, sgpr, vgpr) for n, scratch, sgpr, vgpr in kernel_meta(text) if _ragged(n)}
+
+
+def _phi_body(text):
+    """the instruction lines of ensemble_phi_kernel<RaggedDiagParams>"""
+    (name,) = _meta(text)
+    lines = text[text.index(name + ":"):].split(".Lfunc_end")[0].splitlines()[1:]
+    body = [ln.split(";")[0].strip() for ln in lines if ln.startswith("\t")]
+    return [ln for ln in body if ln and not ln.startswith(".")]
 
 
 def test_the_new_kernels_exist_and_are_not_mistaken_for_the_uniform_ones(isa):
     step = sorted(_meta(isa["kernels.hip"]))
-    assert len(step) == 4 and sum("ragged_lane_split_kernel" in n for n in step) == 2, step
-    assert any("ragged_chain_kernel" in n for n in step) and any("ragged_trace_chain_kernel" in n for n in step)
-    # tests/test_batch_cpu.py and tests/test_isa.py select kernels by these substrings
-    assert not [n for n in step if "batch_chain_kernel" in n or "batch_lane_split_kernel" in n or "step_kernel" in n]
-    assert len(_meta(isa["ragged_diag.hip"])) == 1 and len(kernel_meta(isa["ragged_diag.hip"])) == 1
-    assert len(_meta(isa["convert.hip"])) == 3
+    assert len(step) == 4 and sum("batch_lane_split_kernel" in n for n in step) == 2, step
+    assert any("batch_chain_kernel" in n for n in step) and any("batch_trace_chain_kernel" in n for n in step)
+    # tests/test_batch_cpu.py selects the uniform instantiations by their parameter type, tests/test_isa.py step kernels by name
+    assert not _batch(step) and not [n for n in step if "step_kernel" in n]
+    assert len(_meta(isa["batch_diag.hip"])) == 1 and "ensemble_phi_kernel" in next(iter(_meta(isa["batch_diag.hip"])))
+    assert len(kernel_meta(isa["batch_diag.hip"])) == 3          # beside the two of the uniform ensemble
+    convert = sorted(_meta(isa["convert.hip"]))
+    assert len(convert) == 3, convert
+    assert [sum(k in n for n in convert) for k in ("batch_split_kernel", "batch_merge_kernel", "ragged_copy_rows_kernel")] == [1, 1, 1]
 
 
 def test_the_new_kernels_fit_their_launch_bounds_without_scratch(isa):
@@ -226,16 +243,16 @@ def test_the_new_kernels_fit_their_launch_bounds_without_scratch(isa):
         # 512 VGPRs per SIMD lane, waves of a workgroup spread over 4 SIMDs: a W-wave workgroup must fit once
         waves = 16 if "chain_kernel" in name else int(re.search(r"kernelILi(\d+)ELi\d+E", name).group(1))
         assert vgpr <= 512 // ((waves + 3) // 4), (name, vgpr)
-    for src in ("ragged_diag.hip", "convert.hip"):
+    for src in ("batch_diag.hip", "convert.hip"):
         for name, (scratch, sgpr, vgpr) in _meta(isa[src]).items():
             assert scratch == 0 and sgpr <= 102, (name, scratch, sgpr)
             assert vgpr <= 64, (name, vgpr)      # 256-thread workgroups at full occupancy
-    assert not re.search(r"^\s+scratch_", isa["ragged_diag.hip"], re.M)
+    assert not re.search(r"^\s+scratch_", isa["batch_diag.hip"], re.M)
 
 
 def test_the_new_step_kernels_keep_the_wait_state_behind_every_rsq(isa):
     fns = functions(isa["kernels.hip"])
-    names = [n for n in fns if "ragged" in n]
+    names = [n for n in fns if _ragged(n)]
     assert len(names) == 4, names
     for name in names:
         total = check_rsq_wait_states(name, fns[name])
@@ -243,11 +260,9 @@ def test_the_new_step_kernels_keep_the_wait_state_behind_every_rsq(isa):
 
 
 def test_the_ragged_potential_kernel_keeps_the_scalar_route_and_the_wait_state(isa):
-    """ragged_phi_kernel is the potential half of ensemble_phi_kernel: sources through the scalar cache, one wait state
-    behind every v_rsq_f32, no LDS."""
-    text = isa["ragged_diag.hip"]
-    body = [ln.split(";")[0].strip() for ln in text.splitlines() if ln.startswith("\t")]
-    body = [ln for ln in body if ln and not ln.startswith(".")]
+    """ensemble_phi_kernel<RaggedDiagParams> is the potential half of the uniform one: sources through the scalar cache, one
+    wait state behind every v_rsq_f32, no LDS."""
+    body = _phi_body(isa["batch_diag.hip"])
     ops = [ln.split()[0] for ln in body]
     assert "s_load_dwordx16" in ops and "s_load_dwordx8" in ops
     assert not [o for o in ops if o.startswith("ds_")]
