@@ -61,8 +61,14 @@ def pipe_env(n, frac):
             s.update(2, 0.01)
             states.append(s.get_data())
             s.close()
+        sd.assert_premise(*states)          # finite, no -0.0: what the leapfrog kinds rest on (sequence_driver's docstring)
         _envs[(n, frac)] = (sd.Env("pipeline", states[0], states[1], views(states[0][0, 0:2]), lambda k: _points[:k]), m)
     return _envs[(n, frac)]
+
+
+def as_kind(env, kind):
+    """the same states, views and points under another kind: the leapfrog kinds run on their base kind's worlds"""
+    return sd.Env(kind, env.start, env.other, env.view, env.points, env.members)
 
 
 def pipe_maker(n, m, knobs):
@@ -73,12 +79,12 @@ def pipe_maker(n, m, knobs):
     return make
 
 
-def run_row(row, ops, seed=None):
+def run_row(row, ops, seed=None, kind="pipeline"):
     n, frac, knobs = PIPE_ROWS[row]
     env, m = pipe_env(n, frac)
     t0 = time.perf_counter()
-    compared = sd.check(pipe_maker(n, m, knobs), ops, env, seed)
-    print(f"[sequence] {row} seed {seed}: {len(ops)} operations, {compared} outputs compared, {time.perf_counter() - t0:.2f} s")
+    compared = sd.check(pipe_maker(n, m, knobs), ops, env if kind == "pipeline" else as_kind(env, kind), seed)
+    print(f"[sequence] {row} {kind} seed {seed}: {len(ops)} operations, {compared} outputs compared, {time.perf_counter() - t0:.2f} s")
     return compared
 
 
@@ -87,6 +93,19 @@ def run_row(row, ops, seed=None):
 def test_a_long_lived_pipeline_is_a_chain_of_fresh_ones(row, seed):
     ops = sd.generate("pipeline", seed)
     assert run_row(row, ops, seed) > len(ops) // 2
+
+
+LEAPFROG_PIPE_ROWS = ["chain-200", "lanes-600-graph1", "classic-4133", "classic-4133-graph2", "classic-4133-lds", "split3-finish-9000",
+                      "fused-finish-9000", "passes2-1500"]
+
+
+@pytest.mark.parametrize("seed", sd.SEEDS["pipeline-lf"])
+@pytest.mark.parametrize("row", LEAPFROG_PIPE_ROWS)
+def test_a_long_lived_pipeline_with_leapfrog_calls_is_a_chain_of_fresh_ones(row, seed):
+    """Leapfrog calls, fixed and adaptive, blocking and async, among everything the "pipeline" kind draws; and after every
+    one of them last_leapfrog_info() against the driver's model of "acc is current": it primed exactly when it had to."""
+    ops = sd.generate("pipeline-lf", seed)
+    assert run_row(row, ops, seed, "pipeline-lf") > len(ops) // 2
 
 
 # ---- ensembles -----------------------------------------------------------------------------------------------------------------
@@ -102,6 +121,7 @@ def batch_env(count, n):
             s.update(2, 0.01)
             states.append(s.get_data())
             s.close()
+        sd.assert_premise(*states)
         _envs[(count, n)] = (sd.Env("batch", states[0], states[1], views(states[0][0, 0, 0:2]), None, members=count), ms)
     return _envs[(count, n)]
 
@@ -115,6 +135,18 @@ def test_a_long_lived_ensemble_is_a_chain_of_fresh_ones(row, seed):
     t0 = time.perf_counter()
     compared = sd.check(lambda: nb.SimBatch(n, ms), ops, env, seed)
     print(f"[sequence] {row} seed {seed}: {len(ops)} operations, {compared} outputs compared, {time.perf_counter() - t0:.2f} s")
+    assert compared > len(ops) // 2
+
+
+@pytest.mark.parametrize("seed", sd.SEEDS["batch-lf"])
+@pytest.mark.parametrize("row", list(BATCH_ROWS))
+def test_a_long_lived_ensemble_with_leapfrog_calls_is_a_chain_of_fresh_ones(row, seed):
+    count, n = BATCH_ROWS[row]
+    env, ms = batch_env(count, n)
+    ops = sd.generate("batch-lf", seed, members=count)
+    t0 = time.perf_counter()
+    compared = sd.check(lambda: nb.SimBatch(n, ms), ops, as_kind(env, "batch-lf"), seed)
+    print(f"[sequence] {row} batch-lf seed {seed}: {len(ops)} operations, {compared} outputs compared, {time.perf_counter() - t0:.2f} s")
     assert compared > len(ops) // 2
 
 

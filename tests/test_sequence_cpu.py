@@ -3,7 +3,17 @@ kinds of state between calls as the real one -- two position buffers and a phase
 validity flag, a cached chain per phase that remembers the step size it was captured with, an adaptive head, async work that
 later calls queue behind, grow-only scratch -- and in which each way of getting that state wrong can be switched on.  Without
 a fault every committed seed passes; with each fault at least one committed seed fails, and the driver names an operation at
-or after the first one the fault could touch.  The seeds are the ones tests/test_gpu_sequences.py runs on the MI355X."""
+or after the first one the fault could touch.  The seeds are the ones tests/test_gpu_sequences.py runs on the MI355X.
+
+The leapfrog kinds ("pipeline-lf", "batch-lf"): the stand-in also makes the kick-drift-kick steps of tests/leapfrog_ref.py
+around its own force, with two kick words in a head that regrows, a host-side "acc is current" flag, the step word at 0 for
+the whole call and last_leapfrog_info(); FakeBatch puts a list of them behind the SimBatch names.  HOW THE SEEDS OF THESE
+KINDS WERE CHOSEN (sequence_driver.SEEDS): among the seeds from 0 up whose sequence generates (assert_covers holds) and
+passes on the clean stand-in, the first pair in lexicographic order that between them (a) fail every fault of LF_FAULTS that
+the kind can show and (b) issue every operation the kind draws and every drawn form of the adaptive calls
+(sequence_driver.assert_union_covers, at the member counts of the GPU rows) -- test_the_leapfrog_seeds_are_the_first_pair_that_catches_every_fault recomputes it."""
+import hashlib
+import itertools
 import types
 
 import numpy as np
@@ -23,6 +33,19 @@ FAULTS = {
     6: "a diagnostic behind an async step sees the state before the step",
     7: "potential() after energy() returns the previous call's buffer",
 }
+LF_FAULTS = {
+    8: "an Euler update leaves acc_current set",
+    9: "set_data leaves acc_current set",
+    10: "an Euler adaptive call leaves acc_current set",
+    11: "trace leaves acc_current set (FakeBatch)",
+    12: "after a leapfrog call the next fixed-step call with an already-used step size steps with the word still at 0",
+    13: "an adaptive leapfrog call of odd n closes its last step with the wrong kick-word row",
+    14: "a regrown head loses the kick words",
+    15: "an async leapfrog call is not waited for by the diagnostic behind it",
+    16: "a leapfrog call primes every time (bits cannot show it: only the info oracle can)",
+}
+LF_FAULTS_OF = {"pipeline-lf": (8, 9, 10, 12, 13, 14, 15, 16), "batch-lf": (8, 9, 10, 11, 12, 13, 16)}
+HEAD_LOG = 64          # the step sizes the adaptive head logs before it regrows
 
 
 def world(seed):
@@ -52,6 +75,10 @@ class FakePipeline:
         self.scratch = np.zeros(0, F32)                                  # grow-only, shared by the field calls
         self.phi, self.phi_fresh = None, False
         self.collected = None
+        # leapfrog: two kick words in the adaptive head (which regrows), what the host believes word 0 to hold, whether acc
+        # is F(x) of the latest state (host side, decided when a call is issued), the record of the last leapfrog call
+        self.kick, self.kick_host, self.head_room = np.zeros(2, F32), None, HEAD_LOG
+        self.acc_current, self.lf_info = False, (0, False)
 
     def close(self):
         pass
@@ -69,6 +96,8 @@ class FakePipeline:
         self.mass, self.radius = a[:, 6].copy(), a[:, 7].copy()
         if self.fault != 5:
             self.armed = False
+        if self.fault != 9:
+            self.acc_current = False
 
     def get_data(self):
         self._flush()
@@ -79,7 +108,8 @@ class FakePipeline:
 
     def _latest(self):
         """the positions a reading call works on"""
-        if self.fault != 6:
+        behind_leapfrog = self.fault == 15 and self.queue and getattr(self.queue[-1], "leapfrog", False)
+        if self.fault != 6 and not behind_leapfrog:
             self._flush()
         return self.pos[self.cur ^ 1] if self.fault == 2 else self.pos[self.cur]
 
@@ -110,12 +140,75 @@ class FakePipeline:
         for _ in range(n):
             self._step(use)
 
+    def _issued(self, leapfrog):
+        """host side, when a stepping call is issued: does it prime, and what it leaves of acc_current"""
+        primed = leapfrog and (not self.acc_current or self.fault == 16)
+        self.acc_current = leapfrog
+        return primed
+
     def update(self, n, dt):
         self._flush()
+        if self.fault != 8:
+            self._issued(False)
         self._fixed(n, dt)
 
     def step_async(self, n, dt):
+        if self.fault != 8:
+            self._issued(False)
         self.queue.append(lambda: self._fixed(n, dt))
+
+    # -- leapfrog (tests/leapfrog_ref.py: open, force, close; nothing merged) ---------------------------------------------
+    def _grow_head(self, log):
+        if log > self.head_room:
+            self.head_room = log
+            if self.fault == 14:
+                self.kick = np.zeros(2, F32)         # the new buffer; the host goes on believing what it uploaded
+
+    def _kick(self, row):
+        self.vel = self.vel + self.acc * (F32(0.5) * self.kick[row])
+
+    def _open(self, row):
+        self._kick(row)
+        self.pos[self.cur] = self.pos[self.cur] + self.vel * self.kick[row]          # the drift, in place
+
+    def _begin_leapfrog(self, primed):
+        self.dt_dev = F32(0)                  # the step word: every launch of the call is a force evaluation
+        if primed:
+            self._step(self.dt_dev)
+
+    def _end_leapfrog(self):
+        if self.fault != 12:
+            self.dt_valid = False
+
+    def _leapfrog(self, n, dt, primed):
+        self._grow_head(0)
+        dt = F32(dt)
+        if self.kick_host != dt:
+            self.kick[0], self.kick_host = dt, dt
+        self._begin_leapfrog(primed)
+        for i in range(n):
+            if i > 0:
+                self._kick(0)
+            self._open(0)
+            self._step(self.dt_dev)
+        self._kick(0)
+        self._end_leapfrog()
+
+    def update_leapfrog(self, n, dt):
+        self._flush()
+        primed = self._issued(True)
+        self.lf_info = (n + primed, primed)
+        self._leapfrog(n, dt, primed)
+
+    def update_leapfrog_async(self, n, dt):
+        primed = self._issued(True)
+        self.lf_info = (n + primed, primed)
+        work = lambda: self._leapfrog(n, dt, primed)          # noqa: E731
+        work.leapfrog = True
+        self.queue.append(work)
+
+    def last_leapfrog_info(self):
+        return self.lf_info
 
     def _criterion(self, eta, dt_max):
         a2 = (self.acc.astype(np.float64) ** 2).sum(axis=1).astype(F32)
@@ -126,8 +219,12 @@ class FakePipeline:
         self.head_min = min(self.head_min, q)
         return F32(min(F32(eta) * np.sqrt(np.sqrt(self.head_min, dtype=F32), dtype=F32), F32(dt_max)))
 
-    def _adaptive(self, n, eta, dt_max, span, prime):
-        if prime:
+    def _adaptive(self, n, eta, dt_max, span, prime, leapfrog=False, primed=False):
+        self._grow_head(n)
+        if leapfrog:
+            self.kick_host = None             # the criterion writes the kick words
+            self._begin_leapfrog(primed)
+        elif prime:
             self._step(0.0)
         t, log, res = 0.0, np.zeros(n, F32), dict(elapsed=0.0, steps=0, idle_steps=0, dt_last=0.0, dt_smallest=0.0)
         for i in range(n):
@@ -144,20 +241,47 @@ class FakePipeline:
                 res["dt_smallest"] = float(dt) if res["dt_smallest"] == 0 else min(res["dt_smallest"], float(dt))
             else:
                 res["idle_steps"] += 1
+            if leapfrog:                       # the device writes the step size into kick word i & 1
+                row = i & 1
+                log[i] = self.kick[row] = dt
+                if i > 0:
+                    self._kick(row ^ 1)
+                self._open(row)
+                self._step(self.dt_dev)
+                continue
             log[i] = self.dt_dev = dt          # the device writes the step size where the step reads it
             self._step(dt)
         res["elapsed"] = t
-        if self.fault != 1:
+        if leapfrog:
+            last = (n - 1) & 1
+            self._kick(last ^ 1 if self.fault == 13 and n % 2 == 1 else last)
+            self._end_leapfrog()
+        elif self.fault != 1:
             self.dt_valid = False
         self.collected = (log, res)
 
-    def update_adaptive(self, n, eta, dt_max, span=float("inf"), prime=False):
+    def _issued_adaptive(self, leapfrog):
+        if leapfrog or self.fault != 10:
+            primed = self._issued(leapfrog)
+        else:
+            primed = False
+        return primed
+
+    def update_adaptive(self, n, eta, dt_max, span=float("inf"), prime=False, leapfrog=False):
         self._flush()
-        self._adaptive(n, eta, dt_max, span, prime)
+        primed = self._issued_adaptive(leapfrog)
+        if leapfrog:
+            self.lf_info = (n + primed, primed)
+        self._adaptive(n, eta, dt_max, span, prime, leapfrog, primed)
         return self.collected
 
-    def update_adaptive_async(self, n, eta, dt_max, span=float("inf"), prime=False):
-        self.queue.append(lambda: self._adaptive(n, eta, dt_max, span, prime))
+    def update_adaptive_async(self, n, eta, dt_max, span=float("inf"), prime=False, leapfrog=False):
+        primed = self._issued_adaptive(leapfrog)
+        if leapfrog:
+            self.lf_info = (n + primed, primed)
+        work = lambda: self._adaptive(n, eta, dt_max, span, prime, leapfrog, primed)          # noqa: E731
+        work.leapfrog = leapfrog
+        self.queue.append(work)
 
     def adaptive_collect(self, n):
         self._flush()
@@ -240,12 +364,99 @@ class FakePipeline:
         return np.minimum(c.transpose(1, 2, 0) * 80, 255).astype(np.uint8)
 
 
+class FakeBatch:
+    """A list of FakePipeline members behind the method names of nb.SimBatch that the driver calls; step sizes one for all
+    or one per member; trace records energy() rows."""
+
+    def __init__(self, count, n, m, fault=0):
+        self.members, self.fault = [FakePipeline(n, m, fault) for _ in range(count)], fault
+
+    def close(self):
+        pass
+
+    def _dts(self, dt):
+        return [float(dt)] * len(self.members) if np.ndim(dt) == 0 else [float(x) for x in dt]
+
+    def set_data(self, a):
+        for s, part in zip(self.members, a):
+            s.set_data(part)
+
+    def get_data(self):
+        return np.stack([s.get_data() for s in self.members])
+
+    def get_member(self, b):
+        return self.members[b].get_data()
+
+    def update(self, n, dt):
+        for s, d in zip(self.members, self._dts(dt)):
+            s.update(n, d)
+
+    def step_async(self, n, dts):
+        for s, d in zip(self.members, self._dts(dts)):
+            s.step_async(n, d)
+
+    def update_leapfrog(self, n, dt):
+        for s, d in zip(self.members, self._dts(dt)):
+            s.update_leapfrog(n, d)
+
+    def last_leapfrog_info(self):
+        return self.members[0].last_leapfrog_info()
+
+    def update_adaptive(self, n, eta, dt_max, span=float("inf"), prime=False, leapfrog=False):
+        outs = [s.update_adaptive(n, eta, dt_max, span, prime, leapfrog) for s in self.members]
+        return np.stack([log for log, _ in outs], axis=1), [res for _, res in outs]
+
+    def trace(self, n, dt, every):
+        def row():
+            return [np.frombuffer(sd.ebits(s.energy()), dtype=np.float64) for s in self.members]
+        current = [s.acc_current for s in self.members]
+        rows = [row()]
+        for k in range(n):
+            self.update(1, dt)
+            if (k + 1) % every == 0:
+                rows.append(row())
+        if self.fault == 11:
+            for s, c in zip(self.members, current):
+                s.acc_current = c
+        return np.array(rows)
+
+    def energy(self):
+        return [s.energy() for s in self.members]
+
+    def potential(self):
+        return np.stack([s.potential() for s in self.members])
+
+    def bounds(self):
+        return np.stack([s.bounds() for s in self.members])
+
+    def render_mode(self, mode):
+        self.mode = mode
+
+    def render_counts(self, view):
+        return np.stack([s.render_counts(view) for s in self.members])
+
+    def render(self, view):
+        return np.stack([s.render(view) for s in self.members])
+
+
 def view(w, h):
     return types.SimpleNamespace(target=(0.0, 0.0), offset=(w / 2, h / 2), zoom=w / 300.0, width=w, height=h, core_mass=1000.0)
 
 
 _points = np.random.default_rng(5).standard_normal((max(sd.POINT_COUNTS), 2)).astype(F32) * 60
 ENV = sd.Env("pipeline", world(1), world(2), view, lambda k: _points[:k])
+B = 3
+LF_ENVS = {"pipeline-lf": sd.Env("pipeline-lf", world(1), world(2), view, lambda k: _points[:k]),
+           "batch-lf": sd.Env("batch-lf", np.stack([world(10 + b) for b in range(B)]), np.stack([world(20 + b) for b in range(B)]),
+                              view, None, members=B)}
+for _env in LF_ENVS.values():
+    sd.assert_premise(_env.start, _env.other)          # the premise of the leapfrog kinds, for the stand-in's states
+
+
+def lf_maker(kind, fault=0):
+    if kind == "pipeline-lf":
+        return lambda: FakePipeline(N, M, fault)
+    return lambda: FakeBatch(B, N, M, fault)
 
 
 def first_touch(fault, ops):
@@ -266,7 +477,26 @@ def first_touch(fault, ops):
         return names.index("set_data")
     if fault == 6:
         return first(lambda n, a: n in sd.ASYNC)
-    return names.index("energy")
+    if fault == 7:
+        return names.index("energy")
+    lf = first(lambda n, a: sd.is_leapfrog((n, a)))          # nothing of LF_FAULTS shows before the first leapfrog call
+    if fault == 8:
+        return first(lambda n, a: n in ("update", "step_async"), lf + 1)
+    if fault == 9:
+        return first(lambda n, a: n == "set_data", lf + 1)
+    if fault == 10:
+        return first(lambda n, a: n in sd.ADAPTIVE and not a.get("leapfrog"), lf + 1)
+    if fault == 11:
+        return first(lambda n, a: n == "trace", lf + 1)
+    if fault == 12:
+        return first(lambda n, a: n in sd.FIXED, lf + 1)
+    if fault == 13:
+        return first(lambda n, a: n in sd.ADAPTIVE and a.get("leapfrog") and a["n"] % 2 == 1)
+    if fault == 14:
+        return first(lambda n, a: n in sd.ADAPTIVE and a["n"] > HEAD_LOG)
+    if fault == 15:
+        return first(lambda n, a: n == "update_leapfrog_async")
+    return lf + 1          # 16: the first call primes by right
 
 
 @pytest.mark.parametrize("seed", sd.SEEDS["pipeline"])
@@ -310,3 +540,132 @@ def test_the_generator_notices_a_dropped_requirement():
         sd.assert_covers("pipeline", [op for op in ops if op[0] not in sd.ASYNC and op[0] != "adaptive_collect"])
     with pytest.raises(AssertionError):
         sd.assert_covers("ragged", ops)
+
+
+# ---- the leapfrog kinds ---------------------------------------------------------------------------------------------------------
+
+def lf_members(kind):
+    return B if kind == "batch-lf" else 0
+
+
+def caught_by(kind, seed, fault):
+    """None: the sequence passes; else the SequenceMismatch"""
+    ops = sd.generate(kind, seed, members=lf_members(kind))
+    try:
+        sd.check(lf_maker(kind, fault), ops, LF_ENVS[kind], seed)
+    except sd.SequenceMismatch as e:
+        return e
+    return None
+
+
+@pytest.mark.parametrize("kind", sorted(LF_FAULTS_OF))
+def test_without_a_fault_every_committed_leapfrog_seed_passes(kind):
+    for seed in sd.SEEDS[kind]:
+        ops = sd.generate(kind, seed, members=lf_members(kind))
+        assert sd.check(lf_maker(kind), ops, LF_ENVS[kind], seed) > len(ops) // 2
+
+
+@pytest.mark.parametrize("kind,fault", [(k, f) for k in sorted(LF_FAULTS_OF) for f in LF_FAULTS_OF[k]])
+def test_every_planted_leapfrog_fault_is_caught_by_a_committed_seed(kind, fault):
+    caught = []
+    for seed in sd.SEEDS[kind]:
+        e = caught_by(kind, seed, fault)
+        if e is not None:
+            ops = sd.generate(kind, seed, members=lf_members(kind))
+            assert e.seed == seed and e.index >= first_touch(fault, ops), (LF_FAULTS[fault], e.index, first_touch(fault, ops))
+            assert e.name == (ops[e.index][0] if e.index < len(ops) else "final state")
+            assert f"seed {seed}" in str(e) and sd.show(ops[0]) in str(e)
+            if fault == 16:
+                assert "last_leapfrog_info" in str(e)          # the bits agree: only the second oracle sees it
+            caught.append(seed)
+    assert caught, f"no committed seed of {kind} notices: {LF_FAULTS[fault]}"
+
+
+@pytest.mark.parametrize("kind", sorted(LF_FAULTS_OF))
+def test_the_leapfrog_seeds_are_the_first_pair_that_catches_every_fault(kind):
+    """The rule of the module docstring, recomputed; candidates that do not generate or do not pass clean are left out."""
+    catches = {}
+    for seed in range(max(sd.SEEDS[kind]) + 1):
+        try:
+            if caught_by(kind, seed, 0) is None:
+                catches[seed] = {f for f in LF_FAULTS_OF[kind] if caught_by(kind, seed, f) is not None}
+        except AssertionError:
+            continue          # assert_covers: this seed names no sequence
+
+    def good(pair):
+        if catches[pair[0]] | catches[pair[1]] != set(LF_FAULTS_OF[kind]):
+            return False
+        try:
+            for members in UNION_MEMBERS[kind]:          # the member counts of the GPU rows: get_member draws depend on them
+                sd.assert_union_covers(kind, [sd.generate(kind, seed, members=members) for seed in pair])
+        except AssertionError:
+            return False
+        return True
+    pairs = (p for p in itertools.combinations(sorted(catches), 2) if good(p))
+    assert next(pairs) == tuple(sd.SEEDS[kind]), {s: sorted(c) for s, c in catches.items()}
+
+
+UNION_MEMBERS = {"pipeline-lf": (0,), "batch-lf": (3, 5)}
+
+
+@pytest.mark.parametrize("kind,members", [(k, m) for k in sorted(UNION_MEMBERS) for m in UNION_MEMBERS[k]])
+def test_the_committed_leapfrog_sequences_issue_every_operation_between_them(kind, members):
+    """at the member counts the GPU rows run, too (get_member draws depend on them)"""
+    sd.assert_union_covers(kind, [sd.generate(kind, seed, members=members) for seed in sd.SEEDS[kind]])
+
+
+@pytest.mark.parametrize("kind", sorted(LF_FAULTS_OF))
+def test_committed_leapfrog_sequences_hold_what_they_must(kind):
+    for seed in sd.SEEDS[kind]:
+        ops = sd.generate(kind, seed, members=lf_members(kind))
+        sd.assert_covers(kind, ops)
+        assert sd.LF_LENGTH <= len(ops) <= sd.LF_LENGTH + 4
+        assert ops == sd.generate(kind, seed, members=lf_members(kind))
+        assert not any(a.get("resume") for _, a in ops)
+        if kind == "batch-lf":
+            assert not any(name == "update_leapfrog_async" for name, _ in ops)
+
+
+def test_the_generator_notices_a_dropped_leapfrog_piece():
+    ops = sd.generate("batch-lf", sd.SEEDS["batch-lf"][0], members=B)
+    with pytest.raises(AssertionError, match="trace"):
+        sd.assert_covers("batch-lf", [op for op in ops if op[0] != "trace"])
+    ops = sd.generate("pipeline-lf", sd.SEEDS["pipeline-lf"][0])
+    with pytest.raises(AssertionError, match="64"):
+        sd.assert_covers("pipeline-lf", [op for op in ops if not (op[0] in sd.ADAPTIVE and op[1]["n"] > 64)])
+    with pytest.raises(AssertionError, match="update_leapfrog_async"):
+        sd.assert_covers("pipeline-lf", [op for op in ops if op[0] != "update_leapfrog_async"])
+    with pytest.raises(AssertionError, match="in a row"):
+        sd.assert_covers("pipeline-lf", [op for i, op in enumerate(ops) if not (i and sd.is_leapfrog(op) and sd.is_leapfrog(ops[i - 1]))])
+
+
+def test_the_premise_is_asserted():
+    bad = world(1)
+    bad[3, 2] = -0.0
+    with pytest.raises(AssertionError, match="-0.0"):
+        sd.assert_premise(bad)
+    bad[3, 2] = np.inf
+    with pytest.raises(AssertionError, match="finite"):
+        sd.assert_premise(bad)
+
+
+# generate(kind, seed) of the kinds that existed before the leapfrog kinds, as sha256 of repr(ops): those sequences are what
+# the GPU rows of these kinds have always run, and new code paths of the generator must not move them
+OLD_SEQUENCES = {
+    ("pipeline", 0, 5): "dda975947a605c1d9a64bb1f74159cf6ac82039916466a8851c1b036f369a700",
+    ("pipeline", 0, 8): "8e6dc8b354dca0e4d81e8316ec1e10e96d047428d76b6c2a1137d32479920d5a",
+    ("pipeline", 0, 11): "cf84664908413741d250d581635a96b7336c3de444a54b1597ebea88d48c27b0",
+    ("batch", 5, 5): "23c9cd156ddf97a3e5f1ade6ad7412023b2b4b4587d484871cc17bd15d906888",
+    ("batch", 5, 8): "5552582e06e4823bf216d0564d155efb0ed080a28640610b5bb53ccd25861410",
+    ("batch", 3, 5): "edb86b33734249bd61b723093418b409ee493cd51ea69cba3fc4a3bb389ca095",
+    ("batch", 3, 8): "5552582e06e4823bf216d0564d155efb0ed080a28640610b5bb53ccd25861410",
+    ("ragged", 12, 5): "04a2856e26e0b414a5f1698a4d8c67eb47b96dfacf93140c895f82303cd2495a",
+    ("ragged", 12, 8): "e13dfd1687918aa805171449ab74d2b5b1f8917d6615d5d49b19da90e993437d",
+}
+
+
+@pytest.mark.parametrize("kind,members,seed", sorted(OLD_SEQUENCES))
+def test_the_sequences_of_the_old_kinds_have_not_moved(kind, members, seed):
+    ops = sd.generate(kind, seed, members=members)
+    assert hashlib.sha256(repr(ops).encode()).hexdigest() == OLD_SEQUENCES[(kind, members, seed)]
+    assert not any(sd.is_leapfrog(op) or op[0] in sd.LEAPFROG for op in ops)
