@@ -7,7 +7,7 @@
 #pragma once
 
 #include "pipeline_internal.h"
-#include "batch_render.h"
+#include "render_kernels.h"
 
 struct SimBatch {
     uint32_t count = 0;     // members
@@ -67,13 +67,13 @@ struct SimBatch {
     int trace_fused = 0;         // what the last traced call did
     uint32_t trace_launches = 0;
 
-    // nb_hip_ensemble_bounds / _render_counts / _render_rgba (kernels: batch_render.hip): scratch made on first use, an
+    // nb_hip_ensemble_bounds / _render_counts / _render_rgba (kernels: render_kernels.hip): scratch made on first use, an
     // interval of their own
     nbi::DevBuf<RenderView> render_views;      // [count]: the views of the last call
     nbi::DevBuf<uint32_t> render_keys;         // [count][4]
     nbi::DevBuf<uint32_t> render_counts;       // tile path: [count][3][h][w]; global path: the disc cursor behind them
     nbi::DevBuf<uint32_t> render_rgba;         // [count][h][w]
-    nbi::DevBuf<nbr::EnsembleDisc> render_discs;   // global path: [count * n]
+    nbi::DevBuf<nb::render::Disc> render_discs;    // global path: [count * n]
     nbi::Interval render_iv;
     int render_mode = 0;                     // tuning hook: 1 = the global path also where the tile path applies
     int render_tile = 0;                     // what the last render did (a bounds call leaves both alone)

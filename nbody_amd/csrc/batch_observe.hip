@@ -1,5 +1,5 @@
 // batch_observe.hip -- the read-only calls on a SimBatch: energy and potential of every member (kernels: batch_diag.hip),
-// bounds, count images and frames (kernels: batch_render.hip), with their tuning hooks and timers.  Each
+// bounds, count images and frames (kernels: render_kernels.hip), with their tuning hooks and timers.  Each
 // looks at the latest state without reading the particles back: a constant number of launches, one copy, one sync for any B.
 #include "batch_internal.h"
 #include "batch_diag.h"
@@ -8,6 +8,7 @@
 #include "render_common.h"
 
 using namespace nbi;
+namespace rd = nb::render;
 
 namespace {
 
@@ -76,15 +77,15 @@ void check_views(const SimBatch *s, const RenderView *views, const char *what) {
 void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint32_t *launches) {
     const uint32_t width = views[0].width, height = views[0].height;
     const size_t plane = (size_t)width * height;
-    const bool tile = nbr::tile_fits(width, height) && s->render_mode == 0;
+    const bool tile = rd::tile_fits(width, height) && s->render_mode == 0;
     if (!s->render_views) s->render_views.alloc(s->count);
     if (palette) s->render_rgba.grown(s->stream, (size_t)s->count * plane);
-    if (!tile || !palette) s->render_counts.grown(s->stream, nbr::global_count_words(s->count, width, height));
+    if (!tile || !palette) s->render_counts.grown(s->stream, rd::global_count_words(s->count, width, height));
     if (!tile && !s->render_discs) s->render_discs.alloc((size_t)s->count * s->n);
     ASSERT_HIP(hipMemcpyAsync(s->render_views, views, (size_t)s->count * sizeof(RenderView), hipMemcpyHostToDevice, s->stream),
                "H2D of %u views", s->count);
     s->render_iv.begin(s->stream);
-    nbr::EnsembleRenderParams p{};
+    rd::EnsembleRenderParams p{};
     p.pos = s->pos[s->cur];
     p.mass = s->mass;
     p.radius = s->radius;
@@ -95,15 +96,15 @@ void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *p
     p.height = height;
     p.views = s->render_views;
     if (tile) {
-        nbr::launch_ensemble_tile(s->stream, p, s->render_counts, palette, s->render_rgba);
+        rd::launch_ensemble_tile(s->stream, p, s->render_counts, palette, s->render_rgba);
         *launches = 1;
     } else {
-        ASSERT_HIP(hipMemsetAsync(s->render_counts, 0, nbr::global_count_words(s->count, width, height) * sizeof(uint32_t), s->stream),
+        ASSERT_HIP(hipMemsetAsync(s->render_counts, 0, rd::global_count_words(s->count, width, height) * sizeof(uint32_t), s->stream),
                    "clear %u count images and the disc cursor", s->count);
-        nbr::launch_ensemble_global(s->stream, p, s->render_counts, s->render_discs);
+        rd::launch_ensemble_global(s->stream, p, s->render_counts, s->render_discs);
         *launches = 3;
         if (palette) {
-            nbr::launch_ensemble_shade(s->stream, s->render_counts, s->count, (uint32_t)plane, *palette, s->render_rgba);
+            rd::launch_ensemble_shade(s->stream, s->render_counts, s->count, (uint32_t)plane, *palette, s->render_rgba);
             *launches = 4;
         }
     }
@@ -164,7 +165,7 @@ void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {
     use_device();
     s->render_iv.begin(s->stream);
     if (!s->render_keys) s->render_keys.alloc((size_t)s->count * 4);
-    nbr::launch_ensemble_bounds(s->stream, s->pos[s->cur], s->n, s->stride, s->count, s->render_keys);
+    rd::launch_ensemble_bounds(s->stream, s->pos[s->cur], s->n, s->stride, s->count, s->render_keys);
     ASSERT_HIP(hipGetLastError(), "ensemble_bounds_kernel launch (%u members of %u)", s->count, s->n);
     s->render_iv.end(s->stream);   // the interval is shared with the renders; render_tile / render_launches speak of renders only
     std::vector<uint32_t> keys((size_t)s->count * 4);

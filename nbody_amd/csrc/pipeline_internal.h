@@ -25,6 +25,7 @@
 //   batch_diag.hip   the same for every member of a SimBatch, uniform or ragged: the kernels behind nb_hip_ensemble_energy / _potential
 //                    (batch_diag.h; the arithmetic both share: diag_common.h)
 //   render.hip       bounds, count image and RGBA frame of the state a pipeline holds (nb_hip_bounds, nb_hip_render_*)
+//   render_kernels.hip  the render kernels of a world and of an ensemble, what they share written once, and their launchers (render_kernels.h)
 //   field.hip        the potential and the acceleration at probe points and as maps over a view (nb_hip_potential_at,
 //                    nb_hip_potential_map, nb_hip_acceleration_at, nb_hip_acceleration_map): one sampler, two pair statements
 //   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
@@ -49,6 +50,7 @@
 #include "kernels.h"
 #include "launch_shape.h"
 #include "nbody_hip.h"
+#include "render_kernels.h"
 
 // ---- error convention: print where, abort (reference src/lib/util.h:17-29,47-60) -------------------------
 
@@ -78,7 +80,6 @@
 #define NB_HIDDEN __attribute__((visibility("hidden")))   // not among the library's exported symbols
 
 typedef struct ncclComm *ncclComm_t;  // opaque; rccl_bind.hip holds the rest of the binding
-struct NbSplat;                       // render_common.h: an entry of the pipeline's disc list
 
 namespace nbi {
 
@@ -418,9 +419,9 @@ struct SimPipeline {
     nbi::DevBuf<float> diag_phi;   // nb_hip_potential's device result
     nbi::Interval diag_iv;
 
-    // render.hip (nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba): buffers grown on demand, events of their own
+    // render.hip (nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba; kernels: render_kernels.hip): buffers grown on demand, events of their own
     nbi::DevBuf<uint32_t> render_counts;   // count image [3][height][width]
-    nbi::DevBuf<NbSplat> render_discs;     // compact disc list, total_len entries
+    nbi::DevBuf<nb::render::Disc> render_discs;   // compact disc list, total_len entries
     nbi::DevBuf<uint32_t> render_words;    // [0] discs appended by the last splat, [4..7] the bounds' ordered keys
     nbi::DevBuf<uint32_t> render_rgba;     // frame, one packed RGBA word per pixel
     nbi::Interval render_iv, bounds_iv;

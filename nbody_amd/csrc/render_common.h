@@ -1,5 +1,5 @@
 /*
- * render_common.h -- the arithmetic of include/nbody_render.h written once, for the GPU path (render.hip) and the host
+ * render_common.h -- the arithmetic of include/nbody_render.h written once, for the GPU path (render_kernels.hip) and the host
  * path (render_cpu.c): the screen transform and classification of one particle, the pixel test of a disc, the candidate
  * box of a disc, the shade of one pixel, the total order of floats the bounds use, and the checks of a view and of an ensemble's views.  Both
  * translation units build with -ffp-contract=off, so every float32 operation below is rounded on its own on both sides.

@@ -19,8 +19,8 @@
  * on the device when it holds the newest state, without pulling the array, and
  * on the host (diag_cpu.c) otherwise; neither moves a dirty flag.
  * Extension (include/nbody_render.h): GetWorldBounds / FitWorldView /
- * RenderWorldCounts / RenderWorld follow the same rule (render.hip on the
- * device, render_cpu.c on the host).
+ * RenderWorldCounts / RenderWorld follow the same rule (render.hip and the
+ * kernels of render_kernels.hip on the device, render_cpu.c on the host).
  * Extension (include/nbody_field.h): GetWorldPotentialAt / RenderWorldPotential
  * follow the same rule (field.hip on the device, field_cpu.c on the host).
  * Extension (include/nbody_gravity.h): GetWorldAccelerationAt /

@@ -61,7 +61,7 @@ def test_the_library_exports_the_new_surface_and_the_hooks_stay_out_of_the_publi
         assert re.search(r"\b%s\s*\(" % name, public), name
     assert "WorldBatch is not covered" not in open(os.path.join(ROOT, "include", "nbody_render.h")).read()
     make = open(os.path.join(ROOT, "nbody_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^HIP_TUS\s*:=.*\bbatch_render\b", make, re.M)
+    assert re.search(r"^HIP_TUS\s*:=.*\brender_kernels\b", make, re.M)
 
 
 @pytest.mark.parametrize("count", [1, 3])

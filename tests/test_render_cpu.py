@@ -1,6 +1,6 @@
 """Rendering (include/nbody_render.h) without a GPU: the host path of GetWorldBounds / FitWorldView / RenderWorldCounts /
 RenderWorld against the numpy restatement of the definitions (tests/render_ref.py), BITWISE; the header / binding / export
-agreement; and static checks on the ISA of nbody_amd/csrc/render.hip."""
+agreement; and static checks on the ISA of nbody_amd/csrc/render_kernels.hip (the kernels of a world and of an ensemble)."""
 import ctypes as C
 import os
 import re
@@ -365,24 +365,32 @@ def test_a_sharded_world_aborts_with_the_diagnostics_message():
     assert re.search(r"\.c:\d+ \[\w+\]", r.stderr) and "sharded pipeline needs a collective" in r.stderr, r.stderr
 
 
-# ---- static ISA of render.hip -----------------------------------------------------------------------------------------------------
+# ---- static ISA of render_kernels.hip -----------------------------------------------------------------------------------------------------
 
 @pytest.fixture(scope="module")
 def render_isa(tmp_path_factory):
-    return compile_isa(tmp_path_factory.mktemp("render_isa"), "render.hip")
+    return compile_isa(tmp_path_factory.mktemp("render_isa"), "render_kernels.hip")
 
 
 def test_render_kernels_exist_without_scratch_and_add_with_native_integer_atomics(render_isa):
     make = open(os.path.join(ROOT, "nbody_amd", "csrc", "Makefile")).read()
     assert re.search(r"^HIP_TUS\s*:=.*\brender\b", make, re.M) and re.search(r"^WORLD_SRCS\s*:=.*render_cpu\.c", make, re.M)
+    assert re.search(r"^HIP_TUS\s*:=.*\brender_kernels\b", make, re.M)
     meta = kernel_meta(render_isa)
-    for kernel in ("bounds_kernel", "splat_kernel", "disc_kernel", "shade_kernel"):
+    for kernel in ("bounds_kernel", "splat_kernel", "disc_kernel", "shade_kernel", "ensemble_bounds_kernel", "ensemble_splat_kernel",
+                   "ensemble_tile_kernel", "ensemble_disc_kernel", "ensemble_shade_kernel"):
         rows = [m for m in meta if kernel in m[0]]
         assert rows and all(m[0].startswith("_ZN2nb") for m in rows), (kernel, [m[0] for m in meta])
         for name, scratch, sgpr, vgpr in rows:
             print(f"[render isa] {name}: scratch {scratch}, {sgpr} SGPRs, {vgpr} VGPRs")
             assert scratch == 0 and vgpr <= 64, (name, scratch, vgpr)     # 64 VGPRs: eight waves per SIMD
-    assert len([m for m in meta if "splat_kernel" in m[0]]) == 2      # the shipped merge and the one-atomic-per-lane A/B build
+    # a world's splat: the shipped merge and the one-atomic-per-lane A/B build; the tile kernel: counts and frames; the disc pass
+    # and the shade: one plain kernel for a world, one for an ensemble (DESIGN.md "Rendering an ensemble" says why not one for both)
+    instances = {k: len([m for m in meta if re.search(r"\d%s(I|E)" % k, m[0])])
+                 for k in ("splat_kernel", "ensemble_splat_kernel", "ensemble_tile_kernel", "disc_kernel", "shade_kernel",
+                           "ensemble_disc_kernel", "ensemble_shade_kernel")}
+    assert instances == {"splat_kernel": 2, "ensemble_splat_kernel": 1, "ensemble_tile_kernel": 2, "disc_kernel": 1, "shade_kernel": 1,
+                         "ensemble_disc_kernel": 1, "ensemble_shade_kernel": 1}, instances
     body = functions(render_isa)
     ops = {k: [i.split()[0] for i in v] for k, v in body.items()}
     # the 32-bit unsigned integer add: gfx950 (like every gfx9) spells it global_atomic_add; gfx11+ assemblers print the same
@@ -393,11 +401,13 @@ def test_render_kernels_exist_without_scratch_and_add_with_native_integer_atomic
             assert any(add.match(o) for o in ops[name]), name
     every = [o for v in ops.values() for o in v]
     assert not [o for o in every if "cmpswap" in o or "atomic_add_f" in o or "atomic_pk" in o or o.startswith("scratch_")]
+    # every atomic on device memory is a global_ one, never flat_ or buffer_ (the tile kernel's LDS adds are ds_ operations)
     assert not [o for o in every if "atomic" in o and not o.startswith("global_atomic_")]
     # no-return adds (no sc0) on the count image; the only returning add is the disc list's cursor
     merged = next(n for n in body if "splat_kernel" in n and "Lb1" in n)
-    adds = [i for i in body[merged] if add.match(i.split()[0])]
-    assert [i for i in adds if "sc0" not in i] and any("sc0" in i for i in adds)
+    for name in [n for n in body if "splat_kernel" in n]:   # a world's two and the ensemble's
+        adds = [i for i in body[name] if add.match(i.split()[0])]
+        assert [i for i in adds if "sc0" not in i] and any("sc0" in i for i in adds), name
     assert all("sc0" not in i for n in body if "disc_kernel" in n for i in body[n] if add.match(i.split()[0]))
     # the merge: a broadcast of the first live lane's word and a population count of the ballot
     assert "v_readlane_b32" in ops[merged] and any(o.startswith("s_bcnt1_i32_b64") for o in ops[merged])
