@@ -572,6 +572,38 @@ uint32_t nb_hip_ragged_launch_shape(const SimBatch *batch, uint32_t group, int *
 void nb_hip_ragged_member_shape(const SimBatch *batch, uint32_t member, uint32_t *group, int *k, int *w, int *lanes);
 
 /*
+ * The potential and the acceleration field of EVERY member of an ensemble away from its particles, in one launch
+ * (definitions: include/nbody_field.h and include/nbody_gravity.h with M = mass_len[b]; the World-level calls are
+ * include/nbody_batch_field.h; kernel: nbody_amd/csrc/batch_field.hip).  Every member has the same number of samples:
+ *   nb_hip_ensemble_potential_at      phi[count][n]: Phi(points[b][i]; softening) of member b, points[count][n] (x, y) pairs
+ *   nb_hip_ensemble_potential_map     phi[count][height][width]: Phi at every pixel centre of views[b], one view per member
+ *   nb_hip_ensemble_acceleration_at   acc[count][n][2]: g at the same kind of points
+ *   nb_hip_ensemble_acceleration_map  acc[count][height][width][2]
+ * Member b's values are BIT-IDENTICAL to nb_hip_potential_at / _map / nb_hip_acceleration_at / _map of a SimPipeline holding
+ * the same particles, on either of that pipeline's kernel shapes: they do not depend on count, on the member's index, on the
+ * other members or on their sizes.  Uniform and ragged ensembles alike (a ragged member's sources are its mass_len[b], the
+ * samples are not packed: n per member).  One softening per call, finite and > 0.  A point with a non-finite coordinate
+ * gives NaN in every component, a member with mass_len[b] = 0 gives 0, n = 0 does nothing and touches no device.  All views
+ * share width and height (a mismatch aborts, naming the first member that differs) and each is within the limits of
+ * include/nbody_render.h; the host computes every view's width column and height row coordinates, so a map is exactly the
+ * probes product at the member's pixel centres, row-major.  count * n and count * width * height are each at most 2^24.
+ * Each call is one upload, one launch, one copy and one stream sync for any count.  Like the diagnostics: enqueued on the
+ * ensemble's stream behind any nb_hip_batch_step_async work, they read the buffer that holds the latest state, block until
+ * the result is on the host and change nothing observable (the state, the ping-pong phase, the step sizes,
+ * nb_hip_batch_dt_uploads and nb_hip_batch_last_ms are as before).  Scratch belongs to the SimBatch, grows on demand and is
+ * freed by nb_hip_batch_destroy.  Abort before nb_hip_batch_set_data, for a NULL argument, a softening that is not finite
+ * and > 0, an invalid view and too many samples.  Added WITHOUT a version bump: detect them by symbol
+ * (dlsym "nb_hip_ensemble_potential_map").
+ */
+void nb_hip_ensemble_potential_at(SimBatch *batch, const float *points /* [count][n][2] */, uint32_t n, float softening,
+                                  float *phi /* [count][n] */);
+void nb_hip_ensemble_potential_map(SimBatch *batch, const RenderView *views /* [count] */, float softening, float *phi /* [count][h][w] */);
+void nb_hip_ensemble_acceleration_at(SimBatch *batch, const float *points /* [count][n][2] */, uint32_t n, float softening,
+                                     float *acc /* [count][n][2] */);
+void nb_hip_ensemble_acceleration_map(SimBatch *batch, const RenderView *views /* [count] */, float softening,
+                                      float *acc /* [count][h][w][2] */);
+
+/*
  * Adaptive time steps chosen on the device (definitions: include/nbody_adaptive.h; kernels: nbody_amd/csrc/timestep.hip).
  *   nb_hip_adaptive_steps         n steps, each of the size the criterion gives for the state before it; blocking
  *   nb_hip_adaptive_steps_async   the same, enqueue only

@@ -206,6 +206,10 @@ HIP_API = {
                                                 C.POINTER(C.c_int), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "nb_hip_ragged_member_shape": (None, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                           C.POINTER(C.c_int)]),
+    "nb_hip_ensemble_potential_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "nb_hip_ensemble_potential_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    "nb_hip_ensemble_acceleration_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "nb_hip_ensemble_acceleration_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_adaptive_steps": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
     "nb_hip_adaptive_steps_async": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive)]),
     "nb_hip_adaptive_collect": (None, [C.c_void_p, C.c_void_p, C.POINTER(NbAdaptiveResult)]),
@@ -244,7 +248,7 @@ PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
 # include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h +
-# include/nbody_adaptive.h + include/nbody_leapfrog.h
+# include/nbody_adaptive.h + include/nbody_leapfrog.h + include/nbody_batch_field.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -290,6 +294,11 @@ NBODY_API = {
     "RenderWorldBatch": (None, [C.c_void_p, C.POINTER(RenderView), C.POINTER(RenderPalette), C.c_void_p]),
     # include/nbody_batch_ragged.h
     "CreateWorldBatchRagged": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
+    # include/nbody_batch_field.h
+    "GetWorldBatchPotentialAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "RenderWorldBatchPotential": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    "GetWorldBatchAccelerationAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "RenderWorldBatchAcceleration": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     # include/nbody_adaptive.h
     "UpdateWorld_GPU_Adaptive": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
     "UpdateWorld_CPU_Adaptive": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
@@ -709,6 +718,31 @@ def _dt_array(dts, count):
     return a
 
 
+def _member_points(points, count):
+    """(n, 2) points for every member, or (count, n, 2) with one set per member -> contiguous float32 (count, n, 2)."""
+    a = np.asarray(points, dtype=np.float32)
+    if a.ndim == 2:
+        a = np.broadcast_to(a, (count,) + a.shape)
+    if a.ndim != 3 or a.shape[0] != count or a.shape[2] != 2:
+        raise ValueError(f"points must have shape (n, 2) or ({count}, n, 2)")
+    return np.ascontiguousarray(a)
+
+
+def _ensemble_field(fn, handle, count, components, softening, points=None, views=None):
+    """One of the four field calls of an ensemble (fn: nb_hip_ensemble_* of a SimBatch, include/nbody_batch_field.h of a
+    WorldBatch) at `points` or, where they are None, under `views`: float32 (B, n) / (B, h, w), with a last axis of 2 for g."""
+    tail = (2,) if components == 2 else ()
+    if points is not None:
+        pts = _member_points(points, count)
+        out = np.empty((count, pts.shape[1]) + tail, dtype=np.float32)
+        fn(handle, pts.ctypes.data, pts.shape[1], softening, out.ctypes.data)
+        return out
+    arr, w, h = _view_array(views, count)
+    out = np.empty((count, h, w) + tail, dtype=np.float32)
+    fn(handle, arr, softening, out.ctypes.data)
+    return out
+
+
 def _view_array(views, count):
     """One RenderView for every member, or a sequence of `count` of them -> (RenderView[count], width, height)."""
     if isinstance(views, RenderView):
@@ -897,8 +931,28 @@ class SimBatch:
         hip_lib().nb_hip_ensemble_potential(self._h, out.ctypes.data)
         return out
 
+    def potential_at(self, points, softening):
+        """nb_hip_ensemble_potential_at: Phi of every member at its points -- (n, 2) for all members or (B, n, 2), one set
+        per member -- with one softening; float32 (B, n).  Member b's row is bit-identical to SimPipeline.potential_at of
+        the same particles.  Ragged ensembles included."""
+        return _ensemble_field(hip_lib().nb_hip_ensemble_potential_at, self._h, self.count, 1, softening, points=points)
+
+    def potential_map(self, views, softening):
+        """nb_hip_ensemble_potential_map: Phi at every pixel centre, float32 (B, height, width); views: one RenderView for
+        all, or one per member."""
+        return _ensemble_field(hip_lib().nb_hip_ensemble_potential_map, self._h, self.count, 1, softening, views=views)
+
+    def acceleration_at(self, points, softening):
+        """nb_hip_ensemble_acceleration_at: g of every member at its points, float32 (B, n, 2)."""
+        return _ensemble_field(hip_lib().nb_hip_ensemble_acceleration_at, self._h, self.count, 2, softening, points=points)
+
+    def acceleration_map(self, views, softening):
+        """nb_hip_ensemble_acceleration_map: g at every pixel centre, float32 (B, height, width, 2)."""
+        return _ensemble_field(hip_lib().nb_hip_ensemble_acceleration_map, self._h, self.count, 2, softening, views=views)
+
     def last_diag_ms(self):
-        """tuning hook: device ms of the kernels of the last energy() / potential()."""
+        """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
+        acceleration_at() / acceleration_map()."""
         return float(hip_lib().nb_hip_ensemble_last_diag_ms(self._h))
 
     def bounds(self):
@@ -1069,6 +1123,23 @@ class WorldBatch:
         out = np.empty((self.count, self.size), dtype=np.float32)
         nbody_lib().GetWorldBatchPotential(self._h, out.ctypes.data)
         return out
+
+    def potential_at(self, points, softening):
+        """GetWorldBatchPotentialAt (include/nbody_batch_field.h): Phi of every member at its points -- (n, 2) for all
+        members or (B, n, 2) -- float32 (B, n); ragged batches included."""
+        return _ensemble_field(nbody_lib().GetWorldBatchPotentialAt, self._h, self.count, 1, softening, points=points)
+
+    def potential_map(self, views, softening):
+        """RenderWorldBatchPotential: float32 (B, height, width); views: one RenderView for all, or one per member."""
+        return _ensemble_field(nbody_lib().RenderWorldBatchPotential, self._h, self.count, 1, softening, views=views)
+
+    def acceleration_at(self, points, softening):
+        """GetWorldBatchAccelerationAt: g of every member at its points, float32 (B, n, 2)."""
+        return _ensemble_field(nbody_lib().GetWorldBatchAccelerationAt, self._h, self.count, 2, softening, points=points)
+
+    def acceleration_map(self, views, softening):
+        """RenderWorldBatchAcceleration: float32 (B, height, width, 2)."""
+        return _ensemble_field(nbody_lib().RenderWorldBatchAcceleration, self._h, self.count, 2, softening, views=views)
 
     def bounds(self):
         """GetWorldBatchBounds (include/nbody_batch_render.h): float32 (B, 4)."""

@@ -1,9 +1,12 @@
 // batch_observe.hip -- the read-only calls on a SimBatch: energy and potential of every member (kernels: batch_diag.hip),
-// bounds, count images and frames (kernels: render_kernels.hip), with their tuning hooks and timers.  Each
+// bounds, count images and frames (kernels: render_kernels.hip), the potential and the acceleration field at probe points and
+// over views (kernel: batch_field.hip), with their tuning hooks and timers.  Each
 // looks at the latest state without reading the particles back: a constant number of launches, one copy, one sync for any B.
 #include "batch_internal.h"
 #include "batch_diag.h"
+#include "batch_field.h"
 #include "diag_sums.h"
+#include "field_common.h"
 #include "nbody_hip_tuning.h"
 #include "render_common.h"
 
@@ -115,6 +118,72 @@ void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *p
     s->render_launches = *launches;
 }
 
+// ---- fields: Phi and g of every member at n samples each, without reading the particles back ------------------------
+
+// what a field call checks before it looks at its samples; `samples` = all members' together
+void check_field(SimBatch *s, const char *what, float softening, uint64_t samples) {
+    NB_ASSERT(s != nullptr, "NULL ensemble");
+    NB_ASSERT(s->has_data, "%s before nb_hip_batch_set_data", what);
+    const char *fault = nb_field_fault(softening, samples);
+    NB_ASSERT(fault == nullptr, "%s: invalid call (softening %g, %u members, %llu points in all): %s", what, (double)softening, s->count,
+              (unsigned long long)samples, fault);
+}
+
+// upload `in_stride` floats per member, evaluate n samples of every member in one launch, one copy of the result, one sync;
+// `in` stays alive until the sync
+void sample_members(SimBatch *s, const char *what, bool acceleration, bool map, const float *in, uint32_t in_stride, uint32_t n,
+                    uint32_t width, float softening, float *out) {
+    const size_t in_floats = (size_t)s->count * in_stride, out_floats = (size_t)s->count * n * (acceleration ? 2 : 1);
+    use_device();
+    s->sample_in.grown(s->stream, in_floats);
+    s->sample_out.grown(s->stream, out_floats);
+    ASSERT_HIP(hipMemcpyAsync(s->sample_in, in, in_floats * sizeof(float), hipMemcpyHostToDevice, s->stream), "%s: H2D of %u members' samples",
+               what, s->count);
+    nb::field::EnsembleParams p{};
+    p.pos = s->pos[s->cur];
+    p.gm = s->gm;
+    p.mass_len = s->mass_len_dev;
+    p.stride = s->stride;
+    p.in = s->sample_in;
+    p.in_stride = in_stride;
+    p.n = n;
+    p.width = width;
+    p.soft = softening;
+    p.out = s->sample_out;
+    s->diag_iv.begin(s->stream);
+    nb::field::launch_ensemble_sample(s->stream, p, s->count, acceleration, map);
+    ASSERT_HIP(hipGetLastError(), "%s: ensemble_sample_kernel launch (%u members, %u samples each)", what, s->count, n);
+    s->diag_iv.end(s->stream);
+    ASSERT_HIP(hipMemcpyAsync(out, s->sample_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream), "%s: D2H of %u members' results",
+               what, s->count);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after %s", what);
+}
+
+void sample_members_at(SimBatch *s, const char *what, bool acceleration, const float *points, uint32_t n, float softening, float *out) {
+    check_field(s, what, softening, s ? (uint64_t)s->count * n : 0);
+    NB_ASSERT((points != nullptr && out != nullptr) || n == 0, "%s: NULL points or result", what);
+    if (n == 0) {
+        s->diag_iv.clear();
+        return;
+    }
+    sample_members(s, what, acceleration, false, points, 2 * n, n, 0, softening, out);
+}
+
+// a map is the probes product at the member's own pixel centres: per member width column coordinates, then height row coordinates
+void sample_members_map(SimBatch *s, const char *what, bool acceleration, const RenderView *views, float softening, float *out) {
+    check_field(s, what, softening, 0);
+    check_views(s, views, what);
+    const uint32_t width = views[0].width, height = views[0].height;
+    check_field(s, what, softening, (uint64_t)s->count * width * height);
+    NB_ASSERT(out != nullptr, "%s: NULL result array", what);
+    std::vector<float> coords((size_t)s->count * (width + height));
+    for (uint32_t b = 0; b < s->count; b++) {
+        float *xs = coords.data() + (size_t)b * (width + height);
+        nb_render_pixel_centres(&views[b], xs, xs + width);
+    }
+    sample_members(s, what, acceleration, true, coords.data(), width + height, width * height, width, softening, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -151,7 +220,23 @@ void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_potential");
 }
 
-// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_ensemble_energy / _potential
+void nb_hip_ensemble_potential_at(SimBatch *s, const float *points, uint32_t n, float softening, float *phi) {
+    sample_members_at(s, "nb_hip_ensemble_potential_at", false, points, n, softening, phi);
+}
+
+void nb_hip_ensemble_potential_map(SimBatch *s, const RenderView *views, float softening, float *phi) {
+    sample_members_map(s, "nb_hip_ensemble_potential_map", false, views, softening, phi);
+}
+
+void nb_hip_ensemble_acceleration_at(SimBatch *s, const float *points, uint32_t n, float softening, float *acc) {
+    sample_members_at(s, "nb_hip_ensemble_acceleration_at", true, points, n, softening, acc);
+}
+
+void nb_hip_ensemble_acceleration_map(SimBatch *s, const RenderView *views, float softening, float *acc) {
+    sample_members_map(s, "nb_hip_ensemble_acceleration_map", true, views, softening, acc);
+}
+
+// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_ensemble_energy / _potential / field call
 double nb_hip_ensemble_last_diag_ms(SimBatch *s) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
     if (!s->diag_iv.valid()) return 0.0;

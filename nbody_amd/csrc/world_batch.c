@@ -18,11 +18,15 @@
  * chooses per member and step: same upload, same coherence; ragged batches abort.
  * include/nbody_leapfrog.h: UpdateWorldBatch_GPU_Leapfrog(_dts) are updates of kick-drift-kick steps: same upload, same
  * coherence; ragged batches abort.
+ * include/nbody_batch_field.h: the potential and the acceleration field of every member at probe points and over views follow
+ * the diagnostics' protocol (device: nb_hip_ensemble_potential_at and its three siblings, one launch; host: field_cpu.c member
+ * by member), for uniform and ragged batches alike.
  */
 #include "nbody_adaptive.h"
 #include "nbody_leapfrog.h"
 #include "nbody_batch.h"
 #include "nbody_batch_diag.h"
+#include "nbody_batch_field.h"
 #include "nbody_batch_ragged.h"
 #include "nbody_batch_render.h"
 #include "nbody_batch_trace.h"
@@ -31,6 +35,7 @@
 #include <stdbool.h>
 
 #include "diag_sums.h"
+#include "field_common.h"
 #include "nb_util.h"
 #include "render_common.h"
 #include "timestep_common.h"
@@ -307,4 +312,73 @@ void UpdateWorldBatch_GPU_Leapfrog_dts(WorldBatch *w, const float *dt, uint32_t 
     push_once(w);
     nb_hip_ensemble_leapfrog_dts(w->gpu, n, dt);
     w->device_is_newer = true;
+}
+
+/* ---- include/nbody_batch_field.h ------------------------------------------------------------------------------------- */
+
+static void check_field(const char *what, float softening, uint64_t samples) {
+    const char *fault = nb_field_fault(softening, samples);
+    NB_CHECK(fault == NULL, "%s: invalid call (softening %g, %llu points in all): %s", what, (double)softening, (unsigned long long)samples,
+             fault);
+}
+
+/* n probes of every member into phi[] (the potential) or, where phi is NULL, into acc[] */
+static void batch_field_at(WorldBatch *w, const char *what, const V2 *points, uint32_t n, float softening, float *phi, V2 *acc) {
+    NB_CHECK(w != NULL, "%s: NULL argument", what);
+    check_field(what, softening, (uint64_t)w->count * n);
+    NB_CHECK((points != NULL && (phi != NULL || acc != NULL)) || n == 0, "%s: NULL argument", what);
+    if (n == 0) return;
+    if (w->device_is_newer) {
+        if (phi)
+            nb_hip_ensemble_potential_at(w->gpu, (const float *)points, n, softening, phi);
+        else
+            nb_hip_ensemble_acceleration_at(w->gpu, (const float *)points, n, softening, (float *)acc);
+        return;
+    }
+    for (uint32_t b = 0; b < w->count; b++) {
+        const Particle *ps = w->particles + w->offset[b];
+        const size_t at = (size_t)b * n;
+        if (phi)
+            nb_cpu_potential_at(ps, w->massive[b], points + at, n, softening, phi + at);
+        else
+            nb_cpu_acceleration_at(ps, w->massive[b], points + at, n, softening, acc + at);
+    }
+}
+
+/* the map of every member under its view into phi[] or, where phi is NULL, into acc[] */
+static void batch_field_map(WorldBatch *w, const char *what, const RenderView *views, float softening, float *phi, V2 *acc) {
+    NB_CHECK(w != NULL && views != NULL && (phi != NULL || acc != NULL), "%s: NULL argument", what);
+    check_views(w, views);
+    const size_t image = (size_t)views[0].width * views[0].height;
+    check_field(what, softening, (uint64_t)w->count * image);
+    if (w->device_is_newer) {
+        if (phi)
+            nb_hip_ensemble_potential_map(w->gpu, views, softening, phi);
+        else
+            nb_hip_ensemble_acceleration_map(w->gpu, views, softening, (float *)acc);
+        return;
+    }
+    for (uint32_t b = 0; b < w->count; b++) {
+        const Particle *ps = w->particles + w->offset[b];
+        if (phi)
+            nb_cpu_potential_map(ps, w->massive[b], views + b, softening, phi + (size_t)b * image);
+        else
+            nb_cpu_acceleration_map(ps, w->massive[b], views + b, softening, acc + (size_t)b * image);
+    }
+}
+
+void GetWorldBatchPotentialAt(WorldBatch *w, const V2 *points, uint32_t n, float softening, float *phi) {
+    batch_field_at(w, "GetWorldBatchPotentialAt", points, n, softening, phi, NULL);
+}
+
+void RenderWorldBatchPotential(WorldBatch *w, const RenderView *views, float softening, float *phi) {
+    batch_field_map(w, "RenderWorldBatchPotential", views, softening, phi, NULL);
+}
+
+void GetWorldBatchAccelerationAt(WorldBatch *w, const V2 *points, uint32_t n, float softening, V2 *acc) {
+    batch_field_at(w, "GetWorldBatchAccelerationAt", points, n, softening, NULL, acc);
+}
+
+void RenderWorldBatchAcceleration(WorldBatch *w, const RenderView *views, float softening, V2 *acc) {
+    batch_field_map(w, "RenderWorldBatchAcceleration", views, softening, NULL, acc);
 }
