@@ -231,6 +231,10 @@ TUNE_API = {
     "nb_hip_launch_lanes": (C.c_int, [C.c_void_p]),
     "nb_hip_plan_launch_unit": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int]),
     "nb_hip_plan_fused_finish": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int]),
+    "nb_hip_last_deal": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nb_hip_plan_deal": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int]),
+    "nb_hip_deal_item": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "nb_hip_deal_counter": (C.c_uint32, [C.c_void_p]),
     "nb_hip_plan_launch_lanes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
     "nb_hip_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_last_render_ms": (C.c_double, [C.c_void_p, C.POINTER(C.c_double)]),
@@ -452,6 +456,18 @@ def plan_launch(n_recv, n_src, compute_units=256):
     return {"k": k.value, "w": w.value, "split": sp.value, "workgroups": g.value,
             "unit": int(hip_lib().nb_hip_plan_launch_unit(n_recv, n_src, compute_units)), "lanes": lanes, "lanes_w": lw.value,
             "fused_finish": int(hip_lib().nb_hip_plan_fused_finish(n_recv, n_src, compute_units))}
+
+
+def plan_deal(n_recv, n_src, compute_units=256):
+    """tuning hook: whether "deal" = 2 deals the step launches of an unsharded world of that size (host arithmetic)."""
+    return bool(hip_lib().nb_hip_plan_deal(n_recv, n_src, compute_units))
+
+
+def deal_item(ticket, tiles, split):
+    """tuning hook: the (receiver tile, source part) a dealt launch's ticket stands for, or None past the last item."""
+    tile, part = C.c_uint32(0), C.c_uint32(0)
+    live = hip_lib().nb_hip_deal_item(ticket, tiles, split, C.byref(tile), C.byref(part))
+    return (int(tile.value), int(part.value)) if live else None
 
 
 def comm_unique_id():
@@ -676,6 +692,16 @@ class SimPipeline:
     def fused_steps(self):
         """steps of the last update that ran inside one-workgroup chain launches (knob fused_chain)."""
         return int(hip_lib().nb_hip_last_fused_steps(self._h))
+
+    def last_deal(self):
+        """tuning hook: (dealt, items, extra workgroups) of the step launches of the last update (knob deal)."""
+        items, extra = C.c_uint32(0), C.c_uint32(0)
+        dealt = hip_lib().nb_hip_last_deal(self._h, C.byref(items), C.byref(extra))
+        return bool(dealt), int(items.value), int(extra.value)
+
+    def deal_counter(self):
+        """tuning hook: the ticket counter of the dealt launches, read back after a sync (0 between launches)."""
+        return int(hip_lib().nb_hip_deal_counter(self._h))
 
     def configure(self, **knobs):
         """The five knobs of include/nbody_hip.h go through nb_hip_configure; anything else is a launch-shape / experiment

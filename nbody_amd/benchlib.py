@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FLOP_PER_INTERACTION = 14        # reference op count, sim_cpu.c:169-188
 PEAK_FP32_VECTOR_TFLOPS = 157.3  # MI355X_MICROARCH.md "Peak FP32 (vector)"
-KERNEL_SOURCES = ("nbody_amd/csrc/kernels.hip", "nbody_amd/csrc/kernels.h", "nbody_amd/csrc/interaction_asm.h")
+KERNEL_SOURCES = ("nbody_amd/csrc/kernels.hip", "nbody_amd/csrc/step_tile.inc", "nbody_amd/csrc/kernels.h", "nbody_amd/csrc/interaction_asm.h")
 
 
 # ---- the host ------------------------------------------------------------------------------------------------------------

@@ -61,7 +61,23 @@ struct StepParams {
     // Scalar-cache route only: the LDS route stages whole 64-source tiles and always runs with 64 -- the two routes
     // give the same bits whenever the granule is 64.  Two-range (overlapped) steps always use 64.
     uint32_t unit;
+    // dealt launches only (dealt_kernel): the ticket counter of the pipeline, zero between launches, and the number of
+    // (receiver tile, source part) items = tiles x split; null / 0 in every other launch
+    uint32_t *deal;
+    uint32_t deal_items;
 };
+
+// Ticket t of a dealt launch is receiver tile t % tiles of source part t / tiles: the order in which a 2-D grid of
+// (tiles, split) workgroups is linearised, so a dealt launch touches memory in the order the classic one does.  Tickets
+// from tiles x split on stand for nothing (live = false).  The kernel and the host (nb_hip_deal_item) call this one copy.
+struct DealItem {
+    uint32_t tile, part;
+    bool live;
+};
+__host__ __device__ inline DealItem deal_item(uint32_t ticket, uint32_t tiles, uint32_t split) {
+    if (tiles == 0 || ticket / tiles >= split) return DealItem{0, 0, false};
+    return DealItem{ticket % tiles, ticket / tiles, true};
+}
 
 // The parameters of a plain step: one source range [0, n_src), receivers without a gap or a mirror, sums from zero,
 // integrated, unsplit.  The one-world pipeline starts from it (step_chain.hip whole_step), an ensemble member's
@@ -146,6 +162,7 @@ struct LaunchShape;   // launch_shape.h
 // Kernel entry point for a shape; used both for direct launches and for graph nodes.
 const void *step_kernel_fn(LaunchShape s);
 const void *step_kernel_fused_fn(LaunchShape s);   // nullptr when the shape has no fused-finish instantiation
+const void *dealt_kernel_fn(LaunchShape s);        // nullptr when the shape has no dealt instantiation (1-D grid, StepParams::deal)
 // second kernel of a split step (split > 1): adds the parts and finishes like the step kernel's epilogue
 const void *finish_kernel_fn();
 

@@ -42,6 +42,14 @@ LaunchShape choose_shape(LaunchShape want, uint32_t n_recv, uint32_t n_src, int 
 // the auto rule of the "fused_finish" knob: split steps of this size run without the finish kernel
 bool fused_finish_rule(uint32_t n_recv, uint32_t n_src);
 
+// Dealt launches ("deal" knob; kernels.hip dealt_kernel): the (receiver tile, source part) items of a shape, the workgroups
+// launched on top of them, and the auto rule -- launches of at least DEAL_MIN_ROUNDS resident rounds.
+uint32_t deal_items(LaunchShape s, uint32_t n_recv);
+uint32_t deal_extra(uint32_t items);
+bool deal_pays(uint32_t items, int compute_units);
+// ... and for a step of that size on the auto shape: whether it deals at all
+bool deal_rule(uint32_t n_recv, uint32_t n_src, int compute_units);
+
 // Grid, block and dynamic LDS of a shape's step kernel (kernels.h step_kernel_fn), and of the finish kernel.
 dim3 step_grid(LaunchShape s, uint32_t n_recv);
 dim3 step_block(LaunchShape s);

@@ -211,4 +211,37 @@ bool fused_finish_rule(uint32_t n_recv, uint32_t n_src) {
     return (double)n_recv * (double)n_src >= FUSED_FINISH_MIN_PAIRS && n_recv <= FUSED_FINISH_MAX_RECV;
 }
 
+// ---- dealt launches ("deal" knob, auto) -------------------------------------------------------------------------------
+// The grid of a dealt launch is the item count plus `extra` workgroups (kernels.hip dealt_kernel): what a fast XCD takes
+// over from a slow one comes out of the extra ones, so extra bounds the speed difference the scheme can absorb -- items / 32
+// is 3 %, three times what the clocks ask for (the odd XCDs hold 1-2 % less) -- and every extra workgroup that finds the
+// counter spent costs one atomic and leaves.  Eight at least, one per XCD.
+uint32_t deal_items(LaunchShape s, uint32_t n_recv) {
+    const dim3 g = step_grid(s, n_recv);
+    return g.x * g.y;
+}
+
+uint32_t deal_extra(uint32_t items) { return items / 32 > 8 ? items / 32 : 8; }
+
+// What dealing can win is the slow XCDs' lag at the end of a launch, a fixed FRACTION of it; what it costs is fixed per
+// launch (the draws of the first resident round arrive together; the drain of the extra workgroups).  Auto therefore deals
+// only launches of at least DEAL_MIN_ROUNDS rounds of resident workgroups (two 1 024-thread workgroups per CU).  Same-box
+// A/B, kernel ms per launch, classic | dealt, gain against the classic repeats' own spread (profiles/r23_deal_probe.json):
+//   N = 262 144,  8 rounds:  6.107 |  6.132  -0.40 %  (spread 0.58 %)      N = 524 288, 24 rounds: 12.261 | 12.220  +0.33 % (0.22 %)
+//   N = 2^20,    32 rounds: 48.930 | 48.342  +1.20 %  (spread 0.14 %)      (N = 131 072, 10 rounds, runs the fused finish: never dealt)
+// 24 rounds is a gain of 1.5 spreads, 32 rounds one of 8.9: the rule starts where the gain is beyond doubt.
+constexpr uint32_t DEAL_MIN_ROUNDS = 32;
+
+bool deal_pays(uint32_t items, int compute_units) {
+    if (compute_units <= 0) compute_units = 256;
+    return (uint64_t)items >= (uint64_t)DEAL_MIN_ROUNDS * 2u * (uint64_t)compute_units;
+}
+
+bool deal_rule(uint32_t n_recv, uint32_t n_src, int compute_units) {
+    const LaunchShape sh = choose_shape({.lanes = 1}, n_recv, n_src, compute_units);
+    if (dealt_kernel_fn(sh) == nullptr) return false;
+    if (sh.split > 1 && fused_finish_rule(n_recv, n_src)) return false;
+    return deal_pays(deal_items(sh, n_recv), compute_units);
+}
+
 }  // namespace nb

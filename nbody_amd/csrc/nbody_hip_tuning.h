@@ -8,6 +8,8 @@
  *   k, w, split, unit, passes   launch shape; "auto" is within 1.2 % of the best explicit neighbour at every size the
  *                               GPU suite asks the hardware about (test_auto_launch_shape_is_near_the_best_...)
  *   lanes, fused_chain          small-world kernels; auto-selected below N ~ 4 000 / N <= 256, frozen since round 3
+ *   deal, deal_extra            large launches dealt by ticket so that faster XCDs take more; auto from 32 rounds: -1.2 % per
+ *                               launch at N = 2^20 (profiles/r23_deal_probe.json)
  *   fused_finish                the last workgroup of a receiver tile finishes it; auto from N x M >= 4e7, -0.4 ... -2.3 us
  *   readback, zero_copy_upload  the GUI frame loop's eager read-back / zero-copy upload heuristics, frozen since round 2
  */
@@ -35,6 +37,11 @@ extern "C" {
  *   "fused_finish"  split shapes without their second kernel (the tile's last workgroup adds the parts and integrates):
  *               2 (default) = auto (unsharded, scalar-cache route, N x M >= 4e7, <= 200 000 receivers), 1 = whenever the
  *               shape has a split, 0 = never
+ *   "deal"      large step launches whose workgroups draw their (receiver tile, source part) from a ticket counter, over a
+ *               grid a little larger than the item count, so that XCDs holding a higher clock take more of a launch
+ *               (kernels.hip dealt_kernel): 2 (default) = auto (unsharded, scalar-cache route, k = 1 or 2, w = 16, no fused
+ *               finish, at least 32 resident rounds of workgroups), 1 = whenever the shape allows, 0 = never; same bits
+ *   "deal_extra"    workgroups a dealt launch holds on top of its items: 0 (default) = max(8, items / 32)
  *   "readback"  when the device state reaches the array named by nb_hip_note_host_array: 0 = only when GetSimulationData
  *               asks, 1 = at the end of every blocking PerformSimUpdate, 2 (default) = auto (eager once two updates in a
  *               row were each followed by a Get into the noted array)
@@ -74,6 +81,17 @@ int nb_hip_launch_unit(const SimPipeline *sim);
 int nb_hip_plan_launch_lanes(uint32_t n_recv, uint32_t n_src, int *w);
 int nb_hip_plan_fused_finish(uint32_t n_recv, uint32_t n_src, int compute_units);
 int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units);
+
+/* Dealt launches ("deal" hook).  nb_hip_last_deal: 1 when the step launches of the last update were dealt, with their item
+ * count and the workgroups launched on top (either pointer may be NULL).  nb_hip_plan_deal: what "deal" = 2 decides for an
+ * unsharded step of that size on the auto shape, pure host code.  nb_hip_deal_item: the (receiver tile, source part) ticket
+ * `ticket` stands for in a launch of tiles x split items -- the function the kernel calls; returns 0 and writes nothing for
+ * a ticket past the last item.  nb_hip_deal_counter: the pipeline's ticket counter, read back after a sync (0 between
+ * launches; 0 for a pipeline that has none). */
+int nb_hip_last_deal(const SimPipeline *sim, uint32_t *items, uint32_t *extra);
+int nb_hip_plan_deal(uint32_t n_recv, uint32_t n_src, int compute_units);
+int nb_hip_deal_item(uint32_t ticket, uint32_t tiles, uint32_t split, uint32_t *tile, uint32_t *part);
+uint32_t nb_hip_deal_counter(SimPipeline *sim);
 
 /* Device milliseconds of the kernels of the last nb_hip_energy / nb_hip_potential / nb_hip_potential_at /
  * nb_hip_potential_map / nb_hip_acceleration_at / nb_hip_acceleration_map (their own event pair, not the step's); 0 before

@@ -96,6 +96,7 @@ void materialize(SimPipeline *s) {
     s->mass.alloc(cap);
     s->src_gm.alloc(s->n_src);
     s->dt_dev.alloc(1);
+    if (!s->sharded && N > 0) s->deal_counter.alloc(1);   // zeroed in stream order by the first SetSimulationData (zero_tickets)
     s->aos.alloc(N);
     if (!s->sharded) {
         // the first mass_len receivers ARE the sources: no separate source array
@@ -178,6 +179,7 @@ SimPipeline *CreateSimPipeline(WorldData data) {
     struct { const char *env, *key; } presets[] = {
         {"NB_HIP_K", "k"}, {"NB_HIP_W", "w"}, {"NB_HIP_SPLIT", "split"}, {"NB_HIP_UNIT", "unit"}, {"NB_HIP_PASSES", "passes"},
         {"NB_HIP_LANES", "lanes"}, {"NB_HIP_FUSED_CHAIN", "fused_chain"}, {"NB_HIP_FUSED_FINISH", "fused_finish"},
+        {"NB_HIP_DEAL", "deal"}, {"NB_HIP_DEAL_EXTRA", "deal_extra"},
         {"NB_HIP_READBACK", "readback"}, {"NB_HIP_ZERO_COPY_UPLOAD", "zero_copy_upload"},
     };
     for (const auto &p : presets)
@@ -249,6 +251,17 @@ int nb_hip_plan_launch_lanes(uint32_t n_recv, uint32_t n_src, int *w) {
 int nb_hip_plan_fused_finish(uint32_t n_recv, uint32_t n_src, int compute_units) {
     const nb::LaunchShape sh = nb::choose_shape({.lanes = 1}, n_recv, n_src, compute_units);
     return sh.split > 1 && nb_hip_plan_launch_lanes(n_recv, n_src, nullptr) <= 1 && nb::fused_finish_rule(n_recv, n_src) ? 1 : 0;
+}
+
+int nb_hip_plan_deal(uint32_t n_recv, uint32_t n_src, int compute_units) {
+    return nb_hip_plan_launch_lanes(n_recv, n_src, nullptr) <= 1 && nb::deal_rule(n_recv, n_src, compute_units) ? 1 : 0;
+}
+
+int nb_hip_deal_item(uint32_t ticket, uint32_t tiles, uint32_t split, uint32_t *tile, uint32_t *part) {
+    const nb::DealItem it = nb::deal_item(ticket, tiles, split);
+    if (it.live && tile) *tile = it.tile;
+    if (it.live && part) *part = it.part;
+    return it.live ? 1 : 0;
 }
 
 int nb_hip_plan_launch_unit(uint32_t n_recv, uint32_t n_src, int compute_units) {
@@ -479,6 +492,23 @@ uint32_t nb_hip_last_fused_steps(const SimPipeline *s) {
     return s->fused_steps;
 }
 
+int nb_hip_last_deal(const SimPipeline *s, uint32_t *items, uint32_t *extra) {
+    NB_ASSERT(s != nullptr, "NULL pipeline");
+    if (items) *items = s->last_deal_items;
+    if (extra) *extra = s->last_deal_extra;
+    return s->last_deal_items && !s->fused_steps ? 1 : 0;
+}
+
+uint32_t nb_hip_deal_counter(SimPipeline *s) {
+    NB_ASSERT(s != nullptr, "NULL pipeline");
+    if (!s->on_device || !s->deal_counter) return 0;
+    use_device();
+    uint32_t v = 0;
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync before reading the deal counter");
+    ASSERT_HIP(hipMemcpy(&v, s->deal_counter, sizeof v, hipMemcpyDeviceToHost), "read the deal counter");
+    return v;
+}
+
 int nb_hip_launch_lanes(const SimPipeline *s) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
     return s->last_shape.lanes > 1 ? s->last_shape.lanes : 1;
@@ -574,6 +604,14 @@ int nb_hip_tune(SimPipeline *s, const char *key, int value) {
             s->graphs.clear();
         }
         s->fused_finish = value;
+    } else if (!strcmp(key, "deal")) {
+        NB_ASSERT(value >= 0 && value <= 2, "deal must be 0 (never), 1 (whenever the shape allows) or 2 (auto), got %d", value);
+        old = s->deal;
+        s->deal = value;   // cached chains are keyed on it (step_chain.hip find_graph): nothing to rebuild here
+    } else if (!strcmp(key, "deal_extra")) {
+        NB_ASSERT(value >= 0 && value <= (1 << 20), "deal_extra must be 0 (auto) .. 2^20 workgroups, got %d", value);
+        old = s->want_deal_extra;
+        s->want_deal_extra = value;
     } else if (!strcmp(key, "passes")) {
         NB_ASSERT(value >= 0 && value <= 64, "passes must be 0 (auto) .. 64, got %d", value);
         old = s->want_passes;

@@ -295,6 +295,7 @@ struct StepGraph {
     std::vector<nb::StepParams> params; // what each node currently holds
     int phase = -1;                     // which pos buffer the chain reads first
     nb::LaunchShape shape;
+    uint32_t dealt_groups = 0;          // workgroups of its dealt step launches (items + extra); 0: classic launches
     uint64_t last_use = 0;              // for eviction: the cache holds at most GRAPH_CACHE_MAX chains
 };
 
@@ -382,6 +383,10 @@ struct SimPipeline {
                                     // and before a chain is built: a launch that ended part-way must not leave a tile unfinished for ever)
     int fused_finish = 2;         // 0: step kernel + finish kernel; 1: the last workgroup of a tile finishes it, whenever
                                   // the shape allows; 2 (default): auto (launch_shape.hip fused_finish_rule)
+    nbi::DevBuf<uint32_t> deal_counter;   // dealt launches: the ticket counter, zero between launches (zeroed with the tickets); unsharded only
+    int deal = 2;                 // 0: classic launches; 1: dealt whenever the shape allows; 2 (default): auto (step_chain.hip deal_applies)
+    int want_deal_extra = 0;      // workgroups a dealt launch holds on top of its items; 0 = launch_shape.hip deal_extra
+    uint32_t last_deal_items = 0, last_deal_extra = 0;   // what the last resolved step launches: 0 items = not dealt
     int cur = 0;             // pos[cur] is the latest state
 
     hipStream_t stream = nullptr;
@@ -471,7 +476,8 @@ nb::StepParams whole_step(const SimPipeline *s, int in, float dt);
 uint32_t passes_for(const SimPipeline *s, const nb::StepParams &p);
 void launch_step(SimPipeline *s, nb::LaunchShape sh, const nb::StepParams &p, hipStream_t st);
 void upload_dt(SimPipeline *s, float dt);
-void zero_tickets(SimPipeline *s);   // fused finish: all tile tickets back to 0, in stream order
+void zero_tickets(SimPipeline *s);   // fused finish: all tile tickets back to 0, in stream order; and the deal counter
+bool deal_applies(const SimPipeline *s, nb::LaunchShape sh);   // "deal" knob: this shape's step launches are dealt
 // what every step call starts and ends with: the per-call records cleared; the end of step_iv and the launch counts of the timed interval
 void begin_call(SimPipeline *s);
 void end_call(SimPipeline *s, uint32_t launches);

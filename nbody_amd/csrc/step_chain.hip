@@ -39,6 +39,8 @@ void destroy_graph(StepGraph &g) {
     g.params.clear();
 }
 
+uint32_t dealt_extra(const SimPipeline *s, uint32_t items);
+
 nb::LaunchShape resolve_shape(SimPipeline *s) {
     nb::LaunchShape want = s->want;
     // the model sees one launch: with source passes that is 1/passes of the sources
@@ -61,6 +63,8 @@ nb::LaunchShape resolve_shape(SimPipeline *s) {
     }
     s->last_shape = sh;
     s->last_groups = nb::step_grid(sh, s->n_real).x * nb::step_grid(sh, s->n_real).y;
+    s->last_deal_items = deal_applies(s, sh) ? nb::deal_items(sh, s->n_real) : 0u;
+    s->last_deal_extra = s->last_deal_items ? dealt_extra(s, s->last_deal_items) : 0u;
     return sh;
 }
 
@@ -92,10 +96,40 @@ bool fused_finish_applies(const SimPipeline *s, nb::LaunchShape sh) {
     return s->fused_finish == 1 || nb::fused_finish_rule(s->n_real, s->n_src);
 }
 
+// Dealt launches ("deal" knob): the step kernel's workgroups draw their (receiver tile, source part) from one ticket
+// counter, and the grid holds a few more workgroups than items, so an XCD that holds a higher clock takes more of a launch
+// (kernels.hip dealt_kernel; why and what it buys: DESIGN.md section 3 "Dealt launches").  Same items, same code, same
+// finish kernel: the bits of a step do not depend on the knob.  Unsharded steps on the scalar-cache route with sixteen
+// waves per workgroup and no fused finish; 1 = whenever the shape allows, 2 = launches of enough rounds
+// (launch_shape.hip deal_pays).
+bool deal_applies(const SimPipeline *s, nb::LaunchShape sh) {
+    if (s->deal == 0 || s->sharded || !s->deal_counter || s->n_real == 0) return false;
+    if (sh.variant != nb::VARIANT_SMEM || sh.lanes > 1 || sh.w != 16 || (sh.k != 1 && sh.k != 2)) return false;
+    if (nb::dealt_kernel_fn(sh) == nullptr || fused_finish_applies(s, sh)) return false;
+    return s->deal == 1 || nb::deal_pays(nb::deal_items(sh, s->n_real), g_dev.compute_units);
+}
+
+// workgroups a dealt launch holds on top of its items ("deal_extra" hook: 0 = launch_shape.hip deal_extra)
+uint32_t dealt_extra(const SimPipeline *s, uint32_t items) { return s->want_deal_extra > 0 ? (uint32_t)s->want_deal_extra : nb::deal_extra(items); }
+
+dim3 launch_grid(const SimPipeline *s, nb::LaunchShape sh, bool dealt) {
+    if (!dealt) return nb::step_grid(sh, s->n_real);
+    const uint32_t items = nb::deal_items(sh, s->n_real);
+    return dim3(items + dealt_extra(s, items));
+}
+
+const void *launch_fn(nb::LaunchShape sh, bool fused, bool dealt) {
+    return dealt ? nb::dealt_kernel_fn(sh) : fused ? nb::step_kernel_fused_fn(sh) : nb::step_kernel_fn(sh);
+}
+
 nb::StepParams shaped(const SimPipeline *s, nb::StepParams p, nb::LaunchShape sh) {
     p.split = sh.split > 1 ? (uint32_t)sh.split : 1u;
     p.parts = p.split > 1 ? s->parts : nullptr;
     p.tickets = s->tickets;
+    if (deal_applies(s, sh)) {
+        p.deal = s->deal_counter;
+        p.deal_items = nb::deal_items(sh, s->n_real);
+    }
     // finer slice granules only for single-range steps (the overlapped sharded step walks two ranges: 64 there)
     p.unit = (sh.unit >= 8 && sh.unit <= 64 && p.src_end[1] == p.src_begin[1]) ? (uint32_t)sh.unit : 64u;
     return p;
@@ -136,13 +170,13 @@ std::vector<nb::StepParams> step_passes(const SimPipeline *s, const nb::StepPara
 
 void launch_step(SimPipeline *s, nb::LaunchShape sh, const nb::StepParams &p, hipStream_t st) {
     if (s->n_real == 0) return;  // a rank without receivers still takes part in the gathers
-    const bool fused = fused_finish_applies(s, sh);
+    const bool fused = fused_finish_applies(s, sh), dealt = deal_applies(s, sh);
     for (nb::StepParams &copy : step_passes(s, p, sh)) {
         void *args[] = {&copy};
-        ASSERT_HIP(hipLaunchKernel(fused ? nb::step_kernel_fused_fn(sh) : nb::step_kernel_fn(sh), nb::step_grid(sh, s->n_real), nb::step_block(sh), args,
+        ASSERT_HIP(hipLaunchKernel(launch_fn(sh, fused, dealt), launch_grid(s, sh, dealt), nb::step_block(sh), args,
                                    nb::step_lds_bytes(sh, copy.src_end[0] - copy.src_begin[0]), st),
-                   "step kernel launch (k=%d w=%d variant=%d split=%d, %u receivers)", sh.k, sh.w, sh.variant, sh.split,
-                   s->n_real);
+                   "step kernel launch (k=%d w=%d variant=%d split=%d dealt=%d, %u receivers)", sh.k, sh.w, sh.variant, sh.split,
+                   (int)dealt, s->n_real);
         if (copy.split > 1 && !fused)
             ASSERT_HIP(hipLaunchKernel(nb::finish_kernel_fn(), nb::finish_grid(s->n_real), nb::finish_block(), args, 0, st),
                        "finish kernel launch (%u receivers, %u parts)", s->n_real, copy.split);
@@ -153,8 +187,10 @@ void launch_step(SimPipeline *s, nb::LaunchShape sh, const nb::StepParams &p, hi
 // while every launch runs to its end.  A launch that ended part-way (a failed graph replay, a device error the caller
 // survived) would leave non-zero tickets, and every later step would silently skip that tile's integration: so the tickets
 // are re-zeroed, in stream order, whenever a new state is uploaded and before a chain is built.
+// The counter of the dealt launches lives by the same rule (its last draw puts it back to zero) and is zeroed with them.
 void zero_tickets(SimPipeline *s) {
     if (s->tickets) ASSERT_HIP(hipMemsetAsync(s->tickets, 0, s->tickets.count() * sizeof(uint32_t), s->stream), "zero the tile tickets");
+    if (s->deal_counter) ASSERT_HIP(hipMemsetAsync(s->deal_counter, 0, sizeof(uint32_t), s->stream), "zero the deal counter");
 }
 
 // The step size of everything enqueued from here on.  Written in stream order, so steps already queued keep theirs.
@@ -183,16 +219,19 @@ void fill_node(hipKernelNodeParams &kp, void **args, const void *fn, dim3 grid, 
 // key it gets two instantiated graphs and replays them untouched, instead of re-patching every node of one graph on
 // every call.  dt is not part of the key and never forces a rebuild or a patch: the nodes read it from device memory
 // (upload_dt).
+// Whether the chain's step launches are dealt, and over how many workgroups, is part of the key as well: flipping the "deal"
+// knob builds a new chain (other kernel, other grid) and never re-patches one.
 StepGraph *find_graph(SimPipeline *s, uint32_t n, uint32_t passes, nb::LaunchShape sh, int phase) {
+    const uint32_t dealt_groups = deal_applies(s, sh) ? launch_grid(s, sh, true).x : 0u;
     for (auto &c : s->graphs)
-        if (c.n == n && c.passes == passes && c.phase == phase && c.shape == sh) return &c;
+        if (c.n == n && c.passes == passes && c.phase == phase && c.shape == sh && c.dealt_groups == dealt_groups) return &c;
     return nullptr;
 }
 
 StepGraph *find_or_build_graph(SimPipeline *s, uint32_t n, float dt, nb::LaunchShape sh) {
     const uint32_t passes = passes_for(s, whole_step(s, s->cur, dt));
     StepGraph *g = find_graph(s, n, passes, sh, s->cur);
-    const bool fused = fused_finish_applies(s, sh);
+    const bool fused = fused_finish_applies(s, sh), dealt = deal_applies(s, sh);
     const uint32_t per_pass = sh.split > 1 && !fused ? 2 : 1;  // step kernel (+ finish kernel)
     const uint32_t per_step = passes * per_pass;
     const bool fresh = g == nullptr;
@@ -203,13 +242,14 @@ StepGraph *find_or_build_graph(SimPipeline *s, uint32_t n, float dt, nb::LaunchS
         g->n = n;
         g->passes = passes;
         g->shape = sh;
+        g->dealt_groups = dealt ? launch_grid(s, sh, true).x : 0u;
         ASSERT_HIP(hipGraphCreate(&g->graph, 0), "hipGraphCreate");
         g->nodes.resize((size_t)n * per_step);
         g->params.resize((size_t)n * passes);
     }
     g->last_use = ++s->use_clock;
     if (!fresh) return g;
-    if (fused) zero_tickets(s);
+    if (fused || dealt) zero_tickets(s);
     hipGraphNode_t prev = nullptr;
     for (uint32_t i = 0; i < n; i++) {
         const std::vector<nb::StepParams> launches = step_passes(s, whole_step(s, (s->cur + i) & 1, dt), sh);
@@ -219,7 +259,7 @@ StepGraph *find_or_build_graph(SimPipeline *s, uint32_t n, float dt, nb::LaunchS
             for (uint32_t j = 0; j < per_pass; j++) {
                 hipKernelNodeParams kp;
                 if (j == 0)
-                    fill_node(kp, args, fused ? nb::step_kernel_fused_fn(sh) : nb::step_kernel_fn(sh), nb::step_grid(sh, s->n_real), nb::step_block(sh),
+                    fill_node(kp, args, launch_fn(sh, fused, dealt), launch_grid(s, sh, dealt), nb::step_block(sh),
                               nb::step_lds_bytes(sh, launches[q].src_end[0] - launches[q].src_begin[0]));
                 else
                     fill_node(kp, args, nb::finish_kernel_fn(), nb::finish_grid(s->n_real), nb::finish_block());

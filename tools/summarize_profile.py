@@ -26,6 +26,11 @@ def newest(pattern):
     return sorted(best.values())
 
 
+def is_step(name):
+    """a step launch: step_kernel<...>, or dealt_kernel<K, W> where the "deal" hook applies (the headline since round 23)"""
+    return "step_kernel" in name or "dealt_kernel" in name
+
+
 lines = []
 stats = newest(os.path.join(PROF, "stats", "*", "*_kernel_stats.csv"))
 step_avg_ns = None
@@ -33,13 +38,13 @@ if stats:
     lines.append("== rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-extra-configs --steps 10 --warmup 2 ==")
     for r in csv.DictReader(open(stats[0])):
         lines.append(f"{r['Name'][:90]:90s} calls={r['Calls']:>4s} avg_ns={float(r['AverageNs']):14.0f} total_ns={r['TotalDurationNs']:>14s} pct={float(r['Percentage']):7.3f}")
-        if "step_kernel" in r["Name"] and step_avg_ns is None:   # rows are sorted by total time: the headline variant first
+        if is_step(r["Name"]) and step_avg_ns is None:   # rows are sorted by total time: the headline variant first
             step_avg_ns = float(r["AverageNs"])
     with open(os.path.join(out_dir, f"{tag}_kernel_stats.csv"), "w") as f:
         f.write(open(stats[0]).read())
     tr = newest(os.path.join(PROF, "stats", "*", "*_kernel_trace.csv"))
     if tr:
-        rows = [r for r in csv.DictReader(open(tr[0])) if "step_kernel" in r["Kernel_Name"]]
+        rows = [r for r in csv.DictReader(open(tr[0])) if is_step(r["Kernel_Name"])]
         if rows:
             # bench.py's extra_configs (C2 / C3) launch the same template instantiations at smaller sizes: the figure that must
             # agree with roofline.kernel_ms_per_launch is the mean over the HEADLINE dispatches only -- the most frequent kernel
@@ -68,7 +73,7 @@ if os.path.exists(_log):
 # bench.py also times the LDS-tile route (roofline.alt_lds): the counters below are those of the HEADLINE variant only,
 # i.e. of the step_kernel instantiation with the most launches
 files = newest(os.path.join(PROF, "pmc_*", "*", "*_counter_collection.csv"))
-names = collections.Counter(r["Kernel_Name"] for f in files for r in csv.DictReader(open(f)) if "step_kernel" in r["Kernel_Name"])
+names = collections.Counter(r["Kernel_Name"] for f in files for r in csv.DictReader(open(f)) if is_step(r["Kernel_Name"]))
 headline = names.most_common(1)[0][0] if names else None
 agg = collections.defaultdict(list)
 for f in files:
