@@ -12,6 +12,9 @@
  *   UpdateWorldBatch_GPU_Traced(_dts) (nbody_batch_trace.h)
  *   GetWorldBatchEnergy              (nbody_batch_diag.h)
  *   GetWorldBatchPotential           phi is packed like ps: world_size[0] values, then world_size[1], ...
+ *   GetWorldBatchPotentialAt, RenderWorldBatchPotential, GetWorldBatchAccelerationAt, RenderWorldBatchAcceleration
+ *                                    (nbody_batch_field.h) and GetWorldBatchTidalAt, RenderWorldBatchTidal (nbody_batch_tidal.h):
+ *                                    the members differ in size, the samples do not -- results [count][n]
  * Member b's particles, energy, potential and trace rows are bit for bit those of the same particles in a WorldBatch of
  * one member (so a member does not depend on the other members, their sizes or its index).  While the host array is the
  * newest state the diagnostics run on the host, member by member, and need no GPU.

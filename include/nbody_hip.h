@@ -417,6 +417,25 @@ void nb_hip_acceleration_at(SimPipeline *sim, const float *points, uint32_t n, f
 void nb_hip_acceleration_map(SimPipeline *sim, const RenderView *view, float softening, float *acc);
 
 /*
+ * The tidal tensor T = dg/dp of the state the pipeline holds away from its particles (definitions: include/nbody_tidal.h;
+ * kernels: nbody_amd/csrc/tidal.hip), three float32 per sample in the order (xx, xy, yy):
+ *   nb_hip_tidal_at   t[3 * i .. 3 * i + 2] = T(points[i]; softening) for the caller's n points ((x, y) pairs),
+ *                     0 <= n <= 2^24; n = 0 does nothing
+ *   nb_hip_tidal_map  t[height][width][3]: T at every pixel centre of *view, exactly nb_hip_tidal_at of the grid points,
+ *                     row-major; only the width column and height row coordinates travel to the device
+ * The field sampler's third pair statement: one v_rsq_f32 per pair, four running fp32 sums per sample in the sums of
+ * nb_hip_potential_at (blocks of 256 sources, float64 block totals in eight source slices added in order); the factor 3 and
+ * the difference of the two parts of a diagonal component are taken in float64 and each component is rounded once.  A
+ * result is a function of the point and the state alone: not of n, the point's index or the kernel shape.  No term is
+ * excluded: a point on a source gets that source's finite term diag(-G*m s^(-3/2)).  A point with a non-finite coordinate
+ * gives NaN in all three components; mass_len = 0 gives three +0.  Enqueued, blocking and invisible to the steps exactly as
+ * nb_hip_acceleration_at / _map above, with the same buffers and the same aborts.
+ * Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_tidal_map").
+ */
+void nb_hip_tidal_at(SimPipeline *sim, const float *points, uint32_t n, float softening, float *t);
+void nb_hip_tidal_map(SimPipeline *sim, const RenderView *view, float softening, float *t);
+
+/*
  * World ensembles: `count` independent worlds with the same particle count, stepped together.
  *
  * One world of a few hundred to a few thousand particles keeps one or a handful of the chip's 256 compute units busy;
@@ -602,6 +621,20 @@ void nb_hip_ensemble_acceleration_at(SimBatch *batch, const float *points /* [co
                                      float *acc /* [count][n][2] */);
 void nb_hip_ensemble_acceleration_map(SimBatch *batch, const RenderView *views /* [count] */, float softening,
                                       float *acc /* [count][h][w][2] */);
+
+/*
+ * The tidal tensor of EVERY member of an ensemble, in one launch (definitions: include/nbody_tidal.h with M = mass_len[b];
+ * the World-level calls are include/nbody_batch_tidal.h; kernel: nbody_amd/csrc/tidal.hip):
+ *   nb_hip_ensemble_tidal_at   t[count][n][3]: (xx, xy, yy) of T(points[b][i]; softening) of member b
+ *   nb_hip_ensemble_tidal_map  t[count][height][width][3]: T at every pixel centre of views[b]
+ * Everything said of the four calls above holds: member b's values are BIT-IDENTICAL to nb_hip_tidal_at / _map of a
+ * SimPipeline holding the same particles on either of its kernel shapes, uniform and ragged ensembles alike, the same
+ * limits, edge values (three NaN, three +0) and aborts, one upload, one launch, one copy and one sync for any count.
+ * Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_ensemble_tidal_map").
+ */
+void nb_hip_ensemble_tidal_at(SimBatch *batch, const float *points /* [count][n][2] */, uint32_t n, float softening,
+                              float *t /* [count][n][3] */);
+void nb_hip_ensemble_tidal_map(SimBatch *batch, const RenderView *views /* [count] */, float softening, float *t /* [count][h][w][3] */);
 
 /*
  * Adaptive time steps chosen on the device (definitions: include/nbody_adaptive.h; kernels: nbody_amd/csrc/timestep.hip).

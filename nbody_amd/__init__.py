@@ -179,6 +179,8 @@ HIP_API = {
     "nb_hip_potential_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_acceleration_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "nb_hip_acceleration_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    "nb_hip_tidal_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "nb_hip_tidal_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nb_hip_batch_destroy": (None, [C.c_void_p]),
     "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
@@ -210,6 +212,8 @@ HIP_API = {
     "nb_hip_ensemble_potential_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_ensemble_acceleration_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "nb_hip_ensemble_acceleration_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    "nb_hip_ensemble_tidal_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "nb_hip_ensemble_tidal_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_adaptive_steps": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
     "nb_hip_adaptive_steps_async": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive)]),
     "nb_hip_adaptive_collect": (None, [C.c_void_p, C.c_void_p, C.POINTER(NbAdaptiveResult)]),
@@ -252,7 +256,7 @@ PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
 # include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h +
-# include/nbody_adaptive.h + include/nbody_leapfrog.h + include/nbody_batch_field.h
+# include/nbody_adaptive.h + include/nbody_leapfrog.h + include/nbody_batch_field.h + include/nbody_tidal.h + include/nbody_batch_tidal.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -279,6 +283,9 @@ NBODY_API = {
     # include/nbody_gravity.h
     "GetWorldAccelerationAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "RenderWorldAcceleration": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    # include/nbody_tidal.h
+    "GetWorldTidalAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "RenderWorldTidal": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     # include/nbody_batch.h
     "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "DestroyWorldBatch": (None, [C.c_void_p]),
@@ -303,6 +310,9 @@ NBODY_API = {
     "RenderWorldBatchPotential": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "GetWorldBatchAccelerationAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "RenderWorldBatchAcceleration": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    # include/nbody_batch_tidal.h
+    "GetWorldBatchTidalAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
+    "RenderWorldBatchTidal": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     # include/nbody_adaptive.h
     "UpdateWorld_GPU_Adaptive": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
     "UpdateWorld_CPU_Adaptive": (None, [C.c_void_p, C.c_uint32, C.POINTER(NbAdaptive), C.c_void_p, C.POINTER(NbAdaptiveResult)]),
@@ -658,9 +668,23 @@ class SimPipeline:
         hip_lib().nb_hip_acceleration_map(self._h, C.byref(view), softening, out.ctypes.data)
         return out
 
+    def tidal_at(self, points, softening):
+        """nb_hip_tidal_at: the tidal tensor dg/dp at the (n, 2) points with one softening (include/nbody_tidal.h), float32
+        (n, 3) in the order (xx, xy, yy)."""
+        pts = as_points(points)
+        out = np.empty((pts.shape[0], 3), dtype=np.float32)
+        hip_lib().nb_hip_tidal_at(self._h, pts.ctypes.data, pts.shape[0], softening, out.ctypes.data)
+        return out
+
+    def tidal_map(self, view, softening):
+        """nb_hip_tidal_map: the tidal tensor at every pixel centre of the view, float32 (height, width, 3)."""
+        out = np.empty((view.height, view.width, 3), dtype=np.float32)
+        hip_lib().nb_hip_tidal_map(self._h, C.byref(view), softening, out.ctypes.data)
+        return out
+
     def last_diag_ms(self):
         """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
-        acceleration_at() / acceleration_map()."""
+        acceleration_at() / acceleration_map() / tidal_at() / tidal_map()."""
         return float(hip_lib().nb_hip_last_diag_ms(self._h))
 
     def bounds(self):
@@ -755,9 +779,10 @@ def _member_points(points, count):
 
 
 def _ensemble_field(fn, handle, count, components, softening, points=None, views=None):
-    """One of the four field calls of an ensemble (fn: nb_hip_ensemble_* of a SimBatch, include/nbody_batch_field.h of a
-    WorldBatch) at `points` or, where they are None, under `views`: float32 (B, n) / (B, h, w), with a last axis of 2 for g."""
-    tail = (2,) if components == 2 else ()
+    """One of the six field calls of an ensemble (fn: nb_hip_ensemble_* of a SimBatch, include/nbody_batch_field.h of a
+    WorldBatch) at `points` or, where they are None, under `views`: float32 (B, n) / (B, h, w), with a last axis of 2 for g
+    and of 3 for the tidal tensor."""
+    tail = (components,) if components > 1 else ()
     if points is not None:
         pts = _member_points(points, count)
         out = np.empty((count, pts.shape[1]) + tail, dtype=np.float32)
@@ -780,6 +805,19 @@ def _view_array(views, count):
     for b, v in enumerate(views):
         C.memmove(C.byref(arr[b]), C.byref(v), C.sizeof(RenderView))
     return arr, int(arr[0].width), int(arr[0].height)
+
+
+def tidal_invariants(t):
+    """(trace, lambda_plus, lambda_minus) of tidal tensors t (..., 3) in the order (xx, xy, yy), float64: the in-plane trace
+    xx + yy and the eigenvalues trace / 2 +- sqrt(((xx - yy) / 2)^2 + xy^2), lambda_plus >= lambda_minus.  A positive
+    eigenvalue stretches a small body along its axis, a negative one compresses it."""
+    a = np.asarray(t, dtype=np.float64)
+    if a.shape[-1:] != (3,):
+        raise ValueError("tidal tensors must have a last axis of 3: (xx, xy, yy)")
+    xx, xy, yy = a[..., 0], a[..., 1], a[..., 2]
+    trace = xx + yy
+    root = np.sqrt(((xx - yy) / 2.0) ** 2 + xy ** 2)
+    return trace, trace / 2.0 + root, trace / 2.0 - root
 
 
 def contact_sheet(frames, columns):
@@ -976,9 +1014,18 @@ class SimBatch:
         """nb_hip_ensemble_acceleration_map: g at every pixel centre, float32 (B, height, width, 2)."""
         return _ensemble_field(hip_lib().nb_hip_ensemble_acceleration_map, self._h, self.count, 2, softening, views=views)
 
+    def tidal_at(self, points, softening):
+        """nb_hip_ensemble_tidal_at: the tidal tensor of every member at its points, float32 (B, n, 3) in the order (xx, xy,
+        yy).  Member b's rows are bit-identical to SimPipeline.tidal_at of the same particles.  Ragged ensembles included."""
+        return _ensemble_field(hip_lib().nb_hip_ensemble_tidal_at, self._h, self.count, 3, softening, points=points)
+
+    def tidal_map(self, views, softening):
+        """nb_hip_ensemble_tidal_map: the tidal tensor at every pixel centre, float32 (B, height, width, 3)."""
+        return _ensemble_field(hip_lib().nb_hip_ensemble_tidal_map, self._h, self.count, 3, softening, views=views)
+
     def last_diag_ms(self):
         """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
-        acceleration_at() / acceleration_map()."""
+        acceleration_at() / acceleration_map() / tidal_at() / tidal_map()."""
         return float(hip_lib().nb_hip_ensemble_last_diag_ms(self._h))
 
     def bounds(self):
@@ -1167,6 +1214,15 @@ class WorldBatch:
         """RenderWorldBatchAcceleration: float32 (B, height, width, 2)."""
         return _ensemble_field(nbody_lib().RenderWorldBatchAcceleration, self._h, self.count, 2, softening, views=views)
 
+    def tidal_at(self, points, softening):
+        """GetWorldBatchTidalAt (include/nbody_batch_tidal.h): the tidal tensor of every member at its points, float32
+        (B, n, 3) in the order (xx, xy, yy); ragged batches included."""
+        return _ensemble_field(nbody_lib().GetWorldBatchTidalAt, self._h, self.count, 3, softening, points=points)
+
+    def tidal_map(self, views, softening):
+        """RenderWorldBatchTidal: float32 (B, height, width, 3)."""
+        return _ensemble_field(nbody_lib().RenderWorldBatchTidal, self._h, self.count, 3, softening, views=views)
+
     def bounds(self):
         """GetWorldBatchBounds (include/nbody_batch_render.h): float32 (B, 4)."""
         out = np.empty((self.count, 4), dtype=np.float32)
@@ -1347,6 +1403,20 @@ class World:
         """RenderWorldAcceleration: g at every pixel centre of the view, float32 (height, width, 2)."""
         out = np.empty((view.height, view.width, 2), dtype=np.float32)
         nbody_lib().RenderWorldAcceleration(self._h, C.byref(view), softening, out.ctypes.data)
+        return out
+
+    def tidal_at(self, points, softening):
+        """GetWorldTidalAt (include/nbody_tidal.h): the tidal tensor dg/dp at the (n, 2) points with one softening, float32
+        (n, 3) in the order (xx, xy, yy)."""
+        pts = as_points(points)
+        out = np.empty((pts.shape[0], 3), dtype=np.float32)
+        nbody_lib().GetWorldTidalAt(self._h, pts.ctypes.data, pts.shape[0], softening, out.ctypes.data)
+        return out
+
+    def tidal_map(self, view, softening):
+        """RenderWorldTidal: the tidal tensor at every pixel centre of the view, float32 (height, width, 3)."""
+        out = np.empty((view.height, view.width, 3), dtype=np.float32)
+        nbody_lib().RenderWorldTidal(self._h, C.byref(view), softening, out.ctypes.data)
         return out
 
     def bounds(self):

@@ -1,4 +1,4 @@
-// batch_field.h -- what batch_observe.hip needs of batch_field.hip (the ensemble's field sampler).
+// batch_field.h -- what batch_observe.hip needs of batch_field.hip and tidal.hip (the ensemble's field sampler).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,11 +19,14 @@ struct EnsembleParams {
     uint32_t n;                // samples per member
     uint32_t width;            // map only
     float soft;
-    void *out;                 // member b's results start at b * n: float (potential) or float2 (acceleration)
+    void *out;                 // member b's results start at b * n: float (potential), float2 (acceleration) or three floats (tidal)
 };
 
 // Phi (acceleration = false) or g at every sample of every member, one launch: grid (tiles of 128 samples / 4, count)
 void launch_ensemble_sample(hipStream_t stream, const EnsembleParams &p, uint32_t count, bool acceleration, bool map);
+
+// T = dg/dp the same way (tidal.hip): (xx, xy, yy) per sample
+void launch_ensemble_tidal(hipStream_t stream, const EnsembleParams &p, uint32_t count, bool map);
 
 }  // namespace field
 }  // namespace nb

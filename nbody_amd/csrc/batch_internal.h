@@ -60,10 +60,10 @@ struct SimBatch {
     std::vector<double> diag_host;   // the results on the host before they become WorldEnergy
     nbi::Interval diag_iv;
 
-    // nb_hip_ensemble_potential_at / _potential_map / _acceleration_at / _acceleration_map (kernel: batch_field.hip): grown on
-    // demand; they share diag_iv
+    // nb_hip_ensemble_potential_at / _potential_map / _acceleration_at / _acceleration_map (kernel: batch_field.hip) and
+    // nb_hip_ensemble_tidal_at / _tidal_map (kernel: tidal.hip): grown on demand; they share diag_iv
     nbi::DevBuf<float> sample_in;    // [count] probe sets of (x, y) pairs, or [count] maps' width column + height row coordinates
-    nbi::DevBuf<float> sample_out;   // the device result: [count][n] floats (Phi) or float pairs (g)
+    nbi::DevBuf<float> sample_out;   // the device result: [count][n] floats (Phi), float pairs (g) or triples (T)
 
     // nb_hip_ensemble_trace: the rows of the last traced call, on the device and on their way to WorldEnergy
     nbi::DevBuf<double> trace;     // [records][count][NB_DIAG_SUMS]

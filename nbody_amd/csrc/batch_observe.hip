@@ -1,6 +1,6 @@
 // batch_observe.hip -- the read-only calls on a SimBatch: energy and potential of every member (kernels: batch_diag.hip),
-// bounds, count images and frames (kernels: render_kernels.hip), the potential and the acceleration field at probe points and
-// over views (kernel: batch_field.hip), with their tuning hooks and timers.  Each
+// bounds, count images and frames (kernels: render_kernels.hip), the potential, the acceleration field and the tidal tensor at
+// probe points and over views (kernels: batch_field.hip, tidal.hip), with their tuning hooks and timers.  Each
 // looks at the latest state without reading the particles back: a constant number of launches, one copy, one sync for any B.
 #include "batch_internal.h"
 #include "batch_diag.h"
@@ -118,7 +118,7 @@ void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *p
     s->render_launches = *launches;
 }
 
-// ---- fields: Phi and g of every member at n samples each, without reading the particles back ------------------------
+// ---- fields: Phi, g and T of every member at n samples each, without reading the particles back ------------------------
 
 // what a field call checks before it looks at its samples; `samples` = all members' together
 void check_field(SimBatch *s, const char *what, float softening, uint64_t samples) {
@@ -131,9 +131,10 @@ void check_field(SimBatch *s, const char *what, float softening, uint64_t sample
 
 // upload `in_stride` floats per member, evaluate n samples of every member in one launch, one copy of the result, one sync;
 // `in` stays alive until the sync
-void sample_members(SimBatch *s, const char *what, bool acceleration, bool map, const float *in, uint32_t in_stride, uint32_t n,
+// `comps` floats per sample name the quantity: 1 = Phi, 2 = g, 3 = T
+void sample_members(SimBatch *s, const char *what, uint32_t comps, bool map, const float *in, uint32_t in_stride, uint32_t n,
                     uint32_t width, float softening, float *out) {
-    const size_t in_floats = (size_t)s->count * in_stride, out_floats = (size_t)s->count * n * (acceleration ? 2 : 1);
+    const size_t in_floats = (size_t)s->count * in_stride, out_floats = (size_t)s->count * n * comps;
     use_device();
     s->sample_in.grown(s->stream, in_floats);
     s->sample_out.grown(s->stream, out_floats);
@@ -151,7 +152,10 @@ void sample_members(SimBatch *s, const char *what, bool acceleration, bool map, 
     p.soft = softening;
     p.out = s->sample_out;
     s->diag_iv.begin(s->stream);
-    nb::field::launch_ensemble_sample(s->stream, p, s->count, acceleration, map);
+    if (comps == 3)
+        nb::field::launch_ensemble_tidal(s->stream, p, s->count, map);
+    else
+        nb::field::launch_ensemble_sample(s->stream, p, s->count, comps == 2, map);
     ASSERT_HIP(hipGetLastError(), "%s: ensemble_sample_kernel launch (%u members, %u samples each)", what, s->count, n);
     s->diag_iv.end(s->stream);
     ASSERT_HIP(hipMemcpyAsync(out, s->sample_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream), "%s: D2H of %u members' results",
@@ -159,18 +163,18 @@ void sample_members(SimBatch *s, const char *what, bool acceleration, bool map, 
     ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after %s", what);
 }
 
-void sample_members_at(SimBatch *s, const char *what, bool acceleration, const float *points, uint32_t n, float softening, float *out) {
+void sample_members_at(SimBatch *s, const char *what, uint32_t comps, const float *points, uint32_t n, float softening, float *out) {
     check_field(s, what, softening, s ? (uint64_t)s->count * n : 0);
     NB_ASSERT((points != nullptr && out != nullptr) || n == 0, "%s: NULL points or result", what);
     if (n == 0) {
         s->diag_iv.clear();
         return;
     }
-    sample_members(s, what, acceleration, false, points, 2 * n, n, 0, softening, out);
+    sample_members(s, what, comps, false, points, 2 * n, n, 0, softening, out);
 }
 
 // a map is the probes product at the member's own pixel centres: per member width column coordinates, then height row coordinates
-void sample_members_map(SimBatch *s, const char *what, bool acceleration, const RenderView *views, float softening, float *out) {
+void sample_members_map(SimBatch *s, const char *what, uint32_t comps, const RenderView *views, float softening, float *out) {
     check_field(s, what, softening, 0);
     check_views(s, views, what);
     const uint32_t width = views[0].width, height = views[0].height;
@@ -181,7 +185,7 @@ void sample_members_map(SimBatch *s, const char *what, bool acceleration, const 
         float *xs = coords.data() + (size_t)b * (width + height);
         nb_render_pixel_centres(&views[b], xs, xs + width);
     }
-    sample_members(s, what, acceleration, true, coords.data(), width + height, width * height, width, softening, out);
+    sample_members(s, what, comps, true, coords.data(), width + height, width * height, width, softening, out);
 }
 
 }  // namespace
@@ -221,19 +225,27 @@ void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
 }
 
 void nb_hip_ensemble_potential_at(SimBatch *s, const float *points, uint32_t n, float softening, float *phi) {
-    sample_members_at(s, "nb_hip_ensemble_potential_at", false, points, n, softening, phi);
+    sample_members_at(s, "nb_hip_ensemble_potential_at", 1, points, n, softening, phi);
 }
 
 void nb_hip_ensemble_potential_map(SimBatch *s, const RenderView *views, float softening, float *phi) {
-    sample_members_map(s, "nb_hip_ensemble_potential_map", false, views, softening, phi);
+    sample_members_map(s, "nb_hip_ensemble_potential_map", 1, views, softening, phi);
 }
 
 void nb_hip_ensemble_acceleration_at(SimBatch *s, const float *points, uint32_t n, float softening, float *acc) {
-    sample_members_at(s, "nb_hip_ensemble_acceleration_at", true, points, n, softening, acc);
+    sample_members_at(s, "nb_hip_ensemble_acceleration_at", 2, points, n, softening, acc);
 }
 
 void nb_hip_ensemble_acceleration_map(SimBatch *s, const RenderView *views, float softening, float *acc) {
-    sample_members_map(s, "nb_hip_ensemble_acceleration_map", true, views, softening, acc);
+    sample_members_map(s, "nb_hip_ensemble_acceleration_map", 2, views, softening, acc);
+}
+
+void nb_hip_ensemble_tidal_at(SimBatch *s, const float *points, uint32_t n, float softening, float *t) {
+    sample_members_at(s, "nb_hip_ensemble_tidal_at", 3, points, n, softening, t);
+}
+
+void nb_hip_ensemble_tidal_map(SimBatch *s, const RenderView *views, float softening, float *t) {
+    sample_members_map(s, "nb_hip_ensemble_tidal_map", 3, views, softening, t);
 }
 
 // tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_ensemble_energy / _potential / field call

@@ -1,6 +1,6 @@
 /*
- * field_common.h -- what the two paths of include/nbody_field.h and include/nbody_gravity.h share: the argument checks of
- * a field call (the limits of the two headers are the same), written once for the GPU path (field.hip) and the host path
+ * field_common.h -- what the two paths of include/nbody_field.h, include/nbody_gravity.h and include/nbody_tidal.h share: the
+ * argument checks of a field call (the limits of the three headers are the same), written once for the GPU path (field.hip) and the host path
  * (field_cpu.c), and the host path's entry points (hidden, libnbody.so).  The pixel centres of a map come from
  * render_common.h's nb_render_pixel_centres on both paths.
  */
@@ -9,6 +9,7 @@
 
 #include "nbody_field.h"
 #include "nbody_gravity.h"
+#include "nbody_tidal.h"
 #include "render_common.h"
 
 /* NULL when the softening and the sample count are within the limits of include/nbody_field.h, else what is wrong */
@@ -31,6 +32,10 @@ __attribute__((visibility("hidden"))) void nb_cpu_acceleration_at(const Particle
                                                                   float softening, V2 *acc);
 __attribute__((visibility("hidden"))) void nb_cpu_acceleration_map(const Particle *ps, uint32_t mass_len, const RenderView *view,
                                                                    float softening, V2 *acc);
+__attribute__((visibility("hidden"))) void nb_cpu_tidal_at(const Particle *ps, uint32_t mass_len, const V2 *points, uint32_t n,
+                                                           float softening, TidalTensor *t);
+__attribute__((visibility("hidden"))) void nb_cpu_tidal_map(const Particle *ps, uint32_t mass_len, const RenderView *view,
+                                                            float softening, TidalTensor *t);
 
 #ifdef __cplusplus
 }

@@ -58,6 +58,9 @@ extern "C" {
  *               "field_shape": field.hip has one pick_wave_shape and one pair of thresholds; the sweep for this pair body,
  *               profiles/r13_gravity_probe.json, puts its crossover in the same place), 1 = the source split, 2 = one wave
  *               per tile; same bits (tests/test_gpu_gravity.py)
+ *   "tidal_shape"   which kernel nb_hip_tidal_at / nb_hip_tidal_map run: 0 (default) = auto (the same pick_wave_shape and
+ *               thresholds, inherited, not retuned: tools/tidal_probe.py reports where this pair body's crossover lies), 1 = the
+ *               source split, 2 = one wave per tile; same bits (tests/test_gpu_tidal.py)
  *   "zero_copy_upload"  1 (default) = SetSimulationData from the noted, page-locked array lets the split kernel read the
  *               records over PCIe itself; 0 = DMA copy into device staging, then the kernel
  * Returns the previous value; aborts on an unknown key or value.
@@ -94,8 +97,8 @@ int nb_hip_deal_item(uint32_t ticket, uint32_t tiles, uint32_t split, uint32_t *
 uint32_t nb_hip_deal_counter(SimPipeline *sim);
 
 /* Device milliseconds of the kernels of the last nb_hip_energy / nb_hip_potential / nb_hip_potential_at /
- * nb_hip_potential_map / nb_hip_acceleration_at / nb_hip_acceleration_map (their own event pair, not the step's); 0 before
- * the first call. */
+ * nb_hip_potential_map / nb_hip_acceleration_at / nb_hip_acceleration_map / nb_hip_tidal_at / nb_hip_tidal_map (their own
+ * event pair, not the step's); 0 before the first call. */
 double nb_hip_last_diag_ms(SimPipeline *sim);
 
 /* The same for an ensemble: device milliseconds of the kernels of the last nb_hip_ensemble_energy /

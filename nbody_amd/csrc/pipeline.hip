@@ -633,6 +633,10 @@ int nb_hip_tune(SimPipeline *s, const char *key, int value) {
         NB_ASSERT(value >= 0 && value <= 2, "gravity_shape must be 0 (auto), 1 (source split) or 2 (one wave per tile), got %d", value);
         old = s->gravity_shape;
         s->gravity_shape = value;
+    } else if (!strcmp(key, "tidal_shape")) {
+        NB_ASSERT(value >= 0 && value <= 2, "tidal_shape must be 0 (auto), 1 (source split) or 2 (one wave per tile), got %d", value);
+        old = s->tidal_shape;
+        s->tidal_shape = value;
     } else if (!strcmp(key, "render_detail")) {
         old = s->render_detail;
         s->render_detail = value ? 1 : 0;

@@ -28,6 +28,9 @@
 //   render_kernels.hip  the render kernels of a world and of an ensemble, what they share written once, and their launchers (render_kernels.h)
 //   field.hip        the potential and the acceleration at probe points and as maps over a view (nb_hip_potential_at,
 //                    nb_hip_potential_map, nb_hip_acceleration_at, nb_hip_acceleration_map): one sampler, two pair statements
+//                    (the kernel templates and the host side of a call: field_sampler.h)
+//   tidal.hip        the tidal tensor at the same places, for a pipeline and for an ensemble (nb_hip_tidal_at, nb_hip_tidal_map;
+//                    the kernels behind nb_hip_ensemble_tidal_at / _tidal_map): the sampler's third pair statement
 //   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
 //   leapfrog.hip     the kick / drift passes of a kick-drift-kick step around a dt = 0 force launch (leapfrog.h, leapfrog_common.h)
 #pragma once
@@ -434,12 +437,13 @@ struct SimPipeline {
     bool render_detailed = false;          // the last render recorded those two
     int render_merge = 1, render_detail = 0;   // tuning hooks (nbody_hip_tuning.h)
 
-    // field.hip (nb_hip_potential_at / _map, nb_hip_acceleration_at / _map): one pair of buffers grown on demand and shared by
-    // the four calls (each ends in a stream sync, so no two are in flight); the interval is diag_iv
+    // field.hip, tidal.hip (nb_hip_potential_at / _map, nb_hip_acceleration_at / _map, nb_hip_tidal_at / _map): one pair of
+    // buffers grown on demand and shared by the six calls (each ends in a stream sync, so no two are in flight); the interval is diag_iv
     nbi::DevBuf<float> sample_in;    // the probes' (x, y) pairs, or a map's width column + height row coordinates
-    nbi::DevBuf<float> sample_out;   // the device result: one float (Phi) or two (g) per sample
-    int field_shape = 0;           // tuning hooks, Phi and g: 0 auto, 1 source split, 2 one wave per tile
+    nbi::DevBuf<float> sample_out;   // the device result: one float (Phi), two (g) or three (T) per sample
+    int field_shape = 0;           // tuning hooks, Phi, g and T: 0 auto, 1 source split, 2 one wave per tile
     int gravity_shape = 0;
+    int tidal_shape = 0;
 
     // adaptive steps (step_schedule.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
     // ADAPT_HEAD bytes of records (the call's AdaptState, the record and result of nb_hip_timestep), then the call's log

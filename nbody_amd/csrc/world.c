@@ -25,6 +25,8 @@
  * follow the same rule (field.hip on the device, field_cpu.c on the host).
  * Extension (include/nbody_gravity.h): GetWorldAccelerationAt /
  * RenderWorldAcceleration likewise (the same two files).
+ * Extension (include/nbody_tidal.h): GetWorldTidalAt / RenderWorldTidal
+ * likewise (tidal.hip on the device, field_cpu.c on the host).
  * Extension (include/nbody_adaptive.h): adaptive steps.  UpdateWorld_GPU_Adaptive
  * and AdvanceWorld_GPU follow UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Adaptive
  * UpdateWorld_CPU's; GetWorldTimestep follows the diagnostics' (timestep.hip on the
@@ -39,6 +41,7 @@
 #include "nbody_diag.h"
 #include "nbody_field.h"
 #include "nbody_gravity.h"
+#include "nbody_tidal.h"
 #include "nbody_hip.h"
 #include "nbody_leapfrog.h"
 #include "nbody_render.h"
@@ -255,6 +258,22 @@ void RenderWorldAcceleration(World *w, const RenderView *view, float softening, 
         nb_hip_acceleration_map(w->gpu, view, softening, (float *)acc);
     else
         nb_cpu_acceleration_map(w->particles, w->massive, view, softening, acc);
+}
+
+void GetWorldTidalAt(World *w, const V2 *points, uint32_t n, float softening, TidalTensor *t) {
+    NB_CHECK(w != NULL && ((points != NULL && t != NULL) || n == 0), "NULL argument");
+    if (diag_on_device(w, "GetWorldTidalAt"))
+        nb_hip_tidal_at(w->gpu, (const float *)points, n, softening, (float *)t);
+    else
+        nb_cpu_tidal_at(w->particles, w->massive, points, n, softening, t);
+}
+
+void RenderWorldTidal(World *w, const RenderView *view, float softening, TidalTensor *t) {
+    NB_CHECK(w != NULL && view != NULL && t != NULL, "NULL argument");
+    if (diag_on_device(w, "RenderWorldTidal"))
+        nb_hip_tidal_map(w->gpu, view, softening, (float *)t);
+    else
+        nb_cpu_tidal_map(w->particles, w->massive, view, softening, t);
 }
 
 /* ---- include/nbody_adaptive.h ---------------------------------------------------------------------------------------- */

@@ -20,13 +20,15 @@
  * coherence; ragged batches abort.
  * include/nbody_batch_field.h: the potential and the acceleration field of every member at probe points and over views follow
  * the diagnostics' protocol (device: nb_hip_ensemble_potential_at and its three siblings, one launch; host: field_cpu.c member
- * by member), for uniform and ragged batches alike.
+ * by member), for uniform and ragged batches alike.  include/nbody_batch_tidal.h: the tidal tensor likewise
+ * (nb_hip_ensemble_tidal_at / _tidal_map), through the same two functions.
  */
 #include "nbody_adaptive.h"
 #include "nbody_leapfrog.h"
 #include "nbody_batch.h"
 #include "nbody_batch_diag.h"
 #include "nbody_batch_field.h"
+#include "nbody_batch_tidal.h"
 #include "nbody_batch_ragged.h"
 #include "nbody_batch_render.h"
 #include "nbody_batch_trace.h"
@@ -314,7 +316,7 @@ void UpdateWorldBatch_GPU_Leapfrog_dts(WorldBatch *w, const float *dt, uint32_t 
     w->device_is_newer = true;
 }
 
-/* ---- include/nbody_batch_field.h ------------------------------------------------------------------------------------- */
+/* ---- include/nbody_batch_field.h, include/nbody_batch_tidal.h -------------------------------------------------------- */
 
 static void check_field(const char *what, float softening, uint64_t samples) {
     const char *fault = nb_field_fault(softening, samples);
@@ -322,17 +324,20 @@ static void check_field(const char *what, float softening, uint64_t samples) {
              fault);
 }
 
-/* n probes of every member into phi[] (the potential) or, where phi is NULL, into acc[] */
-static void batch_field_at(WorldBatch *w, const char *what, const V2 *points, uint32_t n, float softening, float *phi, V2 *acc) {
+/* n probes of every member into phi[] (the potential) or, where phi is NULL, into acc[] or, where both are NULL, into tid[] */
+static void batch_field_at(WorldBatch *w, const char *what, const V2 *points, uint32_t n, float softening, float *phi, V2 *acc,
+                           TidalTensor *tid) {
     NB_CHECK(w != NULL, "%s: NULL argument", what);
     check_field(what, softening, (uint64_t)w->count * n);
-    NB_CHECK((points != NULL && (phi != NULL || acc != NULL)) || n == 0, "%s: NULL argument", what);
+    NB_CHECK((points != NULL && (phi != NULL || acc != NULL || tid != NULL)) || n == 0, "%s: NULL argument", what);
     if (n == 0) return;
     if (w->device_is_newer) {
         if (phi)
             nb_hip_ensemble_potential_at(w->gpu, (const float *)points, n, softening, phi);
-        else
+        else if (acc)
             nb_hip_ensemble_acceleration_at(w->gpu, (const float *)points, n, softening, (float *)acc);
+        else
+            nb_hip_ensemble_tidal_at(w->gpu, (const float *)points, n, softening, (float *)tid);
         return;
     }
     for (uint32_t b = 0; b < w->count; b++) {
@@ -340,45 +345,60 @@ static void batch_field_at(WorldBatch *w, const char *what, const V2 *points, ui
         const size_t at = (size_t)b * n;
         if (phi)
             nb_cpu_potential_at(ps, w->massive[b], points + at, n, softening, phi + at);
-        else
+        else if (acc)
             nb_cpu_acceleration_at(ps, w->massive[b], points + at, n, softening, acc + at);
+        else
+            nb_cpu_tidal_at(ps, w->massive[b], points + at, n, softening, tid + at);
     }
 }
 
-/* the map of every member under its view into phi[] or, where phi is NULL, into acc[] */
-static void batch_field_map(WorldBatch *w, const char *what, const RenderView *views, float softening, float *phi, V2 *acc) {
-    NB_CHECK(w != NULL && views != NULL && (phi != NULL || acc != NULL), "%s: NULL argument", what);
+/* the map of every member under its view into phi[] or, where phi is NULL, into acc[] or, where both are NULL, into tid[] */
+static void batch_field_map(WorldBatch *w, const char *what, const RenderView *views, float softening, float *phi, V2 *acc,
+                            TidalTensor *tid) {
+    NB_CHECK(w != NULL && views != NULL && (phi != NULL || acc != NULL || tid != NULL), "%s: NULL argument", what);
     check_views(w, views);
     const size_t image = (size_t)views[0].width * views[0].height;
     check_field(what, softening, (uint64_t)w->count * image);
     if (w->device_is_newer) {
         if (phi)
             nb_hip_ensemble_potential_map(w->gpu, views, softening, phi);
-        else
+        else if (acc)
             nb_hip_ensemble_acceleration_map(w->gpu, views, softening, (float *)acc);
+        else
+            nb_hip_ensemble_tidal_map(w->gpu, views, softening, (float *)tid);
         return;
     }
     for (uint32_t b = 0; b < w->count; b++) {
         const Particle *ps = w->particles + w->offset[b];
         if (phi)
             nb_cpu_potential_map(ps, w->massive[b], views + b, softening, phi + (size_t)b * image);
-        else
+        else if (acc)
             nb_cpu_acceleration_map(ps, w->massive[b], views + b, softening, acc + (size_t)b * image);
+        else
+            nb_cpu_tidal_map(ps, w->massive[b], views + b, softening, tid + (size_t)b * image);
     }
 }
 
 void GetWorldBatchPotentialAt(WorldBatch *w, const V2 *points, uint32_t n, float softening, float *phi) {
-    batch_field_at(w, "GetWorldBatchPotentialAt", points, n, softening, phi, NULL);
+    batch_field_at(w, "GetWorldBatchPotentialAt", points, n, softening, phi, NULL, NULL);
 }
 
 void RenderWorldBatchPotential(WorldBatch *w, const RenderView *views, float softening, float *phi) {
-    batch_field_map(w, "RenderWorldBatchPotential", views, softening, phi, NULL);
+    batch_field_map(w, "RenderWorldBatchPotential", views, softening, phi, NULL, NULL);
 }
 
 void GetWorldBatchAccelerationAt(WorldBatch *w, const V2 *points, uint32_t n, float softening, V2 *acc) {
-    batch_field_at(w, "GetWorldBatchAccelerationAt", points, n, softening, NULL, acc);
+    batch_field_at(w, "GetWorldBatchAccelerationAt", points, n, softening, NULL, acc, NULL);
 }
 
 void RenderWorldBatchAcceleration(WorldBatch *w, const RenderView *views, float softening, V2 *acc) {
-    batch_field_map(w, "RenderWorldBatchAcceleration", views, softening, NULL, acc);
+    batch_field_map(w, "RenderWorldBatchAcceleration", views, softening, NULL, acc, NULL);
+}
+
+void GetWorldBatchTidalAt(WorldBatch *w, const V2 *points, uint32_t n, float softening, TidalTensor *t) {
+    batch_field_at(w, "GetWorldBatchTidalAt", points, n, softening, NULL, NULL, t);
+}
+
+void RenderWorldBatchTidal(WorldBatch *w, const RenderView *views, float softening, TidalTensor *t) {
+    batch_field_map(w, "RenderWorldBatchTidal", views, softening, NULL, NULL, t);
 }
