@@ -637,6 +637,31 @@ void nb_hip_ensemble_tidal_at(SimBatch *batch, const float *points /* [count][n]
 void nb_hip_ensemble_tidal_map(SimBatch *batch, const RenderView *views /* [count] */, float softening, float *t /* [count][h][w][3] */);
 
 /*
+ * Radial profiles of the state a pipeline or an ensemble holds: the six float64 annulus moments (count, S, I, L, W, K) of
+ * every row about a centre (definitions, row rule and summation order: include/nbody_profile.h; kernels:
+ * nbody_amd/csrc/profile.hip).  edges: bins + 1 float32 radii, 1 <= bins <= 254; centre: (cx, cy, ux, uy); weights:
+ * NB_PROFILE_BY_MASS = 0 (particles i < mass_len, weight m_i; a massless particle is never read) or NB_PROFILE_BY_NUMBER = 1
+ * (all total_len particles, weight 1); out: [bins + 2][6] doubles; unplaced (nullable): the particles whose squared radius is NaN.
+ *   nb_hip_profile            one workgroup per chunk of 1024 particles stores the chunk's rows to a slab the pipeline owns, one
+ *                             thread per (row, column) then adds the chunks in order.  Upload bins + 1 + 4 floats, download
+ *                             rows * 48 + 4 bytes, one sync.  Enqueued, blocking and invisible to the steps like nb_hip_energy;
+ *                             sharded pipelines abort like it.  Nothing to read (total_len = 0, or mass mode with mass_len = 0)
+ *                             gives +0 everywhere and touches no device.
+ *   nb_hip_ensemble_profile   every member of an ensemble, uniform or ragged, in ONE launch: one workgroup per member walks its
+ *                             three chunks or fewer.  The edges are shared, the centre is per member: centres[count][4].
+ *                             out[count][bins + 2][6], unplaced[count].  Member b's values are BIT-IDENTICAL to nb_hip_profile
+ *                             of a SimPipeline holding the same particles.
+ * No float atomics: a result is a function of the state and the arguments alone.  Every check -- NULL arguments, bins of 0 or
+ * above 254, non-finite, negative or non-increasing edges, a non-finite centre, an unknown weights, a call before the data is
+ * set -- runs before any device touch and ends in "file:line [func] ..." + abort().
+ * Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_profile", dlsym "nb_hip_ensemble_profile").
+ */
+void nb_hip_profile(SimPipeline *sim, const float *edges, uint32_t bins, const float centre[4], int weights, double *out,
+                    uint32_t *unplaced);
+void nb_hip_ensemble_profile(SimBatch *batch, const float *edges, uint32_t bins, const float *centres /* [count][4] */, int weights,
+                             double *out /* [count][bins + 2][6] */, uint32_t *unplaced /* [count] */);
+
+/*
  * Adaptive time steps chosen on the device (definitions: include/nbody_adaptive.h; kernels: nbody_amd/csrc/timestep.hip).
  *   nb_hip_adaptive_steps         n steps, each of the size the criterion gives for the state before it; blocking
  *   nb_hip_adaptive_steps_async   the same, enqueue only

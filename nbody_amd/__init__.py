@@ -121,6 +121,19 @@ def adaptive_cfg(eta, dt_max, dt_min=0.0, span=float("inf"), prime=False, chunk=
     return NbAdaptive(float(eta), float(dt_min), float(dt_max), flags, float(span), int(chunk), 0)
 
 
+NB_PROFILE_BY_MASS = 0     # include/nbody_profile.h
+NB_PROFILE_BY_NUMBER = 1
+NB_PROFILE_MAX_BINS = 254
+NB_PROFILE_QTY = 6
+NB_PROFILE_CHUNK = 1024
+
+
+class WorldProfileSpec(C.Structure):
+    """include/nbody_profile.h WorldProfileSpec; `edges` points into an array the caller keeps alive."""
+    _fields_ = [("edges", C.c_void_p), ("bins", C.c_uint32), ("centre", C.c_float * 2), ("centre_velocity", C.c_float * 2),
+                ("weights", C.c_int)]
+
+
 class NbShardPlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mass_chunk", "zero_chunk", "mass_begin", "mass_count",
                                           "zero_begin", "zero_count", "src_padded")]
@@ -181,6 +194,8 @@ HIP_API = {
     "nb_hip_acceleration_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_tidal_at": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "nb_hip_tidal_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    "nb_hip_profile": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "nb_hip_ensemble_profile": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nb_hip_batch_destroy": (None, [C.c_void_p]),
     "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
@@ -256,7 +271,8 @@ PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb
 
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
 # include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h +
-# include/nbody_adaptive.h + include/nbody_leapfrog.h + include/nbody_batch_field.h + include/nbody_tidal.h + include/nbody_batch_tidal.h
+# include/nbody_adaptive.h + include/nbody_leapfrog.h + include/nbody_batch_field.h + include/nbody_tidal.h + include/nbody_batch_tidal.h +
+# include/nbody_profile.h + include/nbody_batch_profile.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -286,6 +302,9 @@ NBODY_API = {
     # include/nbody_tidal.h
     "GetWorldTidalAt": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]),
     "RenderWorldTidal": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
+    # include/nbody_profile.h, include/nbody_batch_profile.h
+    "GetWorldProfile": (None, [C.c_void_p, C.POINTER(WorldProfileSpec), C.c_void_p, C.c_void_p]),
+    "GetWorldBatchProfile": (None, [C.c_void_p, C.POINTER(WorldProfileSpec), C.c_uint32, C.c_void_p, C.c_void_p]),
     # include/nbody_batch.h
     "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "DestroyWorldBatch": (None, [C.c_void_p]),
@@ -668,6 +687,17 @@ class SimPipeline:
         hip_lib().nb_hip_acceleration_map(self._h, C.byref(view), softening, out.ctypes.data)
         return out
 
+    def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
+        """nb_hip_profile: the annulus moments about `centre` moving with `centre_velocity` (include/nbody_profile.h), float64
+        (bins + 2, 6) with the columns (count, S, I, L, W, K); row 0 lies inside edges[0], row bins + 1 at or beyond edges[-1].
+        weights: "mass" (massive particles, weight m) or "number" (all particles, weight 1).  With return_unplaced also the number
+        of particles whose squared radius is NaN.  A natural centre: energy()["center_of_mass"] and momentum / mass (vel is used
+        as stored, the caveat of include/nbody_diag.h).  nb.profile_curves / nb.lagrangian_radii read the result."""
+        e, bins, c, mode = _profile_args(edges, centre, centre_velocity, weights)
+        out, lost = np.empty((bins + 2, NB_PROFILE_QTY), dtype=np.float64), np.zeros(1, dtype=np.uint32)
+        hip_lib().nb_hip_profile(self._h, e.ctypes.data, bins, c.ctypes.data, mode, out.ctypes.data, lost.ctypes.data)
+        return (out, int(lost[0])) if return_unplaced else out
+
     def tidal_at(self, points, softening):
         """nb_hip_tidal_at: the tidal tensor dg/dp at the (n, 2) points with one softening (include/nbody_tidal.h), float32
         (n, 3) in the order (xx, xy, yy)."""
@@ -684,7 +714,7 @@ class SimPipeline:
 
     def last_diag_ms(self):
         """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
-        acceleration_at() / acceleration_map() / tidal_at() / tidal_map()."""
+        acceleration_at() / acceleration_map() / tidal_at() / tidal_map() / profile()."""
         return float(hip_lib().nb_hip_last_diag_ms(self._h))
 
     def bounds(self):
@@ -805,6 +835,110 @@ def _view_array(views, count):
     for b, v in enumerate(views):
         C.memmove(C.byref(arr[b]), C.byref(v), C.sizeof(RenderView))
     return arr, int(arr[0].width), int(arr[0].height)
+
+
+def _profile_args(edges, centre, centre_velocity, weights, count=None):
+    """(edges float32 (bins + 1,), bins, centres float32 (4,) or (count, 4) as (cx, cy, ux, uy), weights as the C enum)."""
+    e = np.ascontiguousarray(edges, dtype=np.float32)
+    if e.ndim != 1 or e.shape[0] < 2:
+        raise ValueError("edges must be a sequence of at least two radii")
+    modes = {"mass": NB_PROFILE_BY_MASS, "number": NB_PROFILE_BY_NUMBER, NB_PROFILE_BY_MASS: NB_PROFILE_BY_MASS,
+             NB_PROFILE_BY_NUMBER: NB_PROFILE_BY_NUMBER}
+    if isinstance(weights, (str, int)) and weights in modes:
+        mode = modes[weights]
+    elif isinstance(weights, (int, np.integer)):
+        mode = int(weights)          # the library names the fault
+    else:
+        raise ValueError('weights must be "mass" or "number"')
+    c, u = np.asarray(centre, dtype=np.float32), np.asarray(centre_velocity, dtype=np.float32)
+    if count is None:
+        if c.shape != (2,) or u.shape != (2,):
+            raise ValueError("centre and centre_velocity must have shape (2,)")
+        return e, e.shape[0] - 1, np.ascontiguousarray(np.concatenate([c, u])), mode
+    for a in (c, u):
+        if a.shape != (2,) and a.shape != (count, 2):
+            raise ValueError(f"centre and centre_velocity must have shape (2,) or ({count}, 2)")
+    both = np.empty((count, 4), dtype=np.float32)
+    both[:, 0:2], both[:, 2:4] = c, u
+    return e, e.shape[0] - 1, both, mode
+
+
+def _profile_specs(e, bins, centres, mode):
+    """One WorldProfileSpec per row of centres (count, 4), all pointing at the edges e."""
+    specs = (WorldProfileSpec * centres.shape[0])()
+    for b, row in enumerate(centres):
+        specs[b].edges, specs[b].bins, specs[b].weights = e.ctypes.data, bins, mode
+        specs[b].centre[0], specs[b].centre[1] = row[0], row[1]
+        specs[b].centre_velocity[0], specs[b].centre_velocity[1] = row[2], row[3]
+    return specs
+
+
+def profile_edges(r_min, r_max, bins, log=False):
+    """bins + 1 float32 radii from r_min to r_max, equally spaced in r or, with log, in log r (r_min > 0 then)."""
+    if bins < 1 or bins > NB_PROFILE_MAX_BINS:
+        raise ValueError(f"bins must be 1 .. {NB_PROFILE_MAX_BINS}")
+    if not (0.0 <= r_min < r_max) or (log and not r_min > 0.0):
+        raise ValueError("need 0 <= r_min < r_max, and r_min > 0 for logarithmic bins")
+    e = (np.geomspace(r_min, r_max, bins + 1) if log else np.linspace(r_min, r_max, bins + 1)).astype(np.float32)
+    if not np.all(np.diff(e) > 0):
+        raise ValueError("the edges are not strictly increasing in float32: fewer bins or a wider range")
+    return e
+
+
+def profile_curves(rows, edges):
+    """What the annulus moments of .profile() say, per bin of `edges` (rows 1 .. bins of rows (..., bins + 2, 6); the rows
+    inside edges[0] and beyond edges[-1] only enter `enclosed`).  A dict of float64 arrays (..., bins), NaN where a bin's S is
+    0: r_mid, area, surface_density = S / area, enclosed (the cumulative S up to the bin's outer edge, row 0 included),
+    r_rms = sqrt(I / S), omega = L / I, v_rot = omega r_rms, expansion = W / I, v_rad = expansion r_rms and
+    sigma2 = max(0, K - L^2 / I - W^2 / I) / S (the velocity dispersion, both components together)."""
+    r = np.asarray(rows, dtype=np.float64)
+    e = np.asarray(edges, dtype=np.float64)
+    if r.shape[-1:] != (NB_PROFILE_QTY,) or r.ndim < 2 or r.shape[-2] != e.shape[0] + 1:
+        raise ValueError("rows must have shape (..., len(edges) + 1, 6)")
+    S, I, L, W, K = (r[..., 1:-1, c] for c in range(1, 6))
+    area = np.pi * (e[1:] ** 2 - e[:-1] ** 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        empty = S == 0
+        nan = lambda a: np.where(empty, np.nan, a)
+        r_rms = np.sqrt(I / S)
+        omega, expansion = L / I, W / I
+        out = {
+            "r_mid": 0.5 * (e[1:] + e[:-1]) + np.zeros_like(S),
+            "area": area + np.zeros_like(S),
+            "surface_density": nan(S / area),
+            "enclosed": np.cumsum(r[..., :-1, 1], axis=-1)[..., 1:],
+            "r_rms": nan(r_rms),
+            "omega": nan(omega),
+            "v_rot": nan(omega * r_rms),
+            "expansion": nan(expansion),
+            "v_rad": nan(expansion * r_rms),
+            "sigma2": nan(np.maximum(0.0, K - L * L / I - W * W / I) / S),
+        }
+    return out
+
+
+def lagrangian_radii(rows, edges, fractions):
+    """The radii that enclose the given fractions of the total S (all rows) of one profile (bins + 2, 6): the enclosed mass
+    inverted, the mass of a bin taken as uniform in area, that is linear in r^2.  NaN for a fraction reached inside edges[0]
+    or only beyond edges[-1]."""
+    r = np.asarray(rows, dtype=np.float64)
+    e = np.asarray(edges, dtype=np.float64)
+    if r.shape != (e.shape[0] + 1, NB_PROFILE_QTY):
+        raise ValueError("rows must have shape (len(edges) + 1, 6)")
+    f = np.atleast_1d(np.asarray(fractions, dtype=np.float64))
+    at_edge = np.cumsum(r[:-1, 1])          # the S inside edges[t]
+    target = f * r[:, 1].sum()
+    out = np.full(f.shape, np.nan)
+    for i, m in enumerate(target):
+        if not (at_edge[0] <= m <= at_edge[-1]) or not np.isfinite(m):
+            continue
+        t = int(np.searchsorted(at_edge, m, side="left"))       # the first edge with at_edge[t] >= m
+        if t == 0 or at_edge[t] == at_edge[t - 1]:
+            out[i] = e[t]
+            continue
+        x = (m - at_edge[t - 1]) / (at_edge[t] - at_edge[t - 1])
+        out[i] = np.sqrt(e[t - 1] ** 2 + x * (e[t] ** 2 - e[t - 1] ** 2))
+    return out if np.ndim(fractions) else out[0]
 
 
 def tidal_invariants(t):
@@ -1014,6 +1148,16 @@ class SimBatch:
         """nb_hip_ensemble_acceleration_map: g at every pixel centre, float32 (B, height, width, 2)."""
         return _ensemble_field(hip_lib().nb_hip_ensemble_acceleration_map, self._h, self.count, 2, softening, views=views)
 
+    def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
+        """nb_hip_ensemble_profile: the annulus moments of every member (include/nbody_profile.h), float64 (B, bins + 2, 6); the edges are
+        shared, centre and centre_velocity are (2,) for all members or (B, 2).  Member b's rows are bit-identical to
+        SimPipeline.profile of the same particles; ragged ensembles included.  With return_unplaced also the uint32 (B,) counts of
+        particles whose squared radius is NaN."""
+        e, bins, c, mode = _profile_args(edges, centre, centre_velocity, weights, self.count)
+        out, lost = np.empty((self.count, bins + 2, NB_PROFILE_QTY), dtype=np.float64), np.zeros(self.count, dtype=np.uint32)
+        hip_lib().nb_hip_ensemble_profile(self._h, e.ctypes.data, bins, c.ctypes.data, mode, out.ctypes.data, lost.ctypes.data)
+        return (out, lost) if return_unplaced else out
+
     def tidal_at(self, points, softening):
         """nb_hip_ensemble_tidal_at: the tidal tensor of every member at its points, float32 (B, n, 3) in the order (xx, xy,
         yy).  Member b's rows are bit-identical to SimPipeline.tidal_at of the same particles.  Ragged ensembles included."""
@@ -1025,7 +1169,7 @@ class SimBatch:
 
     def last_diag_ms(self):
         """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
-        acceleration_at() / acceleration_map() / tidal_at() / tidal_map()."""
+        acceleration_at() / acceleration_map() / tidal_at() / tidal_map() / profile()."""
         return float(hip_lib().nb_hip_ensemble_last_diag_ms(self._h))
 
     def bounds(self):
@@ -1213,6 +1357,17 @@ class WorldBatch:
     def acceleration_map(self, views, softening):
         """RenderWorldBatchAcceleration: float32 (B, height, width, 2)."""
         return _ensemble_field(nbody_lib().RenderWorldBatchAcceleration, self._h, self.count, 2, softening, views=views)
+
+    def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
+        """GetWorldBatchProfile (include/nbody_batch_profile.h): the annulus moments of every member (include/nbody_profile.h), float64 (B, bins + 2, 6); the edges are
+        shared, centre and centre_velocity are (2,) for all members or (B, 2).  Member b's rows are bit-identical to
+        SimPipeline.profile of the same particles; ragged ensembles included.  With return_unplaced also the uint32 (B,) counts of
+        particles whose squared radius is NaN."""
+        e, bins, c, mode = _profile_args(edges, centre, centre_velocity, weights, self.count)
+        out, lost = np.empty((self.count, bins + 2, NB_PROFILE_QTY), dtype=np.float64), np.zeros(self.count, dtype=np.uint32)
+        specs = _profile_specs(e, bins, c, mode)
+        nbody_lib().GetWorldBatchProfile(self._h, specs, self.count, out.ctypes.data, lost.ctypes.data)
+        return (out, lost) if return_unplaced else out
 
     def tidal_at(self, points, softening):
         """GetWorldBatchTidalAt (include/nbody_batch_tidal.h): the tidal tensor of every member at its points, float32
@@ -1404,6 +1559,18 @@ class World:
         out = np.empty((view.height, view.width, 2), dtype=np.float32)
         nbody_lib().RenderWorldAcceleration(self._h, C.byref(view), softening, out.ctypes.data)
         return out
+
+    def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
+        """GetWorldProfile: the annulus moments about `centre` moving with `centre_velocity` (include/nbody_profile.h), float64
+        (bins + 2, 6) with the columns (count, S, I, L, W, K); row 0 lies inside edges[0], row bins + 1 at or beyond edges[-1].
+        weights: "mass" (massive particles, weight m) or "number" (all particles, weight 1).  With return_unplaced also the number
+        of particles whose squared radius is NaN.  A natural centre: energy()["center_of_mass"] and momentum / mass (vel is used
+        as stored, the caveat of include/nbody_diag.h).  nb.profile_curves / nb.lagrangian_radii read the result."""
+        e, bins, c, mode = _profile_args(edges, centre, centre_velocity, weights)
+        out, lost = np.empty((bins + 2, NB_PROFILE_QTY), dtype=np.float64), np.zeros(1, dtype=np.uint32)
+        spec = _profile_specs(e, bins, c[None, :], mode)
+        nbody_lib().GetWorldProfile(self._h, spec, out.ctypes.data, lost.ctypes.data)
+        return (out, int(lost[0])) if return_unplaced else out
 
     def tidal_at(self, points, softening):
         """GetWorldTidalAt (include/nbody_tidal.h): the tidal tensor dg/dp at the (n, 2) points with one softening, float32

@@ -65,6 +65,11 @@ struct SimBatch {
     nbi::DevBuf<float> sample_in;    // [count] probe sets of (x, y) pairs, or [count] maps' width column + height row coordinates
     nbi::DevBuf<float> sample_out;   // the device result: [count][n] floats (Phi), float pairs (g) or triples (T)
 
+    // nb_hip_ensemble_profile (kernel: profile.hip): grown on demand; it shares diag_iv
+    nbi::DevBuf<double> profile;        // [count][rows][6] float64, then [count] uint32 NaN counts
+    nbi::DevBuf<float> profile_in;      // the edges, then [count][4] centres
+    std::vector<double> profile_host;   // the same bytes on the host
+
     // nb_hip_ensemble_trace: the rows of the last traced call, on the device and on their way to WorldEnergy
     nbi::DevBuf<double> trace;     // [records][count][NB_DIAG_SUMS]
     std::vector<double> trace_host;

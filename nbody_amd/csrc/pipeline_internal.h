@@ -31,6 +31,8 @@
 //                    (the kernel templates and the host side of a call: field_sampler.h)
 //   tidal.hip        the tidal tensor at the same places, for a pipeline and for an ensemble (nb_hip_tidal_at, nb_hip_tidal_map;
 //                    the kernels behind nb_hip_ensemble_tidal_at / _tidal_map): the sampler's third pair statement
+//   profile.hip      radial profiles of a pipeline and of every member of an ensemble (nb_hip_profile, nb_hip_ensemble_profile): the
+//                    chunk, reduce and ensemble kernels and their entry points (the statement: profile_common.h)
 //   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
 //   leapfrog.hip     the kick / drift passes of a kick-drift-kick step around a dt = 0 force launch (leapfrog.h, leapfrog_common.h)
 #pragma once
@@ -444,6 +446,11 @@ struct SimPipeline {
     int field_shape = 0;           // tuning hooks, Phi, g and T: 0 auto, 1 source split, 2 one wave per tile
     int gravity_shape = 0;
     int tidal_shape = 0;
+
+    // profile.hip (nb_hip_profile): the float64 slab grown with the call -- [chunks of 1024][rows * 6 + 1], then the results --
+    // and the uploaded edges + centre; the interval is diag_iv
+    nbi::DevBuf<double> profile;
+    nbi::DevBuf<float> profile_in;
 
     // adaptive steps (step_schedule.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
     // ADAPT_HEAD bytes of records (the call's AdaptState, the record and result of nb_hip_timestep), then the call's log

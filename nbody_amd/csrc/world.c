@@ -27,6 +27,8 @@
  * RenderWorldAcceleration likewise (the same two files).
  * Extension (include/nbody_tidal.h): GetWorldTidalAt / RenderWorldTidal
  * likewise (tidal.hip on the device, field_cpu.c on the host).
+ * Extension (include/nbody_profile.h): GetWorldProfile follows the diagnostics'
+ * rule (profile.hip on the device, profile_cpu.c on the host).
  * Extension (include/nbody_adaptive.h): adaptive steps.  UpdateWorld_GPU_Adaptive
  * and AdvanceWorld_GPU follow UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Adaptive
  * UpdateWorld_CPU's; GetWorldTimestep follows the diagnostics' (timestep.hip on the
@@ -42,6 +44,7 @@
 #include "nbody_field.h"
 #include "nbody_gravity.h"
 #include "nbody_tidal.h"
+#include "nbody_profile.h"
 #include "nbody_hip.h"
 #include "nbody_leapfrog.h"
 #include "nbody_render.h"
@@ -51,6 +54,7 @@
 #include "diag_sums.h"
 #include "field_common.h"
 #include "leapfrog_common.h"
+#include "profile_common.h"
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
@@ -274,6 +278,19 @@ void RenderWorldTidal(World *w, const RenderView *view, float softening, TidalTe
         nb_hip_tidal_map(w->gpu, view, softening, (float *)t);
     else
         nb_cpu_tidal_map(w->particles, w->massive, view, softening, t);
+}
+
+/* ---- include/nbody_profile.h ----------------------------------------------------------------------------------------- */
+
+void GetWorldProfile(World *w, const WorldProfileSpec *spec, double *out, uint32_t *unplaced) {
+    NB_CHECK(w != NULL && spec != NULL && spec->edges != NULL && out != NULL, "NULL argument");
+    const float centre[4] = {spec->centre[0], spec->centre[1], spec->centre_velocity[0], spec->centre_velocity[1]};
+    const char *fault = nb_profile_fault(spec->edges, spec->bins, centre, 1, spec->weights);
+    NB_CHECK(fault == NULL, "GetWorldProfile: %s (bins %u, weights %d)", fault, spec->bins, spec->weights);
+    if (diag_on_device(w, "GetWorldProfile"))
+        nb_hip_profile(w->gpu, spec->edges, spec->bins, centre, spec->weights, out, unplaced);
+    else
+        nb_cpu_profile(w->particles, w->count, w->massive, spec->edges, spec->bins, centre, spec->weights, out, unplaced);
 }
 
 /* ---- include/nbody_adaptive.h ---------------------------------------------------------------------------------------- */

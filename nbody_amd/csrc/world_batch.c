@@ -22,6 +22,8 @@
  * the diagnostics' protocol (device: nb_hip_ensemble_potential_at and its three siblings, one launch; host: field_cpu.c member
  * by member), for uniform and ragged batches alike.  include/nbody_batch_tidal.h: the tidal tensor likewise
  * (nb_hip_ensemble_tidal_at / _tidal_map), through the same two functions.
+ * include/nbody_batch_profile.h: the radial profiles of every member follow the diagnostics' protocol too (device:
+ * nb_hip_ensemble_profile, one launch; host: profile_cpu.c member by member), uniform and ragged batches alike.
  */
 #include "nbody_adaptive.h"
 #include "nbody_leapfrog.h"
@@ -29,6 +31,7 @@
 #include "nbody_batch_diag.h"
 #include "nbody_batch_field.h"
 #include "nbody_batch_tidal.h"
+#include "nbody_batch_profile.h"
 #include "nbody_batch_ragged.h"
 #include "nbody_batch_render.h"
 #include "nbody_batch_trace.h"
@@ -39,6 +42,7 @@
 #include "diag_sums.h"
 #include "field_common.h"
 #include "nb_util.h"
+#include "profile_common.h"
 #include "render_common.h"
 #include "timestep_common.h"
 #include "world_partition.h"
@@ -401,4 +405,41 @@ void GetWorldBatchTidalAt(WorldBatch *w, const V2 *points, uint32_t n, float sof
 
 void RenderWorldBatchTidal(WorldBatch *w, const RenderView *views, float softening, TidalTensor *t) {
     batch_field_map(w, "RenderWorldBatchTidal", views, softening, NULL, NULL, t);
+}
+
+/* ---- include/nbody_batch_profile.h ----------------------------------------------------------------------------------- */
+
+void GetWorldBatchProfile(WorldBatch *w, const WorldProfileSpec *specs, uint32_t nspecs, double *out, uint32_t *unplaced) {
+    NB_CHECK(w != NULL && specs != NULL && specs[0].edges != NULL && out != NULL, "GetWorldBatchProfile: NULL argument");
+    NB_CHECK(nspecs == 1 || nspecs == w->count, "GetWorldBatchProfile: %u specs for %u members (one for all, or one each)", nspecs, w->count);
+    const float *edges = specs[0].edges;
+    const uint32_t bins = specs[0].bins;
+    const int weights = specs[0].weights;
+    float *centres = NB_NEW((size_t)w->count * 4, float);
+    NB_CHECK(centres != NULL, "Failed to alloc %u centres", w->count);
+    for (uint32_t b = 0; b < w->count; b++) {
+        const WorldProfileSpec *s = specs + (nspecs == 1 ? 0 : b);
+        centres[4 * b + 0] = s->centre[0];
+        centres[4 * b + 1] = s->centre[1];
+        centres[4 * b + 2] = s->centre_velocity[0];
+        centres[4 * b + 3] = s->centre_velocity[1];
+    }
+    const char *fault = nb_profile_fault(edges, bins, centres, w->count, weights);
+    NB_CHECK(fault == NULL, "GetWorldBatchProfile: %s (bins %u, weights %d)", fault, bins, weights);
+    for (uint32_t b = 1; b < nspecs; b++) {
+        NB_CHECK(specs[b].edges != NULL, "GetWorldBatchProfile: NULL argument");
+        NB_CHECK(specs[b].bins == bins && specs[b].weights == weights &&
+                     (specs[b].edges == edges || memcmp(specs[b].edges, edges, ((size_t)bins + 1) * sizeof(float)) == 0),
+                 "GetWorldBatchProfile: the spec of member %u differs from member 0's in its edges or weights: per-member edges are "
+                 "not supported", b);
+    }
+    if (w->device_is_newer) {
+        nb_hip_ensemble_profile(w->gpu, edges, bins, centres, weights, out, unplaced);
+    } else {
+        const size_t cells = ((size_t)bins + 2) * NB_PROFILE_QTY;
+        for (uint32_t b = 0; b < w->count; b++)
+            nb_cpu_profile(w->particles + w->offset[b], w->sizes[b], w->massive[b], edges, bins, centres + 4 * b, weights, out + b * cells,
+                           unplaced ? unplaced + b : NULL);
+    }
+    free(centres);
 }
