@@ -662,6 +662,31 @@ void nb_hip_ensemble_profile(SimBatch *batch, const float *edges, uint32_t bins,
                              double *out /* [count][bins + 2][6] */, uint32_t *unplaced /* [count] */);
 
 /*
+ * Pair-separation counts of the state a pipeline or an ensemble holds: how many pairs of particles lie in every row of the
+ * caller's radii, per class of pair (definitions, row rule and columns: include/nbody_paircount.h; kernel:
+ * nbody_amd/csrc/paircount.hip).  edges: bins + 1 float32 radii, 1 <= bins <= 254; classes: a non-empty mask of NB_PAIRS_MM = 1,
+ * NB_PAIRS_MT = 2, NB_PAIRS_TT = 4 (a class not asked for is zeros, and a particle only it would read is never read); out:
+ * [bins + 2][3] uint64, every count exact; unplaced (nullable): [3], the pairs whose q is NaN.
+ *   nb_hip_pair_counts            one launch: a workgroup per (class, tile of 128 receivers, span of sources) counts in LDS and
+ *                                 adds its rows to a table the pipeline owns with 64-bit integer atomics.  No upload (the
+ *                                 thresholds travel with the launch), download (rows + 1) * 24 bytes, one sync.  Enqueued,
+ *                                 blocking and invisible to the steps like nb_hip_profile; sharded pipelines abort like it.
+ *                                 Nothing to count (N < 2, or every requested class without a pair) gives zeros and touches no
+ *                                 device.
+ *   nb_hip_ensemble_pair_counts   every member of an ensemble, uniform or ragged, in ONE launch of the same kernel; one edge set
+ *                                 and one mask for all.  out[count][bins + 2][3], unplaced[count][3].  Member b's counts are
+ *                                 those of nb_hip_pair_counts of a SimPipeline holding the same particles.
+ * Integers add exactly in any order: a result is a function of the state and the arguments alone, and there is no float
+ * atomic.  Every check -- NULL arguments, bins of 0 or above 254, non-finite, negative or non-increasing edges, an empty or
+ * unknown classes, a call before the data is set -- runs before any device touch and ends in "file:line [func] ..." + abort().
+ * Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_pair_counts", dlsym "nb_hip_ensemble_pair_counts").
+ */
+void nb_hip_pair_counts(SimPipeline *sim, const float *edges, uint32_t bins, uint32_t classes, uint64_t *out /* [bins + 2][3] */,
+                        uint64_t *unplaced /* [3] */);
+void nb_hip_ensemble_pair_counts(SimBatch *batch, const float *edges, uint32_t bins, uint32_t classes,
+                                 uint64_t *out /* [count][bins + 2][3] */, uint64_t *unplaced /* [count][3] */);
+
+/*
  * Adaptive time steps chosen on the device (definitions: include/nbody_adaptive.h; kernels: nbody_amd/csrc/timestep.hip).
  *   nb_hip_adaptive_steps         n steps, each of the size the criterion gives for the state before it; blocking
  *   nb_hip_adaptive_steps_async   the same, enqueue only

@@ -134,6 +134,17 @@ class WorldProfileSpec(C.Structure):
                 ("weights", C.c_int)]
 
 
+NB_PAIRS_MM, NB_PAIRS_MT, NB_PAIRS_TT, NB_PAIRS_ALL = 1, 2, 4, 7     # include/nbody_paircount.h
+NB_PAIRS_MAX_BINS = 254
+NB_PAIRS_COLUMNS = 3
+NB_PAIRS_TABLE = 255     # nbody_amd/csrc/paircount_common.h
+
+
+class WorldPairSpec(C.Structure):
+    """include/nbody_paircount.h WorldPairSpec; `edges` points into an array the caller keeps alive."""
+    _fields_ = [("edges", C.c_void_p), ("bins", C.c_uint32), ("classes", C.c_uint32)]
+
+
 class NbShardPlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mass_chunk", "zero_chunk", "mass_begin", "mass_count",
                                           "zero_begin", "zero_count", "src_padded")]
@@ -196,6 +207,8 @@ HIP_API = {
     "nb_hip_tidal_map": (None, [C.c_void_p, C.POINTER(RenderView), C.c_float, C.c_void_p]),
     "nb_hip_profile": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nb_hip_ensemble_profile": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "nb_hip_pair_counts": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "nb_hip_ensemble_pair_counts": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nb_hip_batch_destroy": (None, [C.c_void_p]),
     "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
@@ -256,6 +269,7 @@ TUNE_API = {
     "nb_hip_deal_counter": (C.c_uint32, [C.c_void_p]),
     "nb_hip_plan_launch_lanes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
     "nb_hip_last_diag_ms": (C.c_double, [C.c_void_p]),
+    "nb_hip_pair_thresholds": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "nb_hip_last_render_ms": (C.c_double, [C.c_void_p, C.POINTER(C.c_double)]),
     "nb_hip_ensemble_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_ensemble_trace_mode": (None, [C.c_void_p, C.c_int]),
@@ -272,7 +286,7 @@ PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
 # include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h +
 # include/nbody_adaptive.h + include/nbody_leapfrog.h + include/nbody_batch_field.h + include/nbody_tidal.h + include/nbody_batch_tidal.h +
-# include/nbody_profile.h + include/nbody_batch_profile.h
+# include/nbody_profile.h + include/nbody_batch_profile.h + include/nbody_paircount.h + include/nbody_batch_paircount.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -305,6 +319,9 @@ NBODY_API = {
     # include/nbody_profile.h, include/nbody_batch_profile.h
     "GetWorldProfile": (None, [C.c_void_p, C.POINTER(WorldProfileSpec), C.c_void_p, C.c_void_p]),
     "GetWorldBatchProfile": (None, [C.c_void_p, C.POINTER(WorldProfileSpec), C.c_uint32, C.c_void_p, C.c_void_p]),
+    # include/nbody_paircount.h, include/nbody_batch_paircount.h
+    "GetWorldPairCounts": (None, [C.c_void_p, C.POINTER(WorldPairSpec), C.c_void_p, C.c_void_p]),
+    "GetWorldBatchPairCounts": (None, [C.c_void_p, C.POINTER(WorldPairSpec), C.c_void_p, C.c_void_p]),
     # include/nbody_batch.h
     "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "DestroyWorldBatch": (None, [C.c_void_p]),
@@ -687,6 +704,14 @@ class SimPipeline:
         hip_lib().nb_hip_acceleration_map(self._h, C.byref(view), softening, out.ctypes.data)
         return out
 
+    def pair_counts(self, edges, classes=("mm",), return_unplaced=False):
+        """nb_hip_pair_counts: the pairs of particles per row of separations and per class (include/nbody_paircount.h), uint64
+        (bins + 2, 3) with the columns (massive-massive, massive-massless, massless-massless); row 0 lies inside edges[0], row
+        bins + 1 at or beyond edges[-1].  classes: any subset of "mm", "mt", "tt", or "all"; a class not asked for is zeros and is
+        never evaluated.  With return_unplaced also the pairs per class whose squared separation is NaN.  Every count is exact:
+        device, host and numpy agree bit for bit.  nb.profile_edges makes edges, nb.pair_curves reads the result."""
+        return _pair_counts(hip_lib().nb_hip_pair_counts, self._h, None, edges, classes, return_unplaced)
+
     def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
         """nb_hip_profile: the annulus moments about `centre` moving with `centre_velocity` (include/nbody_profile.h), float64
         (bins + 2, 6) with the columns (count, S, I, L, W, K); row 0 lies inside edges[0], row bins + 1 at or beyond edges[-1].
@@ -714,7 +739,7 @@ class SimPipeline:
 
     def last_diag_ms(self):
         """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
-        acceleration_at() / acceleration_map() / tidal_at() / tidal_map() / profile()."""
+        acceleration_at() / acceleration_map() / tidal_at() / tidal_map() / profile() / pair_counts()."""
         return float(hip_lib().nb_hip_last_diag_ms(self._h))
 
     def bounds(self):
@@ -871,6 +896,58 @@ def _profile_specs(e, bins, centres, mode):
         specs[b].centre[0], specs[b].centre[1] = row[0], row[1]
         specs[b].centre_velocity[0], specs[b].centre_velocity[1] = row[2], row[3]
     return specs
+
+
+def _pair_args(edges, classes):
+    """(edges float32 (bins + 1,), bins, classes as the C bit mask)."""
+    e = np.ascontiguousarray(edges, dtype=np.float32)
+    if e.ndim != 1 or e.shape[0] < 2:
+        raise ValueError("edges must be a sequence of at least two radii")
+    names = {"mm": NB_PAIRS_MM, "mt": NB_PAIRS_MT, "tt": NB_PAIRS_TT, "all": NB_PAIRS_ALL}
+    if isinstance(classes, (int, np.integer)) and not isinstance(classes, bool):
+        return e, e.shape[0] - 1, int(classes) & 0xffffffff          # the library names the fault
+    if isinstance(classes, str):
+        classes = (classes,)
+    mask = 0
+    try:
+        for c in classes:
+            mask |= names[c]
+    except (KeyError, TypeError):
+        raise ValueError('classes must be a subset of "mm", "mt", "tt", or "all"') from None
+    if mask == 0:
+        raise ValueError('classes must name at least one of "mm", "mt", "tt"')
+    return e, e.shape[0] - 1, mask
+
+
+def _pair_counts(call, handle, count, edges, classes, return_unplaced, spec=False):
+    """One pair-count call of the seam (edges, bins, classes) or of the World layer (a WorldPairSpec): uint64 (bins + 2, 3), or
+    (count, bins + 2, 3) for an ensemble."""
+    e, bins, mask = _pair_args(edges, classes)
+    shape = (bins + 2, NB_PAIRS_COLUMNS) if count is None else (count, bins + 2, NB_PAIRS_COLUMNS)
+    out, lost = np.zeros(shape, dtype=np.uint64), np.zeros(shape[:-2] + (NB_PAIRS_COLUMNS,), dtype=np.uint64)
+    if spec:
+        call(handle, C.byref(WorldPairSpec(e.ctypes.data, bins, mask)), out.ctypes.data, lost.ctypes.data)
+    else:
+        call(handle, e.ctypes.data, bins, mask, out.ctypes.data, lost.ctypes.data)
+    return (out, lost) if return_unplaced else out
+
+
+def pair_curves(rows, edges):
+    """What the counts of .pair_counts() say, per class (rows (..., bins + 2, 3)).  A dict of float64 arrays: r_mid and area
+    (bins,) of the caller's annuli; density (..., bins, 3) = pairs of the bin per unit annulus area per pair of the class -- the
+    radial pair density a correlation function is formed from (divide by that of an unclustered set); cumulative
+    (..., bins + 1, 3) = the fraction of the class's pairs within each edge.  NaN where a class has no pair.  The class totals are
+    the sums over all rows: unplaced pairs (a NaN separation) are not among them."""
+    r = np.asarray(rows, dtype=np.float64)
+    e = np.asarray(edges, dtype=np.float64)
+    if r.ndim < 2 or r.shape[-1] != NB_PAIRS_COLUMNS or r.shape[-2] != e.shape[0] + 1:
+        raise ValueError("rows must have shape (..., len(edges) + 1, 3)")
+    area = np.pi * (e[1:] ** 2 - e[:-1] ** 2)
+    total = r.sum(axis=-2, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        density = np.where(total > 0, r[..., 1:-1, :] / area[:, None] / total, np.nan)
+        cumulative = np.where(total > 0, np.cumsum(r[..., :-1, :], axis=-2) / total, np.nan)
+    return {"r_mid": 0.5 * (e[1:] + e[:-1]), "area": area, "density": density, "cumulative": cumulative}
 
 
 def profile_edges(r_min, r_max, bins, log=False):
@@ -1148,6 +1225,14 @@ class SimBatch:
         """nb_hip_ensemble_acceleration_map: g at every pixel centre, float32 (B, height, width, 2)."""
         return _ensemble_field(hip_lib().nb_hip_ensemble_acceleration_map, self._h, self.count, 2, softening, views=views)
 
+    def pair_counts(self, edges, classes=("mm",), return_unplaced=False):
+        """nb_hip_ensemble_pair_counts, one launch for all members: the pairs of particles per row of separations and per class (include/nbody_paircount.h), uint64
+        (B, bins + 2, 3) with the columns (massive-massive, massive-massless, massless-massless); row 0 lies inside edges[0], row
+        bins + 1 at or beyond edges[-1].  classes: any subset of "mm", "mt", "tt", or "all"; a class not asked for is zeros and is
+        never evaluated.  With return_unplaced also the pairs per class whose squared separation is NaN.  Every count is exact:
+        device, host and numpy agree bit for bit.  nb.profile_edges makes edges, nb.pair_curves reads the result."""
+        return _pair_counts(hip_lib().nb_hip_ensemble_pair_counts, self._h, self.count, edges, classes, return_unplaced)
+
     def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
         """nb_hip_ensemble_profile: the annulus moments of every member (include/nbody_profile.h), float64 (B, bins + 2, 6); the edges are
         shared, centre and centre_velocity are (2,) for all members or (B, 2).  Member b's rows are bit-identical to
@@ -1169,7 +1254,7 @@ class SimBatch:
 
     def last_diag_ms(self):
         """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
-        acceleration_at() / acceleration_map() / tidal_at() / tidal_map() / profile()."""
+        acceleration_at() / acceleration_map() / tidal_at() / tidal_map() / profile() / pair_counts()."""
         return float(hip_lib().nb_hip_ensemble_last_diag_ms(self._h))
 
     def bounds(self):
@@ -1357,6 +1442,14 @@ class WorldBatch:
     def acceleration_map(self, views, softening):
         """RenderWorldBatchAcceleration: float32 (B, height, width, 2)."""
         return _ensemble_field(nbody_lib().RenderWorldBatchAcceleration, self._h, self.count, 2, softening, views=views)
+
+    def pair_counts(self, edges, classes=("mm",), return_unplaced=False):
+        """GetWorldBatchPairCounts (include/nbody_batch_paircount.h): the pairs of particles per row of separations and per class (include/nbody_paircount.h), uint64
+        (B, bins + 2, 3) with the columns (massive-massive, massive-massless, massless-massless); row 0 lies inside edges[0], row
+        bins + 1 at or beyond edges[-1].  classes: any subset of "mm", "mt", "tt", or "all"; a class not asked for is zeros and is
+        never evaluated.  With return_unplaced also the pairs per class whose squared separation is NaN.  Every count is exact:
+        device, host and numpy agree bit for bit.  nb.profile_edges makes edges, nb.pair_curves reads the result."""
+        return _pair_counts(nbody_lib().GetWorldBatchPairCounts, self._h, self.count, edges, classes, return_unplaced, spec=True)
 
     def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
         """GetWorldBatchProfile (include/nbody_batch_profile.h): the annulus moments of every member (include/nbody_profile.h), float64 (B, bins + 2, 6); the edges are
@@ -1559,6 +1652,14 @@ class World:
         out = np.empty((view.height, view.width, 2), dtype=np.float32)
         nbody_lib().RenderWorldAcceleration(self._h, C.byref(view), softening, out.ctypes.data)
         return out
+
+    def pair_counts(self, edges, classes=("mm",), return_unplaced=False):
+        """GetWorldPairCounts: the pairs of particles per row of separations and per class (include/nbody_paircount.h), uint64
+        (bins + 2, 3) with the columns (massive-massive, massive-massless, massless-massless); row 0 lies inside edges[0], row
+        bins + 1 at or beyond edges[-1].  classes: any subset of "mm", "mt", "tt", or "all"; a class not asked for is zeros and is
+        never evaluated.  With return_unplaced also the pairs per class whose squared separation is NaN.  Every count is exact:
+        device, host and numpy agree bit for bit.  nb.profile_edges makes edges, nb.pair_curves reads the result."""
+        return _pair_counts(nbody_lib().GetWorldPairCounts, self._h, None, edges, classes, return_unplaced, spec=True)
 
     def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
         """GetWorldProfile: the annulus moments about `centre` moving with `centre_velocity` (include/nbody_profile.h), float64

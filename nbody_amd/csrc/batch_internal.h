@@ -70,6 +70,10 @@ struct SimBatch {
     nbi::DevBuf<float> profile_in;      // the edges, then [count][4] centres
     std::vector<double> profile_host;   // the same bytes on the host
 
+    // nb_hip_ensemble_pair_counts (kernel: paircount.hip): grown on demand; it shares diag_iv
+    nbi::DevBuf<unsigned long long> pairs;   // [count][rows + 1][3] uint64: every member's rows, then its unplaced pairs
+    std::vector<uint64_t> pairs_host;        // the same bytes on the host
+
     // nb_hip_ensemble_trace: the rows of the last traced call, on the device and on their way to WorldEnergy
     nbi::DevBuf<double> trace;     // [records][count][NB_DIAG_SUMS]
     std::vector<double> trace_host;

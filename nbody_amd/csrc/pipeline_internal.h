@@ -33,6 +33,8 @@
 //                    the kernels behind nb_hip_ensemble_tidal_at / _tidal_map): the sampler's third pair statement
 //   profile.hip      radial profiles of a pipeline and of every member of an ensemble (nb_hip_profile, nb_hip_ensemble_profile): the
 //                    chunk, reduce and ensemble kernels and their entry points (the statement: profile_common.h)
+//   paircount.hip    pair-separation counts of a pipeline and of every member of an ensemble (nb_hip_pair_counts,
+//                    nb_hip_ensemble_pair_counts): one kernel and its entry points (the statement: paircount_common.h)
 //   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
 //   leapfrog.hip     the kick / drift passes of a kick-drift-kick step around a dt = 0 force launch (leapfrog.h, leapfrog_common.h)
 #pragma once
@@ -451,6 +453,9 @@ struct SimPipeline {
     // and the uploaded edges + centre; the interval is diag_iv
     nbi::DevBuf<double> profile;
     nbi::DevBuf<float> profile_in;
+
+    // paircount.hip (nb_hip_pair_counts): the uint64 table the launch adds to, [rows + 1][3], made on first use; the interval is diag_iv
+    nbi::DevBuf<unsigned long long> pairs;
 
     // adaptive steps (step_schedule.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
     // ADAPT_HEAD bytes of records (the call's AdaptState, the record and result of nb_hip_timestep), then the call's log

@@ -29,6 +29,8 @@
  * likewise (tidal.hip on the device, field_cpu.c on the host).
  * Extension (include/nbody_profile.h): GetWorldProfile follows the diagnostics'
  * rule (profile.hip on the device, profile_cpu.c on the host).
+ * Extension (include/nbody_paircount.h): GetWorldPairCounts likewise
+ * (paircount.hip on the device, paircount_cpu.c on the host).
  * Extension (include/nbody_adaptive.h): adaptive steps.  UpdateWorld_GPU_Adaptive
  * and AdvanceWorld_GPU follow UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Adaptive
  * UpdateWorld_CPU's; GetWorldTimestep follows the diagnostics' (timestep.hip on the
@@ -45,6 +47,7 @@
 #include "nbody_gravity.h"
 #include "nbody_tidal.h"
 #include "nbody_profile.h"
+#include "nbody_paircount.h"
 #include "nbody_hip.h"
 #include "nbody_leapfrog.h"
 #include "nbody_render.h"
@@ -55,6 +58,7 @@
 #include "field_common.h"
 #include "leapfrog_common.h"
 #include "profile_common.h"
+#include "paircount_common.h"
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
@@ -291,6 +295,18 @@ void GetWorldProfile(World *w, const WorldProfileSpec *spec, double *out, uint32
         nb_hip_profile(w->gpu, spec->edges, spec->bins, centre, spec->weights, out, unplaced);
     else
         nb_cpu_profile(w->particles, w->count, w->massive, spec->edges, spec->bins, centre, spec->weights, out, unplaced);
+}
+
+/* ---- include/nbody_paircount.h --------------------------------------------------------------------------------------- */
+
+void GetWorldPairCounts(World *w, const WorldPairSpec *spec, uint64_t *out, uint64_t *unplaced) {
+    NB_CHECK(w != NULL && spec != NULL && spec->edges != NULL && out != NULL, "NULL argument");
+    const char *fault = nb_pair_fault(spec->edges, spec->bins, spec->classes);
+    NB_CHECK(fault == NULL, "GetWorldPairCounts: %s (bins %u, classes %u)", fault, spec->bins, spec->classes);
+    if (diag_on_device(w, "GetWorldPairCounts"))
+        nb_hip_pair_counts(w->gpu, spec->edges, spec->bins, spec->classes, out, unplaced);
+    else
+        nb_cpu_pair_counts(w->particles, w->count, w->massive, spec->edges, spec->bins, spec->classes, out, unplaced);
 }
 
 /* ---- include/nbody_adaptive.h ---------------------------------------------------------------------------------------- */

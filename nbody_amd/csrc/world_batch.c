@@ -24,6 +24,8 @@
  * (nb_hip_ensemble_tidal_at / _tidal_map), through the same two functions.
  * include/nbody_batch_profile.h: the radial profiles of every member follow the diagnostics' protocol too (device:
  * nb_hip_ensemble_profile, one launch; host: profile_cpu.c member by member), uniform and ragged batches alike.
+ * include/nbody_batch_paircount.h: the pair-separation counts of every member likewise (device: nb_hip_ensemble_pair_counts,
+ * one launch; host: paircount_cpu.c member by member).
  */
 #include "nbody_adaptive.h"
 #include "nbody_leapfrog.h"
@@ -32,6 +34,7 @@
 #include "nbody_batch_field.h"
 #include "nbody_batch_tidal.h"
 #include "nbody_batch_profile.h"
+#include "nbody_batch_paircount.h"
 #include "nbody_batch_ragged.h"
 #include "nbody_batch_render.h"
 #include "nbody_batch_trace.h"
@@ -43,6 +46,7 @@
 #include "field_common.h"
 #include "nb_util.h"
 #include "profile_common.h"
+#include "paircount_common.h"
 #include "render_common.h"
 #include "timestep_common.h"
 #include "world_partition.h"
@@ -442,4 +446,20 @@ void GetWorldBatchProfile(WorldBatch *w, const WorldProfileSpec *specs, uint32_t
                            unplaced ? unplaced + b : NULL);
     }
     free(centres);
+}
+
+/* ---- include/nbody_batch_paircount.h --------------------------------------------------------------------------------- */
+
+void GetWorldBatchPairCounts(WorldBatch *w, const WorldPairSpec *spec, uint64_t *out, uint64_t *unplaced) {
+    NB_CHECK(w != NULL && spec != NULL && spec->edges != NULL && out != NULL, "GetWorldBatchPairCounts: NULL argument");
+    const char *fault = nb_pair_fault(spec->edges, spec->bins, spec->classes);
+    NB_CHECK(fault == NULL, "GetWorldBatchPairCounts: %s (bins %u, classes %u)", fault, spec->bins, spec->classes);
+    if (w->device_is_newer) {
+        nb_hip_ensemble_pair_counts(w->gpu, spec->edges, spec->bins, spec->classes, out, unplaced);
+    } else {
+        const size_t cells = ((size_t)spec->bins + 2) * NB_PAIRS_COLUMNS;
+        for (uint32_t b = 0; b < w->count; b++)
+            nb_cpu_pair_counts(w->particles + w->offset[b], w->sizes[b], w->massive[b], spec->edges, spec->bins, spec->classes, out + b * cells,
+                               unplaced ? unplaced + (size_t)b * NB_PAIRS_COLUMNS : NULL);
+    }
 }
