@@ -3,7 +3,8 @@
 //
 // Every device array and event of a SimBatch is a member of an owner type (pipeline_internal.h DevBuf / Interval): made by
 // materialize or on a call's first use, released by the member's destructor when nb_hip_batch_destroy deletes the struct,
-// after it has drained the stream.  nb_hip_batch_destroy itself only syncs and destroys the stream.
+// after it has drained the stream.  nb_hip_batch_destroy itself only syncs and destroys the stream.  The read-only calls share one
+// scratch and one host protocol with those of a pipeline: pipeline_internal.h ReadScratch / read_call.
 #pragma once
 
 #include "pipeline_internal.h"
@@ -53,26 +54,11 @@ struct SimBatch {
     nbi::DevBuf<uint32_t> n_len_dev;     // ragged only, like offsets_dev
     nbi::DevBuf<uint64_t> offsets_dev;
 
-    // nb_hip_ensemble_energy / nb_hip_ensemble_potential (kernels: batch_diag.hip): scratch made on first use, an interval
-    // of their own (step_iv keeps bracketing the last update)
+    // the read-only calls (batch_observe.hip's energy, potential and field calls, nb_hip_ensemble_profile, nb_hip_ensemble_pair_counts):
+    // their scratch and their interval (pipeline_internal.h ReadScratch)
+    nbi::ReadScratch read;
+    // the energy slab stays a member of its own: traced updates (batch.hip) write it too, and they are no read-only calls
     nbi::DevBuf<double> diag;      // float64 slab: [count][tiles of 128][NB_DIAG_SUMS] + the [count][NB_DIAG_SUMS] results
-    nbi::DevBuf<float> diag_phi;   // the potentials on the device: [count][n]
-    std::vector<double> diag_host;   // the results on the host before they become WorldEnergy
-    nbi::Interval diag_iv;
-
-    // nb_hip_ensemble_potential_at / _potential_map / _acceleration_at / _acceleration_map (kernel: batch_field.hip) and
-    // nb_hip_ensemble_tidal_at / _tidal_map (kernel: tidal.hip): grown on demand; they share diag_iv
-    nbi::DevBuf<float> sample_in;    // [count] probe sets of (x, y) pairs, or [count] maps' width column + height row coordinates
-    nbi::DevBuf<float> sample_out;   // the device result: [count][n] floats (Phi), float pairs (g) or triples (T)
-
-    // nb_hip_ensemble_profile (kernel: profile.hip): grown on demand; it shares diag_iv
-    nbi::DevBuf<double> profile;        // [count][rows][6] float64, then [count] uint32 NaN counts
-    nbi::DevBuf<float> profile_in;      // the edges, then [count][4] centres
-    std::vector<double> profile_host;   // the same bytes on the host
-
-    // nb_hip_ensemble_pair_counts (kernel: paircount.hip): grown on demand; it shares diag_iv
-    nbi::DevBuf<unsigned long long> pairs;   // [count][rows + 1][3] uint64: every member's rows, then its unplaced pairs
-    std::vector<uint64_t> pairs_host;        // the same bytes on the host
 
     // nb_hip_ensemble_trace: the rows of the last traced call, on the device and on their way to WorldEnergy
     nbi::DevBuf<double> trace;     // [records][count][NB_DIAG_SUMS]

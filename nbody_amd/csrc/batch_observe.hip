@@ -2,6 +2,8 @@
 // bounds, count images and frames (kernels: render_kernels.hip), the potential, the acceleration field and the tidal tensor at
 // probe points and over views (kernels: batch_field.hip, tidal.hip), with their tuning hooks and timers.  Each
 // looks at the latest state without reading the particles back: a constant number of launches, one copy, one sync for any B.
+// The energy, potential and field calls run through pipeline_internal.h's read_call, on the ensemble's one ReadScratch; the
+// render calls keep buffers and intervals of their own (a render's buffers hold several roles within one call).
 #include "batch_internal.h"
 #include "batch_diag.h"
 #include "batch_field.h"
@@ -129,45 +131,38 @@ void check_field(SimBatch *s, const char *what, float softening, uint64_t sample
               (unsigned long long)samples, fault);
 }
 
-// upload `in_stride` floats per member, evaluate n samples of every member in one launch, one copy of the result, one sync;
-// `in` stays alive until the sync
+// one read_call: upload `in_stride` floats per member ([count] probe sets of (x, y) pairs, or [count] maps' width column + height
+// row coordinates), evaluate n samples of every member in one launch, copy the [count][n][comps] floats to `out`
 // `comps` floats per sample name the quantity: 1 = Phi, 2 = g, 3 = T
 void sample_members(SimBatch *s, const char *what, uint32_t comps, bool map, const float *in, uint32_t in_stride, uint32_t n,
                     uint32_t width, float softening, float *out) {
-    const size_t in_floats = (size_t)s->count * in_stride, out_floats = (size_t)s->count * n * comps;
-    use_device();
-    s->sample_in.grown(s->stream, in_floats);
-    s->sample_out.grown(s->stream, out_floats);
-    ASSERT_HIP(hipMemcpyAsync(s->sample_in, in, in_floats * sizeof(float), hipMemcpyHostToDevice, s->stream), "%s: H2D of %u members' samples",
-               what, s->count);
-    nb::field::EnsembleParams p{};
-    p.pos = s->pos[s->cur];
-    p.gm = s->gm;
-    p.mass_len = s->mass_len_dev;
-    p.stride = s->stride;
-    p.in = s->sample_in;
-    p.in_stride = in_stride;
-    p.n = n;
-    p.width = width;
-    p.soft = softening;
-    p.out = s->sample_out;
-    s->diag_iv.begin(s->stream);
-    if (comps == 3)
-        nb::field::launch_ensemble_tidal(s->stream, p, s->count, map);
-    else
-        nb::field::launch_ensemble_sample(s->stream, p, s->count, comps == 2, map);
-    ASSERT_HIP(hipGetLastError(), "%s: ensemble_sample_kernel launch (%u members, %u samples each)", what, s->count, n);
-    s->diag_iv.end(s->stream);
-    ASSERT_HIP(hipMemcpyAsync(out, s->sample_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream), "%s: D2H of %u members' results",
-               what, s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after %s", what);
+    const size_t in_bytes = (size_t)s->count * in_stride * sizeof(float), out_bytes = (size_t)s->count * n * comps * sizeof(float);
+    read_call(s, what, in, in_bytes, out_bytes, out, out_bytes, [&](void *in_dev, void *work) -> const void * {
+        nb::field::EnsembleParams p{};
+        p.pos = s->pos[s->cur];
+        p.gm = s->gm;
+        p.mass_len = s->mass_len_dev;
+        p.stride = s->stride;
+        p.in = static_cast<const float *>(in_dev);
+        p.in_stride = in_stride;
+        p.n = n;
+        p.width = width;
+        p.soft = softening;
+        p.out = work;
+        if (comps == 3)
+            nb::field::launch_ensemble_tidal(s->stream, p, s->count, map);
+        else
+            nb::field::launch_ensemble_sample(s->stream, p, s->count, comps == 2, map);
+        ASSERT_HIP(hipGetLastError(), "%s: ensemble_sample_kernel launch (%u members, %u samples each)", what, s->count, n);
+        return work;
+    });
 }
 
 void sample_members_at(SimBatch *s, const char *what, uint32_t comps, const float *points, uint32_t n, float softening, float *out) {
     check_field(s, what, softening, s ? (uint64_t)s->count * n : 0);
     NB_ASSERT((points != nullptr && out != nullptr) || n == 0, "%s: NULL points or result", what);
     if (n == 0) {
-        s->diag_iv.clear();
+        s->read.iv.clear();
         return;
     }
     sample_members(s, what, comps, false, points, 2 * n, n, 0, softening, out);
@@ -195,33 +190,27 @@ extern "C" {
 void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
     check_diag(s, out, "nb_hip_ensemble_energy");
     constexpr size_t Q = NB_DIAG_SUMS;
-    use_device();
-    s->diag_iv.begin(s->stream);
-    double *res = energy_slab(s) + (size_t)s->count * nbd::ensemble_tiles(s->n) * Q;
-    launch_energy_sums(s, res);
-    s->diag_iv.end(s->stream);
-    s->diag_host.resize((size_t)s->count * Q);
-    ASSERT_HIP(hipMemcpyAsync(s->diag_host.data(), res, (size_t)s->count * Q * sizeof(double), hipMemcpyDeviceToHost, s->stream),
-               "D2H of %u members' energy sums", s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_energy");
-    for (uint32_t b = 0; b < s->count; b++) nb_energy_from_sums(s->diag_host.data() + (size_t)b * Q, out + b);
+    // the workspace is the ensemble's own slab, which traced updates use too: only the results come back through the protocol
+    const void *host = read_call(s, "nb_hip_ensemble_energy", nullptr, 0, 0, nullptr, (size_t)s->count * Q * sizeof(double),
+                                 [&](void *, void *) -> const void * {
+        double *res = energy_slab(s) + (size_t)s->count * nbd::ensemble_tiles(s->n) * Q;
+        launch_energy_sums(s, res);
+        return res;
+    });
+    for (uint32_t b = 0; b < s->count; b++) nb_energy_from_sums(static_cast<const double *>(host) + (size_t)b * Q, out + b);
 }
 
 void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
     check_diag(s, phi, "nb_hip_ensemble_potential");
-    use_device();
-    s->diag_iv.begin(s->stream);
-    nbd::EnsembleDiagParams p = diag_params(s);
-    const size_t total = (size_t)s->offsets[s->count];
-    s->diag_phi.grown(s->stream, total);
-    p.phi = s->diag_phi;
-    // packed member after member; the member sizes and offsets on the device are null in a uniform ensemble
-    nbd::launch_ensemble_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
-    ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
-    s->diag_iv.end(s->stream);
-    ASSERT_HIP(hipMemcpyAsync(phi, p.phi, total * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u members' potentials",
-               s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_potential");
+    const size_t bytes = (size_t)s->offsets[s->count] * sizeof(float);
+    read_call(s, "nb_hip_ensemble_potential", nullptr, 0, bytes, phi, bytes, [&](void *, void *work) -> const void * {
+        nbd::EnsembleDiagParams p = diag_params(s);
+        p.phi = static_cast<float *>(work);
+        // packed member after member; the member sizes and offsets on the device are null in a uniform ensemble
+        nbd::launch_ensemble_potential(s->stream, p, s->count, s->n_len_dev, s->offsets_dev);
+        ASSERT_HIP(hipGetLastError(), "ensemble_phi_kernel launch (%u members of %u)", s->count, s->n);
+        return work;
+    });
 }
 
 void nb_hip_ensemble_potential_at(SimBatch *s, const float *points, uint32_t n, float softening, float *phi) {
@@ -248,12 +237,12 @@ void nb_hip_ensemble_tidal_map(SimBatch *s, const RenderView *views, float softe
     sample_members_map(s, "nb_hip_ensemble_tidal_map", 3, views, softening, t);
 }
 
-// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_ensemble_energy / _potential / field call
+// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last read-only call (pipeline_internal.h read_call)
 double nb_hip_ensemble_last_diag_ms(SimBatch *s) {
     NB_ASSERT(s != nullptr, "NULL ensemble");
-    if (!s->diag_iv.valid()) return 0.0;
+    if (!s->read.iv.valid()) return 0.0;
     use_device();
-    return s->diag_iv.ms();
+    return s->read.iv.ms();
 }
 
 void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {

@@ -167,23 +167,21 @@ void nb_hip_energy(SimPipeline *s, WorldEnergy *out) {
     const uint32_t M = s->data.mass_len;
     double q[QTY] = {0};
     if (M > 0) {
-        use_device();
-        s->diag_iv.begin(s->stream);
         const uint32_t rows = (M + nbd::TILE - 1) / nbd::TILE;
-        s->diag.grown(s->stream, (size_t)(rows + 1) * QTY);   // QTY per workgroup + QTY results
-        double *slab = s->diag;
-        nbd::DiagParams p = diag_params(s, M);
-        p.slab = slab;
-        hipLaunchKernelGGL(nbd::potential_kernel, dim3(rows), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
-        ASSERT_HIP(hipGetLastError(), "potential_kernel launch (energy, %u receivers)", M);
-        double *res = slab + (size_t)rows * QTY;
-        hipLaunchKernelGGL(nbd::energy_reduce_kernel, dim3(1), dim3(nbd::REDUCE_THREADS), 0, s->stream, slab, rows, res);
-        ASSERT_HIP(hipGetLastError(), "energy_reduce_kernel launch");
-        s->diag_iv.end(s->stream);
-        ASSERT_HIP(hipMemcpyAsync(q, res, sizeof(q), hipMemcpyDeviceToHost, s->stream), "D2H of the energy sums");
-        ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_energy");
+        // the float64 slab: QTY per workgroup + the QTY results
+        read_call(s, "nb_hip_energy", nullptr, 0, (size_t)(rows + 1) * QTY * sizeof(double), q, sizeof(q), [&](void *, void *work) -> const void * {
+            double *slab = static_cast<double *>(work);
+            nbd::DiagParams p = diag_params(s, M);
+            p.slab = slab;
+            hipLaunchKernelGGL(nbd::potential_kernel, dim3(rows), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
+            ASSERT_HIP(hipGetLastError(), "potential_kernel launch (energy, %u receivers)", M);
+            double *res = slab + (size_t)rows * QTY;
+            hipLaunchKernelGGL(nbd::energy_reduce_kernel, dim3(1), dim3(nbd::REDUCE_THREADS), 0, s->stream, slab, rows, res);
+            ASSERT_HIP(hipGetLastError(), "energy_reduce_kernel launch");
+            return res;
+        });
     } else {
-        s->diag_iv.clear();
+        s->read.iv.clear();
     }
     nb_energy_from_sums(q, out);
 }
@@ -193,27 +191,25 @@ void nb_hip_potential(SimPipeline *s, float *phi) {
     const uint32_t N = s->data.total_len;
     NB_ASSERT(phi != nullptr || N == 0, "NULL phi");
     if (N == 0) {
-        s->diag_iv.clear();
+        s->read.iv.clear();
         return;
     }
-    use_device();
-    s->diag_iv.begin(s->stream);
-    s->diag_phi.grown(s->stream, N);
-    nbd::DiagParams p = diag_params(s, N);
-    p.phi = s->diag_phi;
-    hipLaunchKernelGGL(nbd::potential_kernel, dim3((N + nbd::TILE - 1) / nbd::TILE), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
-    ASSERT_HIP(hipGetLastError(), "potential_kernel launch (%u receivers)", N);
-    s->diag_iv.end(s->stream);
-    ASSERT_HIP(hipMemcpyAsync(phi, s->diag_phi, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, s->stream), "D2H of %u potentials", N);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_potential");
+    const size_t bytes = (size_t)N * sizeof(float);
+    read_call(s, "nb_hip_potential", nullptr, 0, bytes, phi, bytes, [&](void *, void *work) -> const void * {
+        nbd::DiagParams p = diag_params(s, N);
+        p.phi = static_cast<float *>(work);
+        hipLaunchKernelGGL(nbd::potential_kernel, dim3((N + nbd::TILE - 1) / nbd::TILE), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);
+        ASSERT_HIP(hipGetLastError(), "potential_kernel launch (%u receivers)", N);
+        return work;
+    });
 }
 
-// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last nb_hip_energy / nb_hip_potential
+// tuning hook (nbody_hip_tuning.h): device time of the kernels of the last read-only call (pipeline_internal.h read_call)
 double nb_hip_last_diag_ms(SimPipeline *s) {
     NB_ASSERT(s != nullptr, "NULL pipeline");
-    if (!s->diag_iv.valid()) return 0.0;
+    if (!s->read.iv.valid()) return 0.0;
     use_device();
-    return s->diag_iv.ms();
+    return s->read.iv.ms();
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // field_sampler.h -- the sampler of one pipeline, for the translation units that instantiate it: field.hip (Potential,
 // Acceleration) and tidal.hip (Tidal).  The two kernel shapes, the one rule that picks between them and the host side of a
-// call (upload, one launch, one copy, one sync).  The statements are field_kernels.h's; the definitions and the summation
-// order are stated at the head of field.hip.  The kernels are templates over the quantity policy, so each translation unit
+// call: its checks, and its launch inside pipeline_internal.h's read_call.  The statements are field_kernels.h's; the
+// definitions and the summation order are stated at the head of field.hip.  The kernels are templates over the quantity policy, so each translation unit
 // holds the kernels of its own policies only.  Include it from a .hip file after field_kernels.h.
 #pragma once
 
@@ -130,31 +130,28 @@ void launch(SimPipeline *s, const fd::Params &p) {
     ASSERT_HIP(hipGetLastError(), "%s kernel launch (%u samples, %u sources)", Q::NOUN, p.n, p.n_src);
 }
 
-// upload `in_floats` floats, evaluate n samples, one copy of the result, one sync; `in` stays alive until the sync
+// one read_call: upload `in_floats` floats (the probes' (x, y) pairs, or a map's width column + height row coordinates), evaluate
+// n samples into Q::OUT floats each, copy them to `out`
 template <typename Q>
-void run(SimPipeline *s, bool map, const float *in, size_t in_floats, uint32_t n, uint32_t width, float softening, typename Q::Out *out) {
-    use_device();
-    s->sample_in.grown(s->stream, in_floats);
-    s->sample_out.grown(s->stream, (size_t)n * Q::OUT);
-    ASSERT_HIP(hipMemcpyAsync(s->sample_in, in, in_floats * sizeof(float), hipMemcpyHostToDevice, s->stream), "H2D of the %s samples", Q::NOUN);
-    fd::Params p{};
-    p.pos = s->pos[s->cur];
-    p.src_gm = s->src_gm;
-    p.n_src = s->data.mass_len;
-    p.in = s->sample_in;
-    p.n = n;
-    p.width = width;
-    p.soft = softening;
-    p.out = s->sample_out;
-    s->diag_iv.begin(s->stream);
-    if (map)
-        launch<Q, true>(s, p);
-    else
-        launch<Q, false>(s, p);
-    s->diag_iv.end(s->stream);
-    ASSERT_HIP(hipMemcpyAsync(out, s->sample_out, (size_t)n * sizeof(typename Q::Out), hipMemcpyDeviceToHost, s->stream),
-               "D2H of %u %s results", n, Q::NOUN);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after the %s kernel", Q::NOUN);
+void run(SimPipeline *s, const char *what, bool map, const float *in, size_t in_floats, uint32_t n, uint32_t width, float softening,
+         typename Q::Out *out) {
+    const size_t out_bytes = (size_t)n * sizeof(typename Q::Out);
+    read_call(s, what, in, in_floats * sizeof(float), out_bytes, out, out_bytes, [&](void *in_dev, void *work) -> const void * {
+        fd::Params p{};
+        p.pos = s->pos[s->cur];
+        p.src_gm = s->src_gm;
+        p.n_src = s->data.mass_len;
+        p.in = static_cast<const float *>(in_dev);
+        p.n = n;
+        p.width = width;
+        p.soft = softening;
+        p.out = work;
+        if (map)
+            launch<Q, true>(s, p);
+        else
+            launch<Q, false>(s, p);
+        return work;
+    });
 }
 
 inline void check(const char *noun, float softening, uint64_t samples) {
@@ -168,10 +165,10 @@ void sample_at(SimPipeline *s, const char *what, const float *points, uint32_t n
     check(Q::NOUN, softening, n);
     NB_ASSERT((points != nullptr && out != nullptr) || n == 0, "NULL points or result");
     if (n == 0) {
-        s->diag_iv.clear();
+        s->read.iv.clear();
         return;
     }
-    run<Q>(s, false, points, (size_t)n * 2, n, 0, softening, out);
+    run<Q>(s, what, false, points, (size_t)n * 2, n, 0, softening, out);
 }
 
 // a map is the probes product at the view's pixel centres: width column coordinates, then height row coordinates
@@ -185,7 +182,7 @@ void sample_map(SimPipeline *s, const char *what, const RenderView *view, float 
     NB_ASSERT(out != nullptr, "NULL %s map", Q::NOUN);
     std::vector<float> coords((size_t)view->width + view->height);
     nb_render_pixel_centres(view, coords.data(), coords.data() + view->width);
-    run<Q>(s, true, coords.data(), coords.size(), view->width * view->height, view->width, softening, out);
+    run<Q>(s, what, true, coords.data(), coords.size(), view->width * view->height, view->width, softening, out);
 }
 
 }  // namespace

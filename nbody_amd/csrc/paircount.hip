@@ -331,23 +331,21 @@ void nb_hip_pair_counts(SimPipeline *s, const float *edges, uint32_t bins, uint3
     if (requested_pairs(classes, n, m) == 0) {
         memset(out, 0, (size_t)rows * NB_PAIRS_COLUMNS * sizeof(uint64_t));
         if (unplaced) memset(unplaced, 0, NB_PAIRS_COLUMNS * sizeof(uint64_t));
-        s->diag_iv.clear();
+        s->read.iv.clear();
         return;
     }
-    use_device();
-    if (!s->pairs) s->pairs.alloc((size_t)pc::SLOTS * NB_PAIRS_COLUMNS);
-    pc::Params p{};
-    p.pos = s->pos[s->cur];
-    p.n = n;
-    p.m = m;
-    p.out = s->pairs;
-    s->diag_iv.begin(s->stream);
-    launch_pairs(p, edges, bins, classes, 1, n, s->stream);
-    s->diag_iv.end(s->stream);
-    uint64_t host[pc::SLOTS * NB_PAIRS_COLUMNS];
-    ASSERT_HIP(hipMemcpyAsync(host, p.out, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream), "D2H of %u rows of pair counts", rows);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_pair_counts");
-    unpack(host, rows, out, unplaced);
+    // the uint64 table the launch adds to: [rows + 1][3]
+    const size_t bytes = cells * sizeof(uint64_t);
+    const void *host = read_call(s, "nb_hip_pair_counts", nullptr, 0, bytes, nullptr, bytes, [&](void *, void *work) -> const void * {
+        pc::Params p{};
+        p.pos = s->pos[s->cur];
+        p.n = n;
+        p.m = m;
+        p.out = static_cast<unsigned long long *>(work);
+        launch_pairs(p, edges, bins, classes, 1, n, s->stream);
+        return work;
+    });
+    unpack(static_cast<const uint64_t *>(host), rows, out, unplaced);
 }
 
 void nb_hip_ensemble_pair_counts(SimBatch *s, const float *edges, uint32_t bins, uint32_t classes, uint64_t *out, uint64_t *unplaced) {
@@ -361,28 +359,25 @@ void nb_hip_ensemble_pair_counts(SimBatch *s, const float *edges, uint32_t bins,
     if (pairs == 0) {
         memset(out, 0, (size_t)count * rows * NB_PAIRS_COLUMNS * sizeof(uint64_t));
         if (unplaced) memset(unplaced, 0, (size_t)count * NB_PAIRS_COLUMNS * sizeof(uint64_t));
-        s->diag_iv.clear();
+        s->read.iv.clear();
         return;
     }
-    use_device();
-    s->pairs.grown(s->stream, count * cells);
-    pc::Params p{};
-    p.pos = s->pos[s->cur];
-    p.mass_len = s->mass_len_dev;
-    p.n_len = s->n_len_dev;   // null in a uniform ensemble
-    p.n = s->n;
-    p.stride = s->stride;
-    p.out = s->pairs;
-    s->diag_iv.begin(s->stream);
-    launch_pairs(p, edges, bins, classes, count, s->n, s->stream);
-    s->diag_iv.end(s->stream);
-    s->pairs_host.resize(count * cells);
-    ASSERT_HIP(hipMemcpyAsync(s->pairs_host.data(), p.out, count * cells * sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream),
-               "D2H of %u members' pair counts", count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_pair_counts");
+    // [count][rows + 1][3] uint64: every member's rows, then its unplaced pairs
+    const size_t bytes = count * cells * sizeof(uint64_t);
+    const void *landed = read_call(s, "nb_hip_ensemble_pair_counts", nullptr, 0, bytes, nullptr, bytes, [&](void *, void *work) -> const void * {
+        pc::Params p{};
+        p.pos = s->pos[s->cur];
+        p.mass_len = s->mass_len_dev;
+        p.n_len = s->n_len_dev;   // null in a uniform ensemble
+        p.n = s->n;
+        p.stride = s->stride;
+        p.out = static_cast<unsigned long long *>(work);
+        launch_pairs(p, edges, bins, classes, count, s->n, s->stream);
+        return work;
+    });
+    const uint64_t *host = static_cast<const uint64_t *>(landed);
     for (uint32_t b = 0; b < count; b++)
-        unpack(s->pairs_host.data() + b * cells, rows, out + (size_t)b * rows * NB_PAIRS_COLUMNS,
-               unplaced ? unplaced + (size_t)b * NB_PAIRS_COLUMNS : nullptr);
+        unpack(host + b * cells, rows, out + (size_t)b * rows * NB_PAIRS_COLUMNS, unplaced ? unplaced + (size_t)b * NB_PAIRS_COLUMNS : nullptr);
 }
 
 // tuning hook (nbody_hip_tuning.h): the device's threshold table for these edges, NB_PAIRS_TABLE floats; returns top.  Host only.

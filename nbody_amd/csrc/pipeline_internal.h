@@ -2,7 +2,8 @@
 //
 //   this header      besides the two structs' shared declarations: DevBuf<T>, DevEvent and Interval, the owner types every
 //                    device array, event and timed interval of a SimPipeline / SimBatch is a member of.  Nothing in these files
-//                    frees device memory or destroys an event by hand: the member's destructor does, when the struct is deleted
+//                    frees device memory or destroys an event by hand: the member's destructor does, when the struct is deleted.
+//                    And ReadScratch / read_call: the one scratch and the one host protocol of every read-only call below
 //   device_ctx.hip   the process-wide device context (the reference keeps one global vulkan_ctx, vulkan_ctx.c:11); the one
 //                    allocation seam (dev_alloc_bytes / dev_free) and the counters behind nb_hip_live_resources
 //   rccl_bind.hip    RCCL bound lazily with dlopen, the communicator of a sharded pipeline, the watchdog
@@ -264,6 +265,44 @@ class NB_HIDDEN Interval {
     bool valid_ = false;
 };
 
+// The scratch of the read-only calls of a SimPipeline / SimBatch: energy, potential, the six field calls, profiles and pair
+// counts.  Every one of them ends in a stream sync before it returns, so no two are ever in flight and one set serves them all;
+// what a call finds in it is whatever the last call of any kind left, so a call reads only what it wrote or zeroed itself.
+struct NB_HIDDEN ReadScratch {
+    DevBuf<char> args;        // what a call uploads
+    DevBuf<char> work;        // what its kernels write: workspace and result, in the call's own layout
+    std::vector<char> host;   // where the copied-back bytes land when the caller's array has another layout
+    Interval iv;              // around the last call's launches and memsets (nb_hip_last_diag_ms / nb_hip_ensemble_last_diag_ms);
+                              // step_iv keeps bracketing the last step.  A call with nothing to launch clears it and stops there
+};
+
+// The protocol of a read-only call on s (a SimPipeline or a SimBatch: its `read` and its `stream`), written once: grow the two
+// buffers (never shrunk; the stream is drained before one moves), upload `args`, then inside the interval
+// `enqueue(args on the device, work)` launches the call's kernels and returns where on the device the bytes to copy back
+// start, one copy of `back_bytes` to `dst` -- null: to read.host -- and one sync.  Returns where the bytes landed.  `args` stays
+// alive until then.  A size of 0 leaves that buffer alone.
+template <class Owner, class Enqueue>
+void *read_call(Owner *s, const char *what, const void *args, size_t args_bytes, size_t work_bytes, void *dst, size_t back_bytes,
+                Enqueue enqueue) {
+    ReadScratch &r = s->read;
+    use_device();
+    if (args_bytes) r.args.grown(s->stream, args_bytes);
+    if (work_bytes) r.work.grown(s->stream, work_bytes);
+    if (args_bytes)
+        ASSERT_HIP(hipMemcpyAsync(r.args, args, args_bytes, hipMemcpyHostToDevice, s->stream), "%s: H2D of %zu bytes", what, args_bytes);
+    r.iv.begin(s->stream);
+    char *up = r.args, *work = r.work;
+    const void *from = enqueue(static_cast<void *>(up), static_cast<void *>(work));
+    r.iv.end(s->stream);
+    if (!dst) {
+        if (r.host.size() < back_bytes) r.host.resize(back_bytes);   // never shrunk either: a resize back up would zero-fill
+        dst = r.host.data();
+    }
+    ASSERT_HIP(hipMemcpyAsync(dst, from, back_bytes, hipMemcpyDeviceToHost, s->stream), "%s: D2H of %zu bytes", what, back_bytes);
+    ASSERT_HIP(hipStreamSynchronize(s->stream), "%s: sync", what);
+    return dst;
+}
+
 // ---- rccl_bind.hip -------------------------------------------------------------------------------------------
 
 // A collective that never completes (a rank that died, a fabric that does not come up) must not hang the job: every
@@ -425,11 +464,8 @@ struct SimPipeline {
 
     std::vector<nbi::StepGraph> graphs;
 
-    // diagnostics.hip (nb_hip_energy / nb_hip_potential): scratch grown on demand, an interval of their own (step_iv keeps
-    // bracketing the last step)
-    nbi::DevBuf<double> diag;      // float64 slab: NB_DIAG_SUMS per workgroup + the NB_DIAG_SUMS results
-    nbi::DevBuf<float> diag_phi;   // nb_hip_potential's device result
-    nbi::Interval diag_iv;
+    // the read-only calls (diagnostics.hip, field.hip, tidal.hip, profile.hip, paircount.hip): their scratch and their interval
+    nbi::ReadScratch read;
 
     // render.hip (nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba; kernels: render_kernels.hip): buffers grown on demand, events of their own
     nbi::DevBuf<uint32_t> render_counts;   // count image [3][height][width]
@@ -441,21 +477,10 @@ struct SimPipeline {
     bool render_detailed = false;          // the last render recorded those two
     int render_merge = 1, render_detail = 0;   // tuning hooks (nbody_hip_tuning.h)
 
-    // field.hip, tidal.hip (nb_hip_potential_at / _map, nb_hip_acceleration_at / _map, nb_hip_tidal_at / _map): one pair of
-    // buffers grown on demand and shared by the six calls (each ends in a stream sync, so no two are in flight); the interval is diag_iv
-    nbi::DevBuf<float> sample_in;    // the probes' (x, y) pairs, or a map's width column + height row coordinates
-    nbi::DevBuf<float> sample_out;   // the device result: one float (Phi), two (g) or three (T) per sample
+    // field.hip, tidal.hip (nb_hip_potential_at / _map, nb_hip_acceleration_at / _map, nb_hip_tidal_at / _map)
     int field_shape = 0;           // tuning hooks, Phi, g and T: 0 auto, 1 source split, 2 one wave per tile
     int gravity_shape = 0;
     int tidal_shape = 0;
-
-    // profile.hip (nb_hip_profile): the float64 slab grown with the call -- [chunks of 1024][rows * 6 + 1], then the results --
-    // and the uploaded edges + centre; the interval is diag_iv
-    nbi::DevBuf<double> profile;
-    nbi::DevBuf<float> profile_in;
-
-    // paircount.hip (nb_hip_pair_counts): the uint64 table the launch adds to, [rows + 1][3], made on first use; the interval is diag_iv
-    nbi::DevBuf<unsigned long long> pairs;
 
     // adaptive steps (step_schedule.hip enqueue_adaptive; kernels: timestep.hip): one device buffer grown on demand --
     // ADAPT_HEAD bytes of records (the call's AdaptState, the record and result of nb_hip_timestep), then the call's log

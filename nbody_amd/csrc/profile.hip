@@ -296,41 +296,36 @@ void nb_hip_profile(SimPipeline *s, const float *edges, uint32_t bins, const flo
     if (n == 0) {
         for (uint32_t i = 0; i < cells; i++) out[i] = 0.0;
         if (unplaced) *unplaced = 0;
-        s->diag_iv.clear();
+        s->read.iv.clear();
         return;
     }
-    use_device();
     const uint32_t chunks = (n + CHUNK - 1) / CHUNK;
-    s->profile.grown(s->stream, (size_t)(chunks + 1) * (cells + 1));   // a slab row per chunk + the results
-    if (!s->profile_in) s->profile_in.alloc(NB_PROFILE_MAX_BINS + 1 + 4);
     float in[NB_PROFILE_MAX_BINS + 1 + 4];
     memcpy(in, edges, (size_t)(bins + 1) * sizeof(float));
     memcpy(in + bins + 1, centre, 4 * sizeof(float));
-    ASSERT_HIP(hipMemcpyAsync(s->profile_in, in, (size_t)(bins + 5) * sizeof(float), hipMemcpyHostToDevice, s->stream),
-               "H2D of %u edges and the centre", bins + 1);
-    pf::ChunkParams p{};
-    p.src.pos = s->pos[s->cur];
-    p.src.vel = s->vel;
-    p.src.mass = s->mass;
-    p.src.n = n;
-    p.in = s->profile_in;
-    p.bins = bins;
-    p.by_mass = weights == NB_PROFILE_BY_MASS;
-    p.slab = s->profile;
-    double *res = p.slab + (size_t)chunks * (cells + 1);
-    s->diag_iv.begin(s->stream);
-    hipLaunchKernelGGL(pf::profile_chunk_kernel, dim3(chunks), dim3(THREADS), 0, s->stream, p);
-    ASSERT_HIP(hipGetLastError(), "profile_chunk_kernel launch (%u particles, %u bins)", n, bins);
-    hipLaunchKernelGGL(pf::profile_reduce_kernel, dim3((cells + pf::RED_CELLS) / pf::RED_CELLS), dim3(THREADS), 0, s->stream, p.slab, chunks, cells,
-                       res);
-    ASSERT_HIP(hipGetLastError(), "profile_reduce_kernel launch (%u chunks)", chunks);
-    s->diag_iv.end(s->stream);
-    double host[(NB_PROFILE_MAX_BINS + 2) * NB_PROFILE_QTY + 1];
-    ASSERT_HIP(hipMemcpyAsync(host, res, (size_t)cells * sizeof(double) + sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream),
-               "D2H of %u profile rows", rows);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_profile");
+    // the float64 slab: a row of cells + 1 per chunk, then the results -- the cells, then the uint32 NaN count
+    const size_t row_bytes = (size_t)(cells + 1) * sizeof(double), back_bytes = (size_t)cells * sizeof(double) + sizeof(uint32_t);
+    const void *host = read_call(s, "nb_hip_profile", in, (size_t)(bins + 5) * sizeof(float), (chunks + 1) * row_bytes, nullptr, back_bytes,
+                                 [&](void *in_dev, void *work) -> const void * {
+        pf::ChunkParams p{};
+        p.src.pos = s->pos[s->cur];
+        p.src.vel = s->vel;
+        p.src.mass = s->mass;
+        p.src.n = n;
+        p.in = static_cast<const float *>(in_dev);
+        p.bins = bins;
+        p.by_mass = weights == NB_PROFILE_BY_MASS;
+        p.slab = static_cast<double *>(work);
+        double *res = p.slab + (size_t)chunks * (cells + 1);
+        hipLaunchKernelGGL(pf::profile_chunk_kernel, dim3(chunks), dim3(THREADS), 0, s->stream, p);
+        ASSERT_HIP(hipGetLastError(), "profile_chunk_kernel launch (%u particles, %u bins)", n, bins);
+        hipLaunchKernelGGL(pf::profile_reduce_kernel, dim3((cells + pf::RED_CELLS) / pf::RED_CELLS), dim3(THREADS), 0, s->stream, p.slab, chunks,
+                           cells, res);
+        ASSERT_HIP(hipGetLastError(), "profile_reduce_kernel launch (%u chunks)", chunks);
+        return res;
+    });
     memcpy(out, host, (size_t)cells * sizeof(double));
-    if (unplaced) memcpy(unplaced, host + cells, sizeof(uint32_t));
+    if (unplaced) memcpy(unplaced, static_cast<const double *>(host) + cells, sizeof(uint32_t));
 }
 
 void nb_hip_ensemble_profile(SimBatch *s, const float *edges, uint32_t bins, const float *centres, int weights, double *out,
@@ -340,38 +335,32 @@ void nb_hip_ensemble_profile(SimBatch *s, const float *edges, uint32_t bins, con
     NB_ASSERT(s->has_data, "nb_hip_ensemble_profile before nb_hip_batch_set_data");
     const uint32_t rows = bins + 2, count = s->count;
     const size_t cells = (size_t)count * rows * QTY;
-    use_device();
-    s->profile.grown(s->stream, cells + (count + 1) / 2);   // the rows of every member, then their uint32 NaN counts
-    s->profile_in.grown(s->stream, NB_PROFILE_MAX_BINS + 1 + (size_t)count * 4);
     std::vector<float> in(bins + 1 + (size_t)count * 4);
     memcpy(in.data(), edges, (size_t)(bins + 1) * sizeof(float));
     memcpy(in.data() + bins + 1, centres, (size_t)count * 4 * sizeof(float));
-    ASSERT_HIP(hipMemcpyAsync(s->profile_in, in.data(), in.size() * sizeof(float), hipMemcpyHostToDevice, s->stream),
-               "H2D of %u edges and %u centres", bins + 1, count);
-    pf::EnsembleParams p{};
-    p.pos = s->pos[s->cur];
-    p.vel = s->vel;
-    p.mass = s->mass;
-    p.mass_len = s->mass_len_dev;
-    p.n_len = s->n_len_dev;   // null in a uniform ensemble
-    p.n = s->n;
-    p.stride = s->stride;
-    p.in = s->profile_in;
-    p.bins = bins;
-    p.by_mass = weights == NB_PROFILE_BY_MASS;
-    p.out = s->profile;
-    p.lost = reinterpret_cast<uint32_t *>(p.out + cells);
-    s->diag_iv.begin(s->stream);
-    hipLaunchKernelGGL(pf::ensemble_profile_kernel, dim3(count), dim3(THREADS), 0, s->stream, p);
-    ASSERT_HIP(hipGetLastError(), "ensemble_profile_kernel launch (%u members of %u, %u bins)", count, s->n, bins);
-    s->diag_iv.end(s->stream);
-    s->profile_host.resize(cells + (count + 1) / 2);
-    ASSERT_HIP(hipMemcpyAsync(s->profile_host.data(), p.out, cells * sizeof(double) + (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                              s->stream),
-               "D2H of %u members' profile rows", count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_profile");
-    memcpy(out, s->profile_host.data(), cells * sizeof(double));
-    if (unplaced) memcpy(unplaced, s->profile_host.data() + cells, (size_t)count * sizeof(uint32_t));
+    // [count][rows][QTY] float64, then the [count] uint32 NaN counts: the same bytes on the device and on the host
+    const size_t bytes = cells * sizeof(double) + (size_t)count * sizeof(uint32_t);
+    const void *host = read_call(s, "nb_hip_ensemble_profile", in.data(), in.size() * sizeof(float), bytes, nullptr, bytes,
+                                 [&](void *in_dev, void *work) -> const void * {
+        pf::EnsembleParams p{};
+        p.pos = s->pos[s->cur];
+        p.vel = s->vel;
+        p.mass = s->mass;
+        p.mass_len = s->mass_len_dev;
+        p.n_len = s->n_len_dev;   // null in a uniform ensemble
+        p.n = s->n;
+        p.stride = s->stride;
+        p.in = static_cast<const float *>(in_dev);
+        p.bins = bins;
+        p.by_mass = weights == NB_PROFILE_BY_MASS;
+        p.out = static_cast<double *>(work);
+        p.lost = reinterpret_cast<uint32_t *>(p.out + cells);
+        hipLaunchKernelGGL(pf::ensemble_profile_kernel, dim3(count), dim3(THREADS), 0, s->stream, p);
+        ASSERT_HIP(hipGetLastError(), "ensemble_profile_kernel launch (%u members of %u, %u bins)", count, s->n, bins);
+        return work;
+    });
+    memcpy(out, host, cells * sizeof(double));
+    if (unplaced) memcpy(unplaced, static_cast<const double *>(host) + cells, (size_t)count * sizeof(uint32_t));
 }
 
 }  // extern "C"
