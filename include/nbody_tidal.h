@@ -18,9 +18,18 @@
  *               three-dimensional 1/r potential seen in their plane (the missing zz term is -sum G*m_j u_j^3), and the
  *               softening adds its own part.  It is negative within |d|^2 < 2 s of a lone source and positive outside.
  *   On a source no term is excluded -- a probe is never a source -- and a probe that sits exactly on a source gets the
- *               finite term diag(-G*m_j s^(-3/2)) from it.
+ *               finite term diag(-G*m_j s^(-3/2)) from it, with xy = +0, on both paths as long as G*m_j s^(-5/2) is a
+ *               finite float32 (s > (G*m_j / 2^128)^(2/5); for G*m = 10 that is s >= 2^-49).  Beyond that range the two
+ *               paths differ.  The host forms every term in float64 and returns the rounded sum: the finite diagonal
+ *               while G*m_j s^(-3/2) is a float32, -inf on the diagonal and +0 beside it below.  The device evaluates
+ *               G*m_j u_j^5 in float32; once it overflows, the products with an exactly zero d_a are 0 * inf: a probe on
+ *               the source gets three NaN, one within an underflowing distance of it NaN or +-inf components.  The same
+ *               holds for any point whose q_j is that small.  In that range the device never returns a finite value
+ *               that is wrong: a component is the float64 term within the pair bound or it is not finite
+ *               (tests/test_gpu_tidal_pairs.py steps through it).
  *   Softening   one scalar per call, finite and > 0; anything else ends in the library's usual "file:line [func] ..." +
- *               abort().
+ *               abort().  The pair bound (DESIGN.md section 5 "The tidal pair term") is promised where every float32
+ *               intermediate of the statement up to G*m_j u_j^5 and its products with d_a d_b is normal.
  *   Non-finite  a point with a non-finite coordinate gives three NaN, on both paths, whatever M.
  *   M = 0       every T is (+0, +0, +0).
  *   Probes      t[n] for the caller's points[n], 0 <= n <= 2^24 (NB_FIELD_MAX_POINTS).  n = 0 does nothing and touches no

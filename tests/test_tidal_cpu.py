@@ -19,6 +19,7 @@ from gpu_common import synth
 from isa_common import check_rsq_wait_states, compile_isa, functions, kernel_meta
 from test_abi import declared_functions, exported
 from test_gravity_cpu import loops
+from tidal_ref import ulps_off
 
 ROOT = nb.ROOT
 WORLD_FUNCS = ["GetWorldTidalAt", "RenderWorldTidal"]
@@ -478,13 +479,6 @@ def test_the_model_of_the_statement_stays_inside_the_tolerance(golden):
         ratios = [tr.ratio_to_bound(tr.device_model(part, m, pts, SOFT, ulps), t64, mag) for ulps in (0, 1, -1)]
         print(f"[tidal model] {name}: worst error / bound {ratios[0]:.3f} (rsq exact), {ratios[1]:.3f} (+1 ulp), {ratios[2]:.3f} (-1 ulp)")
         assert max(ratios) <= 1.0, (name, ratios)
-
-
-def ulps_off(got, exact):
-    """|got - exact| in float32 ulps at the binade of the exact Fraction; an exact zero must be returned as a zero"""
-    if exact == 0:
-        return 0.0 if float(got) == 0.0 else float("inf")
-    return float(abs(Fraction(float(got)) - exact) / tr.ulp32(exact))
 
 
 # On tidal_ref.exact_world every instruction of the documented statement is exact and one source, or two equal ones, are

@@ -1,5 +1,6 @@
 """float64 restatement of include/nbody_tidal.h in numpy, and a float32 model of the device statement (TEST INFRASTRUCTURE for
-test_tidal_cpu.py / test_gpu_tidal.py / test_gpu_batch_tidal.py; no GPU needed to import).
+test_tidal_cpu.py / test_tidal_pair_cpu.py / test_gpu_tidal.py / test_gpu_batch_tidal.py / test_gpu_tidal_pairs.py /
+test_gpu_tidal_sums.py; no GPU needed to import).
 
 Particles are partitioned (mass > 0 first), m = mass_len.  With d_j = x_j - p, q_j = |d_j|^2 + s and u_j = q_j^(-1/2),
     T_ab(p; s) = sum_{j<m} G*m_j (3 d_a d_b u_j^5 - delta_ab u_j^3)          (xx, xy, yy)
@@ -13,7 +14,9 @@ rounding per instruction:
     A = fma(dx, tx, A);  B = fma(dx, ty, B);  C = fma(dy, ty, C)
 fp32 sums from 0.0f over blocks of 256 sources (j ascending), float64 block totals in eight slices of whole blocks added in
 order from 0.0, then in float64 xx = 3 A - D, xy = 3 B, yy = 3 C - D, each rounded once.  rsq is correctly rounded or moved
-by whole ulps.  Two deliberately wrong variants exist for the checkers of tests/test_tidal_cpu.py to reject:
+by whole ulps.  statement() is that pair statement for arrays, shared by device_model (whole worlds) and pair_model (one pair
+onto sums of +0: what tests/tidal_cases.py holds to the derived pair bound, with PAIR_DEFECTS its one-token changes).  Two
+deliberately wrong variants of the world model exist for the checkers of tests/test_tidal_cpu.py to reject:
     "merged diagonal"  one fp32 running sum per diagonal component, X = fma(dx, 3 * tx, X) - w: the factor 3 and the
                        difference of the two parts are rounded to float32 for every pair
     "f32 totals"       the block totals and the slices are added in float32
@@ -92,6 +95,54 @@ def ratio_to_bound(got, t64, mag):
 
 # ---- the float32 model -----------------------------------------------------------------------------------------------------------
 
+# one-token changes of the statement, for the checkers of tests/tidal_cases.py to reject ("merged diagonal" is VARIANTS' own:
+# 3 * tx rounded in fp32 for every pair)
+PAIR_DEFECTS = ("softening dropped", "softening squared", "w5 = w", "tx = dx w", "C fmac with dx for dy", "B fmac with tx for ty",
+                "D not subtracted from yy", "merged diagonal", "one g u factor dropped")
+
+
+def statement(sx, sy, g, px, py, s, rsq_ulps=0, defect=None):
+    """The pair statement at the head of this file up to its three fmac, one float32 rounding per line, for arrays that
+    broadcast: dict of every intermediate, and the operand pairs fa, fb, fc of the fmac onto A, B and C.  `defect` names one of
+    PAIR_DEFECTS (those that sit in the sums' finish are the caller's: pair_model)."""
+    with np.errstate(all="ignore"):
+        sx, sy, g, px, py, s = (f32(v) for v in (sx, sy, g, px, py, s))
+        if defect == "softening dropped":
+            s = np.zeros_like(s)
+        elif defect == "softening squared":
+            s = f32(s * s)
+        dx, dy = f32(sx - px), f32(sy - py)
+        q = fma32(dy, dy, fma32(dx, dx, s))
+        u = rsq32(q, rsq_ulps)
+        u2 = f32(u * u)
+        gu = f32(g * u)
+        w = f32(g * u2) if defect == "one g u factor dropped" else f32(gu * u2)
+        w5 = w if defect == "w5 = w" else f32(w * u2)
+        tx = f32(dx * (w if defect == "tx = dx w" else w5))
+        ty = f32(dy * w5)
+    return dict(dx=dx, dy=dy, q=q, u=u, u2=u2, gu=gu, w=w, w5=w5, tx=tx, ty=ty, fa=(dx, tx),
+                fb=(dx, tx if defect == "B fmac with tx for ty" else ty), fc=(dx if defect == "C fmac with dx for dy" else dy, ty))
+
+
+def pair_model(sx, sy, g, px, py, s, rsq_ulps=0, defect=None, parts=False):
+    """float32 (n, 3): ONE source's term as the device forms it -- the statement onto sums of +0, the block totals to float64,
+    xx = 3 A - D, xy = 3 B, yy = 3 C - D each rounded once.  With parts=True also the statement's dict, with A, B, C, D added."""
+    assert defect is None or defect in PAIR_DEFECTS
+    st = statement(sx, sy, g, px, py, s, rsq_ulps, defect)
+    zero = F32(0.0)
+    with np.errstate(all="ignore"):
+        a, b, c, d = fma32(*st["fa"], zero), fma32(*st["fb"], zero), fma32(*st["fc"], zero), f32(zero + st["w"])
+        a, b, c, d = (np.atleast_1d(v) for v in np.broadcast_arrays(a, b, c, d))
+        if defect == "merged diagonal":
+            xx = f32(fma32(st["dx"], f32(F32(3.0) * st["tx"]), zero) - st["w"]).astype(F64)
+            yy = f32(fma32(st["dy"], f32(F32(3.0) * st["ty"]), zero) - st["w"]).astype(F64)
+            xx, yy = (np.atleast_1d(v) for v in np.broadcast_arrays(xx, yy))
+        else:
+            xx = 3.0 * a.astype(F64) - d.astype(F64)
+            yy = 3.0 * c.astype(F64) - (0.0 if defect == "D not subtracted from yy" else d.astype(F64))
+        out = np.stack([xx, 3.0 * b.astype(F64), yy], axis=1).astype(F32)
+    return (out, dict(st, A=a, B=b, C=c, D=d)) if parts else out
+
 def _slices(totals, dtype):
     """(n, nblocks) block totals -> (n,): eight slices of whole blocks, each from 0 in block order, joined from 0 in order"""
     nblocks = totals.shape[1]
@@ -126,21 +177,15 @@ def device_model(particles, m, points, softening, rsq_ulps=0, variant=None):
     merged = variant == "merged diagonal"
     with np.errstate(all="ignore"):
         for i in range(BLOCK):                                             # every block at once, its sources in order
-            dx, dy = f32(sx[None, :, i] - px), f32(sy[None, :, i] - py)
-            q = fma32(dy, dy, fma32(dx, dx, s))
-            u = rsq32(q, rsq_ulps)
-            u2 = f32(u * u)
-            w = f32(f32(sg[None, :, i] * u) * u2)
-            w5 = f32(w * u2)
-            tx, ty = f32(dx * w5), f32(dy * w5)
-            sums[1] = fma32(dx, ty, sums[1])
+            st = statement(sx[None, :, i], sy[None, :, i], sg[None, :, i], px, py, s, rsq_ulps)
+            sums[1] = fma32(*st["fb"], sums[1])
             if merged:
-                sums[0] = f32(fma32(dx, f32(F32(3.0) * tx), sums[0]) - w)
-                sums[2] = f32(fma32(dy, f32(F32(3.0) * ty), sums[2]) - w)
+                sums[0] = f32(fma32(st["dx"], f32(F32(3.0) * st["tx"]), sums[0]) - st["w"])
+                sums[2] = f32(fma32(st["dy"], f32(F32(3.0) * st["ty"]), sums[2]) - st["w"])
             else:
-                sums[0] = fma32(dx, tx, sums[0])
-                sums[2] = fma32(dy, ty, sums[2])
-                sums[3] = f32(sums[3] + w)
+                sums[0] = fma32(*st["fa"], sums[0])
+                sums[2] = fma32(*st["fc"], sums[2])
+                sums[3] = f32(sums[3] + st["w"])
         dt = F32 if variant == "f32 totals" else F64
         a, b, c, d = (_slices(v, dt).astype(F64) for v in sums)
         if merged:
@@ -201,3 +246,10 @@ def ulp32(x):
     while Fraction(2) ** (e + 1) <= x:
         e += 1
     return Fraction(2) ** (e - 23)
+
+
+def ulps_off(got, exact):
+    """|got - exact| in float32 ulps at the binade of the exact Fraction; an exact zero must be returned as a zero"""
+    if exact == 0:
+        return 0.0 if float(got) == 0.0 else float("inf")
+    return float(abs(Fraction(float(got)) - exact) / ulp32(exact))
