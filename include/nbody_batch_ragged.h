@@ -17,6 +17,7 @@
  *                                    the members differ in size, the samples do not -- results [count][n]
  *   GetWorldBatchProfile             (nbody_batch_profile.h): out [count][bins + 2][6] whatever the sizes
  *   GetWorldBatchPairCounts          (nbody_batch_paircount.h): out [count][bins + 2][3] whatever the sizes
+ *   GetWorldBatchNeighbours          (nbody_batch_neighbour.h): packed like the potential
  * Member b's particles, energy, potential and trace rows are bit for bit those of the same particles in a WorldBatch of
  * one member (so a member does not depend on the other members, their sizes or its index).  While the host array is the
  * newest state the diagnostics run on the host, member by member, and need no GPU.

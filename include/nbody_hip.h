@@ -687,6 +687,33 @@ void nb_hip_ensemble_pair_counts(SimBatch *batch, const float *edges, uint32_t b
                                  uint64_t *out /* [count][bins + 2][3] */, uint64_t *unplaced /* [count][3] */);
 
 /*
+ * The nearest neighbour and the neighbour count of every particle of the state a pipeline or an ensemble holds: which other
+ * particle is closest, its squared distance, and how many lie within a radius (definitions, candidates, ties and the order-free
+ * key: include/nbody_neighbour.h; kernel: nbody_amd/csrc/neighbour.hip).  receivers, sources: each a non-empty mask of
+ * NB_NEIGH_MASSIVE = 1, NB_NEIGH_MASSLESS = 2 (a class that is neither is never read; a particle that is no receiver gets
+ * (+inf, NB_NEIGH_NONE, 0)); radius: finite and >= 0, read only when count is given; q, index: [total_len]; count (nullable):
+ * [total_len], and without it no count is evaluated.
+ *   nb_hip_neighbours             one launch: a workgroup per (tile of 128 receivers, span of sources) merges in LDS and meets the
+ *                                 other spans in a table of the call's scratch through one 64-bit integer atomic minimum and one
+ *                                 32-bit integer atomic add per receiver.  No upload, download 8 bytes per particle without the
+ *                                 count and 12 with it, one sync.  Enqueued, blocking and invisible to the steps like
+ *                                 nb_hip_pair_counts; sharded pipelines abort like it.  Nothing to evaluate (no receiver or no
+ *                                 source) fills the defaults and touches no device.
+ *   nb_hip_ensemble_neighbours    every member of an ensemble, uniform or ragged, in ONE launch of the same kernel; one pair of
+ *                                 masks and one radius for all.  The arrays are packed, member b at offsets[b] of
+ *                                 nb_hip_ragged_layout; an index counts within its member.  Member b's entries are those of
+ *                                 nb_hip_neighbours of a SimPipeline holding the same particles.
+ * A minimum of keys and a sum of integers do not depend on order: a result is a function of the state and the arguments alone,
+ * and there is no float atomic.  Every check -- NULL arguments, an empty or unknown mask, a non-finite or negative radius when
+ * count is given, a call before the data is set -- runs before any device touch and ends in "file:line [func] ..." + abort().
+ * Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_neighbours", dlsym "nb_hip_ensemble_neighbours").
+ */
+void nb_hip_neighbours(SimPipeline *sim, uint32_t receivers, uint32_t sources, float radius, float *q /* [total_len] */,
+                       uint32_t *index /* [total_len] */, uint32_t *count /* nullable */);
+void nb_hip_ensemble_neighbours(SimBatch *batch, uint32_t receivers, uint32_t sources, float radius, float *q, uint32_t *index,
+                                uint32_t *count /* packed, member b at offsets[b] */);
+
+/*
  * Adaptive time steps chosen on the device (definitions: include/nbody_adaptive.h; kernels: nbody_amd/csrc/timestep.hip).
  *   nb_hip_adaptive_steps         n steps, each of the size the criterion gives for the state before it; blocking
  *   nb_hip_adaptive_steps_async   the same, enqueue only

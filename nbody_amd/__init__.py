@@ -145,6 +145,15 @@ class WorldPairSpec(C.Structure):
     _fields_ = [("edges", C.c_void_p), ("bins", C.c_uint32), ("classes", C.c_uint32)]
 
 
+NB_NEIGH_MASSIVE, NB_NEIGH_MASSLESS, NB_NEIGH_ALL = 1, 2, 3     # include/nbody_neighbour.h
+NB_NEIGH_NONE = 0xFFFFFFFF
+
+
+class WorldNeighbourSpec(C.Structure):
+    """include/nbody_neighbour.h WorldNeighbourSpec."""
+    _fields_ = [("receivers", C.c_uint32), ("sources", C.c_uint32), ("radius", C.c_float)]
+
+
 class NbShardPlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mass_chunk", "zero_chunk", "mass_begin", "mass_count",
                                           "zero_begin", "zero_count", "src_padded")]
@@ -209,6 +218,8 @@ HIP_API = {
     "nb_hip_ensemble_profile": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "nb_hip_pair_counts": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nb_hip_ensemble_pair_counts": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "nb_hip_neighbours": (None, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nb_hip_ensemble_neighbours": (None, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nb_hip_batch_destroy": (None, [C.c_void_p]),
     "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
@@ -270,6 +281,7 @@ TUNE_API = {
     "nb_hip_plan_launch_lanes": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_int)]),
     "nb_hip_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_pair_thresholds": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nb_hip_neighbour_span": (C.c_uint32, [C.c_uint32]),
     "nb_hip_last_render_ms": (C.c_double, [C.c_void_p, C.POINTER(C.c_double)]),
     "nb_hip_ensemble_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_ensemble_trace_mode": (None, [C.c_void_p, C.c_int]),
@@ -286,7 +298,8 @@ PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb
 # include/nbody.h + include/galaxy.h + include/nbody_diag.h + include/nbody_batch.h + include/nbody_batch_diag.h +
 # include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h +
 # include/nbody_adaptive.h + include/nbody_leapfrog.h + include/nbody_batch_field.h + include/nbody_tidal.h + include/nbody_batch_tidal.h +
-# include/nbody_profile.h + include/nbody_batch_profile.h + include/nbody_paircount.h + include/nbody_batch_paircount.h
+# include/nbody_profile.h + include/nbody_batch_profile.h + include/nbody_paircount.h + include/nbody_batch_paircount.h +
+# include/nbody_neighbour.h + include/nbody_batch_neighbour.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -322,6 +335,9 @@ NBODY_API = {
     # include/nbody_paircount.h, include/nbody_batch_paircount.h
     "GetWorldPairCounts": (None, [C.c_void_p, C.POINTER(WorldPairSpec), C.c_void_p, C.c_void_p]),
     "GetWorldBatchPairCounts": (None, [C.c_void_p, C.POINTER(WorldPairSpec), C.c_void_p, C.c_void_p]),
+    # include/nbody_neighbour.h, include/nbody_batch_neighbour.h
+    "GetWorldNeighbours": (None, [C.c_void_p, C.POINTER(WorldNeighbourSpec), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "GetWorldBatchNeighbours": (None, [C.c_void_p, C.POINTER(WorldNeighbourSpec), C.c_void_p, C.c_void_p, C.c_void_p]),
     # include/nbody_batch.h
     "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "DestroyWorldBatch": (None, [C.c_void_p]),
@@ -712,6 +728,15 @@ class SimPipeline:
         device, host and numpy agree bit for bit.  nb.profile_edges makes edges, nb.pair_curves reads the result."""
         return _pair_counts(hip_lib().nb_hip_pair_counts, self._h, None, edges, classes, return_unplaced)
 
+    def neighbours(self, radius=None, receivers="all", sources="all"):
+        """nb_hip_neighbours: the nearest neighbour of every particle (include/nbody_neighbour.h): (q, index), or (q, index, count)
+        when a radius is given -- q float32, the squared distance to the closest other particle of `sources` (+inf without one);
+        index uint32, which one (the smallest index among equal q; nb.NB_NEIGH_NONE without one); count uint32, how many lie
+        within `radius`.  receivers / sources: "massive", "massless" or "all"; a particle that is no receiver gets
+        (+inf, NONE, 0) and a class that is neither is never read.  Device, host and numpy agree bit for bit.
+        nb.neighbour_distance and nb.closest_pairs read the result.  Shapes (N,)."""
+        return _neighbours(hip_lib().nb_hip_neighbours, self.total_len, None, radius, receivers, sources)(self._h)
+
     def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
         """nb_hip_profile: the annulus moments about `centre` moving with `centre_velocity` (include/nbody_profile.h), float64
         (bins + 2, 6) with the columns (count, S, I, L, W, K); row 0 lies inside edges[0], row bins + 1 at or beyond edges[-1].
@@ -930,6 +955,57 @@ def _pair_counts(call, handle, count, edges, classes, return_unplaced, spec=Fals
     else:
         call(handle, e.ctypes.data, bins, mask, out.ctypes.data, lost.ctypes.data)
     return (out, lost) if return_unplaced else out
+
+
+def _neigh_mask(name, what):
+    names = {"massive": NB_NEIGH_MASSIVE, "massless": NB_NEIGH_MASSLESS, "all": NB_NEIGH_ALL}
+    if isinstance(name, (int, np.integer)) and not isinstance(name, bool):
+        return int(name) & 0xffffffff          # the library names the fault
+    try:
+        return names[name]
+    except (KeyError, TypeError):
+        raise ValueError(f'{what} must be "massive", "massless" or "all"') from None
+
+
+def _neighbours(call, entries, offsets, radius, receivers, sources, spec=False, shape=None):
+    """One neighbour call of the seam (receivers, sources, radius) or of the World layer (a WorldNeighbourSpec) over `entries`
+    particles: a function of the handle that returns (q, index[, count]) -- flat, reshaped to `shape`, or split at `offsets`."""
+    r, s = _neigh_mask(receivers, "receivers"), _neigh_mask(sources, "sources")
+    h = 0.0 if radius is None else float(radius)
+
+    def run(handle):
+        q, index = np.empty(entries, dtype=np.float32), np.empty(entries, dtype=np.uint32)
+        count = None if radius is None else np.empty(entries, dtype=np.uint32)
+        where = None if count is None else count.ctypes.data
+        if spec:
+            call(handle, C.byref(WorldNeighbourSpec(r, s, h)), q.ctypes.data, index.ctypes.data, where)
+        else:
+            call(handle, r, s, h, q.ctypes.data, index.ctypes.data, where)
+        out = (q, index) if count is None else (q, index, count)
+        if offsets is not None:
+            return tuple(_unpacked(a, offsets) for a in out)
+        return tuple(a.reshape(shape) for a in out) if shape is not None else out
+    return run
+
+
+def neighbour_distance(q):
+    """float64 sqrt(q) of the q of .neighbours(): the distance to the nearest neighbour, +inf kept where there is none."""
+    return np.sqrt(np.asarray(q, dtype=np.float64))
+
+
+def closest_pairs(q, index, k=1):
+    """The k closest unordered pairs among the nearest-neighbour links of one world's .neighbours(): a list of (i, j, q) with
+    i < j, sorted by (q, i, j); a mutual pair appears once, a particle without a neighbour in none.  The first row is the closest
+    encounter of the world: the two particles that set an adaptive step."""
+    q, index = np.asarray(q, dtype=np.float32), np.asarray(index, dtype=np.uint32)
+    if q.ndim != 1 or index.shape != q.shape:
+        raise ValueError("q and index must be the (N,) arrays of one world")
+    if k < 0:
+        raise ValueError("k must not be negative")
+    has = np.nonzero(index != NB_NEIGH_NONE)[0]
+    pairs = {(min(int(i), int(index[i])), max(int(i), int(index[i]))): float(q[i]) for i in has}
+    rows = sorted((v, i, j) for (i, j), v in pairs.items())[:k]
+    return [(i, j, v) for v, i, j in rows]
 
 
 def pair_curves(rows, edges):
@@ -1233,6 +1309,19 @@ class SimBatch:
         device, host and numpy agree bit for bit.  nb.profile_edges makes edges, nb.pair_curves reads the result."""
         return _pair_counts(hip_lib().nb_hip_ensemble_pair_counts, self._h, self.count, edges, classes, return_unplaced)
 
+    def neighbours(self, radius=None, receivers="all", sources="all"):
+        """nb_hip_ensemble_neighbours, one launch for all members: the nearest neighbour of every particle (include/nbody_neighbour.h): (q, index), or (q, index, count)
+        when a radius is given -- q float32, the squared distance to the closest other particle of `sources` (+inf without one);
+        index uint32, which one (the smallest index among equal q; nb.NB_NEIGH_NONE without one); count uint32, how many lie
+        within `radius`.  receivers / sources: "massive", "massless" or "all"; a particle that is no receiver gets
+        (+inf, NONE, 0) and a class that is neither is never read.  Device, host and numpy agree bit for bit.
+        nb.neighbour_distance and nb.closest_pairs read the result.  Shapes (B, N); a
+        ragged ensemble gives lists of per-member arrays, as potential() does.  An index counts within its member."""
+        if self.is_ragged:
+            return _neighbours(hip_lib().nb_hip_ensemble_neighbours, int(self.offsets[-1]), self.offsets, radius, receivers, sources)(self._h)
+        return _neighbours(hip_lib().nb_hip_ensemble_neighbours, self.count * self.total_len, None, radius, receivers, sources,
+                           shape=(self.count, self.total_len))(self._h)
+
     def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
         """nb_hip_ensemble_profile: the annulus moments of every member (include/nbody_profile.h), float64 (B, bins + 2, 6); the edges are
         shared, centre and centre_velocity are (2,) for all members or (B, 2).  Member b's rows are bit-identical to
@@ -1451,6 +1540,19 @@ class WorldBatch:
         device, host and numpy agree bit for bit.  nb.profile_edges makes edges, nb.pair_curves reads the result."""
         return _pair_counts(nbody_lib().GetWorldBatchPairCounts, self._h, self.count, edges, classes, return_unplaced, spec=True)
 
+    def neighbours(self, radius=None, receivers="all", sources="all"):
+        """GetWorldBatchNeighbours (include/nbody_batch_neighbour.h): the nearest neighbour of every particle (include/nbody_neighbour.h): (q, index), or (q, index, count)
+        when a radius is given -- q float32, the squared distance to the closest other particle of `sources` (+inf without one);
+        index uint32, which one (the smallest index among equal q; nb.NB_NEIGH_NONE without one); count uint32, how many lie
+        within `radius`.  receivers / sources: "massive", "massless" or "all"; a particle that is no receiver gets
+        (+inf, NONE, 0) and a class that is neither is never read.  Device, host and numpy agree bit for bit.
+        nb.neighbour_distance and nb.closest_pairs read the result.  Shapes (B, N), in
+        member(b)'s order; a ragged batch gives lists of per-member arrays, as potential() does."""
+        if self.is_ragged:
+            return _neighbours(nbody_lib().GetWorldBatchNeighbours, int(self.offsets[-1]), self.offsets, radius, receivers, sources, spec=True)(self._h)
+        return _neighbours(nbody_lib().GetWorldBatchNeighbours, self.count * self.size, None, radius, receivers, sources, spec=True,
+                           shape=(self.count, self.size))(self._h)
+
     def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
         """GetWorldBatchProfile (include/nbody_batch_profile.h): the annulus moments of every member (include/nbody_profile.h), float64 (B, bins + 2, 6); the edges are
         shared, centre and centre_velocity are (2,) for all members or (B, 2).  Member b's rows are bit-identical to
@@ -1660,6 +1762,15 @@ class World:
         never evaluated.  With return_unplaced also the pairs per class whose squared separation is NaN.  Every count is exact:
         device, host and numpy agree bit for bit.  nb.profile_edges makes edges, nb.pair_curves reads the result."""
         return _pair_counts(nbody_lib().GetWorldPairCounts, self._h, None, edges, classes, return_unplaced, spec=True)
+
+    def neighbours(self, radius=None, receivers="all", sources="all"):
+        """GetWorldNeighbours: the nearest neighbour of every particle (include/nbody_neighbour.h): (q, index), or (q, index, count)
+        when a radius is given -- q float32, the squared distance to the closest other particle of `sources` (+inf without one);
+        index uint32, which one (the smallest index among equal q; nb.NB_NEIGH_NONE without one); count uint32, how many lie
+        within `radius`.  receivers / sources: "massive", "massless" or "all"; a particle that is no receiver gets
+        (+inf, NONE, 0) and a class that is neither is never read.  Device, host and numpy agree bit for bit.
+        nb.neighbour_distance and nb.closest_pairs read the result.  Shapes (N,), in the order particles() returns them."""
+        return _neighbours(nbody_lib().GetWorldNeighbours, self.size, None, radius, receivers, sources, spec=True)(self._h)
 
     def profile(self, edges, centre=(0.0, 0.0), centre_velocity=(0.0, 0.0), weights="mass", return_unplaced=False):
         """GetWorldProfile: the annulus moments about `centre` moving with `centre_velocity` (include/nbody_profile.h), float64

@@ -36,6 +36,9 @@
 //                    chunk, reduce and ensemble kernels and their entry points (the statement: profile_common.h)
 //   paircount.hip    pair-separation counts of a pipeline and of every member of an ensemble (nb_hip_pair_counts,
 //                    nb_hip_ensemble_pair_counts): one kernel and its entry points (the statement: paircount_common.h)
+//   neighbour.hip    the nearest neighbour and the neighbour count of every particle of a pipeline and of every member of an
+//                    ensemble (nb_hip_neighbours, nb_hip_ensemble_neighbours): one kernel template, its span policy and its
+//                    entry points (the statement: neighbour_common.h)
 //   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
 //   leapfrog.hip     the kick / drift passes of a kick-drift-kick step around a dt = 0 force launch (leapfrog.h, leapfrog_common.h)
 #pragma once

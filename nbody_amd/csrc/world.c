@@ -31,6 +31,8 @@
  * rule (profile.hip on the device, profile_cpu.c on the host).
  * Extension (include/nbody_paircount.h): GetWorldPairCounts likewise
  * (paircount.hip on the device, paircount_cpu.c on the host).
+ * Extension (include/nbody_neighbour.h): GetWorldNeighbours likewise
+ * (neighbour.hip on the device, neighbour_cpu.c on the host).
  * Extension (include/nbody_adaptive.h): adaptive steps.  UpdateWorld_GPU_Adaptive
  * and AdvanceWorld_GPU follow UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Adaptive
  * UpdateWorld_CPU's; GetWorldTimestep follows the diagnostics' (timestep.hip on the
@@ -48,6 +50,7 @@
 #include "nbody_tidal.h"
 #include "nbody_profile.h"
 #include "nbody_paircount.h"
+#include "nbody_neighbour.h"
 #include "nbody_hip.h"
 #include "nbody_leapfrog.h"
 #include "nbody_render.h"
@@ -59,6 +62,7 @@
 #include "leapfrog_common.h"
 #include "profile_common.h"
 #include "paircount_common.h"
+#include "neighbour_common.h"
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
@@ -307,6 +311,18 @@ void GetWorldPairCounts(World *w, const WorldPairSpec *spec, uint64_t *out, uint
         nb_hip_pair_counts(w->gpu, spec->edges, spec->bins, spec->classes, out, unplaced);
     else
         nb_cpu_pair_counts(w->particles, w->count, w->massive, spec->edges, spec->bins, spec->classes, out, unplaced);
+}
+
+/* ---- include/nbody_neighbour.h --------------------------------------------------------------------------------------- */
+
+void GetWorldNeighbours(World *w, const WorldNeighbourSpec *spec, float *q, uint32_t *index, uint32_t *count) {
+    NB_CHECK(w != NULL && spec != NULL && q != NULL && index != NULL, "NULL argument");
+    const char *fault = nb_neigh_fault(spec->receivers, spec->sources, spec->radius, count != NULL);
+    NB_CHECK(fault == NULL, "GetWorldNeighbours: %s (receivers %u, sources %u, radius %g)", fault, spec->receivers, spec->sources, (double)spec->radius);
+    if (diag_on_device(w, "GetWorldNeighbours"))
+        nb_hip_neighbours(w->gpu, spec->receivers, spec->sources, spec->radius, q, index, count);
+    else
+        nb_cpu_neighbours(w->particles, w->count, w->massive, spec->receivers, spec->sources, spec->radius, q, index, count);
 }
 
 /* ---- include/nbody_adaptive.h ---------------------------------------------------------------------------------------- */

@@ -35,6 +35,7 @@
 #include "nbody_batch_tidal.h"
 #include "nbody_batch_profile.h"
 #include "nbody_batch_paircount.h"
+#include "nbody_batch_neighbour.h"
 #include "nbody_batch_ragged.h"
 #include "nbody_batch_render.h"
 #include "nbody_batch_trace.h"
@@ -47,6 +48,7 @@
 #include "nb_util.h"
 #include "profile_common.h"
 #include "paircount_common.h"
+#include "neighbour_common.h"
 #include "render_common.h"
 #include "timestep_common.h"
 #include "world_partition.h"
@@ -461,5 +463,21 @@ void GetWorldBatchPairCounts(WorldBatch *w, const WorldPairSpec *spec, uint64_t 
         for (uint32_t b = 0; b < w->count; b++)
             nb_cpu_pair_counts(w->particles + w->offset[b], w->sizes[b], w->massive[b], spec->edges, spec->bins, spec->classes, out + b * cells,
                                unplaced ? unplaced + (size_t)b * NB_PAIRS_COLUMNS : NULL);
+    }
+}
+
+/* ---- include/nbody_batch_neighbour.h --------------------------------------------------------------------------------- */
+
+void GetWorldBatchNeighbours(WorldBatch *w, const WorldNeighbourSpec *spec, float *q, uint32_t *index, uint32_t *count) {
+    NB_CHECK(w != NULL && spec != NULL && q != NULL && index != NULL, "GetWorldBatchNeighbours: NULL argument");
+    const char *fault = nb_neigh_fault(spec->receivers, spec->sources, spec->radius, count != NULL);
+    NB_CHECK(fault == NULL, "GetWorldBatchNeighbours: %s (receivers %u, sources %u, radius %g)", fault, spec->receivers, spec->sources,
+             (double)spec->radius);
+    if (w->device_is_newer) {
+        nb_hip_ensemble_neighbours(w->gpu, spec->receivers, spec->sources, spec->radius, q, index, count);
+    } else {
+        for (uint32_t b = 0; b < w->count; b++)
+            nb_cpu_neighbours(w->particles + w->offset[b], w->sizes[b], w->massive[b], spec->receivers, spec->sources, spec->radius, q + w->offset[b],
+                              index + w->offset[b], count ? count + w->offset[b] : NULL);
     }
 }
