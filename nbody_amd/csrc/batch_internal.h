@@ -54,8 +54,8 @@ struct SimBatch {
     nbi::DevBuf<uint32_t> n_len_dev;     // ragged only, like offsets_dev
     nbi::DevBuf<uint64_t> offsets_dev;
 
-    // the read-only calls (batch_observe.hip's energy, potential and field calls, nb_hip_ensemble_profile, nb_hip_ensemble_pair_counts):
-    // their scratch and their interval (pipeline_internal.h ReadScratch)
+    // the read-only calls (batch_observe.hip's energy, potential and field calls, nb_hip_ensemble_profile, nb_hip_ensemble_pair_counts,
+    // nb_hip_ensemble_neighbours): their scratch and their interval (pipeline_internal.h ReadScratch)
     nbi::ReadScratch read;
     // the energy slab stays a member of its own: traced updates (batch.hip) write it too, and they are no read-only calls
     nbi::DevBuf<double> diag;      // float64 slab: [count][tiles of 128][NB_DIAG_SUMS] + the [count][NB_DIAG_SUMS] results

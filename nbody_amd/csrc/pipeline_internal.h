@@ -268,22 +268,27 @@ class NB_HIDDEN Interval {
     bool valid_ = false;
 };
 
-// The scratch of the read-only calls of a SimPipeline / SimBatch: energy, potential, the six field calls, profiles and pair
-// counts.  Every one of them ends in a stream sync before it returns, so no two are ever in flight and one set serves them all;
-// what a call finds in it is whatever the last call of any kind left, so a call reads only what it wrote or zeroed itself.
+// The scratch of the read-only calls of a SimPipeline / SimBatch: energy, potential, the six field calls, profiles, pair
+// counts and neighbours.  Every one of them ends in a stream sync before it returns, so no two are ever in flight and one set serves them all;
+// what a call finds in it is whatever the last call of any kind left, so a call reads only what it wrote or reset itself: the
+// pair-count table it adds into is zeroed, the neighbour keys it takes minima into are set to all ones, and the neighbour
+// counts are zeroed when a radius asks for them.
 struct NB_HIDDEN ReadScratch {
     DevBuf<char> args;        // what a call uploads
     DevBuf<char> work;        // what its kernels write: workspace and result, in the call's own layout
     std::vector<char> host;   // where the copied-back bytes land when the caller's array has another layout
     Interval iv;              // around the last call's launches and memsets (nb_hip_last_diag_ms / nb_hip_ensemble_last_diag_ms);
-                              // step_iv keeps bracketing the last step.  A call with nothing to launch clears it and stops there
+                              // step_iv keeps bracketing the last step.  A call with nothing to launch (no probe; no neighbour
+                              // receiver or source under the masks) returns its defaults, clears it and stops there
 };
 
 // The protocol of a read-only call on s (a SimPipeline or a SimBatch: its `read` and its `stream`), written once: grow the two
 // buffers (never shrunk; the stream is drained before one moves), upload `args`, then inside the interval
 // `enqueue(args on the device, work)` launches the call's kernels and returns where on the device the bytes to copy back
 // start, one copy of `back_bytes` to `dst` -- null: to read.host -- and one sync.  Returns where the bytes landed.  `args` stays
-// alive until then.  A size of 0 leaves that buffer alone.
+// alive until then.  A size of 0 leaves that buffer alone.  Its callers: diagnostics.hip and batch_observe.hip (energy, potential),
+// field_sampler.h and batch_observe.hip (the six field calls), profile.hip, paircount.hip and neighbour.hip, each for a pipeline
+// and for an ensemble.  tests/sequence_driver.py (the reads kinds) issues them all in drawn orders on one long-lived object.
 template <class Owner, class Enqueue>
 void *read_call(Owner *s, const char *what, const void *args, size_t args_bytes, size_t work_bytes, void *dst, size_t back_bytes,
                 Enqueue enqueue) {
@@ -467,7 +472,7 @@ struct SimPipeline {
 
     std::vector<nbi::StepGraph> graphs;
 
-    // the read-only calls (diagnostics.hip, field.hip, tidal.hip, profile.hip, paircount.hip): their scratch and their interval
+    // the read-only calls (diagnostics.hip, field.hip, tidal.hip, profile.hip, paircount.hip, neighbour.hip): their scratch and their interval
     nbi::ReadScratch read;
 
     // render.hip (nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba; kernels: render_kernels.hip): buffers grown on demand, events of their own

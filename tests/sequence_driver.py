@@ -29,6 +29,16 @@ false after set_data, any Euler step and a trace of n > 0 steps) and compares la
 with it directly after every leapfrog call: primed == not current, force launches == n + primed (the force evaluations of
 the call, include/nbody_leapfrog.h: n + 1 for the first call of a sequence, n for every following one).
 
+The reads kinds ("pipeline-reads", "batch-reads", "ragged-reads").  energy, potential, the six field calls, profile, pair_counts
+and neighbours share one scratch and one host protocol (nbody_amd/csrc/pipeline_internal.h ReadScratch, read_call): two grow-only
+device buffers, one grow-only host vector and one timed interval.  pair_counts adds into a table it must zero itself, neighbours
+takes minima into keys it must set to all ones and adds into counts it must zero when a radius is given, and a call with nothing
+to launch returns defaults and clears the interval.  A reads kind draws everything its base kind draws plus these calls (an
+ensemble kind: the four Phi / g field calls too), with drawn arguments -- for an ensemble also whether points, views and centres
+are one for all members or one per member -- and plants the pieces of _reads_pieces.  In these kinds the output of every call of
+DIAG_READS is its bytes followed by ONE BYTE, last_diag_ms() > 0: "the interval was recorded by a call that launched and cleared
+by one that did not" is part of the bitwise verdict, and no time is compared.
+
 This module imports no GPU code: `make` builds the object and `env` (Env below) turns plain arguments into the objects the
 calls want, so tests/test_sequence_cpu.py drives a numpy stand-in with planted faults through the very same code."""
 import struct
@@ -45,14 +55,26 @@ MAP_SIZES = ((16, 9), (40, 30))
 RENDER_SIZES = ((32, 18), (80, 45))
 SOFT = 0.75
 TRACE_EVERY = (1, 2, 5)
+BINS = (4, 64)                    # profile and pair_counts: growing, too
+PROFILE_WEIGHTS = ("mass", "number")
+PAIR_CLASSES = (("mm",), ("mm", "mt"), "all")
+MASKS = ("massive", "massless", "all")
+EMPTY_MASKS = ("massless", "massless")          # nothing to launch in a world (or an ensemble) without a massless particle
 LENGTH = 40
+READS_LENGTH = 84                 # the reads kinds: about 40 planted operations and as many drawn ones
 LF_LENGTH = 60                    # the leapfrog kinds: 40 and the planted leapfrog pieces
 LONG_ADAPT = 70                   # > 64 logged steps: the adaptive head regrows (planted, "pipeline-lf" only)
 # the committed seeds: tests/test_gpu_sequences.py runs exactly these, and tests/test_sequence_cpu.py shows that the
 # "pipeline" ones catch every planted fault, and that each pair of the leapfrog kinds catches every leapfrog fault (and how
-# those pairs were chosen)
-SEEDS = {"pipeline": (5, 8, 11), "batch": (5, 8), "ragged": (5, 8), "pipeline-lf": (0, 6), "batch-lf": (2, 3)}
+# those pairs were chosen), and each pair of the reads kinds every fault of the shared read scratch, chosen the same way
+SEEDS ={"pipeline": (5, 8, 11), "batch": (5, 8), "ragged": (5, 8), "pipeline-lf": (0, 6), "batch-lf": (2, 3),
+         "pipeline-reads": (0, 1), "batch-reads": (0, 1), "ragged-reads": (0, 1)}
 BASE = {"pipeline-lf": "pipeline", "batch-lf": "batch"}          # a leapfrog kind draws everything its base kind draws
+READS = {"pipeline-reads": "pipeline", "batch-reads": "batch", "ragged-reads": "ragged"}          # and so does a reads kind
+
+
+def base_of(kind):
+    return BASE.get(kind) or READS.get(kind, kind)
 
 # name -> (N, frac_massive, configure knobs): the smallest sizes at which each step route and launch shape exists
 # (tests/test_gpu_sequences.py, tests/test_gpu_adaptive.py).  At N = 9 000 the auto rule drops the finish kernel of a split
@@ -79,6 +101,14 @@ STEPPING = FIXED + ADAPTIVE + LEAPFROG
 ASYNC = ("step_async", "update_adaptive_async", "update_leapfrog_async")
 DIAGNOSTICS = ("energy", "potential", "potential_at", "acceleration_at", "potential_map", "acceleration_map", "bounds",
                "render_counts", "render")
+AT_CALLS = ("potential_at", "acceleration_at", "tidal_at")
+MAP_CALLS = ("potential_map", "acceleration_map", "tidal_map")
+FAMILY = {"tidal_at": "tidal", "tidal_map": "tidal", "profile": "profile", "pair_counts": "pair_counts", "neighbours": "neighbours"}
+NEW_READS = tuple(FAMILY)
+# the calls of read_call: what last_diag_ms() speaks of
+DIAG_READS = ("energy", "potential") + AT_CALLS[:2] + MAP_CALLS[:2] + NEW_READS
+# of those, the ones that launch in every world of the rows whatever their drawn arguments (a probe set is never drawn empty)
+LAUNCHED = tuple(n for n in DIAG_READS if n != "neighbours")
 
 # name -> weight; the stepping operations of a kind sum to 1/3, everything else to 2/3
 WEIGHTS = {
@@ -89,8 +119,9 @@ WEIGHTS = {
     "batch": ({"update": 0.12, "step_async": 0.07, "update_adaptive": 0.08, "trace": 0.06},
               {"energy": 0.11, "potential": 0.10, "bounds": 0.07, "render_counts": 0.09, "render": 0.10, "get_data": 0.07,
                "get_member": 0.07, "set_data": 0.06}),
-    # include/nbody_batch_ragged.h: steps, trace, energy, potential, get, set -- NOTHING else (render, bounds and adaptive
-    # calls abort on a ragged ensemble by contract)
+    # include/nbody_batch_ragged.h lists steps, trace, energy, potential, get and set, and the field, tidal, profile, pair-count and
+    # neighbour calls, which this kind has never drawn ("ragged-reads" below does); render, bounds and adaptive calls abort on
+    # a ragged ensemble by contract
     "ragged": ({"update": 0.15, "step_async": 0.10, "trace": 0.08},
                {"energy": 0.18, "potential": 0.17, "get_data": 0.12, "get_member": 0.10, "set_data": 0.10}),
     # the leapfrog kinds: the planted pieces are mostly steps, so the drawn segments step less often and the whole sequence
@@ -104,16 +135,46 @@ WEIGHTS = {
     "batch-lf": ({"update": 0.02, "step_async": 0.05, "update_adaptive": 0.04, "trace": 0.02, "update_leapfrog": 0.02},
                  {"energy": 0.11, "potential": 0.10, "bounds": 0.07, "render_counts": 0.09, "render": 0.10, "get_data": 0.07,
                   "get_member": 0.07, "set_data": 0.06}),
+    # the reads kinds: the steps of the base kind, and the new calls take about a third of the whole from the other calls
+    "pipeline-reads": ({"update": 0.12, "step_async": 0.07, "update_adaptive": 0.08, "update_adaptive_async": 0.06},
+                       {"timestep": 0.03, "energy": 0.04, "potential": 0.03, "potential_at": 0.03, "acceleration_at": 0.03,
+                        "potential_map": 0.03, "acceleration_map": 0.03, "bounds": 0.02, "render_counts": 0.03, "render": 0.03,
+                        "get_data": 0.04, "set_data": 0.03, "sync": 0.02, "tidal_at": 0.05, "tidal_map": 0.05, "profile": 0.06,
+                        "pair_counts": 0.06, "neighbours": 0.08}),
+    "batch-reads": ({"update": 0.12, "step_async": 0.07, "update_adaptive": 0.08, "trace": 0.06},
+                    {"energy": 0.05, "potential": 0.05, "bounds": 0.03, "render_counts": 0.04, "render": 0.04, "get_data": 0.05,
+                     "get_member": 0.04, "set_data": 0.04, "potential_at": 0.03, "acceleration_at": 0.03, "potential_map": 0.03,
+                     "acceleration_map": 0.03, "tidal_at": 0.04, "tidal_map": 0.04, "profile": 0.05, "pair_counts": 0.05,
+                     "neighbours": 0.06}),
+    # include/nbody_batch_ragged.h: the above, and the field, tidal, profile, pair-count and neighbour calls (render, bounds and
+    # adaptive calls still abort)
+    "ragged-reads": ({"update": 0.15, "step_async": 0.10, "trace": 0.08},
+                     {"energy": 0.07, "potential": 0.07, "get_data": 0.06, "get_member": 0.05, "set_data": 0.05, "potential_at": 0.03,
+                      "acceleration_at": 0.03, "potential_map": 0.03, "acceleration_map": 0.03, "tidal_at": 0.04, "tidal_map": 0.04,
+                      "profile": 0.06, "pair_counts": 0.06, "neighbours": 0.08}),
 }
 RAGGED_ALLOWED = frozenset(WEIGHTS["ragged"][0]) | frozenset(WEIGHTS["ragged"][1])
+RAGGED_READS_ALLOWED = frozenset(WEIGHTS["ragged-reads"][0]) | frozenset(WEIGHTS["ragged-reads"][1])
+
+
+def ragged_allowed(kind):
+    return RAGGED_READS_ALLOWED if kind == "ragged-reads" else RAGGED_ALLOWED
 
 
 class Env:
     """What a sequence runs on: the state it starts from, the state set_data brings in, the member count of an ensemble (0: a
-    single world) and two factories that turn plain arguments into what the calls take."""
+    single world) and the factories that turn plain arguments into what the calls take; the states' scale is the test
+    file's, not the driver's.  view(w, h) and points(count) serve the old kinds.  A reads kind also calls
+      view(w, h, b)             member b's own view of that size
+      points(count, which, per_member)
+                                probe set 0 or 1: (count, 2), or (members, count, 2) with one set per member
+      edges(bins)               bins + 1 radii for profile and pair_counts
+      centre(which, per_member) (centre, centre velocity) 0 or 1, the velocity not zero: each (2,), or (members, 2)
+      radius                    the finite radius of neighbours"""
 
-    def __init__(self, kind, start, other, view, points, members=0):
+    def __init__(self, kind, start, other, view, points, members=0, edges=None, centre=None, radius=None):
         self.kind, self.start, self.other, self.view, self.points, self.members = kind, start, other, view, points, members
+        self.edges, self.centre, self.radius = edges, centre, radius
 
 
 def assert_premise(*states):
@@ -193,11 +254,44 @@ def _adaptive_kw(args):
     return kw
 
 
+def _probes(a, env):
+    if "which" not in a:
+        return env.points(a["count"])
+    return env.points(a["count"], a["which"], bool(a.get("per_member")))
+
+
+def _views(a, env):
+    if a.get("per_member"):
+        return [env.view(a["w"], a["h"], b) for b in range(env.members)]
+    return env.view(a["w"], a["h"])
+
+
+def _read(obj, name, a, env):
+    """one of the calls the reads kinds add, with the arguments the environment makes of the drawn ones"""
+    if name == "tidal_at":
+        return obj.tidal_at(_probes(a, env), SOFT)
+    if name == "tidal_map":
+        return obj.tidal_map(_views(a, env), SOFT)
+    if name == "profile":
+        centre, velocity = env.centre(a["centre"], bool(a.get("per_member")))
+        return obj.profile(env.edges(a["bins"]), centre, velocity, a["weights"], return_unplaced=True)
+    if name == "pair_counts":
+        return obj.pair_counts(env.edges(a["bins"]), classes=a["classes"], return_unplaced=True)
+    return obj.neighbours(env.radius if a["radius"] else None, a["receivers"], a["sources"])
+
+
 def apply(obj, op, env):
-    """Issue one operation; its output as bytes, or None."""
+    """Issue one operation; its output as bytes, or None.  A reads kind: the interval's byte behind every call of DIAG_READS."""
+    out = _apply(obj, op, env)
+    if env.kind in READS and op[0] in DIAG_READS:
+        out += b"\1" if obj.last_diag_ms() > 0 else b"\0"
+    return out
+
+
+def _apply(obj, op, env):
     name, a = op
-    if env.kind == "ragged":
-        assert name in RAGGED_ALLOWED, f"{name} aborts on a ragged ensemble by contract: the generator must never emit it"
+    if base_of(env.kind) == "ragged":
+        assert name in ragged_allowed(env.kind), f"{name} aborts on a ragged ensemble by contract: the generator must never emit it"
     if name == "update":
         obj.update(a["n"], _dt(a, env))
     elif name == "step_async":
@@ -224,13 +318,15 @@ def apply(obj, op, env):
     elif name == "potential":
         return blob(obj.potential())
     elif name == "potential_at":
-        return blob(obj.potential_at(env.points(a["count"]), SOFT))
+        return blob(obj.potential_at(_probes(a, env), SOFT))
     elif name == "acceleration_at":
-        return blob(obj.acceleration_at(env.points(a["count"]), SOFT))
+        return blob(obj.acceleration_at(_probes(a, env), SOFT))
     elif name == "potential_map":
-        return blob(obj.potential_map(env.view(a["w"], a["h"]), SOFT))
+        return blob(obj.potential_map(_views(a, env), SOFT))
     elif name == "acceleration_map":
-        return blob(obj.acceleration_map(env.view(a["w"], a["h"]), SOFT))
+        return blob(obj.acceleration_map(_views(a, env), SOFT))
+    elif name in NEW_READS:
+        return blob(_read(obj, name, a, env))
     elif name == "bounds":
         return blob(obj.bounds())
     elif name in ("render_counts", "render"):
@@ -324,7 +420,9 @@ def _pick(rng, seq):
 
 def _make(rng, kind, name, members):
     """One operation of that name with drawn arguments."""
-    base = BASE.get(kind, kind)
+    base = base_of(kind)
+    if kind in READS and name in DIAG_READS:
+        return _make_read(rng, name, base != "pipeline")
     if name in ("update", "step_async", "update_leapfrog", "update_leapfrog_async"):
         a = {"n": int(_pick(rng, STEP_COUNTS)), "dt": float(_pick(rng, STEP_DTS))}
         if base != "pipeline":
@@ -357,6 +455,26 @@ def _make(rng, kind, name, members):
     if name == "get_member":
         return name, {"b": int(rng.integers(members))}
     return name, {}
+
+
+def _make_read(rng, name, ensemble):
+    """A call of DIAG_READS in a reads kind: every argument drawn; an ensemble also draws one for all / one per member."""
+    if name in AT_CALLS:
+        a = {"count": int(_pick(rng, POINT_COUNTS)), "which": int(rng.integers(2))}
+    elif name in MAP_CALLS:
+        w, h = _pick(rng, MAP_SIZES)
+        a = {"w": w, "h": h}
+    elif name == "profile":
+        a = {"bins": int(_pick(rng, BINS)), "weights": _pick(rng, PROFILE_WEIGHTS), "centre": int(rng.integers(2))}
+    elif name == "pair_counts":
+        return name, {"bins": int(_pick(rng, BINS)), "classes": _pick(rng, PAIR_CLASSES)}
+    elif name == "neighbours":
+        return name, {"radius": bool(rng.random() < 0.5), "receivers": _pick(rng, MASKS), "sources": _pick(rng, MASKS)}
+    else:
+        return name, {}
+    if ensemble:
+        a["per_member"] = bool(rng.random() < 0.5)
+    return name, a
 
 
 def _flips(op):
@@ -431,6 +549,8 @@ def generate(kind, seed, length=None, members=0):
     The leapfrog kinds plant the four groups of _leapfrog_pieces between them."""
     if kind in BASE:
         return _generate_leapfrog(kind, seed, LF_LENGTH if length is None else length, members)
+    if kind in READS:
+        return _generate_reads(kind, seed, READS_LENGTH if length is None else length, members)
     length = LENGTH if length is None else length
     rng = np.random.default_rng(seed)
     if kind == "ragged":
@@ -488,6 +608,171 @@ def _generate_leapfrog(kind, seed, length, members):
             ops += planted[i]
     assert_covers(kind, ops)
     return ops
+
+
+def _sized(op, size):
+    """the same call at the smallest (0) or the largest (-1) drawn size"""
+    name, a = op
+    a = dict(a)
+    if name in AT_CALLS:
+        a["count"] = POINT_COUNTS[size]
+    elif name in MAP_CALLS:
+        a["w"], a["h"] = MAP_SIZES[size]
+    else:
+        a["bins"] = BINS[size]
+    return name, a
+
+
+def _size(op):
+    name, a = op
+    return a["count"] if name in AT_CALLS else a["w"] * a["h"] if name in MAP_CALLS else a["bins"] if "bins" in a else None
+
+
+def _reads_pieces(rng, kind, members, odd, middle):
+    """The planted pieces of the reads kinds (R: one of NEW_READS; the two R of a piece are the same call):
+      step_async, R                 four times, one R of each family (tidal, profile, pair_counts, neighbours): a read queues
+                                    behind async steps and sees the state after them
+      update_adaptive_async, R, adaptive_collect
+                                    a single world: the same behind the adaptive async call
+      field(small), field(large), field(small); profile(4 bins), profile(64), profile(4)
+                                    grow and shrink: the second small call runs inside buffers larger than it needs, over
+                                    what the large one left
+      neighbours(radius, A, B), neighbours(None, C, D), pair_counts, neighbours(radius, C, D)   with (A, B) != (C, D)
+                                    the counts of the first call lie where the last one adds; the call between them with no
+                                    radius must not have touched them, the table of pair_counts lies over the keys
+      pair_counts, pair_counts      other classes: a table that is not zeroed keeps the first call's columns
+      R, an odd number of steps, R  the phase bit flips between them (`odd`: the base kind's odd call)
+      R, set_data, R                (`middle`: the base kind's set_data piece)
+      X, potential_at(no points), Y; X, neighbours(EMPTY_MASKS), Y
+                                    nothing to launch -- always for an empty probe set, and for these masks where no member has a
+                                    massless particle -- between two reads of LAUNCHED: defaults come back, the interval is
+                                    cleared, and neither the scratch nor the host vector is what the next call may rest on"""
+    ensemble = base_of(kind) != "pipeline"
+
+    def mk(name):
+        return _make(rng, kind, name, members)
+
+    def queued():
+        op = mk("step_async")
+        if ensemble:
+            op[1]["per_member"] = True
+        return op
+    behind = [[queued(), mk(_pick(rng, fam))] for fam in (("tidal_at", "tidal_map"), ("profile",), ("pair_counts",), ("neighbours",))]
+    if not ensemble:
+        behind.append([("update_adaptive_async", {"n": 3}), mk(_pick(rng, NEW_READS)), ("adaptive_collect", {"n": 3})])
+    field = mk(_pick(rng, AT_CALLS + MAP_CALLS))
+    prof = mk("profile")
+    grow = [[_sized(field, 0), _sized(field, -1), _sized(field, 0)], [_sized(prof, 0), _sized(prof, -1), _sized(prof, 0)]]
+    first = (_pick(rng, MASKS), _pick(rng, MASKS))
+    second = first
+    while second == first:
+        second = (_pick(rng, MASKS), _pick(rng, MASKS))
+
+    def neigh(radius, masks):
+        return "neighbours", {"radius": radius, "receivers": masks[0], "sources": masks[1]}
+    c1 = int(rng.integers(len(PAIR_CLASSES)))
+    c2 = (c1 + 1 + int(rng.integers(len(PAIR_CLASSES) - 1))) % len(PAIR_CLASSES)
+    bins = int(_pick(rng, BINS))
+    accumulate = [[neigh(True, first), neigh(False, second), mk("pair_counts"), neigh(True, second)],
+                  [("pair_counts", {"bins": bins, "classes": PAIR_CLASSES[c1]}), ("pair_counts", {"bins": bins, "classes": PAIR_CLASSES[c2]})]]
+    r1, r2 = mk(_pick(rng, NEW_READS)), mk(_pick(rng, NEW_READS))
+    phase = [[r1, odd, (r1[0], dict(r1[1]))], [r2] + middle + [(r2[0], dict(r2[1]))]]
+    no_points = {"count": 0, "which": 0}
+    if ensemble:
+        no_points["per_member"] = False
+    nothing = [[mk(_pick(rng, [n for n in LAUNCHED if n != "potential_at"])), ("potential_at", no_points), mk(_pick(rng, [n for n in LAUNCHED if n != "potential_at"]))],
+               [mk(_pick(rng, LAUNCHED)), neigh(bool(rng.random() < 0.5), EMPTY_MASKS), mk(_pick(rng, LAUNCHED))]]
+    return behind, grow, accumulate, phase, nothing
+
+
+def _generate_reads(kind, seed, length, members):
+    rng = np.random.default_rng([seed, len(kind), 1])          # a stream of its own: no list of another kind moves
+    base = READS[kind]
+    if base == "ragged":
+        odd = ("update", {"n": 3, "dt": float(_pick(rng, STEP_DTS)), "per_member": True})
+    else:
+        odd = ("update_adaptive", {"n": int(_pick(rng, (1, 3)))})
+    first = _make(rng, kind, "step_async", members)
+    if base != "pipeline":
+        first[1]["per_member"] = True
+    old_behind = [first, _make(rng, kind, _pick(rng, ("energy", "potential")), members)]
+    middle = [("timestep", {}), ("set_data", {}), ("timestep", {})] if base == "pipeline" else [("set_data", {})]
+    chain = _make(rng, kind, "update", members)
+    chain[1]["n"] = int(_pick(rng, (2, 7, 20)))
+    behind, grow, accumulate, phase, nothing = _reads_pieces(rng, kind, members, odd, middle)
+    # the odd call first and the chain last (the base kind's order), set_data in the middle
+    planted = [phase[0]] + behind[:4] + [grow[0], accumulate[0]] + behind[4:] + [phase[1], grow[1], accumulate[1]] + nothing + [old_behind, [chain]]
+    gaps = len(planted) + 1
+    free = max(length - sum(len(p) for p in planted), gaps)
+    ops = []
+    for i in range(gaps):
+        ops += _segment(rng, kind, free // gaps + (1 if i < free % gaps else 0), members)
+        if i < len(planted):
+            ops += planted[i]
+    assert_covers(kind, ops)
+    return ops
+
+
+def _same_around(ops, inner, outer=lambda op: op[0] in NEW_READS):
+    """is there a call `outer` accepts, then one or more operations that `inner` accepts as a list, then the very same call?"""
+    for i, op in enumerate(ops):
+        if outer(op):
+            for j in range(i + 2, len(ops)):
+                if ops[j] == op and inner(ops[i + 1:j]):
+                    return True
+    return False
+
+
+def assert_covers_reads(kind, ops):
+    """The planted pieces of the reads kinds (_reads_pieces), on the list itself."""
+    pairs = list(zip(ops, ops[1:]))
+    for family in sorted(set(FAMILY.values())):
+        assert any(a[0] == "step_async" and FAMILY.get(b[0]) == family for a, b in pairs), f"no {family} call directly behind step_async"
+    if READS[kind] == "pipeline":
+        assert any(a[0] == "update_adaptive_async" and b[0] in NEW_READS for a, b in pairs), "no new read directly behind update_adaptive_async"
+
+    def grows(names):
+        return any(a == c and a[0] == b[0] and a[0] in names and _size(a) == _size(_sized(a, 0)) and _size(b) == _size(_sized(a, -1))
+                   for a, b, c in zip(ops, ops[1:], ops[2:]))
+    assert grows(AT_CALLS + MAP_CALLS), "no field call small, large and small again"
+    assert grows(("profile",)), "no profile small, large and small again"
+
+    def neigh(op, radius):
+        return op[0] == "neighbours" and op[1]["radius"] == radius
+
+    def masks(op):
+        return op[1]["receivers"], op[1]["sources"]
+    assert any(neigh(a, True) and neigh(b, False) and c[0] == "pair_counts" and neigh(d, True) and masks(b) == masks(d) != masks(a)
+               for a, b, c, d in zip(ops, ops[1:], ops[2:], ops[3:])), \
+        "no neighbours(radius), neighbours(None) under other masks, pair_counts, neighbours(radius) under those masks"
+    assert any(a[0] == b[0] == "pair_counts" and a[1]["classes"] != b[1]["classes"] for a, b in pairs), "no two pair_counts in a row with other classes"
+    assert _same_around(ops, lambda inner: len(inner) == 1 and inner[0][0] in STEPPING and _flips(inner[0]) % 2 == 1), \
+        "no new read before and after an odd number of steps"
+    assert _same_around(ops, lambda inner: any(op[0] == "set_data" for op in inner) and all(op[0] in ("set_data", "timestep") for op in inner)), \
+        "no new read before and after set_data"
+
+    def launched(op, but):
+        return op[0] in LAUNCHED and op[0] != but and _size(op) != 0
+    assert any(launched(a, "potential_at") and b[0] == "potential_at" and b[1]["count"] == 0 and launched(c, "potential_at")
+               for a, b, c in zip(ops, ops[1:], ops[2:])), "no empty probe set between two launched reads of another kind"
+    assert any(launched(a, "neighbours") and b[0] == "neighbours" and masks(b) == EMPTY_MASKS and launched(c, "neighbours")
+               for a, b, c in zip(ops, ops[1:], ops[2:])), "no neighbours under EMPTY_MASKS between two launched reads of another kind"
+
+
+def assert_union_covers_reads(kind, lists):
+    """What the committed sequences of a reads kind must hold BETWEEN them: every operation the kind draws, neighbours with and
+    without a radius, and each ensemble argument (points, views, centres) one for all and one per member."""
+    ops = [op for lst in lists for op in lst]
+    names = {name for name, _ in ops}
+    every = set(WEIGHTS[kind][0]) | set(WEIGHTS[kind][1])
+    assert every <= names, f"the committed {kind} sequences never issue {sorted(every - names)}"
+    for radius in (True, False):
+        assert any(n == "neighbours" and a["radius"] == radius for n, a in ops), f"no neighbours with radius {radius}"
+    if READS[kind] != "pipeline":
+        for what, calls in (("points", AT_CALLS), ("views", MAP_CALLS), ("centres", ("profile",))):
+            for per_member in (True, False):
+                assert any(n in calls and a.get("count") != 0 and a["per_member"] == per_member for n, a in ops), \
+                    f"no {what} {'one per member' if per_member else 'one for all'}"
 
 
 def _between_leapfrog(ops, inner):
@@ -549,8 +834,12 @@ def assert_covers(kind, ops):
     if lf:
         assert_covers_leapfrog(kind, ops)
         kind = BASE[kind]
+    allowed = ragged_allowed(kind)
+    if kind in READS:
+        assert_covers_reads(kind, ops)
+        kind = READS[kind]
     if kind == "ragged":
-        assert set(names) <= RAGGED_ALLOWED, sorted(set(names) - RAGGED_ALLOWED)
+        assert set(names) <= allowed, sorted(set(names) - allowed)
     flipping = ADAPTIVE if kind != "ragged" else FIXED
     odd = [i for i, op in enumerate(ops) if op[0] in flipping and _flips(op) % 2 == 1]
     assert odd and any(op[0] in FIXED and op[1]["n"] >= 2 for op in ops[odd[0] + 1:]), \

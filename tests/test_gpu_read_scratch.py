@@ -1,10 +1,13 @@
-"""One scratch for every read-only call, on the MI355X: energy, potential, the six field calls, profile and pair_counts of a
-SimPipeline / SimBatch share two device buffers, one host vector and one interval (nbody_amd/csrc/pipeline_internal.h
-ReadScratch, read_call).  What that could break is a call that sees what a call of another kind left behind, or a buffer
-another call sized.  So one long-lived object makes all ten calls in a fixed order, at small sizes, at large ones and at the
-small ones again (inside buffers now larger than it needs), and every output must equal, byte for byte, the same call on a
-fresh object of the same sizes in the same state -- one fresh object per call.  The interval must have been recorded by
-every call that launched something, and cleared by the one that had nothing to launch."""
+"""One scratch for every read-only call, on the MI355X: energy, potential, the six field calls, profile, pair_counts and
+neighbours of a SimPipeline / SimBatch share two device buffers, one host vector and one interval
+(nbody_amd/csrc/pipeline_internal.h ReadScratch, read_call).  What that could break is a call that sees what a call of another
+kind left behind, or a buffer another call sized.  So one long-lived object makes all twelve calls in a fixed order, at small
+sizes, at large ones and at the small ones again (inside buffers now larger than it needs), and every output must equal, byte
+for byte, the same call on a fresh object of the same sizes in the same state -- one fresh object per call.  The two neighbour
+calls are the ones that merge into the scratch by atomicMin and atomicAdd: one with a radius, then one without under other masks.
+The ragged ensemble has a member with no massless particle, for which the second of them has nothing to launch while the
+other members do.  The interval must have been recorded by every call that launched something, and cleared by the one that had
+nothing to launch.  tests/test_gpu_sequences.py (the reads kinds) issues the same calls in drawn orders, among steps."""
 import numpy as np
 import pytest
 
@@ -16,6 +19,7 @@ pytestmark = pytest.mark.gpu
 DT = 0.01
 SOFT = 1.0
 R_MAX = 8.0e3      # synth's worlds span 1e4
+RADIUS = 600.0     # neighbours: a few inside it in the middle of a world, none at its rim
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -53,7 +57,7 @@ def uniform():
 
 
 def ragged():
-    sizes, mass_lens = [100, 600, 2000], [50, 300, 1000]
+    sizes, mass_lens = [100, 600, 2000, 130], [50, 300, 1000, 130]          # the last member: no massless particle
     s = nb.SimBatch.ragged(sizes, mass_lens)
     s.set_data([world(n, m) for n, m in zip(sizes, mass_lens)])
     s.update(2, DT)
@@ -66,7 +70,7 @@ def points(n):
 
 
 def round_calls(n_points, map_size, bins):
-    """the ten calls of a round, in order: (name, call on an object)"""
+    """the twelve calls of a round, in order: (name, call on an object)"""
     pts, v, edges = points(n_points), view(*map_size), nb.profile_edges(0.0, R_MAX, bins)
     return [
         ("energy", lambda s: s.energy()),
@@ -79,6 +83,8 @@ def round_calls(n_points, map_size, bins):
         ("potential_map", lambda s: s.potential_map(v, SOFT)),
         ("tidal_at", lambda s: s.tidal_at(pts, SOFT)),
         ("acceleration_map", lambda s: s.acceleration_map(v, SOFT)),
+        ("neighbours", lambda s: s.neighbours(RADIUS)),
+        ("neighbours_massless", lambda s: s.neighbours(None, "massless", "massive")),
     ]
 
 

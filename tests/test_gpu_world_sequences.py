@@ -13,6 +13,7 @@ import nbody_amd as nb
 import sequence_driver as sd
 import world_sequence as ws
 from gpu_common import synth
+from reads_common import assert_the_reads_have_something_to_say, factories
 from test_gpu_ragged import MASS as RAGGED_MASS, SIZES as RAGGED_SIZES, world as ragged_world
 from test_gpu_sequences import views
 
@@ -104,6 +105,52 @@ def test_a_long_lived_world_batch_is_a_chain_of_fresh_ones(row, seed):
 
 @pytest.mark.parametrize("seed", ws.SEEDS["ragged"])
 def test_a_long_lived_ragged_world_batch_is_a_chain_of_fresh_ones(seed):
-    """The ensemble of tests/test_gpu_ragged.py; only the calls include/nbody_batch_ragged.h lists."""
+    """The ensemble of tests/test_gpu_ragged.py; steps, traced steps, energy, potential and the read-backs of the calls
+    include/nbody_batch_ragged.h lists ("ragged-reads" below draws the rest)."""
     ops = ws.generate("ragged", seed, members=len(RAGGED_SIZES))
     assert run("world-batch ragged", ragged_env(), ops, seed) > len(ops) // 2
+
+
+# ---- the reads kinds: tidal calls under the path rule; profile, pair_counts and neighbours bit for bit on either side -----------
+
+_reads = {}
+
+
+def as_reads(kind, env, worlds):
+    """the same start state, makers and seam object under a reads kind, with the arguments of tests/reads_common.py"""
+    if (kind, id(env)) not in _reads:
+        assert_the_reads_have_something_to_say(worlds)
+        f = factories(env.members, env.view)
+        _reads[(kind, id(env))] = ws.Env(kind, env.start, env.make, env.device, f["view"], f["points"], members=env.members, edges=f["edges"],
+                                         centre=f["centre"], radius=f["radius"])
+    return _reads[(kind, id(env))]
+
+
+def massive(part):
+    return int(np.count_nonzero(part[:, 6] > 0))
+
+
+@pytest.mark.parametrize("seed", ws.SEEDS["world-reads"])
+@pytest.mark.parametrize("row", list(ws.WORLD_ROWS))
+def test_a_long_lived_world_with_every_read_only_call_is_a_chain_of_fresh_ones(row, seed):
+    """tidal_at and tidal_map answered by the side the rule names; profile, pair_counts and neighbours equal to the fresh World's
+    and to the seam object's, whichever side answered"""
+    env = world_env(*ws.WORLD_ROWS[row])
+    ops = ws.generate("world-reads", seed)
+    assert run(f"world-reads {row}", as_reads("world-reads", env, [(env.start, massive(env.start))]), ops, seed) > len(ops) // 2
+
+
+@pytest.mark.parametrize("seed", ws.SEEDS["batch-reads"])
+@pytest.mark.parametrize("row", list(ws.BATCH_ROWS))
+def test_a_long_lived_world_batch_with_every_read_only_call_is_a_chain_of_fresh_ones(row, seed):
+    count, n = ws.BATCH_ROWS[row]
+    env = batch_env(count, n)
+    ops = ws.generate("batch-reads", seed, members=count)
+    assert run(f"world-batch-reads {row}", as_reads("batch-reads", env, [(p, massive(p)) for p in env.start]), ops, seed) > len(ops) // 2
+
+
+@pytest.mark.parametrize("seed", ws.SEEDS["ragged-reads"])
+def test_a_long_lived_ragged_world_batch_with_every_read_only_call_is_a_chain_of_fresh_ones(seed):
+    env = ragged_env()
+    ops = ws.generate("ragged-reads", seed, members=len(RAGGED_SIZES))
+    assert run("world-batch-reads ragged", as_reads("ragged-reads", env, list(zip(env.start, RAGGED_MASS))), ops, seed) > len(ops) // 2

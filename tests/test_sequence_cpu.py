@@ -11,7 +11,17 @@ the whole call and last_leapfrog_info(); FakeBatch puts a list of them behind th
 KINDS WERE CHOSEN (sequence_driver.SEEDS): among the seeds from 0 up whose sequence generates (assert_covers holds) and
 passes on the clean stand-in, the first pair in lexicographic order that between them (a) fail every fault of LF_FAULTS that
 the kind can show and (b) issue every operation the kind draws and every drawn form of the adaptive calls
-(sequence_driver.assert_union_covers, at the member counts of the GPU rows) -- test_the_leapfrog_seeds_are_the_first_pair_that_catches_every_fault recomputes it."""
+(sequence_driver.assert_union_covers, at the member counts of the GPU rows) -- test_the_leapfrog_seeds_are_the_first_pair_that_catches_every_fault recomputes it.
+
+The reads kinds ("pipeline-reads", "batch-reads", "ragged-reads"): the stand-in makes tidal_at, tidal_map, profile, pair_counts
+and neighbours (an ensemble: the four Phi / g field calls too) through a model of the one ReadScratch they share (FakeReads): one
+grow-only args array, one grow-only work array and one grow-only host array that KEEP their old contents, every call writing its
+result into work in its own layout by merging -- pair counts and neighbour counts by addition, neighbour keys by minimum
+(tests/paircount_ref.py and tests/neighbour_ref.py give the numbers) -- after resetting what it merges into, and a flag for the
+interval.  READ_FAULTS plants one fault for each way of not doing so.  FakeBatch.ragged makes members of different sizes.  The
+seeds of these kinds are chosen by the same procedure, with READ_FAULTS_OF for (a) and sequence_driver.assert_union_covers_reads
+for (b); a single world is run in two environments, mixed and all massive, and a seed catches a fault if either run does --
+test_the_reads_seeds_are_the_first_pair_that_catches_every_fault recomputes it."""
 import hashlib
 import itertools
 import types
@@ -19,9 +29,12 @@ import types
 import numpy as np
 import pytest
 
+import neighbour_ref as nref
+import paircount_ref as pref
 import sequence_driver as sd
 
 F32 = np.float32
+MASK_OF = {name: mask for mask, name in nref.NAMES.items()}
 N, M = 24, 13
 
 FAULTS = {
@@ -59,11 +72,200 @@ def world(seed):
     return a
 
 
-class FakePipeline:
+class ReadScratch:
+    """nbody_amd/csrc/pipeline_internal.h ReadScratch as what it is: what a call uploads, what its kernels write, where the
+    copied-back bytes land -- all three grow-only, all three KEEPING their old contents -- and whether the interval is valid."""
+
+    def __init__(self):
+        self.args, self.work, self.host = np.zeros(0, F32), np.zeros(0, np.uint8), np.zeros(0, np.uint8)
+        self.uploaded, self.iv = -1, False          # the size of the last upload
+        self.stride = 0                             # entries per member of the last call's layout; 0: packed at the offsets
+
+
+def grown(buf, size):
+    if buf.size >= size:
+        return buf
+    new = np.zeros(size, buf.dtype)
+    new[:buf.size] = buf
+    return new
+
+
+def sample(comp, p, mass, at, soft):
+    """Phi (comp 1), g (2) or the tidal tensor (3) of the sources (p, mass) at the points `at`, crude, float32 (k, comp)"""
+    d = p[None, :, :].astype(np.float64) - at[:, None, :].astype(np.float64)
+    r2 = (d * d).sum(axis=2) + soft
+    if comp == 1:
+        out = -(mass / np.sqrt(r2)).sum(axis=1)[:, None]
+    elif comp == 2:
+        out = (d * (mass / (r2 * np.sqrt(r2)))[:, :, None]).sum(axis=1)
+    else:
+        w3, w5 = mass / r2 ** 1.5, 3 * mass / r2 ** 2.5
+        out = np.stack([(w5 * d[:, :, 0] ** 2 - w3).sum(axis=1), (w5 * d[:, :, 0] * d[:, :, 1]).sum(axis=1),
+                        (w5 * d[:, :, 1] ** 2 - w3).sum(axis=1)], axis=1)
+    return out.astype(F32)
+
+
+def pixels(view):
+    ys, xs = np.mgrid[0:view.height, 0:view.width]
+    return np.stack([(xs.reshape(-1) + 0.5 - view.offset[0]) / view.zoom + view.target[0],
+                     (ys.reshape(-1) + 0.5 - view.offset[1]) / view.zoom + view.target[1]], axis=1).astype(F32)
+
+
+class FakeReads:
+    """The read-only calls that go through one ReadScratch (self.read), for one world or an ensemble.  The owner gives
+    _worlds(call) -> [(pos, vel, mass, mass_len) per member] and _out(arrays per member) -> the caller's shape.  Every call
+    uploads its arguments into `args` and computes from what `args` then HOLDS, writes into `work` in its own layout over
+    whatever is there -- pair counts and neighbour counts by adding, neighbour keys by minimum, after resetting what it merges
+    into -- and the result is what comes back through `host`.  `fault` plants one entry of READ_FAULTS."""
+
+    def _read_call(self, args, work_bytes, back_bytes, enqueue):
+        r, up = self.read, None
+        if args is not None:
+            args = np.ascontiguousarray(args, dtype=F32).ravel()
+            r.args = grown(r.args, args.size)
+            if not (self.fault == 24 and args.size == r.uploaded):
+                r.args[:args.size] = args
+            r.uploaded = args.size
+            up = r.args[:args.size]
+        had = r.work.size
+        r.work = grown(r.work, work_bytes)
+        r.iv = True
+        enqueue(up, r.work)
+        if self.fault == 25 and 0 < had < work_bytes:
+            r.work[had:work_bytes] = 0               # the tail never arrives: what the new buffer held stays
+        r.host = grown(r.host, back_bytes)
+        r.host[:back_bytes] = r.work[:back_bytes]
+        return r.host[:back_bytes].copy()
+
+    def _nothing(self, defaults):
+        """a call with nothing to launch: the defaults, and the interval cleared"""
+        r = self.read
+        if self.fault != 21:
+            r.iv = False
+        if self.fault == 20:
+            r.host = grown(r.host, defaults.size)
+            return r.host[:defaults.size].copy()
+        return defaults
+
+    def last_diag_ms(self):
+        return 1.0 if self.read.iv else 0.0
+
+    def _field(self, call, comp, pts, soft):
+        """pts float32 (members, k, 2) -> float32 (members, k, comp)"""
+        worlds = self._worlds(call)
+        count, k = pts.shape[:2]
+        nbytes = count * k * comp * 4
+        self.read.stride = k
+        if k == 0:
+            return self._nothing(np.zeros(0, np.uint8)).view(F32).reshape(count, 0, comp)
+
+        def enqueue(up, work):
+            at, out = up.reshape(count, k, 2), work[:nbytes].view(F32).reshape(count, k, comp)
+            for b, (pos, _, mass, m) in enumerate(worlds):
+                out[b] = sample(comp, pos[:m], mass[:m], at[b], soft)
+        return self._read_call(pts, nbytes, nbytes, enqueue).view(F32).reshape(count, k, comp)
+
+    def _profile(self, edges, centres, weights):
+        """centres float32 (members, 4) -> (float64 (members, bins + 2, 6), uint32 (members,))"""
+        worlds = self._worlds("profile")
+        e = np.asarray(edges, dtype=F32)
+        count, rows = len(worlds), e.size + 1
+        self.read.stride = rows
+        table_bytes = count * rows * 6 * 8
+        nbytes = table_bytes + 4 * count
+
+        def enqueue(up, work):
+            edge, c = up[:e.size].astype(np.float64), up[e.size:].reshape(count, 4).astype(np.float64)
+            table, lost = work[:table_bytes].view(np.float64).reshape(count, rows, 6), work[table_bytes:nbytes].view(np.uint32)
+            for b, (pos, vel, mass, m) in enumerate(worlds):
+                top = m if weights == "mass" else pos.shape[0]
+                w = mass[:top].astype(np.float64) if weights == "mass" else np.ones(top)
+                d, u = pos[:top] - c[b, 0:2], vel[:top] - c[b, 2:4]
+                r2 = (d * d).sum(axis=1)
+                row = np.searchsorted(edge, np.sqrt(r2), side="right")
+                table[b], lost[b] = 0.0, 0
+                for col, v in enumerate((np.ones(top), w, w * r2, w * (d[:, 0] * u[:, 1] - d[:, 1] * u[:, 0]), w * (d * u).sum(axis=1),
+                                         0.5 * w * (u * u).sum(axis=1))):
+                    np.add.at(table[b, :, col], row, v)
+        back = self._read_call(np.concatenate([e, np.asarray(centres, dtype=F32).ravel()]), nbytes, nbytes, enqueue)
+        return back[:table_bytes].view(np.float64).reshape(count, rows, 6), back[table_bytes:].view(np.uint32)
+
+    def _pair_counts(self, edges, classes):
+        """-> (uint64 (members, bins + 2, 3), uint64 (members, 3)): tests/paircount_ref.py's model, ADDED into the table"""
+        worlds = self._worlds("pair_counts")
+        e = np.asarray(edges, dtype=F32)
+        count, rows = len(worlds), e.size + 1
+        mask = sum({"mm": pref.MM, "mt": pref.MT, "tt": pref.TT, "all": pref.ALL}[c] for c in ((classes,) if isinstance(classes, str) else classes))
+        self.read.stride = rows
+        table_bytes = count * rows * 3 * 8
+        nbytes = table_bytes + count * 3 * 8
+
+        def enqueue(up, work):
+            table = work[:nbytes].view(np.uint64)
+            if self.fault != 19:
+                table[:] = 0
+            out, lost = table[:count * rows * 3].reshape(count, rows, 3), table[count * rows * 3:].reshape(count, 3)
+            for b, (pos, _, _, m) in enumerate(worlds):
+                part = np.zeros((pos.shape[0], 8), F32)
+                part[:, 0:2] = pos
+                o, unplaced = pref.model(part, m, e, mask)
+                out[b] += o
+                lost[b] += unplaced
+        back = self._read_call(None, nbytes, nbytes, enqueue).view(np.uint64)
+        return back[:count * rows * 3].reshape(count, rows, 3), back[count * rows * 3:].reshape(count, 3)
+
+    def _neighbours(self, radius, receivers, sources):
+        """-> per member (q, index[, count]): tests/neighbour_ref.py's model, keys merged by minimum and counts by addition"""
+        worlds = self._worlds("neighbours")
+        sizes = [pos.shape[0] for pos, _, _, _ in worlds]
+        true = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        # the packed layout: member b at its offset -- or, the planted fault, at the uniform stride the last call left behind
+        stride = self.read.stride if self.fault == 26 and getattr(self, "is_ragged", False) else 0
+        self.read.stride = 0
+        at = [b * stride for b in range(len(sizes))] if stride else list(true[:-1])
+        entries = max(int(true[-1]), at[-1] + sizes[-1])
+        r, s = MASK_OF[receivers], MASK_OF[sources]
+        counted = radius is not None
+        back_bytes = entries * (12 if counted else 8)
+
+        def spans(n, m):
+            (r0, r1), (s0, s1) = nref.span(r, n, m), nref.span(s, n, m)
+            return r1 > r0 and s1 > s0
+
+        def enqueue(up, work):
+            keys, counts = work[:entries * 8].view(np.uint64), work[entries * 8:entries * 12].view(np.uint32)
+            if self.fault != 17:
+                keys[:] = nref.KEY_NONE
+            if counted and self.fault != 18:
+                counts[:] = 0
+            for b, (pos, _, _, m) in enumerate(worlds):
+                part = np.zeros((sizes[b], 8), F32)
+                part[:, 0:2] = pos
+                q, index, cnt = nref.model(part, m, r, s, radius)
+                key = np.where(index == nref.NONE, nref.KEY_NONE, (q.view(np.uint32).astype(np.uint64) << np.uint64(32)) | index.astype(np.uint64))
+                sl = slice(at[b], at[b] + sizes[b])
+                keys[sl] = np.minimum(keys[sl], key)
+                if counted:
+                    counts[sl] += cnt
+        if any(spans(n, w[3]) for n, w in zip(sizes, worlds)):
+            back = self._read_call(None, entries * 12, back_bytes, enqueue)
+        else:
+            defaults = np.zeros(back_bytes, np.uint8)
+            defaults[:entries * 8] = 0xff
+            back = self._nothing(defaults)
+        keys = back[:entries * 8].view(np.uint64)
+        index = (keys & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        q = np.where(index == nref.NONE, np.uint64(nref.INF_BITS), keys >> np.uint64(32)).astype(np.uint32).view(F32)
+        out = (q, index, back[entries * 8:].view(np.uint32)) if counted else (q, index)
+        return [tuple(a[true[b]:true[b + 1]].copy() for a in out) for b in range(len(sizes))]
+
+
+class FakePipeline(FakeReads):
     """float32 Euler steps with the method names of nb.SimPipeline; `fault` plants one entry of FAULTS."""
 
     def __init__(self, n, m, fault=0):
         self.n, self.m, self.fault = n, m, fault
+        self.read = ReadScratch()
         self.pos = [np.zeros((n, 2), F32), np.zeros((n, 2), F32)]
         self.cur = 0
         self.vel, self.acc = np.zeros((n, 2), F32), np.zeros((n, 2), F32)
@@ -298,10 +500,12 @@ class FakePipeline:
 
     def energy(self):
         p = self._latest().astype(np.float64)
+        self.read.iv = True
         self.phi, self.phi_fresh = self._phi(p, p, 1.0).astype(F32), True
         mass, v = self.mass.astype(np.float64), self.vel.astype(np.float64)
         mom = (mass[:, None] * v).sum(axis=0)
-        com = (mass[:, None] * p).sum(axis=0) / mass.sum()
+        with np.errstate(invalid="ignore"):          # a world of massless particles: 0 / 0, the same NaN every time
+            com = (mass[:, None] * p).sum(axis=0) / mass.sum()
         return {"kinetic": float(0.5 * (mass * (v * v).sum(axis=1)).sum()), "potential": float(0.5 * (mass * self.phi).sum()),
                 "mass": float(mass.sum()), "momentum": (float(mom[0]), float(mom[1])),
                 "angular_momentum": float((mass * (p[:, 0] * v[:, 1] - p[:, 1] * v[:, 0])).sum()),
@@ -309,6 +513,7 @@ class FakePipeline:
 
     def potential(self):
         p = self._latest().astype(np.float64)
+        self.read.iv = True
         if not (self.fault == 7 and self.phi_fresh):
             self.phi = self._phi(p, p, 1.0).astype(F32)
         self.phi_fresh = False
@@ -316,6 +521,9 @@ class FakePipeline:
 
     def _into_scratch(self, values):
         """the result travels through the scratch buffer, which grows when a call needs more"""
+        if values.size == 0:                                 # no probe: nothing to launch
+            return self._nothing(np.zeros(0, np.uint8)).view(F32)
+        self.read.iv = True
         had = self.scratch.size
         if had < values.size:
             self.scratch = np.zeros(values.size, F32)
@@ -363,13 +571,49 @@ class FakePipeline:
         c = self.render_counts(view)
         return np.minimum(c.transpose(1, 2, 0) * 80, 255).astype(np.uint8)
 
+    # -- the calls of FakeReads, for one world ---------------------------------------------------------------------------
+    def _state(self, call):
+        """(pos, vel, mass, mass_len) as a call of FakeReads finds them"""
+        if not (self.fault == 22 and call.startswith("tidal")):
+            self._flush()
+        pos = self.pos[self.cur ^ 1] if self.fault == 23 and call == "pair_counts" else self.pos[self.cur]
+        return pos, self.vel, self.mass, self.m
 
-class FakeBatch:
+    def _worlds(self, call):
+        return [self._state(call)]
+
+    def tidal_at(self, points, soft):
+        return self._field("tidal_at", 3, np.asarray(points, dtype=F32)[None], soft)[0]
+
+    def tidal_map(self, view, soft):
+        return self._field("tidal_map", 3, pixels(view)[None], soft)[0].reshape(view.height, view.width, 3)
+
+    def profile(self, edges, centre, centre_velocity, weights, return_unplaced):
+        out, lost = self._profile(edges, np.concatenate([centre, centre_velocity])[None], weights)
+        return out[0], int(lost[0])
+
+    def pair_counts(self, edges, classes, return_unplaced):
+        out, lost = self._pair_counts(edges, classes)
+        return out[0], lost[0]
+
+    def neighbours(self, radius, receivers, sources):
+        return self._neighbours(radius, receivers, sources)[0]
+
+
+class FakeBatch(FakeReads):
     """A list of FakePipeline members behind the method names of nb.SimBatch that the driver calls; step sizes one for all
     or one per member; trace records energy() rows."""
 
     def __init__(self, count, n, m, fault=0):
-        self.members, self.fault = [FakePipeline(n, m, fault) for _ in range(count)], fault
+        self.members, self.fault, self.is_ragged = [FakePipeline(n, m, fault) for _ in range(count)], fault, False
+        self.read = ReadScratch()          # the ensemble's own: its reads are one launch for all members
+
+    @classmethod
+    def ragged(cls, sizes, mass_lens, fault=0):
+        """members of different sizes (nb.SimBatch.ragged): lists of per-member arrays where a uniform ensemble stacks"""
+        self = cls(0, 0, 0, fault)
+        self.members, self.is_ragged = [FakePipeline(n, m, fault) for n, m in zip(sizes, mass_lens)], True
+        return self
 
     def close(self):
         pass
@@ -377,12 +621,61 @@ class FakeBatch:
     def _dts(self, dt):
         return [float(dt)] * len(self.members) if np.ndim(dt) == 0 else [float(x) for x in dt]
 
+    def _out(self, per_member):
+        return list(per_member) if self.is_ragged else np.stack(per_member)
+
     def set_data(self, a):
         for s, part in zip(self.members, a):
             s.set_data(part)
 
     def get_data(self):
-        return np.stack([s.get_data() for s in self.members])
+        return self._out([s.get_data() for s in self.members])
+
+    # -- the calls of FakeReads, one launch for all members -------------------------------------------------------------------
+    def _worlds(self, call):
+        return [s._state(call) for s in self.members]
+
+    def _points(self, points):
+        a = np.asarray(points, dtype=F32)
+        return np.ascontiguousarray(np.broadcast_to(a, (len(self.members),) + a.shape) if a.ndim == 2 else a)
+
+    def _pixels(self, views):
+        views = views if isinstance(views, list) else [views] * len(self.members)
+        return np.stack([pixels(v) for v in views]), views[0].height, views[0].width
+
+    def potential_at(self, points, soft):
+        return self._field("potential_at", 1, self._points(points), soft)[:, :, 0]
+
+    def acceleration_at(self, points, soft):
+        return self._field("acceleration_at", 2, self._points(points), soft)
+
+    def tidal_at(self, points, soft):
+        return self._field("tidal_at", 3, self._points(points), soft)
+
+    def _map(self, call, comp, views, soft):
+        pts, h, w = self._pixels(views)
+        out = self._field(call, comp, pts, soft)
+        return out.reshape((len(self.members), h, w) + ((comp,) if comp > 1 else ()))
+
+    def potential_map(self, views, soft):
+        return self._map("potential_map", 1, views, soft)
+
+    def acceleration_map(self, views, soft):
+        return self._map("acceleration_map", 2, views, soft)
+
+    def tidal_map(self, views, soft):
+        return self._map("tidal_map", 3, views, soft)
+
+    def profile(self, edges, centre, centre_velocity, weights, return_unplaced):
+        both = np.empty((len(self.members), 4), F32)
+        both[:, 0:2], both[:, 2:4] = centre, centre_velocity
+        return self._profile(edges, both, weights)
+
+    def pair_counts(self, edges, classes, return_unplaced):
+        return self._pair_counts(edges, classes)
+
+    def neighbours(self, radius, receivers, sources):
+        return tuple(self._out(list(arrays)) for arrays in zip(*self._neighbours(radius, receivers, sources)))
 
     def get_member(self, b):
         return self.members[b].get_data()
@@ -421,10 +714,12 @@ class FakeBatch:
         return np.array(rows)
 
     def energy(self):
+        self.read.iv = True
         return [s.energy() for s in self.members]
 
     def potential(self):
-        return np.stack([s.potential() for s in self.members])
+        self.read.iv = True
+        return self._out([s.potential() for s in self.members])
 
     def bounds(self):
         return np.stack([s.bounds() for s in self.members])
@@ -669,3 +964,258 @@ def test_the_sequences_of_the_old_kinds_have_not_moved(kind, members, seed):
     ops = sd.generate(kind, seed, members=members)
     assert hashlib.sha256(repr(ops).encode()).hexdigest() == OLD_SEQUENCES[(kind, members, seed)]
     assert not any(sd.is_leapfrog(op) or op[0] in sd.LEAPFROG for op in ops)
+
+
+# ---- the reads kinds ------------------------------------------------------------------------------------------------------------
+
+READ_FAULTS = {
+    17: "neighbours does not reset the keys it takes minima into",
+    18: "neighbours with a radius does not zero the counts it adds into",
+    19: "pair_counts does not zero the table it adds into",
+    20: "a call with nothing to launch returns what the host vector already held instead of the defaults",
+    21: "a call with nothing to launch leaves the interval valid",
+    22: "tidal_at / tidal_map do not wait for queued async work",
+    23: "pair_counts reads pos[cur ^ 1]",
+    24: "an argument upload of the same size as the previous one is skipped: stale centres or probes",
+    25: "a regrown work buffer returns the old, shorter contents for the tail of the call that grew it",
+    26: "a member of a ragged ensemble is addressed with the uniform stride b * n the last call's layout left behind, not its offset",
+}
+# 20 shows only where a call that returns something has nothing to launch: neighbours in a world without a massless particle.
+# The ensembles of the GPU rows have massless particles in some member, and so have these; 26 needs members of other sizes.
+READ_FAULTS_OF = {"pipeline-reads": (17, 18, 19, 20, 21, 22, 23, 24, 25), "batch-reads": (17, 18, 19, 21, 22, 23, 24, 25),
+                  "ragged-reads": (17, 18, 19, 21, 22, 23, 24, 25, 26)}
+READS_MEMBERS = {"pipeline-reads": (0,), "batch-reads": (3, 5), "ragged-reads": (12,)}          # the member counts of the GPU rows
+RAGGED_SIZES, RAGGED_MASS = [24, 1, 7, 13, 30, 9, 16, 2, 11, 5, 19, 3], [13, 1, 0, 13, 20, 1, 9, 1, 6, 2, 19, 2]
+
+
+def world_of(n, m, seed):
+    rng = np.random.default_rng([seed, n])
+    a = np.zeros((n, 8), dtype=F32)
+    a[:, 0:2] = rng.standard_normal((n, 2)) * 50
+    a[:, 2:4] = rng.standard_normal((n, 2))
+    a[:m, 7] = 1.5 + 3 * rng.random(m)
+    a[m:, 7] = 0.5
+    a[:m, 6] = 40 * a[:m, 7] ** 3
+    return a
+
+
+_probe_sets = np.random.default_rng(6).standard_normal((2, len(RAGGED_SIZES), max(sd.POINT_COUNTS), 2)).astype(F32) * 60
+
+
+def read_points(members):
+    def points(count, which=0, per_member=False):
+        return _probe_sets[which][:members, :count] if per_member else _probe_sets[which][0, :count]
+    return points
+
+
+def read_view(w, h, b=None):
+    v = view(w, h)
+    if b is not None:
+        v.target = (7.0 * b, -4.0 * b)
+    return v
+
+
+def read_edges(bins):
+    return np.linspace(5.0, 150.0, bins + 1).astype(F32)
+
+
+_CENTRES = (((3.0, -4.0), (0.5, -0.25)), ((-10.0, 6.0), (-1.0, 2.0)))
+
+
+def read_centre(members):
+    def centre(which, per_member=False):
+        c, u = (np.array(x, dtype=F32) for x in _CENTRES[which])
+        if not per_member:
+            return c, u
+        shift = np.arange(members, dtype=F32)[:, None]
+        return c + 2 * shift, u - 0.125 * shift
+    return centre
+
+
+def reads_env(kind, start, other, members=0):
+    return sd.Env(kind, start, other, read_view, read_points(members), members=members, edges=read_edges, centre=read_centre(members),
+                  radius=30.0)
+
+
+def reads_cases(kind, members):
+    """[(environment, maker of the stand-in with a fault)] of a kind at a member count.  A single world runs twice: mixed, and --
+    the classic row of the MI355X -- with every particle massive, where neighbours under EMPTY_MASKS has nothing to launch."""
+    if kind == "pipeline-reads":
+        return [(reads_env(kind, world(1), world(2)), lambda fault: (lambda: FakePipeline(N, M, fault))),
+                (reads_env(kind, world_of(N, N, 3), world_of(N, N, 4)), lambda fault: (lambda: FakePipeline(N, N, fault)))]
+    if kind == "batch-reads":
+        env = reads_env(kind, np.stack([world(10 + b) for b in range(members)]), np.stack([world(20 + b) for b in range(members)]), members)
+        return [(env, lambda fault: (lambda: FakeBatch(members, N, M, fault)))]
+    sizes, masses = RAGGED_SIZES[:members], RAGGED_MASS[:members]
+    env = reads_env(kind, [world_of(n, m, 30 + b) for b, (n, m) in enumerate(zip(sizes, masses))],
+                    [world_of(n, m, 50 + b) for b, (n, m) in enumerate(zip(sizes, masses))], members)
+    return [(env, lambda fault: (lambda: FakeBatch.ragged(sizes, masses, fault)))]
+
+
+def reads_first_touch(fault, ops):
+    """index of the first operation a fault of READ_FAULTS could change the output of"""
+    def first(pred):
+        return next(i for i, (n, a) in enumerate(ops) if pred(n, a))
+    if fault in (17, 26):
+        return first(lambda n, a: n == "neighbours")
+    if fault == 18:
+        return first(lambda n, a: n == "neighbours" and a["radius"])
+    if fault in (19, 23):
+        return first(lambda n, a: n == "pair_counts")
+    if fault in (20, 21):
+        return first(lambda n, a: n == "neighbours" or a.get("count") == 0)
+    if fault == 22:
+        return first(lambda n, a: n in sd.ASYNC)
+    if fault == 24:
+        return first(lambda n, a: n in sd.AT_CALLS + sd.MAP_CALLS + ("profile",))
+    return first(lambda n, a: n in sd.DIAG_READS)
+
+
+_reads_runs = {}
+
+
+def reads_caught(kind, seed, fault, members):
+    """None: the sequence passes in every environment of the kind; else the first SequenceMismatch.  Remembered: the seed
+    search asks for every (seed, fault) once more."""
+    key = (kind, seed, fault, members)
+    if key not in _reads_runs:
+        ops = sd.generate(kind, seed, members=members)
+        _reads_runs[key] = None
+        for env, maker in reads_cases(kind, members):
+            try:
+                sd.check(maker(fault), ops, env, seed)
+            except sd.SequenceMismatch as e:
+                _reads_runs[key] = e
+                break
+    return _reads_runs[key]
+
+
+READS_ROWS = [(k, m) for k in sorted(READS_MEMBERS) for m in READS_MEMBERS[k]]
+
+
+@pytest.mark.parametrize("kind,members", READS_ROWS)
+def test_without_a_fault_every_committed_reads_seed_passes(kind, members):
+    for seed in sd.SEEDS[kind]:
+        ops = sd.generate(kind, seed, members=members)
+        for env, maker in reads_cases(kind, members):
+            assert sd.check(maker(0), ops, env, seed) > len(ops) // 2
+
+
+@pytest.mark.parametrize("kind,fault", [(k, f) for k in sorted(READ_FAULTS_OF) for f in READ_FAULTS_OF[k]])
+def test_every_planted_reads_fault_is_caught_by_a_committed_seed(kind, fault):
+    members = READS_MEMBERS[kind][0]
+    caught = []
+    for seed in sd.SEEDS[kind]:
+        e = reads_caught(kind, seed, fault, members)
+        if e is not None:
+            ops = sd.generate(kind, seed, members=members)
+            assert e.seed == seed and e.index >= reads_first_touch(fault, ops), (READ_FAULTS[fault], e.index, reads_first_touch(fault, ops))
+            assert e.name == (ops[e.index][0] if e.index < len(ops) else "final state")
+            assert f"seed {seed}" in str(e) and sd.show(ops[0]) in str(e)
+            caught.append(seed)
+    assert caught, f"no committed seed of {kind} notices: {READ_FAULTS[fault]}"
+
+
+def test_a_fault_a_kind_cannot_show_is_not_claimed():
+    """20 on an ensemble with a massless particle somewhere, 26 on members of one size: the committed seeds pass, which is why
+    READ_FAULTS_OF leaves them out"""
+    for kind, fault in (("batch-reads", 20), ("batch-reads", 26), ("ragged-reads", 20), ("pipeline-reads", 26)):
+        assert all(reads_caught(kind, seed, fault, READS_MEMBERS[kind][0]) is None for seed in sd.SEEDS[kind]), (kind, fault)
+
+
+@pytest.mark.parametrize("kind", sorted(READ_FAULTS_OF))
+def test_the_reads_seeds_are_the_first_pair_that_catches_every_fault(kind):
+    """The rule of the module docstring for the reads kinds, recomputed; candidates that do not generate or do not pass clean
+    are left out."""
+    members = READS_MEMBERS[kind][0]
+    catches = {}
+    for seed in range(max(sd.SEEDS[kind]) + 1):
+        try:
+            if reads_caught(kind, seed, 0, members) is None:
+                catches[seed] = {f for f in READ_FAULTS_OF[kind] if reads_caught(kind, seed, f, members) is not None}
+        except AssertionError:
+            continue          # assert_covers: this seed names no sequence
+
+    def good(pair):
+        if catches[pair[0]] | catches[pair[1]] != set(READ_FAULTS_OF[kind]):
+            return False
+        try:
+            for count in READS_MEMBERS[kind]:
+                sd.assert_union_covers_reads(kind, [sd.generate(kind, seed, members=count) for seed in pair])
+        except AssertionError:
+            return False
+        return True
+    pairs = (p for p in itertools.combinations(sorted(catches), 2) if good(p))
+    assert next(pairs) == tuple(sd.SEEDS[kind]), {s: sorted(c) for s, c in catches.items()}
+
+
+@pytest.mark.parametrize("kind,members", READS_ROWS)
+def test_the_committed_reads_sequences_issue_every_operation_between_them(kind, members):
+    sd.assert_union_covers_reads(kind, [sd.generate(kind, seed, members=members) for seed in sd.SEEDS[kind]])
+
+
+@pytest.mark.parametrize("kind,members", READS_ROWS)
+def test_committed_reads_sequences_hold_what_they_must(kind, members):
+    for seed in sd.SEEDS[kind]:
+        ops = sd.generate(kind, seed, members=members)
+        sd.assert_covers(kind, ops)
+        assert sd.READS_LENGTH <= len(ops) <= sd.READS_LENGTH + 4
+        assert ops == sd.generate(kind, seed, members=members)          # a seed names one sequence
+        names = {name for name, _ in ops}
+        if kind == "ragged-reads":
+            assert names <= sd.RAGGED_READS_ALLOWED and not names & {"bounds", "render", "render_counts", "update_adaptive", "timestep"}
+
+
+def _without(ops, drop):
+    """the list without the operations at which drop(i) holds"""
+    return [op for i, op in enumerate(ops) if not drop(i)]
+
+
+def test_the_generator_notices_a_dropped_reads_piece():
+    ops = sd.generate("pipeline-reads", sd.SEEDS["pipeline-reads"][0])
+    names = [name for name, _ in ops]
+
+    def behind(first, family):
+        return lambda i: i and names[i - 1] in first and sd.FAMILY.get(names[i]) == family
+    for family in ("tidal", "profile", "pair_counts", "neighbours"):
+        with pytest.raises(AssertionError, match=f"no {family} call directly behind step_async"):
+            sd.assert_covers("pipeline-reads", _without(ops, behind(("step_async",), family)))
+    with pytest.raises(AssertionError, match="update_adaptive_async"):
+        sd.assert_covers("pipeline-reads", _without(ops, lambda i: i and names[i - 1] == "update_adaptive_async" and names[i] in sd.NEW_READS))
+
+    def large(calls):          # the large call between the two small ones
+        return lambda i: 0 < i < len(ops) - 1 and names[i] in calls and names[i - 1] == names[i] and ops[i - 1] == ops[i + 1]
+    with pytest.raises(AssertionError, match="field call small, large"):
+        sd.assert_covers("pipeline-reads", _without(ops, large(sd.AT_CALLS + sd.MAP_CALLS)))
+    with pytest.raises(AssertionError, match="profile small, large"):
+        sd.assert_covers("pipeline-reads", _without(ops, large(("profile",))))
+    with pytest.raises(AssertionError, match=r"neighbours\(None\)"):
+        sd.assert_covers("pipeline-reads", _without(ops, lambda i: 0 < i < len(ops) - 1 and names[i - 1] == names[i] == "neighbours" and
+                                                    not ops[i][1]["radius"] and names[i + 1] == "pair_counts"))
+    with pytest.raises(AssertionError, match="two pair_counts in a row"):
+        sd.assert_covers("pipeline-reads", _without(ops, lambda i: i and names[i] == names[i - 1] == "pair_counts"))
+    with pytest.raises(AssertionError, match="odd number of steps"):
+        sd.assert_covers("pipeline-reads", _without(ops, lambda i: 0 < i < len(ops) - 1 and ops[i - 1] == ops[i + 1] and names[i] in sd.STEPPING))
+    with pytest.raises(AssertionError, match="set_data"):
+        sd.assert_covers("pipeline-reads", _without(ops, lambda i: names[i] == "set_data"))
+    with pytest.raises(AssertionError, match="empty probe set"):
+        sd.assert_covers("pipeline-reads", _without(ops, lambda i: ops[i][1].get("count") == 0))
+    with pytest.raises(AssertionError, match="EMPTY_MASKS"):
+        sd.assert_covers("pipeline-reads", _without(ops, lambda i: names[i] == "neighbours" and
+                                                    (ops[i][1]["receivers"], ops[i][1]["sources"]) == sd.EMPTY_MASKS))
+    ragged = sd.generate("ragged-reads", sd.SEEDS["ragged-reads"][0], members=12)
+    with pytest.raises(AssertionError):
+        sd.assert_covers("ragged-reads", ragged + [("bounds", {})])
+    with pytest.raises(AssertionError, match="aborts on a ragged ensemble"):
+        sd.apply(None, ("render", {"w": 32, "h": 18}), sd.Env("ragged-reads", None, None, None, None, members=12))
+
+
+def test_the_interval_is_part_of_the_verdict():
+    """a reads kind appends last_diag_ms() > 0 to the output of every call of DIAG_READS; an old kind does not"""
+    env = reads_cases("pipeline-reads", 0)[0][0]
+    s = FakePipeline(N, M)
+    s.set_data(env.start)
+    launched = sd.apply(s, ("tidal_at", {"count": 1, "which": 0}), env)
+    assert len(launched) == 3 * 4 + 1 and launched[-1:] == b"\1"
+    assert sd.apply(s, ("potential_at", {"count": 0, "which": 0}), env) == b"\0"
+    assert len(sd.apply(s, ("potential_at", {"count": 1}), ENV)) == 4

@@ -13,7 +13,12 @@
 HOW THE SEEDS WERE CHOSEN (world_sequence.SEEDS): among the seeds from 0 up whose sequence generates and passes on the clean
 stand-in, the first pair in lexicographic order that between them (a) fail every fault the kind can show and (b) issue every
 operation the kind draws and every drawn form of the adaptive calls (world_sequence.assert_union_covers, at the member counts
-the GPU rows run with); test_the_seeds_are_the_first_pair_that_catches_every_fault recomputes that choice."""
+the GPU rows run with); test_the_seeds_are_the_first_pair_that_catches_every_fault recomputes that choice.
+
+The reads kinds: against the real library the CPU-only run also drives the host paths of tidal_at, tidal_map, profile, pair_counts
+and neighbours in long sequences; the stand-in answers the tidal calls in its two arithmetics and the three exact calls the same on
+either side (tests/paircount_ref.py, tests/neighbour_ref.py), and has two more faults: a new read answered by the side that is not
+the newest (11), and a new read that flips device_is_newer (12)."""
 import itertools
 import types
 
@@ -21,10 +26,14 @@ import numpy as np
 import pytest
 
 import nbody_amd as nb
+import neighbour_ref as nref
+import paircount_ref as pref
+import reads_common
 import sequence_driver as sd
 import world_sequence as ws
 from gpu_common import synth
 from test_leapfrog_cpu import child
+from test_sequence_cpu import MASK_OF, read_centre, read_edges, read_points, read_view, sample
 
 F32, F64 = np.float32, np.float64
 SKEW = F32(1 + 2.0 ** -10)          # what tells the device's arithmetic from the host's
@@ -40,9 +49,12 @@ FAULTS = {
     8: "an n = 0 GPU call marks the device newer",
     9: "a traced batch update of n > 0 does not mark the device newer",
     10: "a member() read does not refresh the array",
+    11: "tidal_at, tidal_map, profile, pair_counts or neighbours answers from the side that is not the newest",
+    12: "tidal_at, tidal_map, profile, pair_counts or neighbours flips device_is_newer",
 }
 # a WorldBatch uploads once in its life (nothing on the host changes the array), so fault 3 has no meaning for it
-FAULTS_OF = {"world": (1, 2, 3, 4, 5, 6, 7, 8), "batch": (8, 9, 10), "ragged": (8, 9, 10)}
+FAULTS_OF = {"world": (1, 2, 3, 4, 5, 6, 7, 8), "batch": (8, 9, 10), "ragged": (8, 9, 10),
+             "world-reads": (1, 2, 3, 4, 5, 6, 7, 8, 11, 12), "batch-reads": (8, 9, 10, 11, 12), "ragged-reads": (8, 9, 10, 11, 12)}
 
 
 # ---- the physics of the stand-in: float32, one force for the host and a skewed one for the device -------------------------------
@@ -159,7 +171,33 @@ class Reader:
     def acceleration_map(self, view, soft):
         return self.acceleration_at(self._pixels(view), soft).reshape(view.height, view.width, 2)
 
+    def tidal_at(self, points, soft):
+        return self._out(sample(3, self.a[:self.m, 0:2], self.a[:self.m, 6], np.asarray(points, F32), soft))
+
+    def tidal_map(self, view, soft):
+        return self.tidal_at(self._pixels(view), soft).reshape(view.height, view.width, 3)
+
     # bitwise the same on both paths
+    def profile(self, edges, centre, centre_velocity, weights, return_unplaced=False):
+        top = self.m if weights == "mass" else self.a.shape[0]
+        a = self.a[:top].astype(F64)
+        w = a[:, 6] if weights == "mass" else np.ones(top)
+        d, u = a[:, 0:2] - np.asarray(centre, F64), a[:, 2:4] - np.asarray(centre_velocity, F64)
+        r2 = (d * d).sum(axis=1)
+        out = np.zeros((len(edges) + 1, 6))
+        row = np.searchsorted(np.asarray(edges, F64), np.sqrt(r2), side="right")
+        for col, v in enumerate((np.ones(top), w, w * r2, w * (d[:, 0] * u[:, 1] - d[:, 1] * u[:, 0]), w * (d * u).sum(axis=1),
+                                 0.5 * w * (u * u).sum(axis=1))):
+            np.add.at(out[:, col], row, v)
+        return out, 0
+
+    def pair_counts(self, edges, classes=("mm",), return_unplaced=False):
+        mask = sum({"mm": pref.MM, "mt": pref.MT, "tt": pref.TT, "all": pref.ALL}[c] for c in ((classes,) if isinstance(classes, str) else classes))
+        return pref.model(self.a, self.m, edges, mask)
+
+    def neighbours(self, radius=None, receivers="all", sources="all"):
+        return tuple(x for x in nref.model(self.a, self.m, MASK_OF[receivers], MASK_OF[sources], radius) if x is not None)
+
     def timestep(self, eta, dt_max):
         return float(criterion(self.a, eta, dt_max))
 
@@ -219,7 +257,18 @@ class FakeWorld:
                 on_device = True                # the right state, the wrong path
             elif self.fault == 5:
                 a, on_device = self.d, True     # the device's older state
+        if name in sd.NEW_READS:
+            if self.fault == 11:                # the side that is not the newest
+                a, on_device = (self.h if on_device else self.d), not on_device
+            if self.fault == 12:
+                return self._flipping(getattr(Reader(a, on_device), name))
         return getattr(Reader(a, on_device), name)
+
+    def _flipping(self, call):
+        def run(*args, **kw):
+            self.device_is_newer = not self.device_is_newer
+            return call(*args, **kw)
+        return run
 
     # -- CPU steps ---------------------------------------------------------------------------------------------------------
     def _cpu_begin(self):
@@ -303,16 +352,21 @@ class BatchReader:
     def close(self):
         pass
 
-    def _all(self, name, *args):
-        out = [getattr(r, name)(*args) for r in self.readers]
-        return out if self.ragged or name == "energy" else np.stack(out)
+    def _all(self, name, *args, **kw):
+        """one call per member; an argument given per member -- points (B, k, 2), a list of views, centres (B, 2) -- is dealt out"""
+        def of(b, x):
+            if isinstance(x, list):
+                return x[b]
+            return x[b] if isinstance(x, np.ndarray) and x.ndim == (3 if name.endswith("_at") else 2) and name != "pair_counts" else x
+        out = [getattr(r, name)(*(of(b, x) for x in args), **kw) for b, r in enumerate(self.readers)]
+        return out if self.ragged or name == "energy" or isinstance(out[0], tuple) else np.stack(out)
 
     def __getattr__(self, name):
         if name == "fit_views":
             return lambda w, h: self._all("fit_view", w, h)
         if name not in READS:
             raise AttributeError(name)
-        return lambda *args: self._all(name, *args)
+        return lambda *args, **kw: self._all(name, *args, **kw)
 
 
 class FakeWorldBatch:
@@ -342,7 +396,13 @@ class FakeWorldBatch:
     def __getattr__(self, name):
         if name not in READS + ("fit_views",):
             raise AttributeError(name)
-        return getattr(BatchReader(self.d if self.device_is_newer else self.h, self.device_is_newer, self.ragged), name)
+        on_device = self.device_is_newer
+        if name in sd.NEW_READS and self.fault == 11:          # the side that is not the newest
+            on_device = not on_device
+        call = getattr(BatchReader(self.d if on_device else self.h, on_device, self.ragged), name)
+        if name in sd.NEW_READS and self.fault == 12:
+            return FakeWorld._flipping(self, call)
+        return call
 
     def _dts(self, dt):
         return [float(dt)] * len(self.h) if np.ndim(dt) == 0 else [float(x) for x in dt]
@@ -425,17 +485,20 @@ B, RAGGED = 3, ((20, 11), (7, 7), (33, 1), (12, 0))
 
 
 def fake_env(kind, fault=0):
-    if kind == "world":
-        return ws.Env("world", small_world(1), lambda s: FakeWorld(s, fault), lambda s: Reader(np.array(s, dtype=F32), True), fake_view,
-                      lambda k: _points[:k])
-    ragged = kind == "ragged"
+    base = ws.base_of(kind)
+    # a reads kind: the factories of the seam's stand-in (tests/test_sequence_cpu.py), at the same scale
+    more = {} if kind == base else dict(edges=read_edges, centre=read_centre(members_of(kind)), radius=30.0)
+    view, points = (fake_view, lambda k: _points[:k]) if kind == base else (read_view, read_points(members_of(kind)))
+    if base == "world":
+        return ws.Env(kind, small_world(1), lambda s: FakeWorld(s, fault), lambda s: Reader(np.array(s, dtype=F32), True), view, points, **more)
+    ragged = base == "ragged"
     start = [small_world(30 + b, n, m) for b, (n, m) in enumerate(RAGGED)] if ragged else np.stack([small_world(20 + b) for b in range(B)])
     return ws.Env(kind, start, lambda s: FakeWorldBatch(s, fault, ragged), lambda s: BatchReader([np.array(p, dtype=F32) for p in s], True, ragged),
-                  fake_view, None, members=len(start))
+                  view, points if kind != base else None, members=len(start), **more)
 
 
 def members_of(kind):
-    return {"world": 0, "batch": B, "ragged": len(RAGGED)}[kind]
+    return {"world": 0, "batch": B, "ragged": len(RAGGED)}[ws.base_of(kind)]
 
 
 def caught_by(kind, seed, fault):
@@ -468,6 +531,8 @@ def first_touch(fault, ops):
         return first(lambda op: op[0] in ws.GPU_STEPS and not ws._moves(op))
     if fault == 9:
         return first(lambda op: op[0] == "update_gpu_traced" and ws._moves(op))
+    if fault in (11, 12):
+        return first(lambda op: op[0] in sd.NEW_READS)
     return first(lambda op: op[0] == "member", first(gpu) + 1)
 
 
@@ -499,11 +564,34 @@ def test_a_long_lived_world_on_the_host_cores_is_a_chain_of_fresh_ones(row, seed
     assert ws.check(real_env(*ws.WORLD_ROWS[row]), ops, seed) > len(ops) // 2
 
 
+def real_reads_env(n, frac):
+    """the same start state under "world-reads", with the arguments of tests/reads_common.py held to have something to say"""
+    if ("reads", n) not in _real:
+        env = real_env(n, frac)
+        reads_common.assert_the_reads_have_something_to_say([(env.start, int(np.count_nonzero(env.start[:, 6] > 0)))])
+        f = reads_common.factories(0, env.view)
+        _real[("reads", n)] = ws.Env("world-reads", env.start, nb.World, None, f["view"], f["points"], edges=f["edges"], centre=f["centre"],
+                                     radius=f["radius"])
+    return _real[("reads", n)]
+
+
+@pytest.mark.parametrize("seed", ws.SEEDS["world-reads"])
+@pytest.mark.parametrize("row", ["chain-200", "lanes-600"])
+def test_a_long_lived_world_on_the_host_cores_answers_every_read_only_call_like_a_fresh_one(row, seed):
+    """the host paths of tidal_at, tidal_map, profile, pair_counts and neighbours of the real library, in long sequences among
+    CPU steps of every kind"""
+    ops = ws.cpu_only(ws.generate("world-reads", seed))
+    assert set(sd.NEW_READS) <= {n for n, _ in ops} and {"update_cpu", "update_cpu_leapfrog", "update_cpu_adaptive"} <= {n for n, _ in ops}
+    assert ws.check(real_reads_env(*ws.WORLD_ROWS[row]), ops, seed) > len(ops) // 2
+
+
 def test_the_host_sequences_open_no_device():
     code = ("import os, test_world_sequence_cpu as t, world_sequence as ws\n"
             "for row in ('chain-200', 'lanes-600'):\n"
             "    for seed in ws.SEEDS['world']:\n"
             "        ws.check(t.real_env(*ws.WORLD_ROWS[row]), ws.cpu_only(ws.generate('world', seed)), seed)\n"
+            "    for seed in ws.SEEDS['world-reads']:\n"
+            "        ws.check(t.real_reads_env(*ws.WORLD_ROWS[row]), ws.cpu_only(ws.generate('world-reads', seed)), seed)\n"
             "fds = []\n"
             "for f in os.listdir('/proc/self/fd'):\n"
             "    try: fds.append(os.readlink('/proc/self/fd/' + f))\n"
@@ -586,11 +674,31 @@ def test_committed_sequences_hold_what_they_must(kind):
     for seed in ws.SEEDS[kind]:
         ops = ws.generate(kind, seed, members=members_of(kind))
         ws.assert_covers(kind, ops)
-        assert len(ops) == ws.LENGTH and ops == ws.generate(kind, seed, members=members_of(kind))
-        if kind == "ragged":
-            assert {name for name, _ in ops} <= ws.RAGGED_ALLOWED
-        if kind == "world":
+        assert len(ops) == (ws.READS_LENGTH if kind in ws.READS_BASE else ws.LENGTH) and ops == ws.generate(kind, seed, members=members_of(kind))
+        if ws.base_of(kind) == "ragged":
+            assert {name for name, _ in ops} <= ws.ragged_allowed(kind)
+            assert not {name for name, _ in ops} & {"bounds", "fit_views", "render", "render_counts", "update_gpu_adaptive", "advance_gpu"}
+        if ws.base_of(kind) == "world":
             assert not set(n for n, _ in ws.cpu_only(ops)) & set(ws.GPU_STEPS)
+
+
+def test_the_generator_notices_a_dropped_reads_piece():
+    ops = ws.generate("world-reads", ws.SEEDS["world-reads"][0])
+    names = [n for n, _ in ops]
+
+    def without(drop):
+        return [op for i, op in enumerate(ops) if not drop(i)]
+    with pytest.raises(AssertionError, match=r"neighbours\(None\)"):
+        ws.assert_covers("world-reads", without(lambda i: 0 < i < len(ops) - 1 and names[i - 1] == names[i] == "neighbours" and
+                                                names[i + 1] == "pair_counts"))
+    with pytest.raises(AssertionError, match="particles"):
+        ws.assert_covers("world-reads", without(lambda i: 0 < i < len(ops) - 1 and names[i] == "particles" and names[i - 1] in ws.EXACT_READS and
+                                                names[i + 1] in ("tidal_at", "tidal_map")))
+    with pytest.raises(AssertionError, match="after CPU steps"):
+        ws.assert_covers("world-reads", without(lambda i: 0 < i and names[i] in ("tidal_at", "tidal_map") and names[i - 1] in ws.CPU_STEPS))
+    ragged = ws.generate("ragged-reads", ws.SEEDS["ragged-reads"][0], members=len(RAGGED))
+    with pytest.raises(AssertionError):
+        ws.assert_covers("ragged-reads", ragged + [("bounds", {})])
 
 
 def test_the_generator_notices_a_dropped_piece():

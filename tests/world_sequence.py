@@ -28,6 +28,12 @@ A value that equals the OTHER path's is reported as a path error, one that equal
 fit_view(s), render_counts, render and timestep are bitwise the same on both paths by contract and are compared with the
 fresh World directly.
 
+The reads kinds ("world-reads", "batch-reads", "ragged-reads") add tidal_at, tidal_map, profile, pair_counts and neighbours with
+the drawn arguments of sequence_driver's reads kinds (an ensemble kind: the four Phi / g field calls too).  The path rule follows
+the headers: the host path of tidal_at / tidal_map runs in float64 and does not agree with the device in bits, so they join
+PATH_READS and the one-bit model; profile, pair_counts and neighbours promise "bit for bit on device, host and numpy", so they are
+compared with the fresh World directly and, where env.device exists, with the seam object as well (EXACT_READS).
+
 A long-lived object that rightly skips a leapfrog call's priming launch is compared with fresh ones that make it, so these
 sequences rest on the premise of sequence_driver's leapfrog kinds: start states are finite and hold no -0.0 position or
 velocity (sequence_driver.assert_premise, called where the environments are built).
@@ -39,18 +45,28 @@ import struct
 
 import numpy as np
 
-from sequence_driver import (ADAPT_SPAN, DT_MAX, ETA, MAP_SIZES, POINT_COUNTS, RENDER_SIZES, SOFT, STEP_DTS, TRACE_EVERY,
-                             SequenceMismatch, _pick, adaptive_bits, blob, ebits, show)
+from sequence_driver import (ADAPT_SPAN, AT_CALLS, DT_MAX, ETA, MAP_CALLS, MAP_SIZES, MASKS, NEW_READS, POINT_COUNTS, RENDER_SIZES, SOFT,
+                             STEP_DTS, TRACE_EVERY, SequenceMismatch, _make_read, _pick, _probes, _read, _views, adaptive_bits, blob,
+                             ebits, show)
 
 STEP_COUNTS = (0, 1, 2, 3, 5)          # 0: the zero-step forms, which must change nothing
 ADAPT_COUNTS = (0, 1, 3, 6)
 ADVANCE_MAX = 48                       # max_steps of an advance call: more than ADAPT_SPAN needs at these sizes
 LENGTH = 64                            # the planted pieces are 29 operations of a World sequence: room for every drawn call
+READS_LENGTH = 88                      # the reads kinds: the base kind's pieces, those of _planted_reads, and as many drawn calls
 # the committed seeds: tests/test_gpu_world_sequences.py runs exactly these, tests/test_world_sequence_cpu.py says how they
 # were chosen and shows that each pair catches every planted fault of its stand-in
-SEEDS = {"world": (0, 1), "batch": (0, 3), "ragged": (0, 1)}
+SEEDS = {"world": (0, 1), "batch": (0, 3), "ragged": (0, 1), "world-reads": (2, 5), "batch-reads": (0, 6), "ragged-reads": (0, 1)}
+# a reads kind draws everything its base kind draws, and tidal_at, tidal_map, profile, pair_counts and neighbours (an ensemble
+# kind: the four Phi / g field calls too, which "batch" and "ragged" never draw), with the drawn arguments of sequence_driver's
+# reads kinds.  env.view, env.points, env.edges, env.centre and env.radius are those of sequence_driver.Env
+READS_BASE = {"world-reads": "world", "batch-reads": "batch", "ragged-reads": "ragged"}
 # the member counts the rows run with: what a sequence draws for member() depends on them
-MEMBERS = {"world": (0,), "batch": (5, 3), "ragged": (12,)}
+MEMBERS = {"world": (0,), "batch": (5, 3), "ragged": (12,), "world-reads": (0,), "batch-reads": (5, 3), "ragged-reads": (12,)}
+
+
+def base_of(kind):
+    return READS_BASE.get(kind, kind)
 
 # the chain, lane-split and classic routes with the frac_massive of sequence_driver.PIPE_ROWS; the ensembles of its GPU rows
 WORLD_ROWS = {"chain-200": (200, 0.5), "lanes-600": (600, 0.5), "classic-4133": (4133, 1.0)}
@@ -60,8 +76,13 @@ CPU_STEPS = ("update_cpu", "update_cpu_leapfrog", "update_cpu_adaptive")
 GPU_STEPS = ("update_gpu", "update_gpu_leapfrog", "update_gpu_adaptive", "advance_gpu", "update_gpu_traced")
 STEPS = CPU_STEPS + GPU_STEPS
 READ_BACK = ("particles", "member")
-PATH_READS = ("energy", "potential", "potential_at", "acceleration_at", "potential_map", "acceleration_map")
-BITWISE_READS = ("timestep", "bounds", "fit_view", "fit_views", "render_counts", "render")
+# the host path of the tidal calls runs in float64 and does not agree with the device in bits (include/nbody_tidal.h,
+# nbody_batch_tidal.h): the path rule and its one-bit model hold for them as for the other field calls
+PATH_READS = ("energy", "potential", "potential_at", "acceleration_at", "potential_map", "acceleration_map", "tidal_at", "tidal_map")
+# "bit for bit on device, host and numpy" (include/nbody_profile.h, nbody_paircount.h, nbody_neighbour.h): compared with the
+# fresh World directly and, where env.device exists, with the seam object as well
+EXACT_READS = ("profile", "pair_counts", "neighbours")
+BITWISE_READS = ("timestep", "bounds", "fit_view", "fit_views", "render_counts", "render") + EXACT_READS
 # every operation of the World kind that cannot reach a device: what the CPU-only run keeps
 CPU_ONLY = CPU_STEPS + READ_BACK + PATH_READS + BITWISE_READS
 
@@ -73,19 +94,40 @@ WEIGHTS = {
     "batch": ({"update_gpu": 0.10, "update_gpu_leapfrog": 0.08, "update_gpu_adaptive": 0.05, "advance_gpu": 0.03, "update_gpu_traced": 0.07},
               {"particles": 0.08, "member": 0.08, "energy": 0.12, "potential": 0.11, "bounds": 0.06, "fit_views": 0.05,
                "render_counts": 0.08, "render": 0.09}),
-    # include/nbody_batch_ragged.h lists these and NOTHING else
+    # include/nbody_batch_ragged.h lists these, and the field, tidal, profile, pair-count and neighbour calls that "ragged-reads"
+    # draws; the bounds, fit and render calls abort on a ragged batch, and it has no adaptive or leapfrog steps
     "ragged": ({"update_gpu": 0.20, "update_gpu_traced": 0.13},
                {"particles": 0.14, "member": 0.14, "energy": 0.20, "potential": 0.19}),
+    # the reads kinds: the steps of the base kind; the new calls take about a third of the whole from the other calls
+    "world-reads": ({"update_cpu": 0.05, "update_gpu": 0.05, "update_cpu_leapfrog": 0.03, "update_gpu_leapfrog": 0.04,
+                     "update_cpu_adaptive": 0.03, "update_gpu_adaptive": 0.03, "advance_gpu": 0.02},
+                    {"timestep": 0.03, "particles": 0.05, "energy": 0.04, "potential": 0.04, "potential_at": 0.03, "acceleration_at": 0.03,
+                     "potential_map": 0.03, "acceleration_map": 0.03, "bounds": 0.02, "fit_view": 0.02, "render_counts": 0.03, "render": 0.03,
+                     "tidal_at": 0.06, "tidal_map": 0.06, "profile": 0.07, "pair_counts": 0.07, "neighbours": 0.09}),
+    "batch-reads": ({"update_gpu": 0.10, "update_gpu_leapfrog": 0.08, "update_gpu_adaptive": 0.05, "advance_gpu": 0.03, "update_gpu_traced": 0.07},
+                    {"particles": 0.06, "member": 0.06, "energy": 0.05, "potential": 0.05, "bounds": 0.03, "fit_views": 0.03,
+                     "render_counts": 0.04, "render": 0.04, "potential_at": 0.03, "acceleration_at": 0.03, "potential_map": 0.03,
+                     "acceleration_map": 0.03, "tidal_at": 0.04, "tidal_map": 0.04, "profile": 0.05, "pair_counts": 0.05, "neighbours": 0.06}),
+    "ragged-reads": ({"update_gpu": 0.20, "update_gpu_traced": 0.13},
+                     {"particles": 0.08, "member": 0.08, "energy": 0.07, "potential": 0.07, "potential_at": 0.03, "acceleration_at": 0.03,
+                      "potential_map": 0.03, "acceleration_map": 0.03, "tidal_at": 0.04, "tidal_map": 0.04, "profile": 0.06,
+                      "pair_counts": 0.06, "neighbours": 0.08}),
 }
 RAGGED_ALLOWED = frozenset(WEIGHTS["ragged"][0]) | frozenset(WEIGHTS["ragged"][1])
+RAGGED_READS_ALLOWED = frozenset(WEIGHTS["ragged-reads"][0]) | frozenset(WEIGHTS["ragged-reads"][1])
+
+
+def ragged_allowed(kind):
+    return RAGGED_READS_ALLOWED if kind == "ragged-reads" else RAGGED_ALLOWED
 
 
 class Env:
     """kind; the first state; make(state) -> World / WorldBatch; device(state) -> the seam object with that state (or None: no
     operation of the sequence may reach a device); view(w, h); points(k); members (0: a single World)."""
 
-    def __init__(self, kind, start, make, device, view, points, members=0):
+    def __init__(self, kind, start, make, device, view, points, members=0, edges=None, centre=None, radius=None):
         self.kind, self.start, self.make, self.device, self.view, self.points, self.members = kind, start, make, device, view, points, members
+        self.edges, self.centre, self.radius = edges, centre, radius          # a reads kind: as in sequence_driver.Env
 
 
 # ---- one operation -------------------------------------------------------------------------------------------------------------
@@ -110,8 +152,8 @@ def _adaptive_kw(a):
 def apply(obj, op, env):
     """Issue one operation on a World / WorldBatch (or, for the PATH_READS, on the seam object of env.device); bytes or None."""
     name, a = op
-    if env.kind == "ragged":
-        assert name in RAGGED_ALLOWED, f"{name}: include/nbody_batch_ragged.h does not list it; the generator must never emit it"
+    if base_of(env.kind) == "ragged":
+        assert name in ragged_allowed(env.kind), f"{name}: include/nbody_batch_ragged.h does not list it; the generator must never emit it"
     if name in ("update_cpu", "update_gpu", "update_cpu_leapfrog", "update_gpu_leapfrog"):
         getattr(obj, name)(_dt(a, env), a["n"])
     elif name in ("update_cpu_adaptive", "update_gpu_adaptive"):
@@ -131,13 +173,15 @@ def apply(obj, op, env):
     elif name == "potential":
         return blob(obj.potential())
     elif name == "potential_at":
-        return blob(obj.potential_at(env.points(a["count"]), SOFT))
+        return blob(obj.potential_at(_probes(a, env), SOFT))
     elif name == "acceleration_at":
-        return blob(obj.acceleration_at(env.points(a["count"]), SOFT))
+        return blob(obj.acceleration_at(_probes(a, env), SOFT))
     elif name == "potential_map":
-        return blob(obj.potential_map(env.view(a["w"], a["h"]), SOFT))
+        return blob(obj.potential_map(_views(a, env), SOFT))
     elif name == "acceleration_map":
-        return blob(obj.acceleration_map(env.view(a["w"], a["h"]), SOFT))
+        return blob(obj.acceleration_map(_views(a, env), SOFT))
+    elif name in NEW_READS:
+        return blob(_read(obj, name, a, env))
     elif name == "bounds":
         return blob(obj.bounds())
     elif name in ("fit_view", "fit_views"):
@@ -156,7 +200,7 @@ def device_answers(kind, on_device, op):
     name, a = op
     if name in GPU_STEPS:
         return True if (name == "advance_gpu" or a["n"] > 0) else on_device
-    if kind == "world":
+    if base_of(kind) == "world":
         if name == "update_cpu" or (name in CPU_STEPS and a["n"] > 0):
             return False
     elif name in READ_BACK:
@@ -215,6 +259,10 @@ def check(env, ops, seed=None):
             want, state = _fresh(env, state, op)
             if got != want:
                 raise SequenceMismatch(seed, i, name, ops, _differs(got, want))
+            if name in EXACT_READS and env.device is not None:
+                seam = _device_value(env, state, op)
+                if got != seam:
+                    raise SequenceMismatch(seed, i, name, ops, "the seam object's value for this state, " + _differs(got, seam))
         compared += got is not None
         on_device = device_answers(env.kind, on_device, op)
     final = blob(obj.particles())
@@ -227,6 +275,10 @@ def check(env, ops, seed=None):
 # ---- the generator -------------------------------------------------------------------------------------------------------------
 
 def _make(rng, kind, name, members):
+    if kind in READS_BASE:
+        if name in AT_CALLS + MAP_CALLS + NEW_READS:
+            return _make_read(rng, name, kind != "world-reads")
+        kind = READS_BASE[kind]
     if name in ("update_cpu", "update_gpu", "update_cpu_leapfrog", "update_gpu_leapfrog", "update_gpu_traced"):
         a = {"n": int(_pick(rng, STEP_COUNTS)), "dt": float(_pick(rng, STEP_DTS))}
         if kind != "world":
@@ -275,7 +327,8 @@ def _planted(rng, kind, members):
         return _steps(rng, kind, name, members, **kw)
     diag = _make(rng, kind, _pick(rng, ("energy", "potential")), members)
     again = _make(rng, kind, _pick(rng, ("energy", "potential")), members)
-    if kind == "world":
+    base = base_of(kind)
+    if base == "world":
         def adaptive(name, flag):
             op = s(name, leapfrog=flag == "leapfrog")
             if flag == "prime":
@@ -308,7 +361,7 @@ def _planted(rng, kind, members):
         ]
     first = [("update_gpu_traced", {"n": 0, "dt": 0.01, "per_member": False, "every": 1}), diag]   # traced, n = 0, never stepped
     later = [s("update_gpu_traced"), ("update_gpu_traced", {"n": 0, "dt": 0.01, "per_member": True, "every": 2}), again, ("particles", {}), again]
-    if kind == "ragged":
+    if base == "ragged":
         return [first, later, [s("update_gpu"), ("member", {"b": int(rng.integers(members))})]]
     return [[("update_gpu", {"n": 0, "dt": 0.01, "per_member": False}), diag] + first, later,
             [s("update_gpu"), _make(rng, kind, "advance_gpu", members), s("update_gpu")],
@@ -323,11 +376,44 @@ def _segment(rng, kind, count, members):
     return [_make(rng, kind, names[int(rng.choice(len(names), p=p))], members) for _ in range(count)]
 
 
-def generate(kind, seed, length=LENGTH, members=0):
+def _planted_reads(rng, kind, members):
+    """The pieces a reads kind adds (T: tidal_at or tidal_map, E: one of EXACT_READS; the same letter is the same call):
+      GPU steps, neighbours(radius, A, B), neighbours(None, C, D), pair_counts, neighbours(radius, C, D)   (A, B) != (C, D)
+                                    on the device: the long-lived object's one scratch, in which the counts of the first call
+                                    lie where the last one adds and the pair-count table lies over the keys
+      GPU steps, T, E, particles, T, E
+                                    the device answers both; a read-back leaves the path of a World where it is and moves
+                                    that of a WorldBatch to the host; E is the same in bits on either side
+      a World: CPU steps, T, E      the host answers, in float64 for T, and E is still the same in bits"""
+    base = READS_BASE[kind]
+
+    def gpu():
+        return _steps(rng, kind, "update_gpu", members)
+    first = (_pick(rng, MASKS), _pick(rng, MASKS))
+    second = first
+    while second == first:
+        second = (_pick(rng, MASKS), _pick(rng, MASKS))
+
+    def neigh(radius, masks):
+        return "neighbours", {"radius": radius, "receivers": masks[0], "sources": masks[1]}
+    t, e = _make(rng, kind, _pick(rng, ("tidal_at", "tidal_map")), members), _make(rng, kind, _pick(rng, EXACT_READS), members)
+    pieces = [[gpu(), neigh(True, first), neigh(False, second), _make(rng, kind, "pair_counts", members), neigh(True, second)],
+              [gpu(), t, e, ("particles", {}), t, e]]
+    if base == "world":
+        pieces.append([_steps(rng, kind, "update_cpu", members), t, e])
+    return pieces
+
+
+def generate(kind, seed, length=None, members=0):
     """The sequence of (kind, seed): the planted pieces in their order, the first one first (nothing may push before it),
-    drawn segments between them and behind the last."""
-    rng = np.random.default_rng([seed, len(kind)])
-    planted = _planted(rng, kind, members)
+    drawn segments between them and behind the last.  A reads kind: a stream of its own, the base kind's pieces and then its own."""
+    length = (READS_LENGTH if kind in READS_BASE else LENGTH) if length is None else length
+    if kind in READS_BASE:
+        rng = np.random.default_rng([seed, len(kind), sorted(READS_BASE).index(kind) + 1])
+        planted = _planted(rng, kind, members) + _planted_reads(rng, kind, members)
+    else:
+        rng = np.random.default_rng([seed, len(kind)])
+        planted = _planted(rng, kind, members)
     free = max(length - sum(len(p) for p in planted), len(planted))
     ops = []
     for i, piece in enumerate(planted):
@@ -357,6 +443,13 @@ def assert_union_covers(kind, lists):
     ops = [op for lst in lists for op in lst]
     every = set(WEIGHTS[kind][0]) | set(WEIGHTS[kind][1])
     assert every <= {name for name, _ in ops}, f"the committed {kind} sequences never issue {sorted(every - {name for name, _ in ops})}"
+    if kind in READS_BASE:          # neighbours with and without a radius; an ensemble: each argument one for all and one per member
+        for radius in (True, False):
+            assert any(n == "neighbours" and a["radius"] == radius for n, a in ops), f"no neighbours with radius {radius}"
+        for what, calls in (("points", AT_CALLS), ("views", MAP_CALLS), ("centres", ("profile",))) if kind != "world-reads" else ():
+            for per_member in (True, False):
+                assert any(n in calls and a["per_member"] == per_member for n, a in ops), f"no {what} with per_member {per_member}"
+        kind = READS_BASE[kind]
 
     def has(name, *flags):
         return any(n == name and a.get("n", 1) > 0 and all(a.get(f) for f in flags) for n, a in ops)
@@ -387,8 +480,25 @@ def assert_covers(kind, ops):
     def diag(op):
         return op[0] in PATH_READS
     pushed = next((i for i, op in enumerate(ops) if gpu(op)), len(ops))
+    allowed = ragged_allowed(kind)
+    if kind in READS_BASE:          # the pieces of _planted_reads
+        def neigh(radius):
+            return lambda op: op[0] == "neighbours" and op[1]["radius"] == radius
+
+        def masks(op):
+            return op[1]["receivers"], op[1]["sources"]
+        assert any(gpu(g) and neigh(True)(a) and neigh(False)(b) and c[0] == "pair_counts" and neigh(True)(d) and masks(b) == masks(d) != masks(a)
+                   for g, a, b, c, d in zip(ops, ops[1:], ops[2:], ops[3:], ops[4:])), \
+            "no neighbours(radius), neighbours(None) under other masks, pair_counts, neighbours(radius) under those masks behind GPU steps"
+        assert any(gpu(g) and t[0] in ("tidal_at", "tidal_map") and e[0] in EXACT_READS and p[0] == "particles" and (t, e) == (t2, e2)
+                   for g, t, e, p, t2, e2 in zip(ops, ops[1:], ops[2:], ops[3:], ops[4:], ops[5:])), \
+            "no tidal call and exact read after GPU steps, particles(), the same two"
+        if kind == "world-reads":
+            assert _run(ops, cpu, lambda op: op[0] in ("tidal_at", "tidal_map"), lambda op: op[0] in EXACT_READS), \
+                "no tidal call and exact read directly after CPU steps"
+        kind = READS_BASE[kind]
     if kind == "ragged":
-        assert set(names) <= RAGGED_ALLOWED, sorted(set(names) - RAGGED_ALLOWED)
+        assert set(names) <= allowed, sorted(set(names) - allowed)
     if kind == "world":
         assert _run(ops[:pushed], lambda op: op[0] in GPU_STEPS and not _moves(op), diag), "no n = 0 GPU call before any push with a diagnostic behind it"
         assert _run(ops, gpu, cpu, gpu), "no CPU step directly after GPU steps with GPU steps directly after it"
