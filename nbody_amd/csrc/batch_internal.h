@@ -3,12 +3,11 @@
 //
 // Every device array and event of a SimBatch is a member of an owner type (pipeline_internal.h DevBuf / Interval): made by
 // materialize or on a call's first use, released by the member's destructor when nb_hip_batch_destroy deletes the struct,
-// after it has drained the stream.  nb_hip_batch_destroy itself only syncs and destroys the stream.  The read-only calls share one
-// scratch and one host protocol with those of a pipeline: pipeline_internal.h ReadScratch / read_call.
+// after it has drained the stream.  nb_hip_batch_destroy itself only syncs and destroys the stream.  Every read-only call, the
+// renders included, shares one scratch and one host protocol with those of a pipeline: pipeline_internal.h ReadScratch / read_call.
 #pragma once
 
 #include "pipeline_internal.h"
-#include "render_kernels.h"
 
 struct SimBatch {
     uint32_t count = 0;     // members
@@ -54,8 +53,8 @@ struct SimBatch {
     nbi::DevBuf<uint32_t> n_len_dev;     // ragged only, like offsets_dev
     nbi::DevBuf<uint64_t> offsets_dev;
 
-    // the read-only calls (batch_observe.hip's energy, potential and field calls, nb_hip_ensemble_profile, nb_hip_ensemble_pair_counts,
-    // nb_hip_ensemble_neighbours): their scratch and their interval (pipeline_internal.h ReadScratch)
+    // every read-only call (all of batch_observe.hip, nb_hip_ensemble_profile, nb_hip_ensemble_pair_counts, nb_hip_ensemble_neighbours):
+    // their scratch, and the interval of all but bounds and the renders (pipeline_internal.h ReadScratch)
     nbi::ReadScratch read;
     // the energy slab stays a member of its own: traced updates (batch.hip) write it too, and they are no read-only calls
     nbi::DevBuf<double> diag;      // float64 slab: [count][tiles of 128][NB_DIAG_SUMS] + the [count][NB_DIAG_SUMS] results
@@ -67,13 +66,7 @@ struct SimBatch {
     int trace_fused = 0;         // what the last traced call did
     uint32_t trace_launches = 0;
 
-    // nb_hip_ensemble_bounds / _render_counts / _render_rgba (kernels: render_kernels.hip): scratch made on first use, an
-    // interval of their own
-    nbi::DevBuf<RenderView> render_views;      // [count]: the views of the last call
-    nbi::DevBuf<uint32_t> render_keys;         // [count][4]
-    nbi::DevBuf<uint32_t> render_counts;       // tile path: [count][3][h][w]; global path: the disc cursor behind them
-    nbi::DevBuf<uint32_t> render_rgba;         // [count][h][w]
-    nbi::DevBuf<nb::render::Disc> render_discs;    // global path: [count * n]
+    // nb_hip_ensemble_bounds / _render_counts / _render_rgba (kernels: render_kernels.hip): an interval of their own
     nbi::Interval render_iv;
     int render_mode = 0;                     // tuning hook: 1 = the global path also where the tile path applies
     int render_tile = 0;                     // what the last render did (a bounds call leaves both alone)

@@ -2,8 +2,8 @@
 // bounds, count images and frames (kernels: render_kernels.hip), the potential, the acceleration field and the tidal tensor at
 // probe points and over views (kernels: batch_field.hip, tidal.hip), with their tuning hooks and timers.  Each
 // looks at the latest state without reading the particles back: a constant number of launches, one copy, one sync for any B.
-// The energy, potential and field calls run through pipeline_internal.h's read_call, on the ensemble's one ReadScratch; the
-// render calls keep buffers and intervals of their own (a render's buffers hold several roles within one call).
+// Every one of them runs through pipeline_internal.h's read_call, on the ensemble's one ReadScratch (what each resets is listed
+// there); bounds and the renders cut its work buffer into sections and bracket an interval of their own.
 #include "batch_internal.h"
 #include "batch_diag.h"
 #include "batch_field.h"
@@ -11,6 +11,7 @@
 #include "field_common.h"
 #include "nbody_hip_tuning.h"
 #include "render_common.h"
+#include "render_kernels.h"
 
 using namespace nbi;
 namespace rd = nb::render;
@@ -77,47 +78,52 @@ void check_views(const SimBatch *s, const RenderView *views, const char *what) {
               views[member].width, views[member].height, (double)views[member].zoom, fault);
 }
 
-// The count images of the latest state on the stream: the tile kernel (straight to the frame when a palette is given) or
-// clear + splat + disc pass (+ shade); *launches = what was enqueued.
-void enqueue_render(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint32_t *launches) {
+// One read_call inside render_iv: the views are its args; the tile kernel (straight to the frame when a palette is given) or
+// clear + splat + disc pass (+ shade); then the count images [count][3][h][w] or the frames [count][h][w] to `out`.  The
+// sections of read.work: the tile path's one result; the global path's count words (the cursor behind the images), its disc
+// list [count * n] and, for frames, the frames.
+void render(SimBatch *s, const char *what, const RenderView *views, const RenderPalette *palette, void *out) {
     const uint32_t width = views[0].width, height = views[0].height;
     const size_t plane = (size_t)width * height;
     const bool tile = rd::tile_fits(width, height) && s->render_mode == 0;
-    if (!s->render_views) s->render_views.alloc(s->count);
-    if (palette) s->render_rgba.grown(s->stream, (size_t)s->count * plane);
-    if (!tile || !palette) s->render_counts.grown(s->stream, rd::global_count_words(s->count, width, height));
-    if (!tile && !s->render_discs) s->render_discs.alloc((size_t)s->count * s->n);
-    ASSERT_HIP(hipMemcpyAsync(s->render_views, views, (size_t)s->count * sizeof(RenderView), hipMemcpyHostToDevice, s->stream),
-               "H2D of %u views", s->count);
-    s->render_iv.begin(s->stream);
-    rd::EnsembleRenderParams p{};
-    p.pos = s->pos[s->cur];
-    p.mass = s->mass;
-    p.radius = s->radius;
-    p.n = s->n;
-    p.stride = s->stride;
-    p.count = s->count;
-    p.width = width;
-    p.height = height;
-    p.views = s->render_views;
-    if (tile) {
-        rd::launch_ensemble_tile(s->stream, p, s->render_counts, palette, s->render_rgba);
-        *launches = 1;
+    const size_t count_bytes = (size_t)s->count * NB_RENDER_CLASSES * plane * sizeof(uint32_t), frame_bytes = (size_t)s->count * plane * sizeof(uint32_t);
+    const size_t clear_bytes = rd::global_count_words(s->count, width, height) * sizeof(uint32_t);
+    size_t work_bytes = 0, counts_at = 0, discs_at = 0, rgba_at = 0;
+    if (tile) {   // one section, at 0 under either name: the counts or the frames, whichever the call returns
+        section(work_bytes, palette ? frame_bytes : count_bytes);
     } else {
-        ASSERT_HIP(hipMemsetAsync(s->render_counts, 0, rd::global_count_words(s->count, width, height) * sizeof(uint32_t), s->stream),
-                   "clear %u count images and the disc cursor", s->count);
-        rd::launch_ensemble_global(s->stream, p, s->render_counts, s->render_discs);
-        *launches = 3;
-        if (palette) {
-            rd::launch_ensemble_shade(s->stream, s->render_counts, s->count, (uint32_t)plane, *palette, s->render_rgba);
-            *launches = 4;
-        }
+        counts_at = section(work_bytes, clear_bytes);
+        discs_at = section(work_bytes, (size_t)s->count * s->n * sizeof(rd::Disc));
+        if (palette) rgba_at = section(work_bytes, frame_bytes);
     }
-    ASSERT_HIP(hipGetLastError(), "ensemble render launch (%u members of %u particles, %u x %u, %s path)", s->count, s->n, width, height,
-               tile ? "tile" : "global");
-    s->render_iv.end(s->stream);
+    read_call(s, s->render_iv, what, views, (size_t)s->count * sizeof(RenderView), work_bytes, out, palette ? frame_bytes : count_bytes,
+              [&](void *views_dev, void *work) -> const void * {
+        char *base = static_cast<char *>(work);
+        uint32_t *counts = reinterpret_cast<uint32_t *>(base + counts_at), *rgba = reinterpret_cast<uint32_t *>(base + rgba_at);
+        rd::EnsembleRenderParams p{};
+        p.pos = s->pos[s->cur];
+        p.mass = s->mass;
+        p.radius = s->radius;
+        p.n = s->n;
+        p.stride = s->stride;
+        p.count = s->count;
+        p.width = width;
+        p.height = height;
+        p.views = static_cast<const RenderView *>(views_dev);
+        if (tile) {
+            rd::launch_ensemble_tile(s->stream, p, counts, palette, rgba);   // it stores to the one of the two the call returns
+            s->render_launches = 1;
+        } else {
+            ASSERT_HIP(hipMemsetAsync(counts, 0, clear_bytes, s->stream), "clear %u count images and the disc cursor", s->count);
+            rd::launch_ensemble_global(s->stream, p, counts, reinterpret_cast<rd::Disc *>(base + discs_at));
+            if (palette) rd::launch_ensemble_shade(s->stream, counts, s->count, (uint32_t)plane, *palette, rgba);
+            s->render_launches = palette ? 4 : 3;
+        }
+        ASSERT_HIP(hipGetLastError(), "ensemble render launch (%u members of %u particles, %u x %u, %s path)", s->count, s->n, width, height,
+                   tile ? "tile" : "global");
+        return palette ? rgba : counts;
+    });
     s->render_tile = tile;
-    s->render_launches = *launches;
 }
 
 // ---- fields: Phi, g and T of every member at n samples each, without reading the particles back ------------------------
@@ -137,7 +143,7 @@ void check_field(SimBatch *s, const char *what, float softening, uint64_t sample
 void sample_members(SimBatch *s, const char *what, uint32_t comps, bool map, const float *in, uint32_t in_stride, uint32_t n,
                     uint32_t width, float softening, float *out) {
     const size_t in_bytes = (size_t)s->count * in_stride * sizeof(float), out_bytes = (size_t)s->count * n * comps * sizeof(float);
-    read_call(s, what, in, in_bytes, out_bytes, out, out_bytes, [&](void *in_dev, void *work) -> const void * {
+    read_call(s, s->read.iv, what, in, in_bytes, out_bytes, out, out_bytes, [&](void *in_dev, void *work) -> const void * {
         nb::field::EnsembleParams p{};
         p.pos = s->pos[s->cur];
         p.gm = s->gm;
@@ -191,7 +197,7 @@ void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
     check_diag(s, out, "nb_hip_ensemble_energy");
     constexpr size_t Q = NB_DIAG_SUMS;
     // the workspace is the ensemble's own slab, which traced updates use too: only the results come back through the protocol
-    const void *host = read_call(s, "nb_hip_ensemble_energy", nullptr, 0, 0, nullptr, (size_t)s->count * Q * sizeof(double),
+    const void *host = read_call(s, s->read.iv, "nb_hip_ensemble_energy", nullptr, 0, 0, nullptr, (size_t)s->count * Q * sizeof(double),
                                  [&](void *, void *) -> const void * {
         double *res = energy_slab(s) + (size_t)s->count * nbd::ensemble_tiles(s->n) * Q;
         launch_energy_sums(s, res);
@@ -203,7 +209,7 @@ void nb_hip_ensemble_energy(SimBatch *s, WorldEnergy *out) {
 void nb_hip_ensemble_potential(SimBatch *s, float *phi) {
     check_diag(s, phi, "nb_hip_ensemble_potential");
     const size_t bytes = (size_t)s->offsets[s->count] * sizeof(float);
-    read_call(s, "nb_hip_ensemble_potential", nullptr, 0, bytes, phi, bytes, [&](void *, void *work) -> const void * {
+    read_call(s, s->read.iv, "nb_hip_ensemble_potential", nullptr, 0, bytes, phi, bytes, [&](void *, void *work) -> const void * {
         nbd::EnsembleDiagParams p = diag_params(s);
         p.phi = static_cast<float *>(work);
         // packed member after member; the member sizes and offsets on the device are null in a uniform ensemble
@@ -248,29 +254,21 @@ double nb_hip_ensemble_last_diag_ms(SimBatch *s) {
 void nb_hip_ensemble_bounds(SimBatch *s, float *bounds) {
     check_not_ragged(s, "nb_hip_ensemble_bounds");
     check_diag(s, bounds, "nb_hip_ensemble_bounds");
-    use_device();
-    s->render_iv.begin(s->stream);
-    if (!s->render_keys) s->render_keys.alloc((size_t)s->count * 4);
-    rd::launch_ensemble_bounds(s->stream, s->pos[s->cur], s->n, s->stride, s->count, s->render_keys);
-    ASSERT_HIP(hipGetLastError(), "ensemble_bounds_kernel launch (%u members of %u)", s->count, s->n);
-    s->render_iv.end(s->stream);   // the interval is shared with the renders; render_tile / render_launches speak of renders only
-    std::vector<uint32_t> keys((size_t)s->count * 4);
-    ASSERT_HIP(hipMemcpyAsync(keys.data(), s->render_keys, keys.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream),
-               "D2H of %u members' bounds", s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_bounds");
-    for (uint32_t b = 0; b < s->count; b++) nb_render_bounds_from_keys(keys.data() + (size_t)b * 4, bounds + (size_t)b * 4);
+    // the interval is shared with the renders; render_tile / render_launches speak of renders only
+    const size_t bytes = (size_t)s->count * 4 * sizeof(uint32_t);
+    const void *host = read_call(s, s->render_iv, "nb_hip_ensemble_bounds", nullptr, 0, bytes, nullptr, bytes, [&](void *, void *work) -> const void * {
+        rd::launch_ensemble_bounds(s->stream, s->pos[s->cur], s->n, s->stride, s->count, static_cast<uint32_t *>(work));
+        ASSERT_HIP(hipGetLastError(), "ensemble_bounds_kernel launch (%u members of %u)", s->count, s->n);
+        return work;
+    });
+    for (uint32_t b = 0; b < s->count; b++) nb_render_bounds_from_keys(static_cast<const uint32_t *>(host) + (size_t)b * 4, bounds + (size_t)b * 4);
 }
 
 void nb_hip_ensemble_render_counts(SimBatch *s, const RenderView *views, uint32_t *counts) {
     check_not_ragged(s, "nb_hip_ensemble_render_counts");
     check_diag(s, counts, "nb_hip_ensemble_render_counts");
     check_views(s, views, "nb_hip_ensemble_render_counts");
-    use_device();
-    uint32_t launches = 0;
-    enqueue_render(s, views, nullptr, &launches);
-    const size_t bytes = (size_t)s->count * NB_RENDER_CLASSES * views[0].width * views[0].height * sizeof(uint32_t);
-    ASSERT_HIP(hipMemcpyAsync(counts, s->render_counts, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u count images", s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_render_counts");
+    render(s, "nb_hip_ensemble_render_counts", views, nullptr, counts);
 }
 
 void nb_hip_ensemble_render_rgba(SimBatch *s, const RenderView *views, const RenderPalette *palette, uint8_t *rgba) {
@@ -279,12 +277,7 @@ void nb_hip_ensemble_render_rgba(SimBatch *s, const RenderView *views, const Ren
     check_views(s, views, "nb_hip_ensemble_render_rgba");
     NB_ASSERT(palette != nullptr, "nb_hip_ensemble_render_rgba: NULL RenderPalette");
     NB_ASSERT(palette->saturation >= 1u, "RenderPalette saturation must be at least 1");
-    use_device();
-    uint32_t launches = 0;
-    enqueue_render(s, views, palette, &launches);
-    const size_t bytes = (size_t)s->count * views[0].width * views[0].height * sizeof(uint32_t);
-    ASSERT_HIP(hipMemcpyAsync(rgba, s->render_rgba, bytes, hipMemcpyDeviceToHost, s->stream), "D2H of %u frames", s->count);
-    ASSERT_HIP(hipStreamSynchronize(s->stream), "sync after nb_hip_ensemble_render_rgba");
+    render(s, "nb_hip_ensemble_render_rgba", views, palette, rgba);
 }
 
 // tuning hooks (nbody_hip_tuning.h)

@@ -169,7 +169,7 @@ void nb_hip_energy(SimPipeline *s, WorldEnergy *out) {
     if (M > 0) {
         const uint32_t rows = (M + nbd::TILE - 1) / nbd::TILE;
         // the float64 slab: QTY per workgroup + the QTY results
-        read_call(s, "nb_hip_energy", nullptr, 0, (size_t)(rows + 1) * QTY * sizeof(double), q, sizeof(q), [&](void *, void *work) -> const void * {
+        read_call(s, s->read.iv, "nb_hip_energy", nullptr, 0, (size_t)(rows + 1) * QTY * sizeof(double), q, sizeof(q), [&](void *, void *work) -> const void * {
             double *slab = static_cast<double *>(work);
             nbd::DiagParams p = diag_params(s, M);
             p.slab = slab;
@@ -195,7 +195,7 @@ void nb_hip_potential(SimPipeline *s, float *phi) {
         return;
     }
     const size_t bytes = (size_t)N * sizeof(float);
-    read_call(s, "nb_hip_potential", nullptr, 0, bytes, phi, bytes, [&](void *, void *work) -> const void * {
+    read_call(s, s->read.iv, "nb_hip_potential", nullptr, 0, bytes, phi, bytes, [&](void *, void *work) -> const void * {
         nbd::DiagParams p = diag_params(s, N);
         p.phi = static_cast<float *>(work);
         hipLaunchKernelGGL(nbd::potential_kernel, dim3((N + nbd::TILE - 1) / nbd::TILE), dim3(nbd::WAVE * nbd::W), 0, s->stream, p);

@@ -136,7 +136,7 @@ template <typename Q>
 void run(SimPipeline *s, const char *what, bool map, const float *in, size_t in_floats, uint32_t n, uint32_t width, float softening,
          typename Q::Out *out) {
     const size_t out_bytes = (size_t)n * sizeof(typename Q::Out);
-    read_call(s, what, in, in_floats * sizeof(float), out_bytes, out, out_bytes, [&](void *in_dev, void *work) -> const void * {
+    read_call(s, s->read.iv, what, in, in_floats * sizeof(float), out_bytes, out, out_bytes, [&](void *in_dev, void *work) -> const void * {
         fd::Params p{};
         p.pos = s->pos[s->cur];
         p.src_gm = s->src_gm;
@@ -175,9 +175,7 @@ void sample_at(SimPipeline *s, const char *what, const float *points, uint32_t n
 template <typename Q>
 void sample_map(SimPipeline *s, const char *what, const RenderView *view, float softening, typename Q::Out *out) {
     check_diag(s, what);
-    NB_ASSERT(view != nullptr, "NULL RenderView");
-    const char *fault = nb_render_view_fault(view);
-    NB_ASSERT(fault == nullptr, "invalid RenderView (%u x %u, zoom %g): %s", view->width, view->height, (double)view->zoom, fault);
+    check_view(view);
     check(Q::NOUN, softening, (uint64_t)view->width * view->height);
     NB_ASSERT(out != nullptr, "NULL %s map", Q::NOUN);
     std::vector<float> coords((size_t)view->width + view->height);

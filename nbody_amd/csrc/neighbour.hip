@@ -281,7 +281,7 @@ void nb_hip_neighbours(SimPipeline *s, uint32_t receivers, uint32_t sources, flo
         return;
     }
     const size_t bytes = (size_t)n * (count ? 12 : 8);
-    const void *host = read_call(s, "nb_hip_neighbours", nullptr, 0, (size_t)n * 12, nullptr, bytes, [&](void *, void *work) -> const void * {
+    const void *host = read_call(s, s->read.iv, "nb_hip_neighbours", nullptr, 0, (size_t)n * 12, nullptr, bytes, [&](void *, void *work) -> const void * {
         ng::Params p{};
         p.pos = s->pos[s->cur];
         p.n = n;
@@ -305,7 +305,7 @@ void nb_hip_ensemble_neighbours(SimBatch *s, uint32_t receivers, uint32_t source
         return;
     }
     const size_t bytes = (size_t)entries * (count ? 12 : 8);
-    const void *host = read_call(s, "nb_hip_ensemble_neighbours", nullptr, 0, (size_t)entries * 12, nullptr, bytes, [&](void *, void *work) -> const void * {
+    const void *host = read_call(s, s->read.iv, "nb_hip_ensemble_neighbours", nullptr, 0, (size_t)entries * 12, nullptr, bytes, [&](void *, void *work) -> const void * {
         ng::Params p{};
         p.pos = s->pos[s->cur];
         p.mass_len = s->mass_len_dev;

@@ -336,7 +336,7 @@ void nb_hip_pair_counts(SimPipeline *s, const float *edges, uint32_t bins, uint3
     }
     // the uint64 table the launch adds to: [rows + 1][3]
     const size_t bytes = cells * sizeof(uint64_t);
-    const void *host = read_call(s, "nb_hip_pair_counts", nullptr, 0, bytes, nullptr, bytes, [&](void *, void *work) -> const void * {
+    const void *host = read_call(s, s->read.iv, "nb_hip_pair_counts", nullptr, 0, bytes, nullptr, bytes, [&](void *, void *work) -> const void * {
         pc::Params p{};
         p.pos = s->pos[s->cur];
         p.n = n;
@@ -364,7 +364,7 @@ void nb_hip_ensemble_pair_counts(SimBatch *s, const float *edges, uint32_t bins,
     }
     // [count][rows + 1][3] uint64: every member's rows, then its unplaced pairs
     const size_t bytes = count * cells * sizeof(uint64_t);
-    const void *landed = read_call(s, "nb_hip_ensemble_pair_counts", nullptr, 0, bytes, nullptr, bytes, [&](void *, void *work) -> const void * {
+    const void *landed = read_call(s, s->read.iv, "nb_hip_ensemble_pair_counts", nullptr, 0, bytes, nullptr, bytes, [&](void *, void *work) -> const void * {
         pc::Params p{};
         p.pos = s->pos[s->cur];
         p.mass_len = s->mass_len_dev;

@@ -21,7 +21,7 @@
 //                    (nb_hip_batch_*, nb_hip_ragged_*): one constructor, and the target of ensemble_walk.h's one launch walk
 //                    (host only, no HIP) for every fixed step; their traced, adaptive and leapfrog updates (the ensemble's
 //                    target of step_schedule.h)
-//   batch_observe.hip  the read-only calls on a SimBatch: energy, potential, bounds, count images and frames
+//   batch_observe.hip  the read-only calls on a SimBatch: energy, potential, the field calls, bounds, count images and frames
 //   diagnostics.hip  energy / momentum / potential of the state a pipeline holds (nb_hip_energy, nb_hip_potential)
 //   batch_diag.hip   the same for every member of a SimBatch, uniform or ragged: the kernels behind nb_hip_ensemble_energy / _potential
 //                    (batch_diag.h; the arithmetic both share: diag_common.h)
@@ -61,7 +61,6 @@
 #include "kernels.h"
 #include "launch_shape.h"
 #include "nbody_hip.h"
-#include "render_kernels.h"
 
 // ---- error convention: print where, abort (reference src/lib/util.h:17-29,47-60) -------------------------
 
@@ -255,53 +254,54 @@ inline double elapsed_ms(hipEvent_t ev0, hipEvent_t ev1) {
 class NB_HIDDEN Interval {
   public:
     void begin(hipStream_t st) { first.record(st); }
-    void end(hipStream_t st) {
-        last.record(st);
-        valid_ = true;
-    }
+    void end(hipStream_t st) { last.record(st), valid_ = true, ms_ = -1.0; }
     void clear() { valid_ = false; }   // the last call had nothing to time
     bool valid() const { return valid_; }
-    double ms() { return valid_ ? elapsed_ms(first.get(), last.get()) : 0.0; }
+    double ms() { return !valid_ ? 0.0 : ms_ >= 0.0 ? ms_ : (ms_ = elapsed_ms(first.get(), last.get())); }
     DevEvent first, last;
 
   private:
     bool valid_ = false;
+    double ms_ = -1.0;   // of the pair as recorded, kept from the first query (below 0: none yet): hipEventElapsedTime asked again moves by a ns
 };
 
-// The scratch of the read-only calls of a SimPipeline / SimBatch: energy, potential, the six field calls, profiles, pair
-// counts and neighbours.  Every one of them ends in a stream sync before it returns, so no two are ever in flight and one set serves them all;
-// what a call finds in it is whatever the last call of any kind left, so a call reads only what it wrote or reset itself: the
-// pair-count table it adds into is zeroed, the neighbour keys it takes minima into are set to all ones, and the neighbour
-// counts are zeroed when a radius asks for them.
+// The scratch of every read-only call of a SimPipeline / SimBatch -- energy, potential, the six field calls, profile, pair counts,
+// neighbours, bounds, count image, frame: fifteen.  Each ends in a stream sync before it returns, so no two are ever in flight and
+// one set serves them all.  A call finds in it whatever the last call of any kind left, so it reads only what it wrote or reset
+// itself.  Energy, potential, the field calls and profile only store.  Pair counts zero the table they add into; neighbours set
+// the keys they take minima into to all ones and zero the counts a radius asks for.  Bounds: a pipeline's two memsets set its four
+// keys to the identities of min and max; an ensemble's workgroups store each member's four.  Count image and frame: the image added
+// into and the disc cursor are zeroed by memset (an ensemble's global path: by one), only discs[0 .. cursor) is ever read, the shade
+// stores every pixel of the frame; an ensemble's tile path builds the image in LDS and stores every word of the counts, or frame.
 struct NB_HIDDEN ReadScratch {
     DevBuf<char> args;        // what a call uploads
-    DevBuf<char> work;        // what its kernels write: workspace and result, in the call's own layout
+    DevBuf<char> work;        // what its kernels write: workspace and result, in the call's own layout (several arrays: section())
     std::vector<char> host;   // where the copied-back bytes land when the caller's array has another layout
-    Interval iv;              // around the last call's launches and memsets (nb_hip_last_diag_ms / nb_hip_ensemble_last_diag_ms);
-                              // step_iv keeps bracketing the last step.  A call with nothing to launch (no probe; no neighbour
-                              // receiver or source under the masks) returns its defaults, clears it and stops there
+    Interval iv;              // around the last call's launches and memsets (nb_hip_last_diag_ms / nb_hip_ensemble_last_diag_ms), but
+                              // for bounds and renders, which bracket render_iv / bounds_iv.  A call with nothing to launch (no probe;
+                              // no neighbour receiver or source under the masks) returns its defaults, clears it and stops there
 };
 
-// The protocol of a read-only call on s (a SimPipeline or a SimBatch: its `read` and its `stream`), written once: grow the two
-// buffers (never shrunk; the stream is drained before one moves), upload `args`, then inside the interval
-// `enqueue(args on the device, work)` launches the call's kernels and returns where on the device the bytes to copy back
-// start, one copy of `back_bytes` to `dst` -- null: to read.host -- and one sync.  Returns where the bytes landed.  `args` stays
-// alive until then.  A size of 0 leaves that buffer alone.  Its callers: diagnostics.hip and batch_observe.hip (energy, potential),
-// field_sampler.h and batch_observe.hip (the six field calls), profile.hip, paircount.hip and neighbour.hip, each for a pipeline
-// and for an ensemble.  tests/sequence_driver.py (the reads kinds) issues them all in drawn orders on one long-lived object.
+// the next section of a call's `work`, on a 256-byte boundary: its offset; `end` moves past it and ends as the size to ask for
+inline size_t section(size_t &end, size_t bytes) { return std::exchange(end, end + (bytes + 255) / 256 * 256); }
+
+// The protocol of every read-only call on s (a SimPipeline or a SimBatch: its `read` and its `stream`), written once: grow the two
+// buffers (never shrunk; the stream is drained before one moves), upload `args`, then inside the interval `iv` `enqueue(args on the
+// device, work)` launches the call's kernels and returns where on the device the bytes to copy back start, one copy of `back_bytes`
+// to `dst` -- null: to read.host -- and one sync.  Returns where the bytes landed.  `args` stays alive until then.  A size of 0 leaves
+// that buffer alone.  tests/sequence_driver.py (the reads kinds) issues all the calls in drawn orders on one long-lived object.
 template <class Owner, class Enqueue>
-void *read_call(Owner *s, const char *what, const void *args, size_t args_bytes, size_t work_bytes, void *dst, size_t back_bytes,
-                Enqueue enqueue) {
+void *read_call(Owner *s, Interval &iv, const char *what, const void *args, size_t args_bytes, size_t work_bytes, void *dst,
+                size_t back_bytes, Enqueue enqueue) {
     ReadScratch &r = s->read;
     use_device();
     if (args_bytes) r.args.grown(s->stream, args_bytes);
     if (work_bytes) r.work.grown(s->stream, work_bytes);
     if (args_bytes)
         ASSERT_HIP(hipMemcpyAsync(r.args, args, args_bytes, hipMemcpyHostToDevice, s->stream), "%s: H2D of %zu bytes", what, args_bytes);
-    r.iv.begin(s->stream);
-    char *up = r.args, *work = r.work;
-    const void *from = enqueue(static_cast<void *>(up), static_cast<void *>(work));
-    r.iv.end(s->stream);
+    iv.begin(s->stream);
+    const void *from = enqueue(static_cast<void *>(r.args), static_cast<void *>(r.work));
+    iv.end(s->stream);
     if (!dst) {
         if (r.host.size() < back_bytes) r.host.resize(back_bytes);   // never shrunk either: a resize back up would zero-fill
         dst = r.host.data();
@@ -472,15 +472,10 @@ struct SimPipeline {
 
     std::vector<nbi::StepGraph> graphs;
 
-    // the read-only calls (diagnostics.hip, field.hip, tidal.hip, profile.hip, paircount.hip, neighbour.hip): their scratch and their interval
+    // every read-only call (diagnostics, field, tidal, profile, paircount, neighbour, render .hip): its scratch; all but render.hip's: its interval
     nbi::ReadScratch read;
 
-    // render.hip (nb_hip_bounds / nb_hip_render_counts / nb_hip_render_rgba; kernels: render_kernels.hip): buffers grown on demand, events of their own
-    nbi::DevBuf<uint32_t> render_counts;   // count image [3][height][width]
-    nbi::DevBuf<nb::render::Disc> render_discs;   // compact disc list, total_len entries
-    nbi::DevBuf<uint32_t> render_words;    // [0] discs appended by the last splat, [4..7] the bounds' ordered keys
-    nbi::DevBuf<uint32_t> render_rgba;     // frame, one packed RGBA word per pixel
-    nbi::Interval render_iv, bounds_iv;
+    nbi::Interval render_iv, bounds_iv;    // render.hip's own: around the last render and the last nb_hip_bounds (nb_hip_last_render_ms)
     nbi::DevEvent ev_splat, ev_disc;       // inside render_iv: after the splat, after the disc pass ("render_detail")
     bool render_detailed = false;          // the last render recorded those two
     int render_merge = 1, render_detail = 0;   // tuning hooks (nbody_hip_tuning.h)
@@ -547,6 +542,10 @@ void check_adaptive_cfg(const void *s, uint32_t n, const NbAdaptive *cfg, const 
 
 // ---- diagnostics.hip -----------------------------------------------------------------------------------------
 
-void check_diag(SimPipeline *s, const char *what);   // aborts on NULL, on a sharded pipeline and before SetSimulationData
+void check_diag(SimPipeline *s, const char *what);   // every read-only call: aborts on NULL, on a sharded pipeline and before SetSimulationData
+
+// ---- render.hip ----------------------------------------------------------------------------------------------
+
+void check_view(const RenderView *view);   // a render's or a map's one view: aborts on NULL and on nb_render_view_fault
 
 }  // namespace nbi

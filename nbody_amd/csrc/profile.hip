@@ -305,7 +305,7 @@ void nb_hip_profile(SimPipeline *s, const float *edges, uint32_t bins, const flo
     memcpy(in + bins + 1, centre, 4 * sizeof(float));
     // the float64 slab: a row of cells + 1 per chunk, then the results -- the cells, then the uint32 NaN count
     const size_t row_bytes = (size_t)(cells + 1) * sizeof(double), back_bytes = (size_t)cells * sizeof(double) + sizeof(uint32_t);
-    const void *host = read_call(s, "nb_hip_profile", in, (size_t)(bins + 5) * sizeof(float), (chunks + 1) * row_bytes, nullptr, back_bytes,
+    const void *host = read_call(s, s->read.iv, "nb_hip_profile", in, (size_t)(bins + 5) * sizeof(float), (chunks + 1) * row_bytes, nullptr, back_bytes,
                                  [&](void *in_dev, void *work) -> const void * {
         pf::ChunkParams p{};
         p.src.pos = s->pos[s->cur];
@@ -340,7 +340,7 @@ void nb_hip_ensemble_profile(SimBatch *s, const float *edges, uint32_t bins, con
     memcpy(in.data() + bins + 1, centres, (size_t)count * 4 * sizeof(float));
     // [count][rows][QTY] float64, then the [count] uint32 NaN counts: the same bytes on the device and on the host
     const size_t bytes = cells * sizeof(double) + (size_t)count * sizeof(uint32_t);
-    const void *host = read_call(s, "nb_hip_ensemble_profile", in.data(), in.size() * sizeof(float), bytes, nullptr, bytes,
+    const void *host = read_call(s, s->read.iv, "nb_hip_ensemble_profile", in.data(), in.size() * sizeof(float), bytes, nullptr, bytes,
                                  [&](void *in_dev, void *work) -> const void * {
         pf::EnsembleParams p{};
         p.pos = s->pos[s->cur];

@@ -18,7 +18,9 @@ and neighbours (an ensemble: the four Phi / g field calls too) through a model o
 grow-only args array, one grow-only work array and one grow-only host array that KEEP their old contents, every call writing its
 result into work in its own layout by merging -- pair counts and neighbour counts by addition, neighbour keys by minimum
 (tests/paircount_ref.py and tests/neighbour_ref.py give the numbers) -- after resetting what it merges into, and a flag for the
-interval.  READ_FAULTS plants one fault for each way of not doing so.  FakeBatch.ragged makes members of different sizes.  The
+interval.  bounds, render_counts and render go through the same three arrays -- the keys and the count image at the head of work,
+where neighbour keys and pair tables lie too, a frame in a section behind its image -- inside an interval of their own
+(FAULTS[27]: the image is not cleared).  READ_FAULTS plants one fault for each way of not doing so.  FakeBatch.ragged makes members of different sizes.  The
 seeds of these kinds are chosen by the same procedure, with READ_FAULTS_OF for (a) and sequence_driver.assert_union_covers_reads
 for (b); a single world is run in two environments, mixed and all massive, and a seed catches a fault if either run does --
 test_the_reads_seeds_are_the_first_pair_that_catches_every_fault recomputes it."""
@@ -45,6 +47,7 @@ FAULTS = {
     5: "set_data leaves the adaptive head armed: the next criterion starts from the old minimum",
     6: "a diagnostic behind an async step sees the state before the step",
     7: "potential() after energy() returns the previous call's buffer",
+    27: "render_counts adds into what the last read-only call left instead of clearing its image",
 }
 LF_FAULTS = {
     8: "an Euler update leaves acc_current set",
@@ -118,7 +121,8 @@ class FakeReads:
     whatever is there -- pair counts and neighbour counts by adding, neighbour keys by minimum, after resetting what it merges
     into -- and the result is what comes back through `host`.  `fault` plants one entry of READ_FAULTS."""
 
-    def _read_call(self, args, work_bytes, back_bytes, enqueue):
+    def _read_call(self, args, work_bytes, back_bytes, enqueue, render=False, at=0):
+        """render: the call brackets the owner's render interval, not the scratch's; at: where in work the result starts"""
         r, up = self.read, None
         if args is not None:
             args = np.ascontiguousarray(args, dtype=F32).ravel()
@@ -129,12 +133,15 @@ class FakeReads:
             up = r.args[:args.size]
         had = r.work.size
         r.work = grown(r.work, work_bytes)
-        r.iv = True
+        if render:
+            self.render_iv = True
+        else:
+            r.iv = True
         enqueue(up, r.work)
         if self.fault == 25 and 0 < had < work_bytes:
             r.work[had:work_bytes] = 0               # the tail never arrives: what the new buffer held stays
         r.host = grown(r.host, back_bytes)
-        r.host[:back_bytes] = r.work[:back_bytes]
+        r.host[:back_bytes] = r.work[at:at + back_bytes]
         return r.host[:back_bytes].copy()
 
     def _nothing(self, defaults):
@@ -149,6 +156,47 @@ class FakeReads:
 
     def last_diag_ms(self):
         return 1.0 if self.read.iv else 0.0
+
+    def last_render_ms(self):
+        return 1.0 if self.render_iv else 0.0
+
+    # bounds, count images and frames: through the same scratch, inside the render interval.  The owner gives _seen() ->
+    # [(pos, mass) per member] as a diagnostic finds them.
+    def _bounds(self):
+        """-> float32 (members, 4): minima and maxima taken into keys that are first set to their identities"""
+        worlds = self._seen()
+        nbytes = 16 * len(worlds)
+
+        def enqueue(up, work):
+            keys = work[:nbytes].view(F32).reshape(-1, 4)
+            keys[:, 0:2], keys[:, 2:4] = np.inf, -np.inf
+            for b, (p, _) in enumerate(worlds):
+                keys[b, 0:2], keys[b, 2:4] = np.minimum(keys[b, 0:2], p.min(axis=0)), np.maximum(keys[b, 2:4], p.max(axis=0))
+        return self._read_call(None, nbytes, nbytes, enqueue, render=True).view(F32).reshape(-1, 4)
+
+    def _render(self, view, frame):
+        """-> uint32 (members, 3, h, w), points ADDED into the image at the head of work; or, shaded from it into the section
+        behind it, uint8 (members, h, w, 3)"""
+        worlds = self._seen()
+        shape = (len(worlds), 3, view.height, view.width)
+        count_bytes = 4 * int(np.prod(shape))
+        frame_bytes = count_bytes // 4 if frame else 0          # one byte per class and pixel
+
+        def enqueue(up, work):
+            img = work[:count_bytes].view(np.uint32).reshape(shape)
+            if self.fault != 27:
+                img[:] = 0
+            for b, (p, mass) in enumerate(worlds):
+                s = (p - np.asarray(view.target, F32)) * F32(view.zoom) + np.asarray(view.offset, F32)
+                ok = (s[:, 0] >= 0) & (s[:, 0] < view.width) & (s[:, 1] >= 0) & (s[:, 1] < view.height)
+                cls = np.where(mass <= 0, 0, np.where(mass < view.core_mass, 1, 2))
+                np.add.at(img[b], (cls[ok], s[ok, 1].astype(np.int64), s[ok, 0].astype(np.int64)), 1)
+            if frame:
+                work[count_bytes:count_bytes + frame_bytes] = np.minimum(img.transpose(0, 2, 3, 1) * 80, 255).astype(np.uint8).ravel()
+        if frame:
+            back = self._read_call(None, count_bytes + frame_bytes, frame_bytes, enqueue, render=True, at=count_bytes)
+            return back.reshape(shape[0], view.height, view.width, 3)
+        return self._read_call(None, count_bytes, count_bytes, enqueue, render=True).view(np.uint32).reshape(shape)
 
     def _field(self, call, comp, pts, soft):
         """pts float32 (members, k, 2) -> float32 (members, k, comp)"""
@@ -265,7 +313,7 @@ class FakePipeline(FakeReads):
 
     def __init__(self, n, m, fault=0):
         self.n, self.m, self.fault = n, m, fault
-        self.read = ReadScratch()
+        self.read, self.render_iv = ReadScratch(), False
         self.pos = [np.zeros((n, 2), F32), np.zeros((n, 2), F32)]
         self.cur = 0
         self.vel, self.acc = np.zeros((n, 2), F32), np.zeros((n, 2), F32)
@@ -554,22 +602,17 @@ class FakePipeline(FakeReads):
     def acceleration_map(self, view, soft):
         return self.acceleration_at(self._pixels(view), soft).reshape(view.height, view.width, 2)
 
+    def _seen(self):
+        return [(self._latest(), self.mass)]
+
     def bounds(self):
-        p = self._latest()
-        return np.concatenate([p.min(axis=0), p.max(axis=0)]).astype(F32)
+        return self._bounds()[0]
 
     def render_counts(self, view):
-        p = self._latest()
-        s = (p - np.asarray(view.target, F32)) * F32(view.zoom) + np.asarray(view.offset, F32)
-        out = np.zeros((3, view.height, view.width), np.uint32)
-        ok = (s[:, 0] >= 0) & (s[:, 0] < view.width) & (s[:, 1] >= 0) & (s[:, 1] < view.height)
-        cls = np.where(self.mass <= 0, 0, np.where(self.mass < view.core_mass, 1, 2))
-        np.add.at(out, (cls[ok], s[ok, 1].astype(np.int64), s[ok, 0].astype(np.int64)), 1)
-        return out
+        return self._render(view, False)[0]
 
     def render(self, view):
-        c = self.render_counts(view)
-        return np.minimum(c.transpose(1, 2, 0) * 80, 255).astype(np.uint8)
+        return self._render(view, True)[0]
 
     # -- the calls of FakeReads, for one world ---------------------------------------------------------------------------
     def _state(self, call):
@@ -606,7 +649,7 @@ class FakeBatch(FakeReads):
 
     def __init__(self, count, n, m, fault=0):
         self.members, self.fault, self.is_ragged = [FakePipeline(n, m, fault) for _ in range(count)], fault, False
-        self.read = ReadScratch()          # the ensemble's own: its reads are one launch for all members
+        self.read, self.render_iv = ReadScratch(), False          # the ensemble's own: its reads are one launch for all members
 
     @classmethod
     def ragged(cls, sizes, mass_lens, fault=0):
@@ -721,17 +764,20 @@ class FakeBatch(FakeReads):
         self.read.iv = True
         return self._out([s.potential() for s in self.members])
 
+    def _seen(self):
+        return [s._seen()[0] for s in self.members]
+
     def bounds(self):
-        return np.stack([s.bounds() for s in self.members])
+        return self._bounds()
 
     def render_mode(self, mode):
         self.mode = mode
 
     def render_counts(self, view):
-        return np.stack([s.render_counts(view) for s in self.members])
+        return self._render(view, False)
 
     def render(self, view):
-        return np.stack([s.render(view) for s in self.members])
+        return self._render(view, True)
 
 
 def view(w, h):
@@ -774,6 +820,8 @@ def first_touch(fault, ops):
         return first(lambda n, a: n in sd.ASYNC)
     if fault == 7:
         return names.index("energy")
+    if fault == 27:
+        return first(lambda n, a: n in ("render_counts", "render"))          # a frame is shaded from the same image
     lf = first(lambda n, a: sd.is_leapfrog((n, a)))          # nothing of LF_FAULTS shows before the first leapfrog call
     if fault == 8:
         return first(lambda n, a: n in ("update", "step_async"), lf + 1)
@@ -1068,7 +1116,9 @@ def reads_first_touch(fault, ops):
         return first(lambda n, a: n in sd.ASYNC)
     if fault == 24:
         return first(lambda n, a: n in sd.AT_CALLS + sd.MAP_CALLS + ("profile",))
-    return first(lambda n, a: n in sd.DIAG_READS)
+    if fault == 25:          # whatever grows the work array: the renders too
+        return first(lambda n, a: n in sd.DIAG_READS + ("bounds", "render_counts", "render"))
+    raise ValueError(f"no first touch known for fault {fault}")
 
 
 _reads_runs = {}
@@ -1114,6 +1164,21 @@ def test_every_planted_reads_fault_is_caught_by_a_committed_seed(kind, fault):
             assert f"seed {seed}" in str(e) and sd.show(ops[0]) in str(e)
             caught.append(seed)
     assert caught, f"no committed seed of {kind} notices: {READ_FAULTS[fault]}"
+
+
+@pytest.mark.parametrize("kind", ["pipeline-reads", "batch-reads"])
+def test_a_render_that_does_not_clear_its_image_is_caught_by_a_committed_reads_seed(kind):
+    """FAULTS[27], among reads that leave neighbour keys, pair tables and float maps where the image goes.  It is no entry of
+    READ_FAULTS_OF: the seeds of the reads kinds were chosen before the renders went through the scratch."""
+    members = READS_MEMBERS[kind][0]
+    caught = []
+    for seed in sd.SEEDS[kind]:
+        e = reads_caught(kind, seed, 27, members)
+        if e is not None:
+            ops = sd.generate(kind, seed, members=members)
+            assert e.seed == seed and e.index >= first_touch(27, ops) and e.name in ("render_counts", "render"), (e.index, e.name)
+            caught.append(seed)
+    assert caught, f"no committed seed of {kind} notices: {FAULTS[27]}"
 
 
 def test_a_fault_a_kind_cannot_show_is_not_claimed():
@@ -1218,4 +1283,8 @@ def test_the_interval_is_part_of_the_verdict():
     launched = sd.apply(s, ("tidal_at", {"count": 1, "which": 0}), env)
     assert len(launched) == 3 * 4 + 1 and launched[-1:] == b"\1"
     assert sd.apply(s, ("potential_at", {"count": 0, "which": 0}), env) == b"\0"
+    for op in (("bounds", {}), ("render_counts", {"w": 32, "h": 18}), ("render", {"w": 32, "h": 18})):
+        s.render_iv = False
+        sd.apply(s, op, env)          # a render brackets an interval of its own and does not move that byte
+        assert s.last_render_ms() > 0 and s.last_diag_ms() == 0
     assert len(sd.apply(s, ("potential_at", {"count": 1}), ENV)) == 4
