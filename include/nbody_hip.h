@@ -714,6 +714,33 @@ void nb_hip_ensemble_neighbours(SimBatch *batch, uint32_t receivers, uint32_t so
                                 uint32_t *count /* packed, member b at offsets[b] */);
 
 /*
+ * The friends-of-friends groups of the state a pipeline or an ensemble holds: every particle labelled with the smallest index of
+ * the structure it is connected to under a linking length (definitions, what links and what follows: include/nbody_group.h; the
+ * union-find and the argument for it: nbody_amd/csrc/group_common.h; kernels: nbody_amd/csrc/group.hip).  members: a non-empty
+ * mask of NB_NEIGH_MASSIVE = 1, NB_NEIGH_MASSLESS = 2 (a class that is not of it is never read and gets NB_GROUP_NONE);
+ * linking_length: finite and >= 0; group: [total_len]; n_groups (nullable): the number of groups, counted on the host from the
+ * copied labels.
+ *   nb_hip_groups             three launches in the stream: the table of the call's scratch set to the identity, the pair scan
+ *                             over j < i whose links meet in that table through agent-scope relaxed integer atomics (load,
+ *                             compare-and-swap, minimum) on global addresses, and the pass that reads the labels off.  No upload,
+ *                             download 4 bytes per particle, one sync.  Enqueued, blocking and invisible to the steps like
+ *                             nb_hip_neighbours; sharded pipelines abort like it.  Nothing to link (linking_length == 0, fewer than
+ *                             two particles of the mask) fills every particle of the mask with its own index and launches nothing.
+ *   nb_hip_ensemble_groups    every member of an ensemble, uniform or ragged, in the same three launches; one mask and one
+ *                             linking length for all.  The labels are packed, member b at offsets[b] of nb_hip_ragged_layout, and
+ *                             count within their member: no group crosses members.  n_groups: [count].  Member b's entries are
+ *                             those of nb_hip_groups of a SimPipeline holding the same particles.
+ * The smallest index of a connected component does not depend on the order the links are met in: a result is a function of the
+ * state and the arguments alone, and there is no float atomic.  Every check -- NULL arguments, an empty or unknown mask, a
+ * non-finite or negative linking length, a call before the data is set -- runs before any device touch and ends in
+ * "file:line [func] ..." + abort().
+ * Added WITHOUT a version bump: detect them by symbol (dlsym "nb_hip_groups", dlsym "nb_hip_ensemble_groups").
+ */
+void nb_hip_groups(SimPipeline *sim, uint32_t members, float linking_length, uint32_t *group /* [total_len] */, uint32_t *n_groups /* nullable */);
+void nb_hip_ensemble_groups(SimBatch *batch, uint32_t members, float linking_length, uint32_t *group /* packed, member b at offsets[b] */,
+                            uint32_t *n_groups /* [count], nullable */);
+
+/*
  * Adaptive time steps chosen on the device (definitions: include/nbody_adaptive.h; kernels: nbody_amd/csrc/timestep.hip).
  *   nb_hip_adaptive_steps         n steps, each of the size the criterion gives for the state before it; blocking
  *   nb_hip_adaptive_steps_async   the same, enqueue only

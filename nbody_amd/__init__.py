@@ -18,14 +18,14 @@ import os             # noqa: F401  os and np have always been reachable through
 import numpy as np    # noqa: F401
 
 from ._abi import (ALLGATHER_FN, CLOCK_SAMPLER_MAX_MS, HIP_API, HIP_SO, LIB_DIR, NB_ADAPT_CONTINUE, NB_ADAPT_LEAPFROG,  # noqa: F401
-                   NB_ADAPT_PRIME, NB_G, NB_NEIGH_ALL, NB_NEIGH_MASSIVE, NB_NEIGH_MASSLESS, NB_NEIGH_NONE, NB_PAIRS_ALL,
+                   NB_ADAPT_PRIME, NB_G, NB_GROUP_NONE, NB_NEIGH_ALL, NB_NEIGH_MASSIVE, NB_NEIGH_MASSLESS, NB_NEIGH_NONE, NB_PAIRS_ALL,
                    NB_PAIRS_COLUMNS, NB_PAIRS_MAX_BINS, NB_PAIRS_MM, NB_PAIRS_MT, NB_PAIRS_TABLE, NB_PAIRS_TT, NB_PROFILE_BY_MASS,
                    NB_PROFILE_BY_NUMBER, NB_PROFILE_CHUNK, NB_PROFILE_MAX_BINS, NB_PROFILE_QTY, NBODY_API, NBODY_SO, PKG_DIR,
                    PUBLIC_KNOBS, ROOT, TUNE_API, UNIQUE_ID_BYTES, NbAdaptive, NbAdaptiveResult, NbShardPlan, RenderPalette,
-                   RenderView, WorldData, WorldEnergy, WorldNeighbourSpec, WorldPairSpec, WorldProfileSpec, adaptive_cfg,
+                   RenderView, WorldData, WorldEnergy, WorldGroupSpec, WorldNeighbourSpec, WorldPairSpec, WorldProfileSpec, adaptive_cfg,
                    as_ensemble, as_particles, as_points, default_palette, energy_row, hip_lib, nbody_lib)
-from .analysis import (closest_pairs, contact_sheet, lagrangian_radii, neighbour_distance, pair_curves, profile_curves,  # noqa: F401
-                       profile_edges, tidal_invariants)
+from .analysis import (closest_pairs, contact_sheet, group_members, group_table, lagrangian_radii, linking_length_for,  # noqa: F401
+                       neighbour_distance, pair_curves, profile_curves, profile_edges, tidal_invariants)
 from .batch import SimBatch, trace_rows  # noqa: F401
 from .device import (clock_sampler_begin, clock_sampler_end, comm_unique_id, deal_item, device_count, device_info,  # noqa: F401
                      hip_error_string, live_resources, plan_deal, plan_launch, preflight_ipc_export, preflight_ipc_open,

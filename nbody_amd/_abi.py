@@ -140,6 +140,14 @@ class WorldNeighbourSpec(C.Structure):
     _fields_ = [("receivers", C.c_uint32), ("sources", C.c_uint32), ("radius", C.c_float)]
 
 
+NB_GROUP_NONE = 0xFFFFFFFF     # include/nbody_group.h
+
+
+class WorldGroupSpec(C.Structure):
+    """include/nbody_group.h WorldGroupSpec."""
+    _fields_ = [("members", C.c_uint32), ("linking_length", C.c_float)]
+
+
 class NbShardPlan(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("mass_chunk", "zero_chunk", "mass_begin", "mass_count",
                                           "zero_begin", "zero_count", "src_padded")]
@@ -206,6 +214,8 @@ HIP_API = {
     "nb_hip_ensemble_pair_counts": (None, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nb_hip_neighbours": (None, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nb_hip_ensemble_neighbours": (None, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nb_hip_groups": (None, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
+    "nb_hip_ensemble_groups": (None, [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
     "nb_hip_batch_create": (C.c_void_p, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "nb_hip_batch_destroy": (None, [C.c_void_p]),
     "nb_hip_batch_set_data": (None, [C.c_void_p, C.c_void_p]),
@@ -268,6 +278,7 @@ TUNE_API = {
     "nb_hip_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_pair_thresholds": (C.c_uint32, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "nb_hip_neighbour_span": (C.c_uint32, [C.c_uint32]),
+    "nb_hip_group_span": (C.c_uint32, [C.c_uint32]),
     "nb_hip_last_render_ms": (C.c_double, [C.c_void_p, C.POINTER(C.c_double)]),
     "nb_hip_ensemble_last_diag_ms": (C.c_double, [C.c_void_p]),
     "nb_hip_ensemble_trace_mode": (None, [C.c_void_p, C.c_int]),
@@ -285,7 +296,7 @@ PUBLIC_KNOBS = ("variant", "graph", "timing", "overlap", "sharded_graph")   # nb
 # include/nbody_render.h + include/nbody_batch_render.h + include/nbody_batch_ragged.h + include/nbody_field.h + include/nbody_gravity.h +
 # include/nbody_adaptive.h + include/nbody_leapfrog.h + include/nbody_batch_field.h + include/nbody_tidal.h + include/nbody_batch_tidal.h +
 # include/nbody_profile.h + include/nbody_batch_profile.h + include/nbody_paircount.h + include/nbody_batch_paircount.h +
-# include/nbody_neighbour.h + include/nbody_batch_neighbour.h
+# include/nbody_neighbour.h + include/nbody_batch_neighbour.h + include/nbody_group.h + include/nbody_batch_group.h
 NBODY_API = {
     "CreateWorld": (C.c_void_p, [C.c_void_p, C.c_uint32]),
     "DestroyWorld": (None, [C.c_void_p]),
@@ -324,6 +335,9 @@ NBODY_API = {
     # include/nbody_neighbour.h, include/nbody_batch_neighbour.h
     "GetWorldNeighbours": (None, [C.c_void_p, C.POINTER(WorldNeighbourSpec), C.c_void_p, C.c_void_p, C.c_void_p]),
     "GetWorldBatchNeighbours": (None, [C.c_void_p, C.POINTER(WorldNeighbourSpec), C.c_void_p, C.c_void_p, C.c_void_p]),
+    # include/nbody_group.h, include/nbody_batch_group.h
+    "GetWorldGroups": (None, [C.c_void_p, C.POINTER(WorldGroupSpec), C.c_void_p, C.c_void_p]),
+    "GetWorldBatchGroups": (None, [C.c_void_p, C.POINTER(WorldGroupSpec), C.c_void_p, C.c_void_p]),
     # include/nbody_batch.h
     "CreateWorldBatch": (C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "DestroyWorldBatch": (None, [C.c_void_p]),

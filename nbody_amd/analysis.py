@@ -1,7 +1,7 @@
 """Readers of what the read-only calls return: numpy only, no library call."""
 import numpy as np
 
-from ._abi import NB_NEIGH_NONE, NB_PAIRS_COLUMNS, NB_PROFILE_MAX_BINS, NB_PROFILE_QTY
+from ._abi import NB_GROUP_NONE, NB_NEIGH_NONE, NB_PAIRS_COLUMNS, NB_PROFILE_MAX_BINS, NB_PROFILE_QTY
 
 
 def neighbour_distance(q):
@@ -22,6 +22,44 @@ def closest_pairs(q, index, k=1):
     pairs = {(min(int(i), int(index[i])), max(int(i), int(index[i]))): float(q[i]) for i in has}
     rows = sorted((v, i, j) for (i, j), v in pairs.items())[:k]
     return [(i, j, v) for v, i, j in rows]
+
+
+def group_table(labels, weights=None, min_members=1):
+    """The groups of one world's .groups() labels: (roots, sizes), or (roots, sizes, sums) with per-particle `weights` (float64
+    sums of the weights of each group's members, mass for instance).  roots uint32, the labels that occur; sizes int64, their
+    member counts.  Sorted by size descending, then by root ascending; groups of fewer than min_members are left out; particles
+    labelled nb.NB_GROUP_NONE (outside the mask) are in none."""
+    lab = np.asarray(labels, dtype=np.uint32)
+    if lab.ndim != 1:
+        raise ValueError("labels must be the (N,) array of one world")
+    of_mask = lab != NB_GROUP_NONE
+    roots, inverse, sizes = np.unique(lab[of_mask], return_inverse=True, return_counts=True)
+    order = np.lexsort((roots, -sizes))
+    order = order[sizes[order] >= min_members]
+    out = (roots[order].astype(np.uint32), sizes[order].astype(np.int64))
+    if weights is None:
+        return out
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape != lab.shape:
+        raise ValueError("weights must have one entry per label")
+    sums = np.bincount(inverse.reshape(-1), weights=w[of_mask], minlength=roots.shape[0])
+    return out + (sums[order],)
+
+
+def group_members(labels, root):
+    """The indices of the particles labelled `root` in one world's .groups() labels, ascending (int64); the first is root itself."""
+    lab = np.asarray(labels, dtype=np.uint32)
+    if lab.ndim != 1:
+        raise ValueError("labels must be the (N,) array of one world")
+    return np.nonzero(lab == np.uint32(root))[0]
+
+
+def linking_length_for(n, area, b=0.2):
+    """b times the mean separation of n particles spread over `area` in the plane, b * sqrt(area / n): the usual way to choose
+    a friends-of-friends linking length (b = 0.2 is the customary value)."""
+    if not n > 0 or not area > 0 or not b >= 0:
+        raise ValueError("need n > 0, area > 0 and b >= 0")
+    return float(b) * float(np.sqrt(float(area) / float(n)))
 
 
 def pair_curves(rows, edges):

@@ -53,7 +53,7 @@ struct SimBatch {
     nbi::DevBuf<uint32_t> n_len_dev;     // ragged only, like offsets_dev
     nbi::DevBuf<uint64_t> offsets_dev;
 
-    // every read-only call (all of batch_observe.hip, nb_hip_ensemble_profile, nb_hip_ensemble_pair_counts, nb_hip_ensemble_neighbours):
+    // every read-only call (all of batch_observe.hip, nb_hip_ensemble_profile, nb_hip_ensemble_pair_counts, nb_hip_ensemble_neighbours, nb_hip_ensemble_groups):
     // their scratch, and the interval of all but bounds and the renders (pipeline_internal.h ReadScratch)
     nbi::ReadScratch read;
     // the energy slab stays a member of its own: traced updates (batch.hip) write it too, and they are no read-only calls

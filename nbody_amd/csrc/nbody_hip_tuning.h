@@ -98,7 +98,7 @@ uint32_t nb_hip_deal_counter(SimPipeline *sim);
 
 /* Device milliseconds of the kernels of the last nb_hip_energy / nb_hip_potential / nb_hip_potential_at /
  * nb_hip_potential_map / nb_hip_acceleration_at / nb_hip_acceleration_map / nb_hip_tidal_at / nb_hip_tidal_map /
- * nb_hip_profile / nb_hip_pair_counts / nb_hip_neighbours (their own event pair, not the step's); 0 before the first call. */
+ * nb_hip_profile / nb_hip_pair_counts / nb_hip_neighbours / nb_hip_groups (their own event pair, not the step's); 0 before the first call. */
 double nb_hip_last_diag_ms(SimPipeline *sim);
 
 /* The float32 thresholds nb_hip_pair_counts compares q against for these edges (nbody_amd/csrc/paircount_common.h): table
@@ -109,6 +109,11 @@ uint32_t nb_hip_pair_thresholds(const float *edges, uint32_t bins, float *table)
  * workgroup walks, for every later call of the process; 0 (default) = auto, the host's policy.  The result is the same for every
  * value: the GPU suite uses it to cross span boundaries at N ~ 1 000.  Returns the previous value.  Host code only. */
 uint32_t nb_hip_neighbour_span(uint32_t blocks);
+
+/* The span of nb_hip_groups / nb_hip_ensemble_groups (nbody_amd/csrc/group.hip): the source blocks of 256 one workgroup of the
+ * pair launch walks, for every later call of the process; 0 (default) = auto, the host's policy.  The result is the same for
+ * every value.  Returns the previous value.  Host code only. */
+uint32_t nb_hip_group_span(uint32_t blocks);
 
 /* The same for an ensemble: device milliseconds of the kernels of the last nb_hip_ensemble_energy /
  * nb_hip_ensemble_potential (an event pair of their own, not the update's); 0 before the first call. */

@@ -39,6 +39,9 @@
 //   neighbour.hip    the nearest neighbour and the neighbour count of every particle of a pipeline and of every member of an
 //                    ensemble (nb_hip_neighbours, nb_hip_ensemble_neighbours): one kernel template, its span policy and its
 //                    entry points (the statement: neighbour_common.h)
+//   group.hip        the friends-of-friends groups of a pipeline and of every member of an ensemble (nb_hip_groups,
+//                    nb_hip_ensemble_groups): the init, pair and flatten kernels, the span policy and the entry points (the
+//                    statement and the union-find: group_common.h)
 //   timestep.hip     the adaptive step size: the criterion kernels between two step launches (timestep.h, timestep_common.h)
 //   leapfrog.hip     the kick / drift passes of a kick-drift-kick step around a dt = 0 force launch (leapfrog.h, leapfrog_common.h)
 #pragma once
@@ -266,10 +269,10 @@ class NB_HIDDEN Interval {
 };
 
 // The scratch of every read-only call of a SimPipeline / SimBatch -- energy, potential, the six field calls, profile, pair counts,
-// neighbours, bounds, count image, frame: fifteen.  Each ends in a stream sync before it returns, so no two are ever in flight and
+// neighbours, groups, bounds, count image, frame: sixteen.  Each ends in a stream sync before it returns, so no two are ever in flight and
 // one set serves them all.  A call finds in it whatever the last call of any kind left, so it reads only what it wrote or reset
 // itself.  Energy, potential, the field calls and profile only store.  Pair counts zero the table they add into; neighbours set
-// the keys they take minima into to all ones and zero the counts a radius asks for.  Bounds: a pipeline's two memsets set its four
+// the keys they take minima into to all ones and zero the counts a radius asks for; groups set the table they hook into to the identity.  Bounds: a pipeline's two memsets set its four
 // keys to the identities of min and max; an ensemble's workgroups store each member's four.  Count image and frame: the image added
 // into and the disc cursor are zeroed by memset (an ensemble's global path: by one), only discs[0 .. cursor) is ever read, the shade
 // stores every pixel of the frame; an ensemble's tile path builds the image in LDS and stores every word of the counts, or frame.
@@ -279,7 +282,7 @@ struct NB_HIDDEN ReadScratch {
     std::vector<char> host;   // where the copied-back bytes land when the caller's array has another layout
     Interval iv;              // around the last call's launches and memsets (nb_hip_last_diag_ms / nb_hip_ensemble_last_diag_ms), but
                               // for bounds and renders, which bracket render_iv / bounds_iv.  A call with nothing to launch (no probe;
-                              // no neighbour receiver or source under the masks) returns its defaults, clears it and stops there
+                              // no neighbour receiver or source under the masks; no pair that could link) returns its defaults, clears it and stops there
 };
 
 // the next section of a call's `work`, on a 256-byte boundary: its offset; `end` moves past it and ends as the size to ask for
@@ -472,7 +475,7 @@ struct SimPipeline {
 
     std::vector<nbi::StepGraph> graphs;
 
-    // every read-only call (diagnostics, field, tidal, profile, paircount, neighbour, render .hip): its scratch; all but render.hip's: its interval
+    // every read-only call (diagnostics, field, tidal, profile, paircount, neighbour, group, render .hip): its scratch; all but render.hip's: its interval
     nbi::ReadScratch read;
 
     nbi::Interval render_iv, bounds_iv;    // render.hip's own: around the last render and the last nb_hip_bounds (nb_hip_last_render_ms)

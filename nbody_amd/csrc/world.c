@@ -33,6 +33,8 @@
  * (paircount.hip on the device, paircount_cpu.c on the host).
  * Extension (include/nbody_neighbour.h): GetWorldNeighbours likewise
  * (neighbour.hip on the device, neighbour_cpu.c on the host).
+ * Extension (include/nbody_group.h): GetWorldGroups likewise
+ * (group.hip on the device, group_cpu.c on the host).
  * Extension (include/nbody_adaptive.h): adaptive steps.  UpdateWorld_GPU_Adaptive
  * and AdvanceWorld_GPU follow UpdateWorld_GPU's coherence rules, UpdateWorld_CPU_Adaptive
  * UpdateWorld_CPU's; GetWorldTimestep follows the diagnostics' (timestep.hip on the
@@ -51,6 +53,7 @@
 #include "nbody_profile.h"
 #include "nbody_paircount.h"
 #include "nbody_neighbour.h"
+#include "nbody_group.h"
 #include "nbody_hip.h"
 #include "nbody_leapfrog.h"
 #include "nbody_render.h"
@@ -63,6 +66,7 @@
 #include "profile_common.h"
 #include "paircount_common.h"
 #include "neighbour_common.h"
+#include "group_common.h"
 #include "render_common.h"
 #include "nb_util.h"
 #include "sim_cpu.h"
@@ -323,6 +327,18 @@ void GetWorldNeighbours(World *w, const WorldNeighbourSpec *spec, float *q, uint
         nb_hip_neighbours(w->gpu, spec->receivers, spec->sources, spec->radius, q, index, count);
     else
         nb_cpu_neighbours(w->particles, w->count, w->massive, spec->receivers, spec->sources, spec->radius, q, index, count);
+}
+
+/* ---- include/nbody_group.h ------------------------------------------------------------------------------------------- */
+
+void GetWorldGroups(World *w, const WorldGroupSpec *spec, uint32_t *group, uint32_t *n_groups) {
+    NB_CHECK(w != NULL && spec != NULL && group != NULL, "NULL argument");
+    const char *fault = nb_group_fault(spec->members, spec->linking_length);
+    NB_CHECK(fault == NULL, "GetWorldGroups: %s (members %u, linking_length %g)", fault, spec->members, (double)spec->linking_length);
+    if (diag_on_device(w, "GetWorldGroups"))
+        nb_hip_groups(w->gpu, spec->members, spec->linking_length, group, n_groups);
+    else
+        nb_cpu_groups(w->particles, w->count, w->massive, spec->members, spec->linking_length, group, n_groups);
 }
 
 /* ---- include/nbody_adaptive.h ---------------------------------------------------------------------------------------- */

@@ -26,6 +26,8 @@
  * nb_hip_ensemble_profile, one launch; host: profile_cpu.c member by member), uniform and ragged batches alike.
  * include/nbody_batch_paircount.h: the pair-separation counts of every member likewise (device: nb_hip_ensemble_pair_counts,
  * one launch; host: paircount_cpu.c member by member).
+ * include/nbody_batch_group.h: the friends-of-friends groups of every member likewise (device: nb_hip_ensemble_groups; host:
+ * group_cpu.c member by member).
  */
 #include "nbody_adaptive.h"
 #include "nbody_leapfrog.h"
@@ -36,6 +38,7 @@
 #include "nbody_batch_profile.h"
 #include "nbody_batch_paircount.h"
 #include "nbody_batch_neighbour.h"
+#include "nbody_batch_group.h"
 #include "nbody_batch_ragged.h"
 #include "nbody_batch_render.h"
 #include "nbody_batch_trace.h"
@@ -49,6 +52,7 @@
 #include "profile_common.h"
 #include "paircount_common.h"
 #include "neighbour_common.h"
+#include "group_common.h"
 #include "render_common.h"
 #include "timestep_common.h"
 #include "world_partition.h"
@@ -479,5 +483,20 @@ void GetWorldBatchNeighbours(WorldBatch *w, const WorldNeighbourSpec *spec, floa
         for (uint32_t b = 0; b < w->count; b++)
             nb_cpu_neighbours(w->particles + w->offset[b], w->sizes[b], w->massive[b], spec->receivers, spec->sources, spec->radius, q + w->offset[b],
                               index + w->offset[b], count ? count + w->offset[b] : NULL);
+    }
+}
+
+/* ---- include/nbody_batch_group.h ------------------------------------------------------------------------------------- */
+
+void GetWorldBatchGroups(WorldBatch *w, const WorldGroupSpec *spec, uint32_t *group, uint32_t *n_groups) {
+    NB_CHECK(w != NULL && spec != NULL && group != NULL, "GetWorldBatchGroups: NULL argument");
+    const char *fault = nb_group_fault(spec->members, spec->linking_length);
+    NB_CHECK(fault == NULL, "GetWorldBatchGroups: %s (members %u, linking_length %g)", fault, spec->members, (double)spec->linking_length);
+    if (w->device_is_newer) {
+        nb_hip_ensemble_groups(w->gpu, spec->members, spec->linking_length, group, n_groups);
+    } else {
+        for (uint32_t b = 0; b < w->count; b++)
+            nb_cpu_groups(w->particles + w->offset[b], w->sizes[b], w->massive[b], spec->members, spec->linking_length, group + w->offset[b],
+                          n_groups ? n_groups + b : NULL);
     }
 }

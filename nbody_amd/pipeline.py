@@ -158,7 +158,7 @@ class SimPipeline(Reads):
 
     def last_diag_ms(self):
         """tuning hook: device ms of the kernels of the last energy() / potential() / potential_at() / potential_map() /
-        acceleration_at() / acceleration_map() / tidal_at() / tidal_map() / profile() / pair_counts() / neighbours(); 0.0 after a
+        acceleration_at() / acceleration_map() / tidal_at() / tidal_map() / profile() / pair_counts() / neighbours() / groups(); 0.0 after a
         call that had nothing to launch."""
         return float(hip_lib().nb_hip_last_diag_ms(self._h))
 

@@ -4,7 +4,7 @@ SimPipeline, SimBatch, World and WorldBatch inherit `Reads` and state only what 
 
     _lib          the library the entry points live in, resolved at the call: hip_lib or nbody_lib
     _ENTRY        method name -> C entry point, one column of ENTRY_POINTS below
-    _WORLD_LAYER  the World layer takes profile / pair_counts / neighbours arguments as a World*Spec structure and fills in a
+    _WORLD_LAYER  the World layer takes profile / pair_counts / neighbours / groups arguments as a World*Spec structure and fills in a
                   NULL palette itself; the seam (nb_hip_*) takes them loose and wants a palette
     _n            particles per world (total_len at the seam, size in the World layer)
     count         an ensemble's members; None for a single world
@@ -19,7 +19,7 @@ import numpy as np
 
 from ._abi import (NB_NEIGH_ALL, NB_NEIGH_MASSIVE, NB_NEIGH_MASSLESS, NB_PAIRS_ALL, NB_PAIRS_COLUMNS, NB_PAIRS_MM, NB_PAIRS_MT,
                    NB_PAIRS_TT, NB_PROFILE_BY_MASS, NB_PROFILE_BY_NUMBER, NB_PROFILE_QTY, RenderView, WorldEnergy,
-                   WorldNeighbourSpec, WorldPairSpec, WorldProfileSpec, as_points, default_palette)
+                   WorldGroupSpec, WorldNeighbourSpec, WorldPairSpec, WorldProfileSpec, as_points, default_palette)
 
 # method             SimPipeline                 SimBatch                            World                      WorldBatch
 ENTRY_POINTS = {
@@ -34,6 +34,7 @@ ENTRY_POINTS = {
     "profile":          ("nb_hip_profile",          "nb_hip_ensemble_profile",          "GetWorldProfile",         "GetWorldBatchProfile"),
     "pair_counts":      ("nb_hip_pair_counts",      "nb_hip_ensemble_pair_counts",      "GetWorldPairCounts",      "GetWorldBatchPairCounts"),
     "neighbours":       ("nb_hip_neighbours",       "nb_hip_ensemble_neighbours",       "GetWorldNeighbours",      "GetWorldBatchNeighbours"),
+    "groups":           ("nb_hip_groups",           "nb_hip_ensemble_groups",           "GetWorldGroups",          "GetWorldBatchGroups"),
     "bounds":           ("nb_hip_bounds",           "nb_hip_ensemble_bounds",           "GetWorldBounds",          "GetWorldBatchBounds"),
     "render_counts":    ("nb_hip_render_counts",    "nb_hip_ensemble_render_counts",    "RenderWorldCounts",       "RenderWorldBatchCounts"),
     "render":           ("nb_hip_render_rgba",      "nb_hip_ensemble_render_rgba",      "RenderWorld",             "RenderWorldBatch"),
@@ -270,6 +271,25 @@ class Reads:
         args = (C.byref(WorldNeighbourSpec(r, s, h)),) if self._WORLD_LAYER else (r, s, h)
         self._fn("neighbours")(self._h, *args, q.ctypes.data, index.ctypes.data, None if count is None else count.ctypes.data)
         return tuple(self._members(a) for a in ((q, index) if count is None else (q, index, count)))
+
+    def groups(self, linking_length, members="all", return_count=False):
+        """The friends-of-friends groups under `linking_length` (include/nbody_group.h): uint32 labels (N,), in the order
+        potential() has -- for every particle the smallest index among the particles it is connected to through any chain of
+        pairs closer than the linking length (its own index with none); nb.NB_GROUP_NONE for a particle outside `members`.
+        members: "massive", "massless" or "all"; a class that is not of it is never read and bridges nothing.  With return_count
+        also the number of groups, an int.  Device, host and numpy agree bit for bit.  nb.group_table and nb.group_members read
+        the result, nb.linking_length_for chooses a length.
+        An ensemble, in one call for all members: (B, N) and uint32 (B,); a ragged one a list of per-member arrays, as
+        neighbours() gives; a label counts within its member, so no group crosses members."""
+        mask = _neigh_mask(members, "members")
+        labels = self._per_particle(np.uint32)
+        found = np.zeros(1 if self.count is None else self.count, dtype=np.uint32)
+        length = float(linking_length)
+        args = (C.byref(WorldGroupSpec(mask, length)),) if self._WORLD_LAYER else (mask, length)
+        self._fn("groups")(self._h, *args, labels.ctypes.data, found.ctypes.data if return_count else None)
+        if not return_count:
+            return self._members(labels)
+        return self._members(labels), (int(found[0]) if self.count is None else found)
 
     def bounds(self):
         """float32 [min.x, min.y, max.x, max.y] over the particles with finite x and y (include/nbody_render.h); an ensemble
