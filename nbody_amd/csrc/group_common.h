@@ -32,6 +32,8 @@
  *      positions come through.
  *   5. The labels are read off in a launch of their own behind the pair launch (the kernel boundary makes the table visible):
  *      group[i] = find(i).
+ * tests/group_schedule.c runs nb_group_find and nb_group_unite as they stand below over every schedule of tiny cases and seeded
+ * schedules of larger ones, a load returning any value its word ever held, and checks 1 to 3 after every operation.
  */
 #ifndef NB_GROUP_COMMON_H
 #define NB_GROUP_COMMON_H
@@ -45,6 +47,10 @@
 #define NB_GROUP_LOAD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define NB_GROUP_CAS(p, expected, desired) atomicCAS((p), (expected), (desired))
 #define NB_GROUP_MIN(p, v) ((void)atomicMin((p), (v)))
+#elif defined(NB_GROUP_OPS_HEADER)
+/* a stand-alone host program supplies the three operations itself: tests/group_schedule.c runs nb_group_find and nb_group_unite
+ * as they stand here under a scheduler that picks every interleaving and every stale value */
+#include NB_GROUP_OPS_HEADER
 #else
 static inline uint32_t nb_group_host_cas(uint32_t *p, uint32_t expected, uint32_t desired) {
     __atomic_compare_exchange_n(p, &expected, desired, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
@@ -77,7 +83,12 @@ NB_PAIR_HD uint32_t nb_group_find(uint32_t *parent, uint32_t x) {
     }
 }
 
-/* Joins the trees of a and b (argument 3) and returns the root the joined tree had when the call ended. */
+/*
+ * Joins the trees of a and b (argument 3) and returns a node of the joined tree that is not above a nor above b: the root as this
+ * call's last operation showed it.  Another thread may have hooked that node lower by the time the call returns, and a stale
+ * find may have ended on a node that was no root any more (tests/group_schedule.c counts such returns), so it is NOT "the root
+ * when the call ended".  The callers need no more than this: they compare it and hand it to the next find or unite.
+ */
 NB_PAIR_HD uint32_t nb_group_unite(uint32_t *parent, uint32_t a, uint32_t b) {
     for (;;) {
         a = nb_group_find(parent, a);
